@@ -1,18 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the DaliID Person-ReID hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload train|vit|distance|epoch]
+    python bench.py --gpus N --steps K --warmup W [--workload train|vit|distance|epoch] [--full] [--dump-outputs DIR]
 
 Prints ONE JSON line (rank 0).  Workloads (BASELINE.json):
   * train    (configs[1]): ResNet-50 ReID bf16, PK batch 16x16=256 per GPU, center + proxy heads, Adam, EMA;
                metric images/sec; data-parallel over N GPUs with RCCL gradient all-reduce (weak scaling).
-               The default run also carries the other half of BASELINE.json's metric as a ``"distance"`` sub-record
+               With --full the run also carries the other half of BASELINE.json's metric as a ``"distance"`` sub-record
                (configs[4], below) unless --no-distance is given.
-  * distance (configs[4]): 10k x 100k x 2048 cosine distmat (+ CMC/mAP timed separately); metric Gpairs/sec.
-  * vit      (configs[3]): TransReID ViT-B/16 train step, batch 128 per GPU (also a ``"vit"`` sub-record of the default run).
+  * distance (configs[4]): 10k x 100k x 2048 cosine distmat (+ CMC/mAP timed separately under --full); metric Gpairs/sec.
+  * vit      (configs[3]): TransReID ViT-B/16 train step, batch 128 per GPU (also a ``"vit"`` sub-record of the --full train run).
   * epoch    one Market-1501-shaped epoch of trainer.train (12,936-image inference + 751-id targets + 46 PK steps of 384), the
-               only thing the reference's logs time; also an ``"epoch"`` sub-record of the default run.
-Inputs are synthetic and resident in HBM before the timed region.
+               only thing the reference's logs time; also an ``"epoch"`` sub-record of the --full train run.
+Inputs are synthetic and resident in HBM before the timed region, and seeded: the same arguments give the same inputs.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line.  ``--full`` adds everything else the line can
+carry: the roofline leg (GEMM launches timed by HIP events in extra steps), the CPU baselines, the all-reduce probe, the
+distance / ViT / epoch sub-records of the train workload and the distance workload's kernel-alone, ranking and oracle-parity legs.
+``--dump-outputs DIR`` writes what the timed path computed in its last timed step as DIR/<name>.npy (float32 / float64; outputs
+larger than a few MB as a fixed, seeded sample of their elements), so that two builds can be compared output for output.
 
 ``--gpus N`` with N > 1: when no launcher has set WORLD_SIZE, this process starts N ranks itself
 (``python -m torch.distributed.run --nproc-per-node N bench.py ...`` as a CHILD process, before anything here touches a
@@ -156,6 +162,14 @@ def bench_distance(args, world, rank):
     dt = max_over_ranks(time.perf_counter() - t0, world)
     ms_step = dt / args.steps * 1e3
     gpairs = world * nq * ng / 1e9 / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {"distmat_sample": dump_sample(out, 1 << 22)})
+    res = {"metric": "gallery-distance Gpairs/sec", "value": round(gpairs, 3), "unit": "Gpairs/s",
+           "ms_per_step": round(ms_step, 4), "dtype": "bf16" if prec == "bf16" else "bf16x3(fp32-grade)",
+           "config": {"workload": "configs[4]: 10k x 100k x 2048 cosine distmat, normalise fused; per GPU; RANDOM features (randn rows, 1000 ids x 100 "
+                                  "gallery / 10 query entries)", "nq": nq, "ng": ng, "d": d, "precision": prec}}
+    if not args.full:
+        return res
 
     # dominant kernel alone (pairdist MFMA kernel on prepared operands), HIP events on the launch stream
     qp, gp = ops_eval.PreparedRows(q, True, prec), ops_eval.PreparedRows(g, True, prec)
@@ -205,15 +219,13 @@ def bench_distance(args, world, rank):
     if rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline_distance()
         parity = distance_parity_vs_oracle(prec)
-    return {"metric": "gallery-distance Gpairs/sec", "value": round(gpairs, 3), "unit": "Gpairs/s",
-            "ms_per_step": round(ms_step, 4), "dtype": "bf16" if prec == "bf16" else "bf16x3(fp32-grade)",
-            "config": {"workload": "configs[4]: 10k x 100k x 2048 cosine distmat, normalise fused; per GPU; RANDOM features (randn rows, 1000 ids x 100 "
-                                   "gallery / 10 query entries): the ranking kernel's worst case (every gallery entry is binned), so mAP is chance level "
-                                   "by construction and says nothing about accuracy (tests/test_gpu_eval.py covers SURVEY 8d's structured gallery)",
-                       "nq": nq, "ng": ng, "d": d, "precision": prec, "mAP_on_random_features": round(float(mAP), 6)},
-            "rank_eval_ms": round(rank_ms, 3), "rank_eval_GBps": round(nq * ng * 4 / 1e9 / (rank_ms * 1e-3), 1),
-            "rank_eval_hbm_frac": round(nq * ng * 4 / 1e9 / (rank_ms * 1e-3) / HBM_PEAK_GBS, 4),
-            "roofline": roofline, "cpu_baseline": cpu, "map_vs_oracle": parity}
+    res["config"]["workload"] += (": the ranking kernel's worst case (every gallery entry is binned), so mAP is chance level by construction and says "
+                                  "nothing about accuracy (tests/test_gpu_eval.py covers SURVEY 8d's structured gallery)")
+    res["config"]["mAP_on_random_features"] = round(float(mAP), 6)
+    res.update({"rank_eval_ms": round(rank_ms, 3), "rank_eval_GBps": round(nq * ng * 4 / 1e9 / (rank_ms * 1e-3), 1),
+                "rank_eval_hbm_frac": round(nq * ng * 4 / 1e9 / (rank_ms * 1e-3) / HBM_PEAK_GBS, 4),
+                "roofline": roofline, "cpu_baseline": cpu, "map_vs_oracle": parity})
+    return res
 
 
 def distance_parity_vs_oracle(prec):
@@ -271,6 +283,41 @@ def committed_traffic(which, key="gemm_kernels_hbm_bytes_per_step"):
 
 def log(msg):
     print("[bench] " + msg, file=sys.stderr, flush=True)
+
+
+DUMP_SAMPLE = 1 << 21          # elements kept of a dumped output larger than this (8 MB in fp32)
+
+
+def dump_sample(t, k=DUMP_SAMPLE, seed=12):
+    """t flattened, or its elements at k fixed, seeded positions (sorted, distinct) when it has more than k"""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() > k:
+        idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), k))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat
+
+
+def write_outputs(out_dir, arrays):
+    """arrays: name -> tensor; written as out_dir/<name>.npy, float64 kept, every other dtype as float32"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    log("outputs: %d arrays, %.1f MB in %s" % (len(arrays), total / 1e6, out_dir))
+
+
+def dump_trainer_outputs(out_dir, tr, extra):
+    """what a train step leaves its caller: the updated online / momentum (EMA) nets' parameters and BatchNorm buffers"""
+    net, mom = tr._net, tr._mom
+    arrays = dict(extra)
+    arrays.update({"online_params_sample": dump_sample(net.flat_params), "online_buffers_sample": dump_sample(net.flat_buffers),
+                   "momentum_params_sample": dump_sample(mom.flat_params), "momentum_buffers_sample": dump_sample(mom.flat_buffers)})
+    write_outputs(out_dir, arrays)
 
 
 def best_cpu_threads(fn, candidates, budget_s=3.0):
@@ -407,13 +454,26 @@ def bench_train(args, world, rank):
     t0 = time.perf_counter()
     ev0.record()
     for _ in range(args.steps):
-        step()
+        stats = step()
     ev1.record()
     barrier_sync(world)
     dt = max_over_ranks(time.perf_counter() - t0, world)
     gpu_ms = ev0.elapsed_time(ev1) / args.steps
     ms_step = dt / args.steps * 1e3
     ips = world * batch / (dt / args.steps)
+    log("GPU: %.3f ms/step (device %.3f ms), %.1f images/s" % (ms_step, gpu_ms, ips))
+    if args.dump_outputs and rank == 0:
+        # the step returns the loss heads' statistics and accumulates into `acc` (running sums since the first warm-up step)
+        dump_trainer_outputs(args.dump_outputs, tr, {"loss_stats": stats, "loss_running_sums": acc})
+    wl = ("configs[3]: TransReID ViT-B/16 bf16 224x224, drop_path 0.1, batch %d per GPU, center+proxy heads, Adam, EMA" % batch) if vit else \
+         "configs[1]: ResNet-50 ReID bf16 256x128, PK batch 16x16=256 per GPU, center+proxy heads, Adam, EMA"
+    final = acc.cpu().numpy()
+    res = {"metric": "images/sec (train step)", "value": round(ips, 2), "unit": "images/s", "ms_per_step": round(ms_step, 3),
+           "dtype": "bf16", "config": {"workload": wl + ("; data-parallel, RCCL all-reduce of gradients" if world > 1 else ""),
+                                       "global_batch": world * batch, "per_gpu_batch": batch, "parallelism": "dp%d" % world,
+                                       "mean_loss": float(final[2] / max(final[4], 1))}}
+    if not args.full:
+        return res
     step_tflops = batch * gflop_img / 1e3 / (gpu_ms * 1e-3)
     # Dominant kernel family = the implicit-GEMM MFMA kernels (igemm_conv_* forward/dgrad + igemm_wgrad_*).  Their
     # launch durations are measured live: the same steps again with every such launch bracketed by HIP events on the
@@ -447,8 +507,6 @@ def bench_train(args, world, rank):
                         "mask output stage, the Gram-scheme products and column sums: launched_gemm_tflop_per_step > the algorithmic figure), so moving "
                         "work into them lowers `frac` while the step gets faster: read whole_step beside it.  hbm_frac = HBM bytes of ALL kernels of "
                         "one step (committed PMC pass) / device time of the step / 8 TB/s" % (gflop_img, batch)}
-    final = acc.cpu().numpy()
-    log("GPU: %.3f ms/step (device %.3f ms), %.1f images/s" % (ms_step, gpu_ms, ips))
     comm = None
     if world > 1:
         comm = allreduce_probe(tr, world, args.steps)
@@ -461,13 +519,8 @@ def bench_train(args, world, rank):
             cpu = cpu_baseline_vit(sd)
         else:
             cpu = cpu_baseline_train()
-    wl = ("configs[3]: TransReID ViT-B/16 bf16 224x224, drop_path 0.1, batch %d per GPU, center+proxy heads, Adam, EMA" % batch) if vit else \
-         "configs[1]: ResNet-50 ReID bf16 256x128, PK batch 16x16=256 per GPU, center+proxy heads, Adam, EMA"
-    return {"metric": "images/sec (train step)", "value": round(ips, 2), "unit": "images/s", "ms_per_step": round(ms_step, 3),
-            "dtype": "bf16", "config": {"workload": wl + ("; data-parallel, RCCL all-reduce of gradients" if world > 1 else ""),
-                                        "global_batch": world * batch, "per_gpu_batch": batch, "parallelism": "dp%d" % world,
-                                        "mean_loss": float(final[2] / max(final[4], 1))},
-            "roofline": roofline, "cpu_baseline": cpu, "comm": comm}
+    res.update({"roofline": roofline, "cpu_baseline": cpu, "comm": comm})
+    return res
 
 
 def bench_epoch(args, world, rank):
@@ -568,6 +621,8 @@ def bench_epoch(args, world, rank):
         barrier_sync(world)
         t_epoch = max_over_ranks(time.perf_counter() - t0, world)
         st = tr.last_epoch_stats
+        if args.dump_outputs and rank == 0:
+            dump_trainer_outputs(args.dump_outputs, tr, {"epoch_loss": torch.tensor([float(st["loss"])], dtype=torch.float64)})
     finally:
         getFeatures.set_image_loader(None); T.set_train_loader(None)
     steps = int(st["steps"])
@@ -700,10 +755,15 @@ def main():
     ap.add_argument("--workload", default="train", choices=["train", "vit", "distance", "epoch"])
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default 256 for train, 128 for vit)")
     ap.add_argument("--precision", default="bf16x3", choices=["bf16x3", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-distance", action="store_true", help="train workload: skip the configs[4] distance sub-record")
-    ap.add_argument("--no-vit", action="store_true", help="train workload: skip the configs[3] ViT-B/16 sub-record")
-    ap.add_argument("--no-epoch", action="store_true", help="train workload: skip the Market-shaped epoch sub-record")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: roofline leg, CPU baselines, all-reduce probe, the train workload's distance / ViT / epoch "
+                         "sub-records, the distance workload's kernel-alone, ranking and oracle-parity legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-distance", action="store_true", help="train workload with --full: skip the configs[4] distance sub-record")
+    ap.add_argument("--no-vit", action="store_true", help="train workload with --full: skip the configs[3] ViT-B/16 sub-record")
+    ap.add_argument("--no-epoch", action="store_true", help="train workload with --full: skip the Market-shaped epoch sub-record")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -716,30 +776,37 @@ def main():
             import torch.distributed as dist
             dist.destroy_process_group()
         sys.exit(0 if os.environ.get("DALIID_BENCH_CHILD") else 3)      # the self-launching parent turns the error line into status 3
+    # synthetic inputs drawn from torch's / numpy's global streams (the AT distortion pairing, DropPath, the epoch's batch order)
+    # are seeded too: the same arguments give the same inputs run after run
+    import numpy as np
+    torch.manual_seed(12 + rank)
+    np.random.seed(12 + rank)
     if args.workload == "distance":
         res = bench_distance(args, world, rank)
     elif args.workload == "epoch":
         res = bench_epoch(args, world, rank)
     else:
         res = bench_train(args, world, rank)
-        if args.workload == "train" and not args.no_distance:
+        sub = argparse.Namespace(**vars(args))
+        sub.dump_outputs = None                             # the sub-records' outputs are not the headline's
+        if args.full and args.workload == "train" and not args.no_distance:
             # the other half of BASELINE.json's metric in the same line: configs[4] on every rank's own synthetic gallery
             # (weak scaling: the gallery shards over ranks with no exchange)
-            d = bench_distance(args, world, rank)
+            d = bench_distance(sub, world, rank)
             d.pop("metric")
             res["distance"] = d
         # (the vit / epoch sub-records belong to the single-GPU line: the scaling runs time the train step and the distance leg only)
-        if args.workload == "train" and not args.no_vit and world == 1:
+        if args.full and args.workload == "train" and not args.no_vit and world == 1:
             # configs[3] in the driver's line as well: 5 warm-up + 20 timed ViT-B/16 steps (~0.6 s)
             torch.cuda.empty_cache()
-            va = argparse.Namespace(**vars(args))
+            va = argparse.Namespace(**vars(sub))
             va.workload, va.batch, va.steps, va.warmup = "vit", 0, 20, 5
             v = bench_train(va, world, rank)
             v.pop("metric"); v["steps"], v["warmup"] = va.steps, va.warmup
             res["vit"] = v
-        if args.workload == "train" and not args.no_epoch and world == 1:
+        if args.full and args.workload == "train" and not args.no_epoch and world == 1:
             torch.cuda.empty_cache()
-            e = bench_epoch(args, world, rank)
+            e = bench_epoch(sub, world, rank)
             res["epoch"] = e
     res.update({"n_gpus": world, "steps": args.steps, "warmup": args.warmup, "higher_is_better": args.workload != "epoch",
                 "scaling": "weak", "vs_baseline": None, "data": "synthetic"})

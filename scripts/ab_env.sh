@@ -3,6 +3,6 @@
 REPS=$1; shift
 for rep in $(seq 1 $REPS); do
 for E in "$@"; do
-env $E timeout -k 10 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-distance $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$E: ms_per_step', d['ms_per_step'], 'gemm', d['roofline']['kernel_ms_per_step'], d['roofline']['by_class_ms_per_step'])" || exit 124
+env $E timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-distance $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$E: ms_per_step', d['ms_per_step'], 'gemm', d['roofline']['kernel_ms_per_step'], d['roofline']['by_class_ms_per_step'])" || exit 124
 done
 done

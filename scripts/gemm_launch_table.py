@@ -1,6 +1,6 @@
 """Per-launch table of the GEMM kernels INSIDE the train step (bench.py's event-bracketed profile steps):
-    DALI_GEMM_PROFILE_DUMP=gpurun_out/gemm_launches.csv python bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-distance
-    python scripts/gemm_launch_table.py gpurun_out/gemm_launches.csv [steps=3]
+    DALI_GEMM_PROFILE_DUMP=gemm_launches.csv python bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --no-distance
+    python scripts/gemm_launch_table.py gemm_launches.csv [steps=3]
 Groups launches by signature, prints count per step, mean us, TFLOP/s and the share of the GEMM time, sorted by total time."""
 import sys, collections
 path = sys.argv[1]; steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3

@@ -7,8 +7,8 @@ shutil.copy(src + "/kernel_stats.csv", "profiles/%s_distance_kernel_stats.csv" %
 last = lambda f: open(src + "/" + f).read().strip().splitlines()[-1]
 rows = list(csv.DictReader(open(src + "/kernel_stats.csv")))
 out = ["# Round %s -- gallery distance (configs[4]) kernel profile\n" % RND[1:].lstrip("0"),
-       "Produced by `bash scripts/profile_distance.sh` on an MI355X box: `python bench.py --workload distance --steps 5 --warmup 2` (unprofiled, with the CPU "
-       "baseline), the same with `--precision bf16`, `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --workload distance --steps 5 "
+       "Produced by `bash scripts/profile_distance.sh` on an MI355X box: `python bench.py --full --workload distance --steps 5 --warmup 2` (unprofiled, with the CPU "
+       "baseline), the same with `--precision bf16`, `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --workload distance --steps 5 "
        "--warmup 2 --no-cpu-baseline`, `python scripts/time_rank.py`; summary by `scripts/make_profile_distance_md.py`.\n",
        "Bench line, unprofiled (bf16x3 = fp32-grade split-bf16):\n\n```\n%s\n```\n" % last("bench.json"),
        "Bench line with `--precision bf16`:\n\n```\n%s\n```\n" % last("bench_bf16.json"),

@@ -12,8 +12,8 @@ open("profiles/%s_gemm_launches_in_step.md" % RND, "w").write("""# Round %s -- e
 
 Produced on an MI355X box by
 
-    DALI_GEMM_PROFILE_DUMP=gpurun_out/gemm_launches.csv python bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-distance --no-vit --no-epoch
-    python scripts/gemm_launch_table.py gpurun_out/gemm_launches.csv 3
+    DALI_GEMM_PROFILE_DUMP=gemm_launches.csv python bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --no-distance --no-vit --no-epoch
+    python scripts/gemm_launch_table.py gemm_launches.csv 3
 
 (`bench.py`'s event-bracketed profile steps: every `igemm_*` / `fused1x1_persist` launch of three consecutive steps between two HIP events on the launch
 stream, grouped by signature).  Step of this run: %.3f ms, GEMM launches %.3f ms per step (forward + data gradient %.3f, weight gradient %.3f).

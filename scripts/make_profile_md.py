@@ -13,10 +13,10 @@ pmc = json.load(open(src + "/pmc_traffic.json"))
 pmd = open(src + "/pmc_traffic.md").read()
 steps = 16
 out = ["# Round %s -- %s kernel profile\n" % (RND[1:].lstrip("0"), name.replace("_", " "))]
-out.append("Produced by `bash scripts/profile_train.sh %s` on an MI355X box: (1) plain `python bench.py --workload %s --steps 10 --warmup 3`, "
-           "(2) `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --workload %s --steps 10 --warmup 3 --no-cpu-baseline`, "
-           "(3)+(4) `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE`, each in its own run, `-- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-distance --no-vit --no-epoch` "
-           "(passes 2-5 profile the train step alone; pass 1 is the driver's default command, with the distance / vit / epoch sub-records); "
+out.append("Produced by `bash scripts/profile_train.sh %s` on an MI355X box: (1) `python bench.py --full --workload %s --steps 10 --warmup 3`, "
+           "(2) `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --workload %s --steps 10 --warmup 3 --no-cpu-baseline`, "
+           "(3)+(4) `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE`, each in its own run, `-- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-distance --no-vit --no-epoch` "
+           "(passes 2-5 profile the train step alone; pass 1 is the full line, with the distance / vit / epoch sub-records); "
            "summary by `scripts/make_profile_md.py`.\n" % (wl, wl, wl))
 out.append("Bench line of run (1) (unprofiled):\n\n```\n%s\n```\n" % bench_full)
 out.append("Bench line of run (2) (under rocprofv3):\n\n```\n%s\n```\n" % bench)
