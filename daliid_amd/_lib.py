@@ -42,6 +42,7 @@ _SIGNATURES = {
     "dali_rank_shard_matches": [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3,
     "dali_rank_shard_bins": [c_void_p] * 7 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p],
     "dali_rank_shard_finish": [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6,
+    "dali_rerank": [c_void_p] * 5 + [c_int] * 4 + [ctypes.c_double, c_void_p],
     "dali_conv2d_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_int, c_void_p],
     "dali_conv2d_bn_act": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_int],
     "dali_stem_fused_supported": [c_int, c_int, c_int],

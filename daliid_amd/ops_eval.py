@@ -268,3 +268,30 @@ def pairdist_blend(distmat, q, g, mags_prev=None, mags=None, precision="bf16x3",
                                                _PREC[precision], int(bool(normalize)), _lib.ptr(m[0]), _lib.ptr(m[1]), _lib.ptr(m[2]),
                                                _lib.ptr(m[3]), _lib.ptr(distmat, f32, "distmat")), "dali_pairdist_blend")
     return distmat
+
+
+RERANK_K1_MAX = 63        # k1 + 1 <= 64: one neighbour per lane of the selection wave (csrc/rerank.hip)
+
+
+def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3):
+    """k-reciprocal re-ranking with torchreid.utils.re_ranking's signature (validateModels.py:49-53; definition: include/daliid.h,
+    dali_rerank).  CUDA tensors in -> CUDA fp32 [nq, ng] out, enqueued on the current stream.  numpy arrays or CPU tensors are copied
+    to the current device and the result comes back as numpy, as torchreid returns it."""
+    on_host = not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (q_g_dist, q_q_dist, g_g_dist))
+    dev = torch.device("cuda", torch.cuda.current_device()) if on_host else q_g_dist.device
+
+    def prep(t):
+        t = torch.as_tensor(np.asarray(t)) if not isinstance(t, torch.Tensor) else t
+        return t.to(dev, dtype=torch.float32).contiguous()
+
+    q_g, q_q, g_g = prep(q_g_dist), prep(q_q_dist), prep(g_g_dist)
+    if q_g.dim() != 2 or q_q.dim() != 2 or g_g.dim() != 2:
+        raise ValueError("re_ranking: the three distance blocks must be 2-D")
+    nq, ng = q_g.shape
+    if tuple(q_q.shape) != (nq, nq) or tuple(g_g.shape) != (ng, ng):
+        raise ValueError("re_ranking: shapes q_g %s, q_q %s, g_g %s do not fit together" % (tuple(q_g.shape), tuple(q_q.shape), tuple(g_g.shape)))
+    out = torch.empty(nq, ng, device=dev, dtype=torch.float32)
+    _lib.check(_lib.lib().dali_rerank(_lib.ctx(dev), _lib.stream_ptr(), _lib.ptr(q_g, torch.float32, "q_g"), _lib.ptr(q_q, torch.float32, "q_q"),
+                                       _lib.ptr(g_g, torch.float32, "g_g"), nq, ng, int(k1), int(k2), float(lambda_value), _lib.ptr(out)),
+               "dali_rerank")
+    return out.cpu().numpy() if on_host else out

@@ -25,6 +25,13 @@ class validateModels:
         queries_fvs = extractFeatures(queries, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
         gallery_fvs = extractFeatures(gallery, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
         distmat = self.distance(queries_fvs, gallery_fvs)
+        if getattr(self, "rerank", False):
+            # validateModels.py:49-53 (commented out in the reference): every block is the same cosine distance, so the three agree
+            print('Applying person re-ranking ...')
+            distmat_qq = self.distance(queries_fvs, queries_fvs)
+            distmat_gg = self.distance(gallery_fvs, gallery_fvs)
+            distmat = ops_eval.re_ranking(distmat, distmat_qq, distmat_gg)
+            del distmat_qq, distmat_gg          # g_g is ng^2 floats (1 GB at Market size): gone before the ranking
         del queries_fvs, gallery_fvs
         cmc, mAP = self.calculateMetrics(distmat, queries, gallery)
         return cmc, mAP, (distmat.cpu() if self.distmat_on_cpu else distmat)
@@ -40,6 +47,9 @@ class validateModels:
         between ranks is refused here, collectively, before any feature is extracted."""
         import torch.distributed as dist
         from . import _lib, parallel
+        if getattr(self, "rerank", False):   # raised on every rank before any collective
+            raise NotImplementedError("validate_sharded: re-ranking needs every gallery row's neighbourhood on one device; "
+                                      "use validate() for rerank=True")
         world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         rank = dist.get_rank(process_group) if dist.is_initialized() else 0
         model.eval()

@@ -133,6 +133,24 @@ int dali_rank_shard_bins(dali_ctx* ctx, void* stream, const float* dist_shard, c
 int dali_rank_shard_finish(dali_ctx* ctx, void* stream, const int32_t* bins, const int32_t* counts_all, int world, int nq, int bins_cap,
                            int max_rank, float* cmc, float* mAP, double* map64, int32_t* num_valid, float* ap, int32_t* first_rank);
 
+/* k-reciprocal re-ranking (Zhong et al., CVPR 2017; torchreid.utils.re_ranking(q_g_dist, q_q_dist, g_g_dist, k1, k2, lambda_value)),
+ * the block validateModels.py:49-53 leaves commented out.  Inputs: the fp32 distance blocks q_g [nq][ng], q_q [nq][nq], g_g [ng][ng]
+ * (row-major, device); output: out [nq][ng] fp32 (device).  Enqueued on `stream`, nothing synchronises; scratch in the workspace.
+ * With N = nq + ng and A = [[q_q, q_g], [q_g^T, g_g]]^2 (elementwise, fp32):
+ *   C = (A / max(A, axis=0))^T                  row i of C = column i of A over its maximum (IEEE fp32 division; the transposed
+ *                                               reading is followed literally: the blocks need not be bitwise symmetric)
+ *   R[i] = stable argsort of row i of C         exact ties by ascending index; only R[i][:k1+1] is used
+ *   KR(i) = {f in R[i][:k1+1] : i in R[f][:k1+1]},  KRh(c) the same with h + 1 neighbours, h = round_half_even(k1 / 2)
+ *   E(i) = sorted union of KR(i) and every KRh(c), c in KR(i), with |KRh(c) & KR(i)| > (2.0/3.0) * |KRh(c)| (in double)
+ *   V[i, e] = w_e / sum(w), w_e = expf(-C[i, e]) for e in E(i) (sum accumulated in fp64, rounded to fp32 once), 0 elsewhere
+ *   k2 != 1: V[i] <- mean of V[R[i][:k2]] (fp32, summed in R order, divided by k2), from the un-expanded V
+ *   t = sum_c min(V[i,c], V[j,c]) over ascending c (fp32);  out[i][j-nq] = (1 - t / (2 - t)) * (float)(1 - lambda) + C[i, j] * (float)lambda
+ * Preconditions: nq, ng >= 1, 1 <= k1, k1 + 1 <= N, 1 <= k2 <= k1 + 1, 0 <= lambda_value <= 1 (DALI_ERR_INVALID otherwise);
+ * k1 <= 63 and ng * (row capacity of V) < 2^31 (DALI_ERR_LIMIT otherwise), where the row capacity is min(N, (k1+1)(h+2)), times k2
+ * when k2 != 1.  Workspace: about (2 N + 2 ng) * capacity * 4 bytes.  Bitwise identical results run to run. */
+int dali_rerank(dali_ctx* ctx, void* stream, const float* q_g, const float* q_q, const float* g_g, int nq, int ng, int k1, int k2,
+                double lambda_value, float* out);
+
 /* ---- training path: Encoders.ResNet50ReID trunk (Encoders.py:330-339) ----------------------------- *
  * Single-op entry points (the parity tests call these; the net plan below chains the same kernels).
  * Layouts: activations NHWC bf16; forward weights [cout][r][s][cin] bf16; dgrad weights
