@@ -386,17 +386,15 @@ __global__ __launch_bounds__(256) void bnlin_row_kernel(const uint16_t* __restri
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------
-// k-steps of loads in flight per wave: as many as K allows (K % (64 D) == 0), at most 8 (DALI_BNLIN_DEPTH caps it: A/B)
-static int bnlin_depth_tn(int K) {         // TN form: 8-deep steps, K % (32 D) == 0; D = 2 is the round-4 kernel
-    const int cap = DALI_ENV_INT("DALI_BNLIN_DEPTH_TN", 4);
+// k-steps of loads in flight per wave: as many as K allows (K % (64 D) == 0), at most 8
+static int bnlin_depth_tn(int K) {         // TN form: 8-deep steps, K % (32 D) == 0, at most 4; D = 2 is the round-4 kernel
     int d = 1;
-    while (d < 8 && 2 * d <= cap && K % (64 * d) == 0) d *= 2;
+    while (d < 4 && K % (64 * d) == 0) d *= 2;
     return d;
 }
 static int bnlin_depth(int K) {
-    const int cap = DALI_ENV_INT("DALI_BNLIN_DEPTH", 8);
     int d = 1;
-    while (d < 8 && 2 * d <= cap && K % (128 * d) == 0) d *= 2;
+    while (d < 8 && K % (128 * d) == 0) d *= 2;
     return d;
 }
 // Wt = W^T [w][C] bf16 (the plain data-gradient image of the convolution); ut [w][C] fp32 and dot ((w/32) * C * 12 bytes: per-tile fp32 quadratic-form and fp64 mean partials) are outputs the
@@ -406,19 +404,15 @@ int launch_bnlin_stats(hipStream_t st, const uint16_t* W, const uint16_t* Wt, co
                        float* mean, float* invstd) {
     if (w % 32 != 0 || C % 32 != 0) { set_error("bnlin: width %d and channels %d must be multiples of 32", w, C); return DALI_ERR_INVALID; }
     // Ut[k'][c] = sum_k G[k'][k] W[c][k]  (G symmetric); dot[tile][c] = sum_{k' in tile} Ut[k'][c] Wt[k'][c]
-    if (C / 32 <= RF_GROUPS && DALI_ENV_INT("DALI_BNLIN_FUSED_FINISH", 1) != 0) {
+    if (C / 32 <= RF_GROUPS) {
         // the statistics finish in the product's own launch, by the last workgroup of every 32-channel column block (see BnlinFin)
         unsigned int* ctr = nullptr;
         if (int rc = rf_counter_base(&ctr)) return rc;
         ctr += (size_t)rf_next_slot() * RF_GROUPS;
         const BnlinFin fin{m2, count, gamma, beta, rm, rv, momentum, eps, scale, shift, mean, invstd, ctr, w, reinterpret_cast<double*>(dot + (size_t)(w / 32) * C)};
-#define BL_FWD_FIN(DEPTH, TNF) hipLaunchKernelGGL((bnlin_nt_gemm_kernel<float, false, false, true, DEPTH, TNF>), dim3(C / 32, w / 32), dim3(256), 0, st, gram, w, TNF ? Wt : W, TNF ? C : w, \
-                                                  (const float*)nullptr, w, ut, (uint16_t*)nullptr, C, Wt, C, dot, C, (const float*)nullptr, (float*)nullptr, fin)
-        if (DALI_ENV_INT("DALI_BNLIN_FWD_NT", 0)) {
-            switch (bnlin_depth(w)) { case 8: BL_FWD_FIN(8, false); break; case 4: BL_FWD_FIN(4, false); break; case 2: BL_FWD_FIN(2, false); break; default: BL_FWD_FIN(1, false); }
-        } else {
-            switch (bnlin_depth_tn(w)) { case 8: BL_FWD_FIN(8, true); break; case 4: BL_FWD_FIN(4, true); break; case 2: BL_FWD_FIN(2, true); break; default: BL_FWD_FIN(1, true); }
-        }
+#define BL_FWD_FIN(DEPTH) hipLaunchKernelGGL((bnlin_nt_gemm_kernel<float, false, false, true, DEPTH, true>), dim3(C / 32, w / 32), dim3(256), 0, st, gram, w, Wt, C, \
+                                             (const float*)nullptr, w, ut, (uint16_t*)nullptr, C, Wt, C, dot, C, (const float*)nullptr, (float*)nullptr, fin)
+        switch (bnlin_depth_tn(w)) { case 4: BL_FWD_FIN(4); break; case 2: BL_FWD_FIN(2); break; default: BL_FWD_FIN(1); }
 #undef BL_FWD_FIN
         DALI_LAUNCH_CHECK();
         return DALI_OK;

@@ -1853,8 +1853,7 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
     const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
     const int m0 = tm * 128, ci0 = tn * 64;
     if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12] = __builtin_amdgcn_s_memrealtime();
-    const bool m_active = m0 + wm * 64 < a.Cm && a.ablate != 2;          // Cout = 64: the upper half of the co tile is padding, its waves only help with the DMA
-    const bool feed = a.ablate != 1;
+    const bool m_active = m0 + wm * 64 < a.Cm;          // Cout = 64: the upper half of the co tile is padding, its waves only help with the DMA
     const GatherGeom g = a.g;
     const int W = g.Wout, H = g.Hout, Cin = g.Ck, lw = g.lw, lhw = g.lhw;
     const int RW = 32 >> lw, HC = W + 2, HP = (RW + 2) * HC;
@@ -1941,7 +1940,7 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
         if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
         int st_cur = 0, st_fill = AHEAD % NSTAGE;
         for (int kt = 0; kt < ksteps; ++kt) {
-            if (kt + AHEAD < ksteps && feed) issue(kt + AHEAD, st_fill);
+            if (kt + AHEAD < ksteps) issue(kt + AHEAD, st_fill);
             const uint16_t* sa = smem + st_cur * W3_STAGE;
             const uint16_t* sb = sa + W3_A_ELEMS;
             if (m_active) {
@@ -2543,11 +2542,7 @@ namespace dali {
 // Tile configuration per problem (measured on MI355X, scripts/bench_convs.py): 64x256 for <= 64 output channels;
 // 256x256 / 16 waves / 4-deep ring when both K and Cm are large (operand traffic per FLOP halves: +25..36 % on the
 // layer4 3x3); 128x256 / 8 waves for Cm = 128..256 with K >= 1024; 128x128 / 4 waves otherwise (small K: prologue-bound).
-enum ConvCfg { CONV_NARROW = 0, CONV_128 = 1, CONV_128x256 = 2, CONV_256x256 = 3, CONV_256x128 = 4, CONV_256x320 = 5 };
-static int conv_cfg_override() { return DALI_ENV_INT("DALI_CONV_CFG", -1); }
-// DALI_CONV_K64 (A/B aid): 0 = k-tile 32 kernels only, 2 (default) = k-tile 64 kernels on the long-K layers, 6 = the same with
-// the unspecialised 128 x 256 kernel, 4 / 3 = k-tile 64 wherever Ck % 64 == 0, the 128 x 128 tile with a 2- / 3-stage ring
-static int conv_k64_mode() { return DALI_ENV_INT("DALI_CONV_K64", 2); }
+enum ConvCfg { CONV_NARROW = 0, CONV_128 = 1, CONV_128x256 = 2, CONV_256x256 = 3, CONV_256x320 = 5 };
 // 256 channels x 320 pixels (k-tile 64, 16 waves of 64 x 80): one workgroup per CU means a launch runs in rounds of 256 tiles, and
 // ViT's 25216 x 768 outputs are 297 tiles of 256 x 256 = 2 rounds for 1.16 rounds of work (measured: 145 us, 144 of 256 CUs busy on
 // average) but 237 tiles of 256 x 320 = one round of 1.25 x the work.  Taken where rounds x tile size says so by a margin; only for
@@ -2561,12 +2556,6 @@ static bool conv_prefers_320(int Cm, int P, int K) {
 }
 int conv_pick_cfg(int Cm, int P, int K) {
     if (Cm <= 64) return CONV_NARROW;
-    const int ov = conv_cfg_override();
-    if (ov == 0 || ov == 1) return CONV_128;
-    if (ov == 4) return Cm >= 256 ? CONV_256x256 : CONV_128;
-    if (ov == 6) return Cm >= 256 ? CONV_128x256 : CONV_128;
-    if (ov == 7) return Cm >= 256 ? CONV_256x128 : CONV_128;
-    if (ov == 9) return Cm >= 128 ? CONV_128x256 : CONV_128;
     if (K >= 1024 && P >= 16384) {
         if (Cm >= 512) return CONV_256x256;              // (the 128 x 256 tile's finer rounds do not pay for ViT's 297-tile launches: +0.7 ms per step)
         if (Cm >= 128) return CONV_128x256;             // Cm = 128 (layer2 3x3): -18 % against 128 x 128
@@ -2580,7 +2569,7 @@ int conv_pick_cfg(int Cm, int P, int K) {
 }
 int igemm_conv_stat_tiles(int Cm, int P, int K) {
     const int c = conv_pick_cfg(Cm, P, K);
-    return (c == CONV_128 || c == CONV_256x128) ? (P + 127) / 128 : (P + 255) / 256;
+    return c == CONV_128 ? (P + 127) / 128 : (P + 255) / 256;
 }
 
 
@@ -2649,7 +2638,7 @@ int launch_igemm_conv(hipStream_t st, const IGemmArgs& a) {
         const bool all_have = nr[0] && nr[1] && ns[0] && ns[1];
         // every class has taps (3x3): ONE launch, the workgroups of the four classes interleaved (parity_block); the four separate launches
         // of a quarter of the pixels each ran one after the other with a short-K tail each (layer2 / layer3 conv2: 96 -> 72 us, 85 -> 53 us)
-        if (all_have && !narrow_cm(a.Cm) && (a.Cm & 7) == 0 && conv_cfg_override() < 0) {
+        if (all_have && !narrow_cm(a.Cm) && (a.Cm & 7) == 0) {
             IGemmArgs s = args;
             s.g.sub = 2; s.g.oph = s.g.opw = 0; s.g.Hfull = g.Hout; s.g.Wfull = g.Wout;
             s.g.Hout = g.Hout / 2; s.g.Wout = g.Wout / 2; s.P = a.P / 4;
@@ -2691,11 +2680,11 @@ bool conv_cat_act_supported(int Cm, int c1, int c2, int P, int parts) {
     const int K = parts * (c1 + c2);
     if (parts != 1 && parts != 2) return false;
     if ((c1 & 63) || (c2 & 63) || (Cm % 128) || (long long)P * Cm * 2 >= 0x7ff00000ll || (long long)P * K * 2 >= 0x7ff00000ll) return false;
-    if (K <= DALI_ENV_INT("DALI_CONV_PERSIST_KMAX", 256) && DALI_ENV_INT("DALI_CONV_PERSIST", 1) != 0) {
+    if (K <= F1_KMAX) {
         const int n_cus = f1_cu_count(), tiles_m = Cm / 128, tiles_n = (P + 127) / 128;
         return n_cus > 0 && (long long)tiles_m * tiles_n >= 2ll * n_cus && (n_cus / 8) % tiles_m == 0;
     }
-    return parts == 1 && K >= 1024 && Cm >= 512 && P >= 16384 && conv_k64_mode() == 2 && conv_cfg_override() < 0;
+    return parts == 1 && K >= 1024 && Cm >= 512 && P >= 16384;
 }
 
 static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
@@ -2710,10 +2699,9 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
     const int K = a.g.nr * a.g.ns * a.g.Ck;               // reduction length actually visited
     int cfg = conv_pick_cfg(a.Cm, a.P, K);
     const bool fused_out = a.out_scale || a.out_shift || a.out_relu || a.bits_out || a.out_mask || a.res_scale;
-    if (!in_bn && dma_ok && !a.stats && !fused_out && !a.g.sub && a.g.Ck % 64 == 0 && (a.Cm & 7) == 0 && conv_k64_mode() == 2 && conv_cfg_override() < 0 &&
-        conv_prefers_320(a.Cm, a.P, K))
+    if (!in_bn && dma_ok && !a.stats && !fused_out && !a.g.sub && a.g.Ck % 64 == 0 && (a.Cm & 7) == 0 && conv_prefers_320(a.Cm, a.P, K))
         cfg = CONV_256x320;
-    if (!dma_ok && !in_bn && a.stats && (cfg == CONV_128x256 || cfg == CONV_256x256 || cfg == CONV_256x128)) {
+    if (!dma_ok && !in_bn && a.stats && (cfg == CONV_128x256 || cfg == CONV_256x256)) {
         set_error("conv: tensors beyond 2 GiB are not supported together with the BatchNorm statistics epilogue");
         return DALI_ERR_LIMIT;
     }
@@ -2728,15 +2716,15 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
     // co-resident workgroups overlap their epilogues better (measured per layer: 256 x 256 -12..-15 %; 128 x 256 wave-specialised
     // -18..-26 % on the 3x3 layers, -10 % on the K = 1024 1x1 layers; K = 512 layers +12..+20 % with either k-tile-64 kernel)
     const bool lin = a.act != 0 || a.O2 != nullptr || a.dact_pre != nullptr || a.row_scale != nullptr;      // linear-layer epilogue extras: the LIN kernel instantiations
-    int k64 = (!in_bn && dma_ok && !narrow && a.g.Ck % 64 == 0) ? conv_k64_mode() : 0;
-    int narrow_k64 = (!in_bn && dma_ok && narrow && a.g.Ck % 64 == 0 && K >= 512) ? conv_k64_mode() : 0;   // layer1's 3x3 (Cin = 64: a pixel is one line)
+    bool k64 = !in_bn && dma_ok && !narrow && a.g.Ck % 64 == 0;
+    bool narrow_k64 = !in_bn && dma_ok && narrow && a.g.Ck % 64 == 0 && K >= 512;   // layer1's 3x3 (Cin = 64: a pixel is one line)
     if (a.X2) {                                         // two operand tensors (IGemmArgs::X2): the SRC2 instantiations of the 128 x 128 / 64 x 256 LDS-DMA kernel
         // a fused output stage beside X2: shift (+ scale) and ReLU only (the inference forward's conv3 + downsample branch as one GEMM), on the two
         // kernels that have that instantiation: the persistent streaming kernel (K <= 256) and the 256 x 256 k-tile-64 kernel
         const bool fo_simple = !a.bits_out && !a.out_mask && !a.res_scale && !a.Res && (a.out_scale || a.out_shift || a.out_relu);
         const bool fo = (a.out_scale || a.out_shift || a.out_relu || a.bits_out || a.out_mask || a.res_scale) && !fo_simple;
         const int xr = a.x_rep > 1 ? a.x_rep : 1;
-        if (xr > 1 && !(fo_simple && a.g.Ck % xr == 0 && conv_cat_act_supported(a.Cm, a.Ck1, a.g.Ck / xr - a.Ck1, a.P, xr) && a.g.Ck <= DALI_ENV_INT("DALI_CONV_PERSIST_KMAX", 256))) {
+        if (xr > 1 && !(fo_simple && a.g.Ck % xr == 0 && conv_cat_act_supported(a.Cm, a.Ck1, a.g.Ck / xr - a.Ck1, a.P, xr) && a.g.Ck <= F1_KMAX)) {
             set_error("conv: split weight images (x_rep = %d) are served by the persistent streaming kernel only (K <= 256, >= 2 tiles per CU)", xr);
             return DALI_ERR_INVALID;
         }
@@ -2749,14 +2737,14 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
             set_error("conv: a second operand tensor needs a plain 1x1 / stride 1 problem with both channel counts multiples of 32");
             return DALI_ERR_INVALID;
         }
-        narrow_k64 = 0;
-        if ((a.Ck1 & 63) || ((a.g.Ck / xr - a.Ck1) & 63)) k64 = 0;
-        if (!(k64 && (cfg == CONV_256x256 || cfg == CONV_128x256)) && !narrow) { cfg = CONV_128; k64 = 0; }
+        narrow_k64 = false;
+        if ((a.Ck1 & 63) || ((a.g.Ck / xr - a.Ck1) & 63)) k64 = false;
+        if (!(k64 && (cfg == CONV_256x256 || cfg == CONV_128x256)) && !narrow) { cfg = CONV_128; k64 = false; }
     }
-    if ((k64 == 2 || k64 == 6) && cfg != CONV_256x320 && !((K >= 1024 && (cfg == CONV_256x256 || cfg == CONV_128x256)) || (K >= 768 && cfg == CONV_256x256))) k64 = 0;
+    if (k64 && cfg != CONV_256x320 && !((K >= 1024 && (cfg == CONV_256x256 || cfg == CONV_128x256)) || (K >= 768 && cfg == CONV_256x256))) k64 = false;
     // a second operand tensor is only read by the SRC2 instantiations: the two k-tile-64 kernels above (k64 still set) or, for every other
     // choice -- including a k64 that the K gate has just cleared -- the 128 x 128 / 64 x 256 LDS-DMA kernel
-    if (a.X2 && !narrow && !(k64 && (cfg == CONV_256x256 || cfg == CONV_128x256))) { cfg = CONV_128; k64 = 0; }
+    if (a.X2 && !narrow && !(k64 && (cfg == CONV_256x256 || cfg == CONV_128x256))) { cfg = CONV_128; k64 = false; }
     // fused output stage (IGemmArgs::out_scale ... out_mask): its own instantiations of three kernels, so that the convolutions' hot
     // instantiations compile none of it (code that is never executed still cost their register allocation 0.4-0.8 ms per step)
     const bool fused = a.out_scale || a.out_shift || a.out_relu || a.bits_out || a.out_mask || a.res_scale;
@@ -2775,8 +2763,8 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
         // 1x1 conv3 forwards and the masked conv1 data gradients, Cm >= 256 and K <= 512)
         // short-K 1x1 with a residual / mask stream: the persistent streaming kernel (fused1x1.h).  K <= 256: at K = 512 (layer4) its four ring
         // producers cannot issue the 32 DMA pieces of a k-step as fast as the consumers multiply it (141 against 125 us; the block is capped at 16 waves)
-        if (DALI_ENV_INT("DALI_CONV_PERSIST", 1) != 0 && a.g.R == 1 && a.g.S == 1 && a.g.stride == 1 && a.g.pad == 0 && !a.g.sub && !a.res_mask &&
-            (a.Cm % F1_TM) == 0 && (a.g.Ck & 63) == 0 && a.g.Ck <= DALI_ENV_INT("DALI_CONV_PERSIST_KMAX", 256) && a.g.pix_pitch == a.g.Ck && a.g.row_pitch == a.g.Win * a.g.Ck &&
+        if (a.g.R == 1 && a.g.S == 1 && a.g.stride == 1 && a.g.pad == 0 && !a.g.sub && !a.res_mask &&
+            (a.Cm % F1_TM) == 0 && (a.g.Ck & 63) == 0 && a.g.Ck <= F1_KMAX && a.g.pix_pitch == a.g.Ck && a.g.row_pitch == a.g.Win * a.g.Ck &&
             a.g.img_pitch == (long long)a.g.Hin * a.g.Win * a.g.Ck && a.g.Hin == a.g.Hout && a.g.Win == a.g.Wout &&
             (long long)a.P * a.Cm * 2 < 0x7ff00000ll && (a.Res || a.out_mask || a.bits_out || a.X2)) {
             const int n_cus = f1_cu_count();
@@ -2787,23 +2775,21 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
 #define DALI_F1_LAUNCH(RES, OM, BITS)                                                                                                                     \
     do {                                                                                                                                                  \
         DALI_ONCE_PER_DEVICE({                                                                                                                            \
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 2, true, RES, OM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 2, true, 128))); \
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 1, true, RES, OM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 1, true, 256))); \
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 1, false, RES, OM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 1, false, 0))); \
+            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 2, RES, OM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 2, 128))); \
+            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 1, RES, OM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 1, 256))); \
         });                                                                                                                                               \
         const int kk = a.g.Ck;                                                                                                                            \
-        if (kk <= 128) hipLaunchKernelGGL((fused1x1_persist_kernel<3, 2, true, RES, OM, BITS>), dim3(n_cus), f1_block, f1_lds_bytes(3, 2, true, kk), st, args, tiles_m, tiles_n); \
-        else if (kk <= 256) hipLaunchKernelGGL((fused1x1_persist_kernel<3, 1, true, RES, OM, BITS>), dim3(n_cus), f1_block, f1_lds_bytes(3, 1, true, kk), st, args, tiles_m, tiles_n); \
-        else hipLaunchKernelGGL((fused1x1_persist_kernel<3, 1, false, RES, OM, BITS>), dim3(n_cus), f1_block, f1_lds_bytes(3, 1, false, kk), st, args, tiles_m, tiles_n); \
+        if (kk <= 128) hipLaunchKernelGGL((fused1x1_persist_kernel<3, 2, RES, OM, BITS>), dim3(n_cus), f1_block, f1_lds_bytes(3, 2, kk), st, args, tiles_m, tiles_n); \
+        else hipLaunchKernelGGL((fused1x1_persist_kernel<3, 1, RES, OM, BITS>), dim3(n_cus), f1_block, f1_lds_bytes(3, 1, kk), st, args, tiles_m, tiles_n); \
     } while (0)
                 const bool f_res = a.Res != nullptr, f_om = a.out_mask != nullptr, f_bits = a.bits_out != nullptr;
                 if (a.X2) {                                                               // [X | X2] against one weight image, shift + ReLU (inference)
                     DALI_ONCE_PER_DEVICE({
-                        DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 2, true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 2, true, 128)));
-                        DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 1, true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 1, true, 256)));
+                        DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 2, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 2, 128)));
+                        DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 1, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 1, 256)));
                     });
-                    if (a.g.Ck <= 128) hipLaunchKernelGGL((fused1x1_persist_kernel<3, 2, true, false, false, false, true>), dim3(n_cus), f1_block, f1_lds_bytes(3, 2, true, a.g.Ck), st, args, tiles_m, tiles_n);
-                    else hipLaunchKernelGGL((fused1x1_persist_kernel<3, 1, true, false, false, false, true>), dim3(n_cus), f1_block, f1_lds_bytes(3, 1, true, a.g.Ck), st, args, tiles_m, tiles_n);
+                    if (a.g.Ck <= 128) hipLaunchKernelGGL((fused1x1_persist_kernel<3, 2, false, false, false, true>), dim3(n_cus), f1_block, f1_lds_bytes(3, 2, a.g.Ck), st, args, tiles_m, tiles_n);
+                    else hipLaunchKernelGGL((fused1x1_persist_kernel<3, 1, false, false, false, true>), dim3(n_cus), f1_block, f1_lds_bytes(3, 1, a.g.Ck), st, args, tiles_m, tiles_n);
                 } else if (f_res && !f_om && f_bits) DALI_F1_LAUNCH(true, false, true);          // conv3 forward of the train step
                 else if (f_res && !f_om && !f_bits) DALI_F1_LAUNCH(true, false, false);   // conv3 forward, inference
                 else if (f_res && f_om && !f_bits) DALI_F1_LAUNCH(true, true, false);     // conv1 data gradient + identity gradient, masked
@@ -2816,7 +2802,7 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
                 return DALI_OK;
             }
         }
-        const bool halo_ok = narrow_k64 == 2 && a.Cm == 64 && a.g.Ck == 64 && a.g.R == 3 && a.g.S == 3 && a.g.stride == 1 && a.g.pad == 1 && !a.g.sub &&
+        const bool halo_ok = narrow_k64 && a.Cm == 64 && a.g.Ck == 64 && a.g.R == 3 && a.g.S == 3 && a.g.stride == 1 && a.g.pad == 1 && !a.g.sub &&
                              (a.g.Wout == 16 || a.g.Wout == 32) && args.g.lhw >= 8 && a.g.Hin == a.g.Hout && a.g.Win == a.g.Wout && a.g.pix_pitch == 64 &&
                              a.g.row_pitch == a.g.Win * 64 && a.g.img_pitch == (long long)a.g.Hin * a.g.Win * 64 && a.P % 256 == 0;
         const bool lean = !a.Res && !a.out_mask && !a.bits_out && !a.res_mask && !a.res_scale && !a.X2;      // scale / shift / bias / ReLU only: the EPI = 5 instantiations
@@ -2829,7 +2815,7 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
             using Cfg = GemmCfg<64, 256, 1, 1, 1>;
             const int tiles_m = (a.Cm + 63) / 64, tiles_n = (a.P + 255) / 256;
             hipLaunchKernelGGL((igemm_conv_dma_kernel<64, 256, 3, 5>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        } else if (lean && k64 && cfg == CONV_128x256 && k64 != 6 && !a.g.sub) {
+        } else if (lean && k64 && cfg == CONV_128x256 && !a.g.sub) {
             const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 255) / 256;
             const int lds = (128 + 256) * 64 * 2 * 3;
             DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
@@ -2854,7 +2840,7 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
             const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 127) / 128;
             hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 3, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
         }
-    } else if (a.g.sub && !in_bn && dma_ok && !narrow && !lin && (a.Cm & 7) == 0 && conv_cfg_override() < 0) {
+    } else if (a.g.sub && !in_bn && dma_ok && !narrow && !lin && (a.Cm & 7) == 0) {
         // a parity class of a stride-2 data gradient: the staged store with scattered pixel rows (EPI = 4)
         DALI_ONCE_PER_DEVICE({
             DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (256 + 256) * 64 * 2 * 2));
@@ -2899,25 +2885,15 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
         const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 255) / 256;
         const int lds = (128 + 256) * 64 * 2 * 3;
         DALI_ONCE_PER_DEVICE({
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<2, 4, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64s_kernel<2, 4, 8, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         });
         if (a.X2) {
             DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
             hipLaunchKernelGGL((igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 0, true>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-        } else if (k64 == 6) hipLaunchKernelGGL((igemm_conv_k64_kernel<2, 4, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(512), lds, st, args, tiles_m, tiles_n);
-        else if (lin) hipLaunchKernelGGL((igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 1>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
+        } else if (lin) hipLaunchKernelGGL((igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 1>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
         else hipLaunchKernelGGL((igemm_conv_k64s_kernel<2, 4, 8, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-    } else if (k64 && cfg == CONV_128) {
-        const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 127) / 128;
-        DALI_ONCE_PER_DEVICE({
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 2 * 2));
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<2, 2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 2 * 3));
-        });
-        if (k64 == 3) hipLaunchKernelGGL((igemm_conv_k64_kernel<2, 2, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(256), 256 * 64 * 2 * 3, st, args, tiles_m, tiles_n);
-        else hipLaunchKernelGGL((igemm_conv_k64_kernel<2, 2, 2>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(256), 256 * 64 * 2 * 2, st, args, tiles_m, tiles_n);
-    } else if (narrow_k64 == 2 && a.Cm == 64 && a.g.Ck == 64 && a.g.R == 3 && a.g.S == 3 && a.g.stride == 1 && a.g.pad == 1 && !a.g.sub && !lin &&
+    } else if (narrow_k64 && a.Cm == 64 && a.g.Ck == 64 && a.g.R == 3 && a.g.S == 3 && a.g.stride == 1 && a.g.pad == 1 && !a.g.sub && !lin &&
                (a.g.Wout == 16 || a.g.Wout == 32) && args.g.lhw >= 8 && a.g.Hin == a.g.Hout && a.g.Win == a.g.Wout && a.g.pix_pitch == 64 &&
                a.g.row_pitch == a.g.Win * 64 && a.g.img_pitch == (long long)a.g.Hin * a.g.Win * 64 && a.P % 256 == 0) {
         // layer1's 3x3 (64 -> 64): the halo patch of a 256-pixel tile fetched once, taps read it at shifted pixels (igemm_conv_halo64_kernel)
@@ -2925,7 +2901,7 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
         DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_halo64_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
         const int tiles_n = a.P / 256;
         hipLaunchKernelGGL((igemm_conv_halo64_kernel<3>), dim3(tiles_n), dim3(512), lds, st, args, tiles_n);
-    } else if (narrow_k64 == 2) {
+    } else if (narrow_k64) {
         // layer1's 3x3 (Cm = Cin = 64, K = 576): k-tile 64 = one full line per pixel and tap, 4 MFMA waves + 4 DMA waves, 2-stage ring,
         // two workgroups per CU: 94 -> 77 us forward, 90 -> 73 us data gradient (unspecialised k-tile 64: 84 / 79; 3-stage ring, one
         // workgroup per CU: 122 / 118)
@@ -2947,11 +2923,6 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
         const int lds = (256 + 256) * 32 * 2 * 4;
         DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_wg_kernel<4, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
         hipLaunchKernelGGL((igemm_conv_wg_kernel<4, 4, 4>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-    } else if (!in_bn && dma_ok && cfg == CONV_256x128) {
-        const int tiles_m = (a.Cm + 255) / 256, tiles_n = (a.P + 127) / 128;
-        const int lds = (256 + 128) * 32 * 2 * 3;
-        DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_wg_kernel<4, 2, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-        hipLaunchKernelGGL((igemm_conv_wg_kernel<4, 2, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(512), lds, st, args, tiles_m, tiles_n);
     } else if (!in_bn && dma_ok && cfg == CONV_128x256) {
         const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 255) / 256;
         const int lds = (128 + 256) * 32 * 2 * 3;
@@ -2967,7 +2938,6 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
         const int grid = xcd_tile_grid(tiles_m, tiles_n);
         if (in_bn) hipLaunchKernelGGL((igemm_conv_kernel<128, 128, true>), dim3(grid), dim3(256), Cfg::LDS_BYTES, st, args, tiles_m, tiles_n);
         else if (dma_ok && a.X2) hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 3, 0, true>), dim3(grid), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        else if (dma_ok && conv_cfg_override() == 0) hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 2>), dim3(grid), dim3(256), Cfg::LDS_BYTES, st, args, tiles_m, tiles_n);
         else if (dma_ok && lin) hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 3, true>), dim3(grid), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
         else if (dma_ok) hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 3>), dim3(grid), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
         else hipLaunchKernelGGL((igemm_conv_kernel<128, 128, false>), dim3(grid), dim3(256), Cfg::LDS_BYTES, st, args, tiles_m, tiles_n);
@@ -2989,18 +2959,15 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
 //  gradients 5.46 -> 4.67 ms -- and at layer4's downsample, 64 tiles: 162 -> 125 us.)
 static bool wgrad_spec(int Cm, int Ntot) { return ((Cm + 127) / 128) * ((Ntot + 255) / 256) <= 100; }
 int wgrad_pick_cfg(int Cm, int Ntot, int taps, int P, int halo_w) {
-    const int ov = DALI_ENV_INT("DALI_WGRAD_CFG", -1);
     // 3 = 3x3 halo kernel (128 co x 64 ci x 9 taps per block)
-    if (ov != 0 && taps == 9 && (halo_w == 8 || halo_w == 16 || halo_w == 32) && Cm % 64 == 0 && (Ntot / 9) % 64 == 0 && P % 32 == 0) return 3;
-    if (ov == 2) return (Ntot >= 256) ? 2 : 0;
-    if (ov >= 0) return (ov == 1 && Cm >= 256 && Ntot >= 256) ? 1 : 0;
+    if (taps == 9 && (halo_w == 8 || halo_w == 16 || halo_w == 32) && Cm % 64 == 0 && (Ntot / 9) % 64 == 0 && P % 32 == 0) return 3;
     if (taps == 7 && Ntot == 224 && P >= 16384) return 2;         // the stem (7 tap rows of 32): one 256-wide n tile, dY read once (187 -> ~155 us)
     return (taps == 1 && Ntot >= 256 && P >= 16384) ? 2 : 0;      // incl. the ViT linears (P = 25216)
 }
 void wgrad_plan(int Cm, int Ntot, int P, int target_blocks, int* splits, int* pix_per_split, size_t* ws_bytes, int taps, int halo_w) {
     const int cfg = wgrad_pick_cfg(Cm, Ntot, taps, P, halo_w);
-    const int TMc = cfg == 1 ? 256 : 128, TNc = cfg == 0 ? 128 : (cfg == 3 ? 9 * 64 : 256);
-    if (cfg == 1 || cfg == 3) target_blocks = 256;  // one 16-wave / 8-wave block per CU
+    const int TMc = 128, TNc = cfg == 0 ? 128 : (cfg == 3 ? 9 * 64 : 256);
+    if (cfg == 3) target_blocks = 256;              // one 8-wave block per CU
     if (cfg == 2) target_blocks = wgrad_spec(Cm, Ntot) ? 256 : 512;     // one 16-wave (specialised) / two 8-wave blocks per CU
     const int tiles = ((Cm + TMc - 1) / TMc) * ((Ntot + TNc - 1) / TNc);
     int sp = (target_blocks + tiles - 1) / tiles;
@@ -3028,7 +2995,6 @@ void wgrad_plan(int Cm, int Ntot, int P, int target_blocks, int* splits, int* pi
 int launch_igemm_wgrad(hipStream_t st, const WGradArgs& a, float* out, int accumulate, float* colsum_out, int colsum_rows) {
     WGradArgs args = a;
     args.stamps = g_conv_stamps;
-    args.ablate = DALI_ENV_INT("DALI_WGRAD_ABLATE", 0);
     args.g.lw = ilog2_exact(a.g.Wout);
     args.g.lhw = ilog2_exact(a.g.Hout * a.g.Wout);
     const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.Ntot + 127) / 128;
@@ -3058,11 +3024,6 @@ int launch_igemm_wgrad(hipStream_t st, const WGradArgs& a, float* out, int accum
         //  conflicts), waves parked at s_waitcnt / barriers 26 % of their cycles: neither the issue order nor the LDS bounds it.)
         const dim3 grid3(((tm3 * tn3 * a.splits + 7) / 8) * 8);
         hipLaunchKernelGGL(igemm_wgrad3x3_kernel<3>, grid3, dim3(512), lds, st, args, tm3, tn3);
-    } else if (!a.in_scale && dma_ok && wcfg == 1) {
-        const int tm2 = (a.Cm + 255) / 256, tn2 = (a.Ntot + 255) / 256;
-        const int lds = 4 * 4 * 32 * 128 * 2;       // 4 stages x 4 images x 8 KiB
-        DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_wg_kernel<4, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-        hipLaunchKernelGGL((igemm_wgrad_wg_kernel<4, 4, 4>), dim3(((tm2 * tn2 * a.splits + 7) / 8) * 8), dim3(1024), lds, st, args, tm2, tn2);
     } else if (!a.in_scale && dma_ok && wcfg == 2) {
         const int tm2 = (a.Cm + 127) / 128, tn2 = (a.Ntot + 255) / 256;
         const int lds = 3 * 3 * 32 * 128 * 2;       // 3 stages x 3 images x 8 KiB

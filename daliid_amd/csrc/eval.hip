@@ -906,9 +906,8 @@ static inline int pair_pitch(int d, bool split) { return split ? 2 * pair_kp(d, 
 
 static int launch_pairdist(int num_cus, hipStream_t st, const uint16_t* g_img, const float* gsq, const uint16_t* q_img, const float* qsq, int nq, int ng,
                            int d, int metric, bool split, float* out, PairBlend blend = PairBlend{nullptr, nullptr, nullptr, nullptr, 0}) {
-    static const bool no_dma = getenv("DALI_PAIRDIST_NODMA") != nullptr;
     const int Kp = pair_kp(d, split), pitch = pair_pitch(d, split);
-    if (!no_dma && (long long)ng * pitch * 2 < 0x7ff00000ll && (long long)nq * pitch * 2 < 0x7ff00000ll) {
+    if ((long long)ng * pitch * 2 < 0x7ff00000ll && (long long)nq * pitch * 2 < 0x7ff00000ll) {
         const int tm2 = (ng + 127) / 128, tn2 = (nq + 255) / 256;
         const int grid2 = xcd_tile_grid(tm2, tn2);
         const int lds = 3 * (128 + 256) * 64 * 2 + 8 * PAIR_STRIP_BYTES;         // 3 stages x 48 KiB + the consumers' store strips = 160 KiB

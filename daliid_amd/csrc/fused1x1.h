@@ -1,7 +1,7 @@
 // fused1x1.h -- persistent streaming kernel for the short-K 1x1 GEMMs that carry the fused output stage (included by conv.hip).
 //
 //   O[p][c] = gate_{out_mask}( relu?( acc[p][c] * out_scale[c] + out_shift[c] + bias[c] + res_scale[c] * Res[p][c] ) ),  bits_out = (O > 0)
-//   acc = X[P][K] W[Cm][K]^T,  K <= 512,  Cm % 128 == 0
+//   acc = X[P][K] W[Cm][K]^T,  K <= F1_KMAX = 256,  Cm % 128 == 0
 //
 // These are conv3 + bn3 + identity + ReLU of every bottleneck (torchvision Bottleneck tail under Encoders.py:336-339), the masked conv1 data
 // gradients of its backward, and in the inference forward the same conv3 with the running-statistics coefficients.  Per 128 x 128 output
@@ -83,28 +83,29 @@ __device__ __forceinline__ void f1_vm_wait_pieces(int n) {
 }
 
 constexpr int F1_TM = 128, F1_TN = 128, F1_NC = 8, F1_NP = 4, F1_NR = 2;
-constexpr int F1_STAGE_ELEMS = (F1_TM + F1_TN) * 64;                  // one k-step of 64 (full 128-byte lines: the L2 -> LDS path retires lines, not bytes): 32 KB
+constexpr int F1_KMAX = 256;                                          // longest K the kernel takes: the whole weight tile, 128 x K, stays in LDS
 constexpr int F1_R_BYTES = F1_TN * F1_TM * 2;                         // residual / result tile: 32 KB
 constexpr int F1_M_BYTES = F1_TN * F1_TM / 8;                         // mask bytes of a tile: 2 KB
 constexpr int F1_C_BYTES = 3 * F1_TM * 4;                             // scale, shift (+ bias), residual scale of the workgroup's channel tile
 // NS ring stages, RB residual buffers: <2, 2> for K <= 128 (the main loop is too short to hide a residual fetch: it is requested a tile ahead),
 // <3, 1> for K >= 256
-// ARES: the workgroup's 128 weight rows (all of K) stay in LDS for the whole launch -- every workgroup keeps ONE channel tile -- and the ring
-// carries the pixel rows only: half the DMA pieces per k-step (the ring producers' issue rate, not the MFMA, set the main beats' length)
-constexpr int f1_lds_bytes(int NS, int RB, bool ARES, int K) {
-    return (ARES ? F1_TM * K * 2 + NS * F1_TN * 64 * 2 : NS * F1_STAGE_ELEMS * 2) + RB * F1_R_BYTES + RB * F1_M_BYTES + F1_C_BYTES;
+// The workgroup's 128 weight rows (all of K) stay in LDS for the whole launch -- every workgroup keeps ONE channel tile -- and the ring
+// carries the pixel rows only, k-steps of 64 (full 128-byte lines: the L2 -> LDS path retires lines, not bytes): half the DMA pieces per
+// k-step of a ring that also carried the weights (the ring producers' issue rate, not the MFMA, set the main beats' length)
+constexpr int f1_lds_bytes(int NS, int RB, int K) {
+    return F1_TM * K * 2 + NS * F1_TN * 64 * 2 + RB * F1_R_BYTES + RB * F1_M_BYTES + F1_C_BYTES;
 }
 
 // HAS_RES / HAS_OM / HAS_BITS: residual, output mask, mask bits of the result -- compile-time, so that the two output-stage beats are straight-line
 // code (with run-time flags every LDS read sat behind a branch and waited for its own latency: 1.4 + 0.7 us per tile)
 // SRC2: the K dimension is the channels of X followed by those of a second plain [P][channels] tensor X2 (IGemmArgs::X2 / Ck1, both multiples of
 // 64): conv3 and the downsample convolution of a bottleneck as ONE GEMM in the inference forward ([a2 | x] against [s3.W3 | sd.Wd])
-template <int F1_NS, int F1_RB, bool ARES, bool HAS_RES, bool HAS_OM, bool HAS_BITS, bool SRC2 = false>
+template <int F1_NS, int F1_RB, bool HAS_RES, bool HAS_OM, bool HAS_BITS, bool SRC2 = false>
 __global__ __launch_bounds__((F1_NC + F1_NP + F1_NR) * 64) void fused1x1_persist_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
     extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
     const int K = a.g.Ck, KT = K >> 6, P = a.P, Cm = a.Cm;
-    constexpr int STAGE = ARES ? F1_TN * 64 : F1_STAGE_ELEMS;             // elements of a ring stage
-    uint16_t* const ring = smem + (ARES ? F1_TM * K : 0);                 // (ARES: the resident weight image [K / 64][128 rows][64] sits in front)
+    constexpr int STAGE = F1_TN * 64;                                     // elements of a ring stage
+    uint16_t* const ring = smem + F1_TM * K;                              // (the resident weight image [K / 64][128 rows][64] sits in front)
     char* const rbuf = reinterpret_cast<char*>(ring + F1_NS * STAGE);
     char* const mbuf = rbuf + F1_RB * F1_R_BYTES;
     float* const cbuf = reinterpret_cast<float*>(mbuf + F1_RB * F1_M_BYTES);         // [3][128]
@@ -136,7 +137,7 @@ __global__ __launch_bounds__((F1_NC + F1_NP + F1_NR) * 64) void fused1x1_persist
         const int r_in = lane >> 3;
         const int kc = (lane & 7) ^ (((pw & 1) << 2) | (r_in >> 1));
         constexpr int NPC = F1_TM / 8 / F1_NP;                        // pieces per producer, operand and k-step: 4
-        constexpr int PK = ARES ? NPC : 2 * NPC;                      // DMA pieces per producer and k-step: 4 (pixels only) or 8
+        constexpr int PK = NPC;                                       // DMA pieces per producer and k-step: 4 (pixels only)
         int issued = 0, it = 0, ik = 0, st_issue = 0;
         uint32_t a_off[NPC], b_off[NPC];
         auto set_tile = [&](int t) {
@@ -152,22 +153,15 @@ __global__ __launch_bounds__((F1_NC + F1_NP + F1_NR) * 64) void fused1x1_persist
             }
         };
         set_tile(0);
-        if constexpr (ARES) {                                         // the weight rows of this workgroup's channel tile, once (older than every ring piece:
-            for (int k = 0; k < KT; ++k)                              //  the first counted wait below covers them)
+        // the weight rows of this workgroup's channel tile, once (older than every ring piece: the first counted wait below covers them)
+        for (int k = 0; k < KT; ++k)
 #pragma unroll
-                for (int i = 0; i < NPC; ++i)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_ptr)(smem + k * (F1_TM * 64) + (pw + F1_NP * i) * 512), 16, a_off[i] + (uint32_t)k * 128u, 0, 0, 0);
-        }
+            for (int i = 0; i < NPC; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_ptr)(smem + k * (F1_TM * 64) + (pw + F1_NP * i) * 512), 16, a_off[i] + (uint32_t)k * 128u, 0, 0, 0);
         auto issue_one = [&]() {
-            uint16_t* sa = ring + st_issue * STAGE;
-            uint16_t* sb = ARES ? sa : sa + F1_TM * 64;
+            uint16_t* sb = ring + st_issue * STAGE;
             st_issue = st_issue == F1_NS - 1 ? 0 : st_issue + 1;
             const uint32_t kb = (uint32_t)ik * 128u;
-            if constexpr (!ARES) {
-#pragma unroll
-                for (int i = 0; i < NPC; ++i)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_ptr)(sa + (pw + F1_NP * i) * 512), 16, a_off[i] + kb, 0, 0, 0);
-            }
             if constexpr (SRC2) {                                     // this k-step lies in X (< Ck1) or in X2: wave-uniform
                 const int kc0 = ik * 64;
                 const bool second = kc0 >= rep * Ck1;
@@ -304,8 +298,8 @@ __global__ __launch_bounds__((F1_NC + F1_NP + F1_NR) * 64) void fused1x1_persist
             for (int j = 0; j < 2; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         for (int k = 0; k < KT; ++k) {
             const unsigned long long s0 = stamp ? __builtin_amdgcn_s_memrealtime() : 0;
-            const uint16_t* sb = ring + st_cur * STAGE + (ARES ? 0 : F1_TM * 64);
-            const uint16_t* sa = ARES ? smem + k * (F1_TM * 64) : ring + st_cur * STAGE;
+            const uint16_t* sb = ring + st_cur * STAGE;
+            const uint16_t* sa = smem + k * (F1_TM * 64);
             st_cur = st_cur == F1_NS - 1 ? 0 : st_cur + 1;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {

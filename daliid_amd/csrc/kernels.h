@@ -74,8 +74,6 @@ struct WGradArgs {
     int splits, pix_per_split;    // pix_per_split multiple of 32
     GatherGeom g;
     unsigned long long* stamps;   // diagnostic, as in IGemmArgs
-    int ablate;                   // diagnostic (DALI_WGRAD_ABLATE, igemm_wgrad3x3_kernel): 1 = no operand requests after the ring's prologue (the k-steps keep
-                                  // their reads, MFMAs and barriers), 2 = requests and barriers only (no fragment reads, no MFMAs); results are wrong
     float* colsum;                // optional [splits][Cm]: per-split column sums over the pixels of dY, by one extra MFMA per fragment against a
                                   // ones operand in the n-tile-0 workgroups (128 x 128 kernel only: wgrad_colsum_supported); bnlin.hip's s / m2
 };

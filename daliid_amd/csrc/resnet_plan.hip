@@ -39,10 +39,9 @@ struct Block {
     bool has_ds;
     int hin, win, hout, wout, cin, width, cout;
     uint8_t* ybits = nullptr;                                  // ReLU mask of y, one bit per element (dali_bn_act mask_out)
-    uint16_t *x, *raw1, *a1, *raw2, *a2, *raw3, *rawd, *y;    // a = relu(bn(raw)), materialised once (fused
+    uint16_t *x, *raw1, *a1, *raw2, *a2, *rawd, *y;           // a = relu(bn(raw)), materialised once (fused
                                                                 // apply-on-load repeats the VALU work per tap and per M-tile)
-    // bn3 behind conv3 through the moments of a2 (bnlin.hip): blocks without a downsample branch never store raw3
-    bool lin3 = false;
+    // bn3 behind conv3 through the moments of a2 (bnlin.hip): conv3's raw output is never stored
     float *gram = nullptr, *m2 = nullptr, *sdz = nullptr, *bvec = nullptr, *qk = nullptr;      // [w][w], [w], [cout], [w], [2][cout]
     float *ut = nullptr, *dot = nullptr;                       // (W3 gram)^T [w][cout] (forward -> backward), [w/32][cout] scratch
     uint16_t* wd1 = nullptr;                                   // data-gradient image [w][cout + w]: (A.W3)^T beside -(W3^T diag(Q) W3)
@@ -155,18 +154,6 @@ GatherGeom conv_geom(const Conv& c, int mode) {
     g.lw = g.lhw = -1;
     return g;
 }
-// bn3 behind conv3 through the moments of conv3's input (bnlin.hip).  The scheme trades passes over [P][4w] tensors for products of size
-// w^2 and ~7 small launches per block.  Until round 4 it paid for w <= 128 only (layer1 / layer2); with the block's two data-gradient GEMMs
-// merged into one launch over [dz | a2] (IGemmArgs::X2) it pays for every block of ResNet-50 at batch 256: 15.71 (w <= 128) / 15.61 (<= 256) /
-// 15.47 ms (all), same box.  DALI_BNLIN_MAXW moves the limit (0: every block keeps the materialised form).
-int bnlin_max_width() {
-    static int v = -1;
-    if (v == -1) { const char* e = getenv("DALI_BNLIN_MAXW"); v = e ? atoi(e) : 512; }
-    return v;
-}
-// inference forward with BatchNorm + ReLU folded into the convolutions' output stages (default); DALI_EVAL_FUSED=0 keeps the training dataflow
-// (raw output, then a bn_act pass) for A/B measurements and for tests of the unfused rounding points
-bool eval_fused() { return DALI_ENV_INT("DALI_EVAL_FUSED", 1) != 0; }
 // a cin = cout = w 1x1 convolution on the grid of conv3: the shape of the Gram GEMM a2^T a2 and of the second data-gradient GEMM
 Conv square_conv(const Conv& c3) {
     Conv q = c3;
@@ -224,12 +211,13 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
                 add_bn(net, b.bd, pre + ".downsample.1", planes * 4);
             }
             b.hout = b.c2.hout; b.wout = b.c2.wout;
-            // bn3 through the moments of a2 (bnlin.hip); in a block with a downsample branch the identity enters conv3's epilogue as
-            // scale_d * rawd + shift_d (res_scale / bias) and the downsample BatchNorm keeps its own two-pass backward
-            b.lin3 = planes % 32 == 0 && planes <= bnlin_max_width();
-            // ... except where the branch is a stride-1 convolution of a narrow input (ResNet-50: layer1's, 64 -> 256 over 524288 pixels at batch
-            // 256), whose Gram matrix costs less than the two passes: there its backward goes through the moments of x as well (block_backward)
-            b.lin_ds = b.has_ds && b.lin3 && st == 1 && inpl % 32 == 0 && inpl <= 128 && net->blocks.empty();   // (first block of the net: no mask on dx)
+            // bn3 through the moments of a2 in every block (bnlin.hip): width_base 32 or 64 keeps every width a multiple of 32 up to 512, and the
+            // scheme pays at every width (15.71 ms per step for w <= 128 only, 15.61 for w <= 256, 15.47 for all, same box).  With a downsample
+            // branch the identity enters conv3's epilogue as scale_d * rawd + shift_d (res_scale / bias) and the downsample BatchNorm keeps its own
+            // two-pass backward, except where the branch is a stride-1 convolution of a narrow input (ResNet-50: layer1's, 64 -> 256 over 524288
+            // pixels at batch 256): its Gram matrix costs less than the two passes, so its backward goes through the moments of x as well
+            // (block_backward)
+            b.lin_ds = b.has_ds && st == 1 && inpl % 32 == 0 && inpl <= 128 && net->blocks.empty();   // (first block of the net: no mask on dx)
             h = b.hout; w = b.wout; inpl = planes * 4;
             net->blocks.push_back(b);
         }
@@ -265,20 +253,17 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
         reserve(net, a, b.a1, pin * b.width * 2);
         reserve(net, a, b.raw2, pout * b.width * 2);
         reserve(net, a, b.a2, pout * b.width * 2);
-        if (!b.lin3) reserve(net, a, b.raw3, pout * b.cout * 2);
-        else {
-            reserve(net, a, b.gram, (size_t)b.width * b.width * 4); reserve(net, a, b.m2, (size_t)b.width * 4);
-            reserve(net, a, b.sdz, (size_t)b.cout * 4); reserve(net, a, b.bvec, (size_t)b.width * 4); reserve(net, a, b.qk, (size_t)b.cout * 8);
-            reserve(net, a, b.wd1, (size_t)b.width * (b.cout + b.width) * 2);          // [w][cout + w]: (A.W3)^T | -(W3^T diag(Q) W3), one data-gradient image
-            reserve(net, a, b.ut, (size_t)b.width * b.cout * 4); reserve(net, a, b.dot, (size_t)(b.width / 32) * b.cout * 12);
-            max_cs = std::max(max_cs, std::max(colsum_partial_floats((int)pout, b.cout), colsum_partial_floats((int)pout, b.width)) * 4);
-            int sp, pps; size_t wsb;
-            wgrad_plan(b.width, b.width, (int)pout, 512, &sp, &pps, &wsb, 1, 0);
-            max_slab = std::max(max_slab, wsb);
-            max_cs = std::max(max_cs, (size_t)wgrad_colsum_rows(b.width, b.width, 1, (int)pout, sp) * b.width * 4);     // per-split column sums riding on the GEMMs
-            wgrad_plan(b.cout, b.width, (int)pout, 512, &sp, &pps, &wsb, 1, 0);
-            max_cs = std::max(max_cs, (size_t)wgrad_colsum_rows(b.cout, b.width, 1, (int)pout, sp) * b.cout * 4);
-        }
+        reserve(net, a, b.gram, (size_t)b.width * b.width * 4); reserve(net, a, b.m2, (size_t)b.width * 4);
+        reserve(net, a, b.sdz, (size_t)b.cout * 4); reserve(net, a, b.bvec, (size_t)b.width * 4); reserve(net, a, b.qk, (size_t)b.cout * 8);
+        reserve(net, a, b.wd1, (size_t)b.width * (b.cout + b.width) * 2);          // [w][cout + w]: (A.W3)^T | -(W3^T diag(Q) W3), one data-gradient image
+        reserve(net, a, b.ut, (size_t)b.width * b.cout * 4); reserve(net, a, b.dot, (size_t)(b.width / 32) * b.cout * 12);
+        max_cs = std::max(max_cs, std::max(colsum_partial_floats((int)pout, b.cout), colsum_partial_floats((int)pout, b.width)) * 4);
+        int sp, pps; size_t wsb;
+        wgrad_plan(b.width, b.width, (int)pout, 512, &sp, &pps, &wsb, 1, 0);
+        max_slab = std::max(max_slab, wsb);
+        max_cs = std::max(max_cs, (size_t)wgrad_colsum_rows(b.width, b.width, 1, (int)pout, sp) * b.width * 4);     // per-split column sums riding on the GEMMs
+        wgrad_plan(b.cout, b.width, (int)pout, 512, &sp, &pps, &wsb, 1, 0);
+        max_cs = std::max(max_cs, (size_t)wgrad_colsum_rows(b.cout, b.width, 1, (int)pout, sp) * b.cout * 4);
         reserve(net, a, b.y, pout * b.cout * 2);
         reserve(net, a, b.ybits, pout * b.cout / 8);
         if (b.has_ds) reserve(net, a, b.rawd, pout * b.cout * 2);
@@ -293,7 +278,7 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
         }
         // (split weight image, 2 parts: folding the scales into ONE bf16 image is a coherent 2^-9 perturbation of the weights, which moved the mAP of
         //  separated identities by 1.1e-3 against the oracle; hi + lo images are fp32-grade.  K = 2 (w + cin) <= 256: layer1's first block.)
-        b.cat_eval = b.has_ds && b.cd.stride == 1 && b.lin3 && conv_cat_act_supported(b.cout, b.width, b.cin, (int)pout, 2);
+        b.cat_eval = b.has_ds && b.cd.stride == 1 && conv_cat_act_supported(b.cout, b.width, b.cin, (int)pout, 2);
         if (b.cat_eval) { reserve(net, a, b.wcat, (size_t)b.cout * 2 * (b.width + b.cin) * 2); reserve(net, a, b.shcat, (size_t)b.cout * 4); }
         reserve_bn(net, a, b.b1); reserve_bn(net, a, b.b2); reserve_bn(net, a, b.b3);
         if (b.has_ds) reserve_bn(net, a, b.bd);
@@ -486,7 +471,7 @@ extern "C" int dali_resnet_forward(dali_resnet* net, void* stream, const float* 
     }
     // ---- stem: conv1 -> bn1 -> (no ReLU) -> maxpool ----
     if ((rc = launch_stem_pack_image(st, images, net->N, net->H, net->W, net->ximg))) return rc;
-    if (!tr && eval_fused() && stem_fused_supported(net->N, net->H, net->W, net->stem.cout)) {
+    if (!tr && stem_fused_supported(net->N, net->H, net->W, net->stem.cout)) {
         // inference: one launch, the convolution's output never stored (stem.hip); bn1 acts on the fp32 accumulators
         if ((rc = launch_stem_conv_bn_pool(st, net->ximg, net->w_stem, net->stem_bn.scale, net->stem_bn.shift, net->N, net->H, net->W, net->pool0))) return rc;
     } else {
@@ -511,7 +496,7 @@ extern "C" int dali_resnet_forward(dali_resnet* net, void* stream, const float* 
     for (auto& b : net->blocks) {
         b.x = const_cast<uint16_t*>(x);
         const size_t e1 = (size_t)net->N * b.hin * b.win * b.width, e2 = (size_t)net->N * b.hout * b.wout * b.width;
-        if (!tr && eval_fused()) {
+        if (!tr) {
             if ((rc = conv_bn_relu_eval(net, st, b.c1, b.b1, x, b.a1))) return rc;
             if ((rc = conv_bn_relu_eval(net, st, b.c2, b.b2, b.a1, b.a2))) return rc;
         } else {
@@ -520,74 +505,61 @@ extern "C" int dali_resnet_forward(dali_resnet* net, void* stream, const float* 
             if ((rc = conv_bn_fwd(net, st, b.c2, b.b2, b.a1, nullptr, b.raw2, tr))) return rc;
             if ((rc = launch_bn_act(st, b.raw2, b.b2.scale, b.b2.shift, nullptr, nullptr, nullptr, nullptr, 1, e2, b.width, b.a2, nullptr))) return rc;
         }
-        const size_t elems = (size_t)net->N * b.hout * b.wout * b.cout;
-        if (b.lin3) {
-            // bn3's batch statistics from the moments of a2 (bnlin.hip), then conv3 writes y = relu(bn3(conv3(a2)) + x) and its ReLU mask itself
-            const int Pout = net->N * b.hout * b.wout;
-            if (tr) {
-                const Conv sq = square_conv(b.c3);
-                WGradArgs wa{};
-                wa.dY = b.a2; wa.X = b.a2; wa.partial = net->wgrad_slab; wa.Cm = b.width; wa.P = Pout; wa.Ntot = b.width;
-                wa.g = conv_geom(sq, 0);
-                size_t wsb;
-                wgrad_plan(wa.Cm, wa.Ntot, wa.P, 512, &wa.splits, &wa.pix_per_split, &wsb, 1, 0);
-                const bool fused_cs = wgrad_colsum_supported(wa.Cm, wa.Ntot, 1, wa.P);      // m2 = colsum(a2) rides on the Gram GEMM
-                if (fused_cs) wa.colsum = net->cs_partial;
-                if ((rc = launch_igemm_wgrad(st, wa, b.gram, 0, fused_cs ? b.m2 : nullptr, fused_cs ? wgrad_colsum_rows(wa.Cm, wa.Ntot, 1, wa.P, wa.splits) : 0))) return rc;
-                if (!fused_cs && (rc = launch_colsum(st, b.a2, Pout, b.width, b.m2, net->cs_partial, net->red_scratch))) return rc;
-                if ((rc = launch_bnlin_stats(st, b.c3.w_bf16, b.c3.wt_bf16, b.gram, b.m2, b.cout, b.width, (double)Pout, net->P + b.b3.g_off, net->P + b.b3.b_off,
-                                             net->B + b.b3.rm_off, net->B + b.b3.rv_off, 0.1f, 1e-5f, b.ut, b.dot, b.b3.scale, b.b3.shift, b.b3.mean,
-                                             b.b3.invstd))) return rc;
-            }
-            if (!tr && b.cat_eval && eval_fused() && DALI_ENV_INT("DALI_EVAL_CAT", 1) != 0) {
-                // inference, stride-1 downsample branch: y = relu([a2 | x] [s3.W3 | sd.Wd]^T + shift3 + shift_d) in one launch: no raw branch
-                // output, no residual read (the scales ride in a split hi + lo weight image: fp32-grade weights, mirrored by the twin)
-                if ((rc = launch_fold_cat_weights(st, net->P + b.c3.w_off, net->P + b.cd.w_off, b.b3.scale, b.bd.scale, b.b3.shift, b.bd.shift, b.cout, b.width,
-                                                  b.cin, 2, b.wcat, b.shcat))) return rc;
-                IGemmArgs ca{};
-                ca.W = b.wcat; ca.X = b.a2; ca.X2 = x; ca.Ck1 = b.width; ca.x_rep = 2; ca.O = b.y; ca.out_shift = b.shcat; ca.out_relu = 1;
-                ca.Cm = b.cout; ca.P = Pout;
-                Conv cat = b.c3;
-                cat.cin = 2 * (b.width + b.cin);
-                ca.g = conv_geom(cat, 0);
-                if ((rc = launch_igemm_conv(st, ca))) return rc;
-                x = b.y;
-                continue;
-            }
-            IGemmArgs a{};
-            a.W = b.c3.w_bf16; a.X = b.a2; a.O = b.y; a.Res = x; a.out_scale = b.b3.scale; a.out_shift = b.b3.shift; a.out_relu = 1;
-            if (b.has_ds) {                               // identity = bnd(convd(x)): raw output + its BatchNorm as residual scale / extra shift
-                if ((rc = conv_bn_fwd(net, st, b.cd, b.bd, x, nullptr, b.rawd, tr))) return rc;
-                a.Res = b.rawd; a.res_scale = b.bd.scale; a.bias = b.bd.shift;
-                if (b.lin_ds && tr) {                         // moments of x for the branch's backward: G_x = x^T x, m2 = colsum(x), Ut = (Wd G_x)^T
-                    Conv sq = b.cd;
-                    sq.cout = b.cd.cin;
-                    WGradArgs wa{};
-                    wa.dY = x; wa.X = x; wa.partial = net->wgrad_slab; wa.Cm = b.cin; wa.P = Pout; wa.Ntot = b.cin;
-                    wa.g = conv_geom(sq, 0);
-                    size_t wsb;
-                    wgrad_plan(wa.Cm, wa.Ntot, wa.P, 512, &wa.splits, &wa.pix_per_split, &wsb, 1, 0);
-                    const bool fused_cs = wgrad_colsum_supported(wa.Cm, wa.Ntot, 1, wa.P);
-                    if (fused_cs) wa.colsum = net->cs_partial;
-                    if ((rc = launch_igemm_wgrad(st, wa, b.gram_d, 0, fused_cs ? b.m2_d : nullptr, fused_cs ? wgrad_colsum_rows(wa.Cm, wa.Ntot, 1, wa.P, wa.splits) : 0))) return rc;
-                    if (!fused_cs && (rc = launch_colsum(st, x, Pout, b.cin, b.m2_d, net->cs_partial, net->red_scratch))) return rc;
-                    if ((rc = launch_bnlin_ut(st, b.cd.w_bf16, b.gram_d, b.cout, b.cin, b.ut_d))) return rc;
-                }
-            }
-            a.bits_out = tr ? b.ybits : nullptr;
-            a.Cm = b.cout; a.P = Pout; a.g = conv_geom(b.c3, 0);
-            if ((rc = launch_igemm_conv(st, a))) return rc;
+        // bn3's batch statistics from the moments of a2 (bnlin.hip), then conv3 writes y = relu(bn3(conv3(a2)) + x) and its ReLU mask itself
+        const int Pout = net->N * b.hout * b.wout;
+        if (tr) {
+            const Conv sq = square_conv(b.c3);
+            WGradArgs wa{};
+            wa.dY = b.a2; wa.X = b.a2; wa.partial = net->wgrad_slab; wa.Cm = b.width; wa.P = Pout; wa.Ntot = b.width;
+            wa.g = conv_geom(sq, 0);
+            size_t wsb;
+            wgrad_plan(wa.Cm, wa.Ntot, wa.P, 512, &wa.splits, &wa.pix_per_split, &wsb, 1, 0);
+            const bool fused_cs = wgrad_colsum_supported(wa.Cm, wa.Ntot, 1, wa.P);      // m2 = colsum(a2) rides on the Gram GEMM
+            if (fused_cs) wa.colsum = net->cs_partial;
+            if ((rc = launch_igemm_wgrad(st, wa, b.gram, 0, fused_cs ? b.m2 : nullptr, fused_cs ? wgrad_colsum_rows(wa.Cm, wa.Ntot, 1, wa.P, wa.splits) : 0))) return rc;
+            if (!fused_cs && (rc = launch_colsum(st, b.a2, Pout, b.width, b.m2, net->cs_partial, net->red_scratch))) return rc;
+            if ((rc = launch_bnlin_stats(st, b.c3.w_bf16, b.c3.wt_bf16, b.gram, b.m2, b.cout, b.width, (double)Pout, net->P + b.b3.g_off, net->P + b.b3.b_off,
+                                         net->B + b.b3.rm_off, net->B + b.b3.rv_off, 0.1f, 1e-5f, b.ut, b.dot, b.b3.scale, b.b3.shift, b.b3.mean,
+                                         b.b3.invstd))) return rc;
+        }
+        if (!tr && b.cat_eval) {
+            // inference, stride-1 downsample branch: y = relu([a2 | x] [s3.W3 | sd.Wd]^T + shift3 + shift_d) in one launch: no raw branch
+            // output, no residual read (the scales ride in a split hi + lo weight image: fp32-grade weights, mirrored by the twin)
+            if ((rc = launch_fold_cat_weights(st, net->P + b.c3.w_off, net->P + b.cd.w_off, b.b3.scale, b.bd.scale, b.b3.shift, b.bd.shift, b.cout, b.width,
+                                              b.cin, 2, b.wcat, b.shcat))) return rc;
+            IGemmArgs ca{};
+            ca.W = b.wcat; ca.X = b.a2; ca.X2 = x; ca.Ck1 = b.width; ca.x_rep = 2; ca.O = b.y; ca.out_shift = b.shcat; ca.out_relu = 1;
+            ca.Cm = b.cout; ca.P = Pout;
+            Conv cat = b.c3;
+            cat.cin = 2 * (b.width + b.cin);
+            ca.g = conv_geom(cat, 0);
+            if ((rc = launch_igemm_conv(st, ca))) return rc;
             x = b.y;
             continue;
         }
-        if ((rc = conv_bn_fwd(net, st, b.c3, b.b3, b.a2, nullptr, b.raw3, tr))) return rc;
-        if (b.has_ds) {
+        IGemmArgs a{};
+        a.W = b.c3.w_bf16; a.X = b.a2; a.O = b.y; a.Res = x; a.out_scale = b.b3.scale; a.out_shift = b.b3.shift; a.out_relu = 1;
+        if (b.has_ds) {                               // identity = bnd(convd(x)): raw output + its BatchNorm as residual scale / extra shift
             if ((rc = conv_bn_fwd(net, st, b.cd, b.bd, x, nullptr, b.rawd, tr))) return rc;
-            rc = launch_bn_act(st, b.raw3, b.b3.scale, b.b3.shift, nullptr, b.rawd, b.bd.scale, b.bd.shift, 1, elems, b.cout, b.y, tr ? b.ybits : nullptr);
-        } else {
-            rc = launch_bn_act(st, b.raw3, b.b3.scale, b.b3.shift, x, nullptr, nullptr, nullptr, 1, elems, b.cout, b.y, tr ? b.ybits : nullptr);
+            a.Res = b.rawd; a.res_scale = b.bd.scale; a.bias = b.bd.shift;
+            if (b.lin_ds && tr) {                         // moments of x for the branch's backward: G_x = x^T x, m2 = colsum(x), Ut = (Wd G_x)^T
+                Conv sq = b.cd;
+                sq.cout = b.cd.cin;
+                WGradArgs wa{};
+                wa.dY = x; wa.X = x; wa.partial = net->wgrad_slab; wa.Cm = b.cin; wa.P = Pout; wa.Ntot = b.cin;
+                wa.g = conv_geom(sq, 0);
+                size_t wsb;
+                wgrad_plan(wa.Cm, wa.Ntot, wa.P, 512, &wa.splits, &wa.pix_per_split, &wsb, 1, 0);
+                const bool fused_cs = wgrad_colsum_supported(wa.Cm, wa.Ntot, 1, wa.P);
+                if (fused_cs) wa.colsum = net->cs_partial;
+                if ((rc = launch_igemm_wgrad(st, wa, b.gram_d, 0, fused_cs ? b.m2_d : nullptr, fused_cs ? wgrad_colsum_rows(wa.Cm, wa.Ntot, 1, wa.P, wa.splits) : 0))) return rc;
+                if (!fused_cs && (rc = launch_colsum(st, x, Pout, b.cin, b.m2_d, net->cs_partial, net->red_scratch))) return rc;
+                if ((rc = launch_bnlin_ut(st, b.cd.w_bf16, b.gram_d, b.cout, b.cin, b.ut_d))) return rc;
+            }
         }
-        if (rc) return rc;
+        a.bits_out = tr ? b.ybits : nullptr;
+        a.Cm = b.cout; a.P = Pout; a.g = conv_geom(b.c3, 0);
+        if ((rc = launch_igemm_conv(st, a))) return rc;
         x = b.y;
     }
     // ---- head: avg-pool + max-pool, BatchNorm1d ----
@@ -604,64 +576,49 @@ static int block_backward(dali_resnet* net, hipStream_t st, Block& b, const uint
     uint16_t* dz = net->cur_dy;                                   // masked grad wrt block output y
     const int Pout = net->N * b.hout * b.wout, Pin = net->N * b.hin * b.win;
     uint16_t *d_a2, *d_rawd = nullptr, *scratch_a;
-    if (b.lin3) {
-        // bn3 + conv3 through the moments of a2 (bnlin.hip): no reduce / apply passes over [P][cout] tensors, raw3 does not exist
-        WGradArgs wa{};
-        wa.dY = dz; wa.X = b.a2; wa.partial = net->wgrad_slab; wa.Cm = b.cout; wa.P = Pout; wa.Ntot = b.width;
-        wa.g = conv_geom(b.c3, 0);
-        size_t wsb;
-        wgrad_plan(wa.Cm, wa.Ntot, wa.P, 512, &wa.splits, &wa.pix_per_split, &wsb, 1, 0);
-        const bool fused_cs = wgrad_colsum_supported(wa.Cm, wa.Ntot, 1, wa.P);              // s = colsum(dz) rides on the weight-gradient GEMM
-        if (fused_cs) wa.colsum = net->cs_partial;
-        if ((rc = launch_igemm_wgrad(st, wa, net->G + b.c3.w_off, 0, fused_cs ? b.sdz : nullptr,
-                                     fused_cs ? wgrad_colsum_rows(wa.Cm, wa.Ntot, 1, wa.P, wa.splits) : 0))) return rc;           // G0 = dz^T a2 into the gradient slot; finished in place below
-        if (!fused_cs && (rc = launch_colsum(st, dz, Pout, b.cout, b.sdz, net->cs_partial, net->red_scratch))) return rc;
-        const int ldw = b.cout + b.width;
-        if ((rc = launch_bnlin_bwd(st, b.c3.w_bf16, b.c3.wt_bf16, b.ut, b.m2, b.sdz, b.cout, b.width, (double)Pout, b.b3.scale, b.b3.mean,
-                                   b.b3.invstd, net->G + b.c3.w_off, net->G + b.b3.g_off, net->G + b.b3.b_off, b.wd1, b.wd1 + b.cout, b.bvec, b.qk, ldw, ldw))) return rc;
-        d_a2 = next_gbuf(net, dz);
-        scratch_a = next_gbuf(net, dz, d_a2);
-        {   // d_a2 = dz (A.W3) + W3^T Kc - a2 (W3^T diag(Q) W3) as ONE GEMM over K = cout + w: [dz | a2] against the concatenated image
-            // (two launches with the partial result stored and re-read before: 190 -> see docs/experiments.md)
-            Conv cat = b.c3;
-            cat.cout = ldw;
-            IGemmArgs ga{};
-            ga.W = b.wd1; ga.X = dz; ga.X2 = b.a2; ga.Ck1 = b.cout; ga.O = d_a2; ga.bias = b.bvec;
-            ga.Cm = b.width; ga.P = Pout;
-            ga.g = conv_geom(cat, 1);
-            if ((rc = launch_igemm_conv(st, ga))) return rc;
-        }
-        if (b.lin_ds) {
-            // downsample branch through the moments of x: G0d = dz^T x into the gradient slot (s = colsum(dz) is bn3's), finished in place by the row
-            // kernel together with dgamma / dbeta and the two data-gradient images; the data gradient itself follows conv1's below
-            WGradArgs wd{};
-            wd.dY = dz; wd.X = b.x; wd.partial = net->wgrad_slab; wd.Cm = b.cout; wd.P = Pout; wd.Ntot = b.cin;
-            wd.g = conv_geom(b.cd, 0);
-            size_t wsb2;
-            wgrad_plan(wd.Cm, wd.Ntot, wd.P, 512, &wd.splits, &wd.pix_per_split, &wsb2, 1, 0);
-            if ((rc = launch_igemm_wgrad(st, wd, net->G + b.cd.w_off, 0))) return rc;
-            const int ldd = b.cout + b.cin;
-            if ((rc = launch_bnlin_bwd(st, b.cd.w_bf16, b.cd.wt_bf16, b.ut_d, b.m2_d, b.sdz, b.cout, b.cin, (double)Pout, b.bd.scale, b.bd.mean, b.bd.invstd,
-                                       net->G + b.cd.w_off, net->G + b.bd.g_off, net->G + b.bd.b_off, b.wdd, b.wdd + b.cout, b.bvec_d, b.qk_d, ldd, ldd))) return rc;
-        } else if (b.has_ds) {                                    // the downsample BatchNorm: its own two passes over (dz, rawd)
-            d_rawd = next_gbuf(net, dz, d_a2, scratch_a);
-            BnBwdSide sd{b.rawd, b.bd.mean, b.bd.invstd, b.bd.scale, b.bd.shift};
-            if ((rc = launch_bn_bwd(st, dz, nullptr, nullptr, sd, nullptr, 0, Pout, b.cout, net->bwd_partial, b.bd.coef, nullptr, net->G + b.bd.g_off,
-                                    net->G + b.bd.b_off, nullptr, nullptr, d_rawd, nullptr, nullptr, net->red_scratch))) return rc;
-        }
-    } else {
-        uint16_t* d_raw3 = next_gbuf(net, dz);
-        d_rawd = b.has_ds ? next_gbuf(net, dz, d_raw3) : nullptr;
-        BnBwdSide s3{b.raw3, b.b3.mean, b.b3.invstd, b.b3.scale, b.b3.shift};
+    // bn3 + conv3 through the moments of a2 (bnlin.hip): no reduce / apply passes over [P][cout] tensors, conv3's raw output does not exist
+    WGradArgs wa{};
+    wa.dY = dz; wa.X = b.a2; wa.partial = net->wgrad_slab; wa.Cm = b.cout; wa.P = Pout; wa.Ntot = b.width;
+    wa.g = conv_geom(b.c3, 0);
+    size_t wsb;
+    wgrad_plan(wa.Cm, wa.Ntot, wa.P, 512, &wa.splits, &wa.pix_per_split, &wsb, 1, 0);
+    const bool fused_cs = wgrad_colsum_supported(wa.Cm, wa.Ntot, 1, wa.P);              // s = colsum(dz) rides on the weight-gradient GEMM
+    if (fused_cs) wa.colsum = net->cs_partial;
+    if ((rc = launch_igemm_wgrad(st, wa, net->G + b.c3.w_off, 0, fused_cs ? b.sdz : nullptr,
+                                 fused_cs ? wgrad_colsum_rows(wa.Cm, wa.Ntot, 1, wa.P, wa.splits) : 0))) return rc;           // G0 = dz^T a2 into the gradient slot; finished in place below
+    if (!fused_cs && (rc = launch_colsum(st, dz, Pout, b.cout, b.sdz, net->cs_partial, net->red_scratch))) return rc;
+    const int ldw = b.cout + b.width;
+    if ((rc = launch_bnlin_bwd(st, b.c3.w_bf16, b.c3.wt_bf16, b.ut, b.m2, b.sdz, b.cout, b.width, (double)Pout, b.b3.scale, b.b3.mean,
+                               b.b3.invstd, net->G + b.c3.w_off, net->G + b.b3.g_off, net->G + b.b3.b_off, b.wd1, b.wd1 + b.cout, b.bvec, b.qk, ldw, ldw))) return rc;
+    d_a2 = next_gbuf(net, dz);
+    scratch_a = next_gbuf(net, dz, d_a2);
+    {   // d_a2 = dz (A.W3) + W3^T Kc - a2 (W3^T diag(Q) W3) as ONE GEMM over K = cout + w: [dz | a2] against the concatenated image
+        // (two launches with the partial result stored and re-read before: 190 -> see docs/experiments.md)
+        Conv cat = b.c3;
+        cat.cout = ldw;
+        IGemmArgs ga{};
+        ga.W = b.wd1; ga.X = dz; ga.X2 = b.a2; ga.Ck1 = b.cout; ga.O = d_a2; ga.bias = b.bvec;
+        ga.Cm = b.width; ga.P = Pout;
+        ga.g = conv_geom(cat, 1);
+        if ((rc = launch_igemm_conv(st, ga))) return rc;
+    }
+    if (b.lin_ds) {
+        // downsample branch through the moments of x: G0d = dz^T x into the gradient slot (s = colsum(dz) is bn3's), finished in place by the row
+        // kernel together with dgamma / dbeta and the two data-gradient images; the data gradient itself follows conv1's below
+        WGradArgs wd{};
+        wd.dY = dz; wd.X = b.x; wd.partial = net->wgrad_slab; wd.Cm = b.cout; wd.P = Pout; wd.Ntot = b.cin;
+        wd.g = conv_geom(b.cd, 0);
+        size_t wsb2;
+        wgrad_plan(wd.Cm, wd.Ntot, wd.P, 512, &wd.splits, &wd.pix_per_split, &wsb2, 1, 0);
+        if ((rc = launch_igemm_wgrad(st, wd, net->G + b.cd.w_off, 0))) return rc;
+        const int ldd = b.cout + b.cin;
+        if ((rc = launch_bnlin_bwd(st, b.cd.w_bf16, b.cd.wt_bf16, b.ut_d, b.m2_d, b.sdz, b.cout, b.cin, (double)Pout, b.bd.scale, b.bd.mean, b.bd.invstd,
+                                   net->G + b.cd.w_off, net->G + b.bd.g_off, net->G + b.bd.b_off, b.wdd, b.wdd + b.cout, b.bvec_d, b.qk_d, ldd, ldd))) return rc;
+    } else if (b.has_ds) {                                    // the downsample BatchNorm: its own two passes over (dz, rawd)
+        d_rawd = next_gbuf(net, dz, d_a2, scratch_a);
         BnBwdSide sd{b.rawd, b.bd.mean, b.bd.invstd, b.bd.scale, b.bd.shift};
-        rc = launch_bn_bwd(st, dz, nullptr, nullptr, s3, b.has_ds ? &sd : nullptr, 0, Pout, b.cout, net->bwd_partial, b.b3.coef, b.has_ds ? b.bd.coef : nullptr,
-                           net->G + b.b3.g_off, net->G + b.b3.b_off, b.has_ds ? net->G + b.bd.g_off : nullptr, b.has_ds ? net->G + b.bd.b_off : nullptr,
-                           d_raw3, d_rawd, nullptr, net->red_scratch);
-        if (rc) return rc;
-        if ((rc = conv_wgrad(net, st, b.c3, b.a2, nullptr, d_raw3))) return rc;
-        d_a2 = next_gbuf(net, dz, d_raw3, d_rawd);
-        if ((rc = conv_dgrad(net, st, b.c3, d_raw3, nullptr, d_a2))) return rc;
-        scratch_a = d_raw3;                                       // d_raw3 is dead from here on
+        if ((rc = launch_bn_bwd(st, dz, nullptr, nullptr, sd, nullptr, 0, Pout, b.cout, net->bwd_partial, b.bd.coef, nullptr, net->G + b.bd.g_off,
+                                net->G + b.bd.b_off, nullptr, nullptr, d_rawd, nullptr, nullptr, net->red_scratch))) return rc;
     }
     // bn2 + relu, in place.  The ReLU mask is recomputed from raw2 (raw*scale+shift > 0 <=> a2 > 0: bf16 rounding cannot
     // flush a positive fp32 to zero) instead of reading a2: one tensor read less in each of the two passes.
@@ -772,7 +729,7 @@ extern "C" int dali_debug_resnet_backward_block(dali_resnet* net, void* stream, 
 }
 
 // Debug/inspection: device pointer + byte size of a named intermediate (valid after a forward).
-// Names: raw0, pool0, feat, grad_cur (gradient wrt the input of the last block processed by backward), block<i>.{raw1,raw2,raw3,rawd,y}, block<i>.bn{1,2,3,d}.{scale,shift,mean,invstd}, bn1.{...}
+// Names: raw0, pool0, feat, grad_cur (gradient wrt the input of the last block processed by backward), block<i>.{raw1,raw2,rawd,y}, block<i>.bn{1,2,3,d}.{scale,shift,mean,invstd}, bn1.{...}
 extern "C" int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void** ptr, int64_t* bytes) {
     DALI_REQUIRE(net && name && ptr && bytes && net->arena, "dali_resnet_debug_tensor: bad argument / net not bound");
     const std::string n(name);
@@ -798,7 +755,6 @@ extern "C" int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void
                 const size_t pin = N * b.hin * b.win, pout = N * b.hout * b.wout;
                 if (f == "raw1") { *ptr = b.raw1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }
                 if (f == "raw2") { *ptr = b.raw2; *bytes = (int64_t)(pout * b.width * 2); return DALI_OK; }
-                if (f == "raw3" && !b.lin3) { *ptr = b.raw3; *bytes = (int64_t)(pout * b.cout * 2); return DALI_OK; }
                 if (f == "rawd" && b.has_ds) { *ptr = b.rawd; *bytes = (int64_t)(pout * b.cout * 2); return DALI_OK; }
                 if (f == "y") { *ptr = b.y; *bytes = (int64_t)(pout * b.cout * 2); return DALI_OK; }
                 if (f == "d_raw1" && b.dbg_d_raw1) { *ptr = b.dbg_d_raw1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }

@@ -13,8 +13,8 @@
 //     are 16 CONTIGUOUS channels of one pixel;
 //   * the bf16 results of the 5 convolution rows go to an LDS tile as order-preserving 16-bit keys of sign(scale) * raw, the pool is nine
 //     packed integer maxima per 8 channels, and bn1's scale / shift act on the selected element only.
-// Two 4-wave workgroups per CU (256 registers per wave: the weights alone take 112).  Measured at batch 500 (scripts/bench_stem.py, the
-// kernel's DALI_STEM_ABLATE switches): 170-190 us against 296 + 168 us of the convolution + pool launches; per tile the MFMA pipe (2240 cycles),
+// Two 4-wave workgroups per CU (256 registers per wave: the weights alone take 112).  Measured at batch 500 (scripts/bench_stem.py, and
+// ablation builds of the kernel, since removed): 170-190 us against 296 + 168 us of the convolution + pool launches; per tile the MFMA pipe (2240 cycles),
 // the LDS port (270 KB = 2100 cycles: 140 KB of B fragments, 74 KB of pool reads, 40 KB of tile writes, 16 KB of patch) and the vector ALU
 // (~2500 cycles of keys, maxima and index arithmetic) each need ~60 us and two waves per SIMD overlap them only in part.
 #include "common.h"
@@ -45,7 +45,6 @@ struct StemArgs {
     uint16_t* out;            // [N][Ho][Wo][64]
     int N, Hp, Wp, Wc, Ho, Wo, tiles;            // Wc = 2 Wo convolution columns; tiles = N * Ho / 2
     int lwo;                  // log2(Wo): W is 32, 64 or 128
-    int ablate;               // diagnostic (DALI_STEM_ABLATE, results wrong): 1 no pool stage, 2 no output stage of the groups, 4 no MFMAs, 8 no prefetch requests
 };
 
 constexpr int SF_THREADS = 256, SF_NST = 4, SF_PATCH_ROWS = 15, SF_CONV_ROWS = 5;
@@ -148,12 +147,10 @@ __global__ __launch_bounds__(SF_THREADS, 2) void stem_conv_bn_pool_kernel(StemAr
             f32x4_t acc[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            if (!(a.ablate & 4)) {
 #pragma unroll
             for (int r = 0; r < 7; ++r)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[i][r], B[r], acc[i], 0, 0, 0);
-            }
             if (g + 4 < ngroups) {
                 const unsigned char* b0 = b_base(g + 4);
                 B[0] = *reinterpret_cast<const bf16x8_t*>(b0);
@@ -161,7 +158,6 @@ __global__ __launch_bounds__(SF_THREADS, 2) void stem_conv_bn_pool_kernel(StemAr
             }
             __builtin_amdgcn_sched_barrier(0);
             const int px = cr * a.Wc + wc0 + n16;
-            if (!(a.ablate & 2)) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 uint32_t k[4];
@@ -172,17 +168,16 @@ __global__ __launch_bounds__(SF_THREADS, 2) void stem_conv_bn_pool_kernel(StemAr
                 }
                 *reinterpret_cast<uint4*>(ctile + px * 128 + (((2 * q + h) ^ (px & 7)) << 4)) = make_uint4(k[0], k[1], k[2], k[3]);
             }
-            }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (more) deposit(sf_smem + (buf ^ 1) * patch_pitch, st);
-        if (t + 2 * (int)gridDim.x < a.tiles && !(a.ablate & 8)) request(t + 2 * gridDim.x, st);
+        if (t + 2 * (int)gridDim.x < a.tiles) request(t + 2 * gridDim.x, st);
         asm volatile("" ::: "memory");             // (the compiler otherwise sinks these LDS writes below the pool's stores)
         // ---- 3x3 / stride 2 max-pool of the tile: window rows / columns outside the image are clamped onto a neighbour inside the window ----
         const int n = t / tiles_per_img, i0 = (t - n * tiles_per_img) * 2;
         const int items = 2 * a.Wo * 8;
-        for (int it = tid; it < items && !(a.ablate & 1); it += SF_THREADS) {
+        for (int it = tid; it < items; it += SF_THREADS) {
             const int cc = it & 7, pix = it >> 3;
             const int pr = pix >> a.lwo, pc = pix - (pr << a.lwo);
             int tr[3] = {2 * pr, 2 * pr + 1, 2 * pr + 2};
@@ -398,7 +393,6 @@ int launch_stem_conv_bn_pool(hipStream_t st, const uint16_t* ximg, const uint16_
     a.tiles = N * (a.Ho / 2);
     a.lwo = W == 32 ? 3 : (W == 64 ? 4 : 5);
     const int lds = 2 * SF_THREADS * SF_NST * 16 + SF_CONV_ROWS * a.Wc * 128 + 512;
-    a.ablate = DALI_ENV_INT("DALI_STEM_ABLATE", 0);
     DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_conv_bn_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)));
     const int n_cus = stem_cu_count();
     if (n_cus <= 0) { set_error("stem_conv_bn_pool: device query failed"); return DALI_ERR_HIP; }

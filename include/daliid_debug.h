@@ -1,5 +1,5 @@
 /* daliid_debug.h -- diagnostic entry points of libdaliid_hip.so.  NOT part of the drop-in surface (include/daliid.h):
- * nothing under daliid_amd/ binds them; scripts/ (A/B timing, in-kernel stamps) and two tests do, through ctypes.
+ * nothing under daliid_amd/ binds them; scripts/ (timing, in-kernel stamps) and tests do, through ctypes.
  * Declared here so that the shared library exports nothing that no header names (tests/test_abi.py compares the
  * two headers with `nm -D` of the library).
  */
@@ -10,8 +10,8 @@
 extern "C" {
 #endif
 
-/* the DALI_* A/B switches (daliid_amd/csrc/common.h) are re-read from the environment at their next use, so that one
- * process can time two variants back to back on the same box */
+/* the DALI_* switches that select a reference path (DALI_TRAIN_STEM, DALI_EVAL_STEM, DALI_PAIRDIST_SMALL; daliid_amd/csrc/common.h)
+ * are re-read from the environment at their next use, so that one process can run both paths back to back */
 int dali_debug_reload_env(void);
 
 /* device buffer of 12 x uint64 per workgroup that the convolution / weight-gradient kernels fill with s_memrealtime

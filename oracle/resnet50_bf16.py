@@ -74,10 +74,9 @@ def _bn_train(u, uq, bn, eps=1e-5):
 
 def stores_raw3(blk):
     """Does the HIP plan store conv3's output of this bottleneck in bf16?  Not where bn3 runs through the moments of a2 (csrc/bnlin.hip):
-    blocks whose width is a multiple of 32 and at most DALI_BNLIN_MAXW (default 512 = every block of ResNet-50; resnet_plan.hip)."""
-    import os
+    blocks whose width is a multiple of 32 and at most 512 (every block the plan builds; resnet_plan.hip)."""
     w = blk.conv3.in_channels
-    return not (w % 32 == 0 and w <= int(os.environ.get("DALI_BNLIN_MAXW", "512")))
+    return not (w % 32 == 0 and w <= 512)
 
 
 def ds_through_moments(blk, first_of_net):
@@ -147,9 +146,8 @@ def cat_eval_supported(blk, n_pixels, n_cus=256):
     `cat_eval`, conv.hip conv_cat_act_supported)?  Stride-1 branch, channel counts multiples of 64, and a size one of the two kernels with that
     size the persistent streaming kernel takes with a split weight image: K = 2 (w + cin) <= 256 and at least two 128 x 128 tiles per CU.
     ResNet-50 at 256 x 128: layer1's first block."""
-    import os
     d = blk.downsample
-    if d is None or d[0].stride != (1, 1) or stores_raw3(blk) or os.environ.get("DALI_EVAL_FUSED", "1") == "0" or os.environ.get("DALI_EVAL_CAT", "1") == "0":
+    if d is None or d[0].stride != (1, 1) or stores_raw3(blk):
         return False
     w, cin, C = blk.conv3.in_channels, d[0].in_channels, blk.conv3.out_channels
     if w % 64 or cin % 64 or C % 128:

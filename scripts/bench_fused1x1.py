@@ -1,6 +1,6 @@
 """The short-K 1x1 launches with the fused output stage (conv3 + bn3 + identity + ReLU forward; masked conv1 data gradient), per layer shape,
-with the persistent streaming kernel (csrc/fused1x1.h, DALI_CONV_PERSIST=1) and with the tile-per-workgroup kernels (0), alternating in one
-process; three operand sets rotate so that nothing is served from the Infinity Cache.   python scripts/bench_fused1x1.py [batch=256]"""
+on the kernels the library picks (the persistent streaming kernel of csrc/fused1x1.h for K <= 256, layer1-3; the tile-per-workgroup kernels for
+layer4); three operand sets rotate so that nothing is served from the Infinity Cache.   python scripts/bench_fused1x1.py [batch=256]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -47,13 +47,8 @@ for name, P, K, Cm in SHAPES:
         _lib.check(lib.dali_conv1x1_fused(L.ctx(xs[i].device), L.stream_ptr(), L.ptr(xs[i]), L.ptr(w), L.ptr(ys[i]), P, K, Cm, L.ptr(sc), L.ptr(sh), None,
                                           L.ptr(rs[i]), 1, None, None, None), "fused eval")
     byts = P * (K + 2 * Cm) * 2 + P * Cm // 8
-    out = []
     for rep in range(2):
-        for mode in ("0", "1"):
-            os.environ["DALI_CONV_PERSIST"] = mode
-            lib.dali_debug_reload_env()
-            out.append((mode, timeit(fwd), timeit(dgrad), timeit(evalf)))
-    for mode, tf, td, te in out:
-        print("%s P=%d K=%d Cm=%d persist=%s: fwd %.1f us (%.2f TB/s)  masked dgrad %.1f us  eval fwd %.1f us | byte roof at 6 TB/s %.1f us"
-              % (name, P, K, Cm, mode, tf, byts / tf / 1e6, td, te, byts / 6e6))
+        tf, td, te = timeit(fwd), timeit(dgrad), timeit(evalf)
+        print("%s P=%d K=%d Cm=%d: fwd %.1f us (%.2f TB/s)  masked dgrad %.1f us  eval fwd %.1f us | byte roof at 6 TB/s %.1f us"
+              % (name, P, K, Cm, tf, byts / tf / 1e6, td, te, byts / 6e6))
     del xs, rs, ys

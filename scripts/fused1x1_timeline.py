@@ -1,4 +1,5 @@
 """Where a workgroup of the persistent streaming kernel (csrc/fused1x1.h) spends its time: in-kernel s_memrealtime sums per phase (diagnostic).
+Layer1-3 only: the kernel takes K <= 256, so layer4's conv3 (K = 512) runs on the tile-per-workgroup kernels.
    python scripts/fused1x1_timeline.py [batch=256]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -6,9 +7,8 @@ import numpy as np, torch
 from daliid_amd import _lib, ops_nn as nn
 bf16 = torch.bfloat16
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-os.environ.setdefault("DALI_CONV_PERSIST_KMAX", "512")            # the diagnostic covers layer4 too (the plan keeps it on the tile-per-workgroup kernel)
 L = _lib.lib(); L.dali_debug_set_conv_stamps.argtypes = [ctypes.c_void_p]
-for name, P, K, Cm in [("layer1", B * 2048, 64, 256), ("layer2", B * 512, 128, 512), ("layer3", B * 128, 256, 1024), ("layer4", B * 128, 512, 2048)]:
+for name, P, K, Cm in [("layer1", B * 2048, 64, 256), ("layer2", B * 512, 128, 512), ("layer3", B * 128, 256, 1024)]:
     x = torch.randn(P, K, device="cuda").to(bf16); w = (torch.randn(Cm, K, device="cuda") / K ** 0.5).to(bf16)
     res = torch.randn(P, Cm, device="cuda").to(bf16)
     sc, sh = torch.rand(Cm, device="cuda") + 0.5, torch.randn(Cm, device="cuda")

@@ -39,8 +39,8 @@ md = open(src + "/pmc_traffic.md").read().rstrip()
 tot = pm["all_kernels_hbm_bytes_per_step"]
 open("profiles/%s_eval_forward.md" % RND, "w").write("""# Round %s -- inference forward (extractFeatures' batch of 500, `getFeatures.py:56-67`) kernel profile
 
-Produced by `bash scripts/profile_eval_forward.sh` on an MI355X box: `python scripts/time_eval_forward.py 500 20` plain (and with `DALI_EVAL_FUSED=0`: the
-training dataflow run with running statistics, for A/B), the same under `rocprofv3 --kernel-trace --stats`, and under `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE`,
+Produced by `bash scripts/profile_eval_forward.sh` on an MI355X box: `python scripts/time_eval_forward.py 500 20`, the same under
+`rocprofv3 --kernel-trace --stats`, and under `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE`,
 each in its own run (4 timed + 3 warm-up forwards per process); summaries by `scripts/kstats.py`, `scripts/pmc_traffic.py`, `scripts/make_profile_extra_md.py`.
 
 ```

@@ -1,5 +1,5 @@
 """Inference forward of the ResNet-50-ReID plan at batch B (extractFeatures forwards the train set / gallery at 500): ms per batch, images / s.
-   python scripts/time_eval_forward.py [B=500] [reps=20]      (DALI_EVAL_FUSED=0: the training dataflow, for A/B)"""
+   python scripts/time_eval_forward.py [B=500] [reps=20]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -19,5 +19,5 @@ with torch.no_grad():
     ev[1].record()
     torch.cuda.synchronize()
 ms = ev[0].elapsed_time(ev[1]) / n
-print("eval forward B=%d fused=%s: %.3f ms per batch -> %.0f img/s, %.1f TFLOP/s (8.107 GF/img)"
-      % (B, os.environ.get("DALI_EVAL_FUSED", "1"), ms, B / ms * 1e3, B * 8.107e9 / (ms * 1e-3) / 1e12))
+print("eval forward B=%d: %.3f ms per batch -> %.0f img/s, %.1f TFLOP/s (8.107 GF/img)"
+      % (B, ms, B / ms * 1e3, B * 8.107e9 / (ms * 1e-3) / 1e12))
