@@ -43,6 +43,9 @@ _SIGNATURES = {
     "dali_rank_shard_bins": [c_void_p] * 7 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p],
     "dali_rank_shard_finish": [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6,
     "dali_rerank": [c_void_p] * 5 + [c_int] * 4 + [ctypes.c_double, c_void_p],
+    "dali_roc_scratch_bytes": [c_int, c_int],
+    "dali_roc_build": [c_void_p] * 5 + [c_int, c_int, c_void_p, c_size_t, c_void_p],
+    "dali_roc_emit": [c_void_p] * 3 + [c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p],
     "dali_conv2d_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_int, c_void_p],
     "dali_conv2d_bn_act": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_int],
     "dali_stem_fused_supported": [c_int, c_int, c_int],
@@ -119,7 +122,7 @@ _SIGNATURES = {
     "dali_vit_backward_stages": [c_void_p, c_void_p, c_void_p, c_int, c_int],
     "dali_vit_set_drop_path": [c_void_p, c_void_p],
 }
-_RESTYPES = {"dali_last_error": ctypes.c_char_p, "dali_pairdist_operand_bytes": ctypes.c_size_t}
+_RESTYPES = {"dali_last_error": ctypes.c_char_p, "dali_pairdist_operand_bytes": ctypes.c_size_t, "dali_roc_scratch_bytes": ctypes.c_size_t}
 
 _lock = threading.Lock()
 _lib = None

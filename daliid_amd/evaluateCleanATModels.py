@@ -25,7 +25,9 @@ def getWeightsByMagnitude(subset, pooling, img_height, img_width, model, gpu_ind
 
 
 def calculateMetrics(queries_images, gallery_images, distmat, pooling=None, version=None, verbose=True):
-    """:259-276: market1501 CMC / mAP of a distance matrix, ranks 1/5/10/20 printed."""
+    """:259-276: market1501 CMC / mAP of a distance matrix, ranks 1/5/10/20 printed.  With ``pooling`` truthy, :276-292 as well: the
+    exact ROC over every query-gallery pair (ops_eval.roc_curve, bitwise sklearn's roc_curve) saved as FPR_<version>.npy,
+    TPR_<version>.npy and Thresholds_<version>.npy in the working directory."""
     cmc, mAP = ops_eval.rank_eval(distmat, queries_images[:, 1], gallery_images[:, 1], queries_images[:, 2], gallery_images[:, 2])
     if verbose:
         print("** Results **")
@@ -33,6 +35,14 @@ def calculateMetrics(queries_images, gallery_images, distmat, pooling=None, vers
         print("CMC curve")
         for r in (1, 5, 10, 20):
             print("Rank-{:<3}: {:.2%}".format(r, cmc[r - 1]))
+    if pooling:
+        nq, ng = queries_images.shape[0], gallery_images.shape[0]
+        print((nq, ng), (nq, ng))                       # the shapes of the reference's repeated id arrays (never built here)
+        fpr, tpr, thresholds = ops_eval.roc_curve(distmat, queries_images[:, 1], gallery_images[:, 1])
+        np.save("FPR_%s" % version, fpr)
+        np.save("TPR_%s" % version, tpr)
+        np.save("Thresholds_%s" % version, thresholds)
+        print("ROC Curve calculated!")
     return cmc, mAP
 
 

@@ -295,3 +295,145 @@ def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3):
                                        _lib.ptr(g_g, torch.float32, "g_g"), nq, ng, int(k1), int(k2), float(lambda_value), _lib.ptr(out)),
                "dali_rerank")
     return out.cpu().numpy() if on_host else out
+
+
+ROC_MAX_PAIRS = 2 ** 31 - 1   # nq * ng the counting kernels index with 32 bits (include/daliid.h, dali_roc_build)
+
+
+class UndefinedMetricWarning(UserWarning):
+    """Raised as sklearn.metrics does when a class is absent (its rate is then NaN)."""
+
+
+def _roc_inputs(distmat, q_pids, g_pids):
+    """-> (device fp32 [nq, ng] 16-byte aligned, q codes, g codes, on_host).  Host input is copied to the current device."""
+    if isinstance(distmat, torch.Tensor) and distmat.is_cuda:
+        dev, on_host = distmat.device, False
+    else:
+        dev, on_host = torch.device("cuda", torch.cuda.current_device()), True
+    shape = tuple(distmat.shape) if hasattr(distmat, "shape") else np.shape(distmat)
+    if len(shape) != 2:
+        raise ValueError("roc_curve: distmat must be 2-D, got shape %s" % (shape,))
+    nq, ng = shape
+    if nq * ng > ROC_MAX_PAIRS:
+        raise _lib.DaliError("roc_curve: %d x %d = %d pairs exceeds the supported 2^31 - 1 (documented limit)" % (nq, ng, nq * ng))
+    if nq == 0 or ng == 0:
+        raise ValueError("roc_curve: empty distance matrix")
+    qp, gp = factorize_ids(q_pids, g_pids)
+    if qp.size != nq or gp.size != ng:
+        raise ValueError("roc_curve: %d query ids and %d gallery ids for a %d x %d matrix" % (qp.size, gp.size, nq, ng))
+    d = distmat if isinstance(distmat, torch.Tensor) else torch.as_tensor(np.asarray(distmat))
+    d = d.to(dev, dtype=torch.float32).contiguous()
+    if d.data_ptr() % 16:
+        d = d.clone()
+    t = lambda a: torch.from_numpy(a).to(dev)
+    return d, t(qp), t(gp), on_host
+
+
+def _roc_build(d, qp, gp):
+    """dali_roc_build: -> (scratch, counts [n_drop, n_all, n_pos, n_neg] as ints).  Reads the five result words once."""
+    nq, ng = d.shape
+    L = _lib.lib()
+    nbytes = int(L.dali_roc_scratch_bytes(nq, ng))
+    scratch = torch.empty(nbytes, device=d.device, dtype=torch.uint8)
+    out = torch.empty(5, device=d.device, dtype=torch.int64)
+    _lib.check(L.dali_roc_build(_lib.ctx(d.device), _lib.stream_ptr(), _lib.ptr(d, torch.float32, "distmat"), _lib.ptr(qp, torch.int32),
+                                _lib.ptr(gp, torch.int32), nq, ng, _lib.ptr(scratch), nbytes, _lib.ptr(out)), "dali_roc_build")
+    n_drop, n_all, n_pos, n_neg, status = (int(v) for v in out.cpu().tolist())
+    if status == 1:
+        raise ValueError("Input contains NaN or infinity: a distance gives a non-finite score 1 - d/2")
+    if status != 0:
+        raise _lib.DaliError("dali_roc_build: internal count mismatch (status %d)" % status)
+    return scratch, (n_drop, n_all, n_pos, n_neg)
+
+
+def _roc_emit(scratch, d, n_points, drop_intermediate):
+    """dali_roc_emit into device arrays with the leading (+inf, 0, 0) point."""
+    nq, ng = d.shape
+    dev = d.device
+    thr = torch.empty(n_points + 1, device=dev, dtype=torch.float32)
+    fps = torch.empty(n_points + 1, device=dev, dtype=torch.int64)
+    tps = torch.empty(n_points + 1, device=dev, dtype=torch.int64)
+    thr[0], fps[0], tps[0] = float("inf"), 0, 0
+    _lib.check(_lib.lib().dali_roc_emit(_lib.ctx(dev), _lib.stream_ptr(), _lib.ptr(scratch), nq, ng, int(bool(drop_intermediate)), n_points,
+                                        _lib.ptr(thr[1:]), _lib.ptr(fps[1:]), _lib.ptr(tps[1:])), "dali_roc_emit")
+    return thr, fps, tps
+
+
+def roc_counts(distmat, q_pids, g_pids, drop_intermediate=True):
+    """Device side of ``roc_curve``: -> (thresholds fp32, fps int64, tps int64) CUDA tensors with the leading (+inf, 0, 0) point, for
+    curves too long to bring to the host.  The partition scratch (12 bytes per pair) is freed before this returns."""
+    d, qp, gp, _ = _roc_inputs(distmat, q_pids, g_pids)
+    scratch, (n_drop, n_all, _, _) = _roc_build(d, qp, gp)
+    out = _roc_emit(scratch, d, n_drop if drop_intermediate else n_all, drop_intermediate)
+    del scratch
+    return out
+
+
+def _rates(fps, tps):
+    """fpr, tpr as sklearn 1.7.2 forms them (float64 division by the last count; NaN and a warning for an absent class)."""
+    import warnings
+    fps, tps = fps.astype(np.float64), tps.astype(np.float64)
+    if fps[-1] <= 0:
+        warnings.warn("No negative samples in y_true, false positive value should be meaningless", UndefinedMetricWarning)
+        fpr = np.repeat(np.nan, fps.shape)
+    else:
+        fpr = fps / fps[-1]
+    if tps[-1] <= 0:
+        warnings.warn("No positive samples in y_true, true positive value should be meaningless", UndefinedMetricWarning)
+        tpr = np.repeat(np.nan, tps.shape)
+    else:
+        tpr = tps / tps[-1]
+    return fpr, tpr
+
+
+def roc_curve(distmat, q_pids, g_pids, drop_intermediate=True):
+    """ROC over every query-gallery pair, bitwise what sklearn.metrics.roc_curve(labels, 1 - distmat.ravel() / 2, pos_label=1,
+    drop_intermediate=...) returns with labels = (q_pids[i] == g_pids[j]) (evaluateCleanATModels.py:276-292; definition:
+    include/daliid.h, dali_roc_build).  distmat: CUDA tensor, or a host array / CPU tensor copied to the current device; converted to
+    fp32.  -> numpy (fpr float64, tpr float64, thresholds float32)."""
+    thr, fps, tps = roc_counts(distmat, q_pids, g_pids, drop_intermediate)
+    fpr, tpr = _rates(fps.cpu().numpy(), tps.cpu().numpy())
+    return fpr, tpr, thr.cpu().numpy()
+
+
+def verification_summary(fpr, tpr, thresholds, fpr_all, tpr_all, thresholds_all, fars):
+    """AUC, EER and TAR@FAR from the dropped curve (fpr, tpr, thresholds) and the undropped one (*_all):
+    auc = np.trapezoid(tpr, fpr); TAR@FAR=f = the largest tpr of an undropped point with fpr <= f, with the threshold of the first such
+    point that reaches it; EER on the first dropped segment (f0, t0)-(f1, t1) where fpr + tpr reaches 1: f0 + lam (f1 - f0),
+    lam = (1 - t0 - f0) / ((f1 - f0) + (t1 - t0)), threshold of the segment's end point."""
+    auc = float(np.trapezoid(tpr, fpr))
+    eer, eer_thr = float("nan"), float("nan")
+    reach = np.nonzero(fpr + tpr >= 1.0)[0]
+    if reach.size:
+        k = int(reach[0])
+        if k == 0:
+            eer, eer_thr = float(fpr[0]), float(thresholds[0])
+        else:
+            f0, t0, f1, t1 = fpr[k - 1], tpr[k - 1], fpr[k], tpr[k]
+            lam = (1.0 - t0 - f0) / ((f1 - f0) + (t1 - t0))
+            eer, eer_thr = float(f0 + lam * (f1 - f0)), float(thresholds[k])
+    tar = {}
+    for f in fars:
+        ok = np.nonzero(fpr_all <= f)[0]
+        if ok.size == 0:
+            tar[f] = (float("nan"), float("nan"))
+            continue
+        best = tpr_all[ok].max()
+        first = int(ok[np.nonzero(tpr_all[ok] == best)[0][0]])
+        tar[f] = (float(best), float(thresholds_all[first]))
+    return auc, eer, eer_thr, tar
+
+
+def verification_metrics(distmat, q_pids, g_pids, fars=(1e-1, 1e-2, 1e-3, 1e-4, 1e-5, 1e-6)):
+    """Verification summary of the pair ROC (roc_curve): one count on the device, both curves emitted from it.
+    -> dict n_pos, n_neg, auc, eer, eer_threshold, tar_at_far {far: (tar, threshold)} (definitions: verification_summary)."""
+    d, qp, gp, _ = _roc_inputs(distmat, q_pids, g_pids)
+    scratch, (n_drop, n_all, n_pos, n_neg) = _roc_build(d, qp, gp)
+    curves = []
+    for drop, n in ((True, n_drop), (False, n_all)):
+        thr, fps, tps = _roc_emit(scratch, d, n, drop)
+        curves.append(_rates(fps.cpu().numpy(), tps.cpu().numpy()) + (thr.cpu().numpy(),))
+        del thr, fps, tps
+    del scratch
+    auc, eer, eer_thr, tar = verification_summary(*curves[0], *curves[1], fars)
+    return dict(n_pos=n_pos, n_neg=n_neg, auc=auc, eer=eer, eer_threshold=eer_thr, tar_at_far=tar)

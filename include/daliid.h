@@ -151,6 +151,27 @@ int dali_rank_shard_finish(dali_ctx* ctx, void* stream, const int32_t* bins, con
 int dali_rerank(dali_ctx* ctx, void* stream, const float* q_g, const float* q_q, const float* g_g, int nq, int ng, int k1, int k2,
                 double lambda_value, float* out);
 
+/* Exact ROC curve over every query-gallery pair: sklearn.metrics.roc_curve(labels, scores, pos_label=1) of
+ * evaluateCleanATModels.calculateMetrics(pooling=...) (evaluateCleanATModels.py:276-292), by counting (no sort, no vendor library).
+ * Inputs (device): distmat [nq][ng] fp32, 16-byte aligned; q_ids [nq], g_ids [ng] int32 codes.  For every pair (i, j):
+ *   score s = fl32(1 - fl32(distmat[i][j] / 2)), label y = (q_ids[i] == g_ids[j]); every pair counts (no camera or junk filter).
+ * The curve: the distinct scores in descending order (-0 and +0 are one score), with fps / tps = the cumulative negative / positive
+ * counts up to and including each score.  drop_intermediate (applied when there are more than 2 points) keeps the first and the last
+ * point and every point j where the next point's increment (negatives, positives) differs from point j's, i.e. where np.diff(fps, 2)
+ * or np.diff(tps, 2) is non-zero.  The leading (0, 0, +inf) point and the division into rates are the caller's (bitwise sklearn 1.7.2).
+ *   dali_roc_scratch_bytes(nq, ng): bytes of the caller-owned scratch, 12 * nq * ng + 16 MiB + min(256, nq * ng, 4096) * 8 MiB (about
+ *                            14.1 GB at 1e9 pairs); 0 when the shape is not supported.  256-byte aligned; the library keeps none of it.
+ *   dali_roc_build  -> out[5] int64 (device): n_points with drop_intermediate, n_points without, n_pos, n_neg, status (0 ok, 1 = a
+ *                      non-finite score, 2 = internal count mismatch).  Nothing synchronises; the scratch then holds the curve.
+ *   dali_roc_emit   -> thresholds [n_points] fp32, fps / tps [n_points] int64 of the curve the build left in the scratch (the same
+ *                      scratch, unchanged), with or without drop_intermediate; n_points = out[0] or out[1] (writes stop there).
+ * Limits: nq, ng >= 1 (DALI_ERR_INVALID); nq * ng <= 2^31 - 1 (DALI_ERR_LIMIT).  Bitwise identical results run to run. */
+size_t dali_roc_scratch_bytes(int nq, int ng);
+int dali_roc_build(dali_ctx* ctx, void* stream, const float* distmat, const int32_t* q_ids, const int32_t* g_ids, int nq, int ng,
+                   void* scratch, size_t scratch_bytes, int64_t* out);
+int dali_roc_emit(dali_ctx* ctx, void* stream, const void* scratch, int nq, int ng, int drop_intermediate, int64_t n_points,
+                  float* thresholds, int64_t* fps, int64_t* tps);
+
 /* ---- training path: Encoders.ResNet50ReID trunk (Encoders.py:330-339) ----------------------------- *
  * Single-op entry points (the parity tests call these; the net plan below chains the same kernels).
  * Layouts: activations NHWC bf16; forward weights [cout][r][s][cin] bf16; dgrad weights
