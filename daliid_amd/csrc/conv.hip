@@ -2567,9 +2567,11 @@ int conv_pick_cfg(int Cm, int P, int K) {
 
     return CONV_128;
 }
-int igemm_conv_stat_tiles(int Cm, int P, int K) {
-    const int c = conv_pick_cfg(Cm, P, K);
-    return c == CONV_128 ? (P + 127) / 128 : (P + 255) / 256;
+// pixel tiles of a launch with BatchNorm statistics, the rows of its partial-sum slab.  With an operand transform (in_scale) the
+// register-staged kernels run: 128-pixel tiles for Cm > 64.  launch_igemm_conv_one refuses a statistics launch whose kernel disagrees.
+int igemm_conv_stat_tiles(int Cm, int P, int K, bool operand_transform) {
+    const int tn = (operand_transform && Cm > 64) || conv_pick_cfg(Cm, P, K) == CONV_128 ? 128 : 256;
+    return (P + tn - 1) / tn;
 }
 
 
@@ -2609,10 +2611,318 @@ void gemm_profile_end(hipStream_t st, int slot) {
     if (slot >= 0 && g_prof) (void)hipEventRecord(g_prof->ev[2 * slot + 1], st);
 }
 
+// ---- the launched GEMM kernel instantiations ------------------------------------------------------------------------------------------------
+// Each instantiation launched here is described once; the choosers (conv_choose, wgrad_choose) pick a description and gemm_launch launches it.
+enum GemmGrid {
+    GRID_XCD,           // xcd_tile_grid(tiles_m, tiles_n)
+    GRID_CLASSES,       // a stride-2 data gradient's parity classes (4 with sub == 2, else 1) of class_grid = xcd_tile_grid(...) workgroups each
+    GRID_CUS,           // one workgroup per CU (f1_cu_count): the persistent kernel
+    GRID_HALO,          // one workgroup per 256-pixel tile; the kernel takes (args, tiles_n)
+    GRID_SPLITS,        // weight gradient: tiles x splits
+    GRID_SPLITS8,       // the same rounded up to whole XCD groups of 8
+};
+struct GemmKernel {
+    const void* fn;
+    int block;                  // threads per workgroup
+    int lds;                    // dynamic LDS bytes; above 64 KiB also the MaxDynamicSharedMemorySize it opts in to (gemm_launch).  The persistent
+                                // kernel's: the most its K takes, f1_lds_bytes(3, f1_rb, Ck) at each launch
+    int tm, tn;                 // tile: output channels x pixels; weight gradient: Cm x Ntot columns
+    GemmGrid grid;
+    int plan_wgs = 0;           // weight gradient: the workgroups a split-K plan fills the chip with (wgrad_plan; 0: the caller's target)
+    int f1_rb = 0;              // the persistent kernel's result buffers (F1_RB)
+    mutable DeviceOnce once{};
+};
+template <class F> static const void* kfn(F* f) { return reinterpret_cast<const void*>(f); }
+constexpr int ring_lds(int tm, int tn, int k_tile, int stages) { return (tm + tn) * k_tile * 2 * stages; }      // a ring of bf16 A and B k-tiles
+constexpr int REG128_LDS = GemmCfg<128, 128, 1, 1, 1>::LDS_BYTES, REG64_LDS = GemmCfg<64, 256, 1, 1, 1>::LDS_BYTES;    // register-staged: 2 stages
+constexpr int DMA128_LDS = REG128_LDS / 2 * 3, DMA64_LDS = REG64_LDS / 2 * 3;                                          // LDS-DMA: 3 stages
+constexpr int HALO64_LDS = (3 * 64 * 64 + HALO64_PX * 64) * 2;                                                         // 3 weight stages + the halo patch
+
+// Forward, data gradient and linear layers (IGemmArgs).  EPI 1: linear-layer extras; 3: the fused output stage; 4: the parity-class store with
+// scattered pixel rows; 5: the fused stage's scale / shift / bias / ReLU alone.  SRC2: a second operand tensor (IGemmArgs::X2).
+static const GemmKernel
+    // 128 x 128 / 4 waves, k-tile 32: register-staged (an operand transform, tensors beyond 2 GiB) and LDS-DMA
+    CONV128_BN{kfn(&igemm_conv_kernel<128, 128, true>), 256, REG128_LDS, 128, 128, GRID_XCD},
+    CONV128{kfn(&igemm_conv_kernel<128, 128, false>), 256, REG128_LDS, 128, 128, GRID_XCD},
+    DMA128{kfn(&igemm_conv_dma_kernel<128, 128, 3>), 256, DMA128_LDS, 128, 128, GRID_XCD},
+    DMA128_LIN{kfn(&igemm_conv_dma_kernel<128, 128, 3, 1>), 256, DMA128_LDS, 128, 128, GRID_XCD},
+    DMA128_FUSED{kfn(&igemm_conv_dma_kernel<128, 128, 3, 3>), 256, DMA128_LDS, 128, 128, GRID_XCD},
+    DMA128_CLS{kfn(&igemm_conv_dma_kernel<128, 128, 3, 4>), 256, DMA128_LDS, 128, 128, GRID_CLASSES},
+    DMA128_SRC2{kfn(&igemm_conv_dma_kernel<128, 128, 3, 0, true>), 256, DMA128_LDS, 128, 128, GRID_XCD},
+    // 64 x 256 for Cm <= 64
+    CONV64_BN{kfn(&igemm_conv_kernel<64, 256, true>), 256, REG64_LDS, 64, 256, GRID_XCD},
+    CONV64{kfn(&igemm_conv_kernel<64, 256, false>), 256, REG64_LDS, 64, 256, GRID_XCD},
+    DMA64{kfn(&igemm_conv_dma_kernel<64, 256, 3>), 256, DMA64_LDS, 64, 256, GRID_XCD},
+    DMA64_LEAN{kfn(&igemm_conv_dma_kernel<64, 256, 3, 5>), 256, DMA64_LDS, 64, 256, GRID_XCD},
+    DMA64_SRC2{kfn(&igemm_conv_dma_kernel<64, 256, 3, 0, true>), 256, DMA64_LDS, 64, 256, GRID_XCD},
+    // layer1's 3x3 (Cm = Cin = 64, K = 576): k-tile 64 = one full line per pixel and tap, 4 MFMA waves + 4 DMA waves, 2-stage ring,
+    // two workgroups per CU: 94 -> 77 us forward, 90 -> 73 us data gradient (unspecialised k-tile 64: 84 / 79; 3-stage ring, one
+    // workgroup per CU: 122 / 118).  (8 producer waves instead of 4: 74 -> 78 us; the L2 -> LDS feed, 9 taps per pixel, bounds it, not the
+    // issue of the DMA pieces)
+    K64S64{kfn(&igemm_conv_k64s_kernel<1, 4, 4, 2>), 512, ring_lds(64, 256, 64, 2), 64, 256, GRID_XCD},
+    // the same problem on halo64_ok's grids: the halo patch of a 256-pixel tile fetched once, taps read it at shifted pixels
+    HALO64{kfn(&igemm_conv_halo64_kernel<3>), 512, HALO64_LDS, 64, 256, GRID_HALO},
+    HALO64_LEAN{kfn(&igemm_conv_halo64_kernel<3, 5>), 512, HALO64_LDS, 64, 256, GRID_HALO},
+    // 128 x 256 / 8 waves, k-tile 32, 3-stage ring
+    WG128{kfn(&igemm_conv_wg_kernel<2, 4, 3>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
+    WG128_LIN{kfn(&igemm_conv_wg_kernel<2, 4, 3, 1>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
+    WG128_FUSED{kfn(&igemm_conv_wg_kernel<2, 4, 3, 3>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
+    WG128_CLS{kfn(&igemm_conv_wg_kernel<2, 4, 3, 4>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_CLASSES},
+    // 256 x 256 / 16 waves, k-tile 32, 4-stage ring
+    WG256{kfn(&igemm_conv_wg_kernel<4, 4, 4>), 1024, ring_lds(256, 256, 32, 4), 256, 256, GRID_XCD},
+    // 128 x 256 k-tile 64, wave-specialised (8 MFMA + 8 DMA waves), 3-stage ring
+    K64S{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
+    K64S_LIN{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 1>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
+    K64S_LEAN{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 5>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
+    K64S_SRC2{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 0, true>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
+    // 256 x 256 k-tile 64, 16 waves of 64 x 64, 2-stage ring.  (8 waves with 128 x 64 per wave, 25 % fewer LDS fragment bytes, 192 VGPRs: measured
+    // 3-5 % slower than 16 waves of 64 x 64) and the wave-specialised form (8 consumers of 128 x 64 + 4 producers, 168 VGPRs, 2-stage ring): -2 % on
+    // layer4's 3x3, +14 % on the stride-2 downsample dgrad -- a 256 x 256 tile has no room for producers beside 16 consumers (1024 threads per workgroup)
+    K64{kfn(&igemm_conv_k64_kernel<4, 4, 2>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
+    K64_LIN{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 1>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
+    K64_FUSED{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 3>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
+    K64_CLS{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 4>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_CLASSES},
+    K64_SRC2{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 0, true>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
+    K64_FUSED_SRC2{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 3, true>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
+    // 256 x 320 k-tile 64 (conv_prefers_320)
+    K64_320{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 5, 1>), 1024, ring_lds(256, 320, 64, 2), 256, 320, GRID_XCD};
+
+// the persistent streaming kernel (fused1x1.h): two result buffers for K <= 128, else one.  It takes launches with a residual, an output mask or
+// mask bits, or with a second operand tensor and none of the three: F1[K > 128][residual][out_mask][bits_out], the none slot the SRC2 instantiation
+template <int RB, bool RES, bool OM, bool BITS, bool SRC2 = false>
+static GemmKernel f1_kernel() {
+    return {kfn(&fused1x1_persist_kernel<3, RB, RES, OM, BITS, SRC2>), (F1_NC + F1_NP + F1_NR) * 64, f1_lds_bytes(3, RB, RB == 2 ? 128 : F1_KMAX),
+            F1_TM, F1_TN, GRID_CUS, 0, RB};
+}
+static const GemmKernel F1[2][2][2][2] = {
+    {{{f1_kernel<2, false, false, false, true>(), f1_kernel<2, false, false, true>()}, {f1_kernel<2, false, true, false>(), f1_kernel<2, false, true, true>()}},
+     {{f1_kernel<2, true, false, false>(), f1_kernel<2, true, false, true>()}, {f1_kernel<2, true, true, false>(), f1_kernel<2, true, true, true>()}}},
+    {{{f1_kernel<1, false, false, false, true>(), f1_kernel<1, false, false, true>()}, {f1_kernel<1, false, true, false>(), f1_kernel<1, false, true, true>()}},
+     {{f1_kernel<1, true, false, false>(), f1_kernel<1, true, false, true>()}, {f1_kernel<1, true, true, false>(), f1_kernel<1, true, true, true>()}}}};
+
+// Weight gradient (WGradArgs): split-K slabs of Cm x Ntot tiles.
+static const GemmKernel
+    WG_BN{kfn(&igemm_wgrad_kernel<true>), 256, 0, 128, 128, GRID_SPLITS},          // register-staged: an operand transform (in_scale)
+    WG_PLAIN{kfn(&igemm_wgrad_kernel<false>), 256, 0, 128, 128, GRID_SPLITS},      // register-staged: tensors beyond 2 GiB
+    // the 3x3 halo kernel (128 co x 64 ci x 9 taps per block), one 8-wave block per CU.  3 stages x 24 KiB (4 and 5 measured the same, before and
+    // after the inline-asm reads: the k-step is bound by its 26 transposing reads + 36 MFMAs per wave, two waves per SIMD).  (measured and removed,
+    // round 3: the same kernel software-pipelined -- layer4 conv2 161 us against 152 -- and as two wave groups half a k-step apart, 195 us.  PMC on
+    // this kernel at the layer4 shape: matrix pipe busy 45 % of the SIMD cycles, LDS active 23 % (28 % of that bank conflicts), waves parked at
+    // s_waitcnt / barriers 26 % of their cycles: neither the issue order nor the LDS bounds it.)
+    WG_3X3{kfn(&igemm_wgrad3x3_kernel<3>), 512, 3 * W3_STAGE * 2, 128, 9 * 64, GRID_SPLITS8, 256};
+static const GemmKernel WG_DMA[2] = {         // [colsum]: 128 x 128 / 4 waves, LDS-DMA
+    {kfn(&igemm_wgrad_dma_kernel<false>), 256, 0, 128, 128, GRID_SPLITS8},
+    {kfn(&igemm_wgrad_dma_kernel<true>), 256, 0, 128, 128, GRID_SPLITS8}};
+static const GemmKernel WG_WG[2] = {          // [colsum]: 128 x 256 / 8 waves, 3 stages x 3 images x 8 KiB, two workgroups per CU
+    {kfn(&igemm_wgrad_wg_kernel<2, 4, 3>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_SPLITS8, 512},
+    {kfn(&igemm_wgrad_wg_kernel<2, 4, 3, true>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_SPLITS8, 512}};
+// [flat][colsum]: the pipelined wave-specialised 128 x 256 kernel, 6 stages x 3 images x 8 KiB, one workgroup per CU.  (measured, interleaved:
+// plain [P][C] operands 92 us with 4 consumers of 128 x 64 + 4 producers against 94 with 8 + 8 and 105 before; strided / gathered operands 83 us
+// with 4 producers of 6 pieces, 75 with 8 of 3)
+static const GemmKernel WG_P[2][2] = {
+    {{kfn(&igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6>), 1024, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256},
+     {kfn(&igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6, true>), 1024, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256}},
+    {{kfn(&igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6>), 512, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256},
+     {kfn(&igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6, true>), 512, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256}}};
+
+// A chosen launch: the kernel, its tile counts and grid; with k == nullptr a refusal (rc, and the message format `why` of one int argument)
+struct GemmChoice {
+    const GemmKernel* k = nullptr;
+    int tiles_m = 0, tiles_n = 0, lds = 0, class_grid = 0;
+    unsigned grid = 0;
+    int rc = DALI_OK, why_arg = 0;
+    const char* why = nullptr;
+    GemmChoice() = default;
+    GemmChoice(int rc_, const char* why_, int why_arg_ = 0) : rc(rc_), why_arg(why_arg_), why(why_) {}
+    int refuse() const { set_error(why, why_arg); return rc; }
+};
+// kernel k on a rows x cols output; mult: the parity classes (GRID_CLASSES), the CUs (GRID_CUS) or the splits (GRID_SPLITS*)
+static GemmChoice gemm_place(const GemmKernel& k, int rows, int cols, int mult, int Ck) {
+    GemmChoice c;
+    c.k = &k;
+    c.tiles_m = (rows + k.tm - 1) / k.tm;
+    c.tiles_n = (cols + k.tn - 1) / k.tn;
+    c.lds = k.f1_rb ? f1_lds_bytes(3, k.f1_rb, Ck) : k.lds;
+    switch (k.grid) {
+        case GRID_XCD: c.grid = xcd_tile_grid(c.tiles_m, c.tiles_n); break;
+        case GRID_CLASSES: c.class_grid = xcd_tile_grid(c.tiles_m, c.tiles_n); c.grid = mult * c.class_grid; break;
+        case GRID_CUS: c.grid = mult; break;
+        case GRID_HALO: c.grid = c.tiles_n; break;
+        case GRID_SPLITS: c.grid = c.tiles_m * c.tiles_n * mult; break;
+        case GRID_SPLITS8: c.grid = (c.tiles_m * c.tiles_n * mult + 7) / 8 * 8; break;
+    }
+    return c;
+}
+// the one launch site: the kernel's LDS opt-in (above the default 64 KiB) once per device, then (args, tiles_m, tiles_n), or (args, tiles_n) for the halo kernels
+template <class Args>
+static int gemm_launch(hipStream_t st, const GemmChoice& c, Args& args) {
+    const GemmKernel& k = *c.k;
+    DeviceOnce::Guard once(k.once);
+    if (k.lds > 64 * 1024 && once.first()) {
+        DALI_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
+        once.done();
+    }
+    int tiles_m = c.tiles_m, tiles_n = c.tiles_n;
+    void* tile_args[] = {&args, &tiles_m, &tiles_n};
+    void* halo_args[] = {&args, &tiles_n};
+    (void)hipLaunchKernel(k.fn, dim3(c.grid), dim3(k.block), k.grid == GRID_HALO ? halo_args : tile_args, c.lds, st);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+
 // Host-side launchers shared with the net plan (resnet_plan.hip).
-static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a);
-static bool narrow_cm(int Cm) { return Cm <= 64; }
 static unsigned long long* g_conv_stamps = nullptr;      // diagnostic only, see dali_debug_set_conv_stamps
+
+// the LDS-DMA kernels address a tensor with 32-bit byte offsets through a buffer descriptor
+static bool dma_addressable(long long bytes) { return bytes < 0x7ff00000ll; }
+// the gathered tensor (every image the P pixels touch) and a second tensor of other_bytes within the descriptors' reach
+static bool gather_dma_ok(const GatherGeom& g, int P, long long other_bytes) {
+    return dma_addressable(g.img_pitch * 2 * ((P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout))) && dma_addressable(other_bytes);
+}
+// the forward / data gradient's LDS-DMA kernels: no operand transform, X and W within reach
+static bool conv_dma_ok(const IGemmArgs& a) { return !a.in_scale && gather_dma_ok(a.g, a.P, (long long)a.Cm * a.g.R * a.g.S * a.g.Ck * 2); }
+// a plain [P][Ck] operand: 1x1, stride 1, no padding, dense rows
+static bool plain_rows(const GatherGeom& g) {
+    return g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0 && g.pix_pitch == g.Ck && g.row_pitch == g.Win * g.Ck &&
+           g.img_pitch == (long long)g.Hin * g.Win * g.Ck && g.Hin == g.Hout && g.Win == g.Wout;
+}
+// the halo kernels' problem: 64 -> 64 channels, 3x3 / stride 1 / pad 1 over dense 16- or 32-wide power-of-two images of whole 256-pixel tiles
+static bool halo64_ok(const IGemmArgs& a) {
+    const GatherGeom& g = a.g;
+    return a.Cm == 64 && g.Ck == 64 && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && !g.sub && (g.Wout == 16 || g.Wout == 32) &&
+           ilog2_exact(g.Hout * g.Wout) >= 8 && g.Hin == g.Hout && g.Win == g.Wout && g.pix_pitch == 64 && g.row_pitch == g.Win * 64 &&
+           g.img_pitch == (long long)g.Hin * g.Win * 64 && a.P % 256 == 0;
+}
+
+// CUs of the current device rounded down to a multiple of 8 (the persistent streaming kernel's grid: one workgroup per CU, whole XCD groups)
+static int f1_cu_count() {
+    static int n_cus = 0;
+    if (!n_cus) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { set_error("conv: device query failed"); return -1; }
+        n_cus = v > 8 ? v & ~7 : 8;
+    }
+    return n_cus;
+}
+// the persistent kernel takes at least 2 tiles per CU, and channel tiles that divide an XCD's CUs (every workgroup keeps one channel tile)
+static bool f1_fills(int Cm, int P, int n_cus) {
+    const int tiles_m = Cm / F1_TM, tiles_n = (P + F1_TN - 1) / F1_TN;
+    return n_cus > 0 && (long long)tiles_m * tiles_n >= 2ll * n_cus && (n_cus / 8) % tiles_m == 0;
+}
+// [X | X2] (c1 + c2 channels, `parts` times against a split weight image) with the scale / shift / ReLU output stage at this size: the persistent
+// kernel (K <= 256) or the 256 x 256 k-tile-64 kernel (K >= 1024, one weight image)
+static bool cat_act_ok(int Cm, int c1, int c2, int P, int parts, int n_cus) {
+    const int K = parts * (c1 + c2);
+    if (parts != 1 && parts != 2) return false;
+    if ((c1 & 63) || (c2 & 63) || (Cm % 128) || !dma_addressable((long long)P * Cm * 2) || !dma_addressable((long long)P * K * 2)) return false;
+    if (K <= F1_KMAX) return f1_fills(Cm, P, n_cus);
+    return parts == 1 && K >= 1024 && conv_pick_cfg(Cm, P, K) == CONV_256x256;
+}
+// (dali_conv1x1_cat_act; the net plan asks before it folds a downsample branch into conv3)
+bool conv_cat_act_supported(int Cm, int c1, int c2, int P, int parts) { return cat_act_ok(Cm, c1, c2, P, parts, f1_cu_count()); }
+
+// The kernel, tiles and grid of one forward / data-gradient / linear-layer GEMM (IGemmArgs after the parity split), or the refusal.  No HIP
+// calls; n_cus is the persistent kernel's grid (f1_cu_count).
+static GemmChoice conv_choose(const IGemmArgs& a, int n_cus) {
+    const GatherGeom& g = a.g;
+    const bool in_bn = a.in_scale != nullptr, narrow = a.Cm <= 64, dma_ok = conv_dma_ok(a);
+    const int K = g.nr * g.ns * g.Ck;               // reduction length actually visited
+    // fused output stage (IGemmArgs::out_scale ... out_mask): its own instantiations of the kernels, so that the convolutions' hot
+    // instantiations compile none of it (code that is never executed still cost their register allocation 0.4-0.8 ms per step)
+    const bool fused = a.out_scale || a.out_shift || a.out_relu || a.bits_out || a.out_mask || a.res_scale;
+    const bool lin = a.act != 0 || a.O2 != nullptr || a.dact_pre != nullptr || a.row_scale != nullptr;      // linear-layer epilogue extras: the LIN instantiations
+    int cfg = conv_pick_cfg(a.Cm, a.P, K);
+    if (dma_ok && !a.stats && !fused && !g.sub && g.Ck % 64 == 0 && (a.Cm & 7) == 0 && conv_prefers_320(a.Cm, a.P, K)) cfg = CONV_256x320;
+    if (!dma_ok && !in_bn && a.stats && (cfg == CONV_128x256 || cfg == CONV_256x256))
+        return GemmChoice(DALI_ERR_LIMIT, "conv: tensors beyond 2 GiB are not supported together with the BatchNorm statistics epilogue");
+    // k-tile 64 pays where the main loop dominates (K >= 1024); with a short K or the 128 x 128 tile the smaller k-tile's 2-3
+    // co-resident workgroups overlap their epilogues better (measured per layer: 256 x 256 -12..-15 %; 128 x 256 wave-specialised
+    // -18..-26 % on the 3x3 layers, -10 % on the K = 1024 1x1 layers; K = 512 layers +12..+20 % with either k-tile-64 kernel)
+    bool k64 = dma_ok && !narrow && g.Ck % 64 == 0;
+    const bool narrow_k64 = dma_ok && narrow && g.Ck % 64 == 0 && K >= 512 && !a.X2;     // layer1's 3x3 (Cin = 64: a pixel is one line)
+    if (a.X2) {
+        // a fused output stage beside X2: shift (+ scale) and ReLU only (the inference forward's conv3 + downsample branch as one GEMM), on the two
+        // kernels that have that instantiation: the persistent streaming kernel (K <= 256) and the 256 x 256 k-tile-64 kernel
+        const bool fo_simple = !a.bits_out && !a.out_mask && !a.res_scale && !a.Res && (a.out_scale || a.out_shift || a.out_relu);
+        const int xr = a.x_rep > 1 ? a.x_rep : 1, c2 = g.Ck / xr - a.Ck1;
+        if (xr > 1 && !(fo_simple && g.Ck % xr == 0 && cat_act_ok(a.Cm, a.Ck1, c2, a.P, xr, n_cus) && g.Ck <= F1_KMAX))
+            return GemmChoice(DALI_ERR_INVALID, "conv: split weight images (x_rep = %d) are served by the persistent streaming kernel only (K <= 256, >= 2 tiles per CU)", xr);
+        if (fo_simple && ((a.Ck1 & 63) || (c2 & 63) || (a.Cm % 128)))
+            return GemmChoice(DALI_ERR_INVALID, "conv: two operand tensors with a fused output stage need channel counts that are multiples of 64 and Cm %% 128 == 0");
+        if (in_bn || !dma_ok || a.stats || (fused && !fo_simple) || lin || g.sub || g.R != 1 || g.S != 1 || g.stride != 1 || g.pad != 0 || a.Ck1 <= 0 ||
+            a.Ck1 >= g.Ck / xr || (a.Ck1 & 31) || (c2 & 31) || (a.Cm & 7))
+            return GemmChoice(DALI_ERR_INVALID, "conv: a second operand tensor needs a plain 1x1 / stride 1 problem with both channel counts multiples of 32");
+        if ((a.Ck1 & 63) || (c2 & 63)) k64 = false;
+    }
+    if (k64 && cfg != CONV_256x320 && !((K >= 1024 && (cfg == CONV_256x256 || cfg == CONV_128x256)) || (K >= 768 && cfg == CONV_256x256))) k64 = false;
+    // a second operand tensor is read by the SRC2 instantiations of the two k-tile-64 kernels (k64 still set) or, for every other choice, of the
+    // 128 x 128 / 64 x 256 LDS-DMA kernel
+    if (a.X2 && !narrow && !(k64 && (cfg == CONV_256x256 || cfg == CONV_128x256))) { cfg = CONV_128; k64 = false; }
+    auto use = [&](const GemmKernel& k) { return gemm_place(k, a.Cm, a.P, k.grid == GRID_CUS ? n_cus : (g.sub == 2 ? 4 : 1), g.Ck); };
+    if (fused) {
+        // (measured, round 4: the 128 x 128 tile for the short-K fused launches instead of 128 x 256: 15.87-15.90 against 15.82-15.84 ms per step)
+        if (in_bn || !dma_ok || (a.Cm & 7) || lin)
+            return GemmChoice(DALI_ERR_INVALID, "conv: the fused output stage needs Cm %% 8 == 0, tensors below 2 GiB, no operand transform and no linear-layer extras");
+        // the inference forward (dali_resnet_forward, training = 0) folds every BatchNorm + ReLU into its convolution's output stage, so the
+        // 3x3 kernels and the narrow 1x1 kernel have fused instantiations too (the train step never reaches them: its fused launches are the
+        // 1x1 conv3 forwards and the masked conv1 data gradients, Cm >= 256 and K <= 512)
+        // short-K 1x1 with a residual / mask stream: the persistent streaming kernel (fused1x1.h).  K <= 256: at K = 512 (layer4) its four ring
+        // producers cannot issue the 32 DMA pieces of a k-step as fast as the consumers multiply it (141 against 125 us; the block is capped at 16 waves)
+        if (plain_rows(g) && !g.sub && !a.res_mask && a.Cm % F1_TM == 0 && (g.Ck & 63) == 0 && g.Ck <= F1_KMAX && dma_addressable((long long)a.P * a.Cm * 2) &&
+            (a.Res || a.out_mask || a.bits_out || a.X2)) {
+            if (n_cus <= 0) return GemmChoice(DALI_ERR_HIP, "conv: device query failed");
+            if (f1_fills(a.Cm, a.P, n_cus)) return use(F1[g.Ck > 128][a.Res != nullptr][a.out_mask != nullptr][a.bits_out != nullptr]);
+        }
+        const bool lean = !a.Res && !a.out_mask && !a.bits_out && !a.res_mask && !a.res_scale && !a.X2;      // scale / shift / bias / ReLU only: the EPI = 5 instantiations
+        if (lean && narrow_k64 && halo64_ok(a)) return use(HALO64_LEAN);
+        if (lean && narrow) return use(DMA64_LEAN);
+        if (lean && k64 && cfg == CONV_128x256 && !g.sub) return use(K64S_LEAN);
+        if (a.X2) {
+            // two operand tensors + fused output: the 256 x 256 k-tile-64 kernel only (the dispatch above sends the short-K case to fused1x1)
+            if (!(k64 && cfg == CONV_256x256))
+                return GemmChoice(DALI_ERR_INVALID, "conv: two operand tensors with a fused output stage need K <= 256 or a 256 x 256 k-tile-64 problem (K >= 1024, Cm >= 512, >= 16384 pixels)");
+            return use(K64_FUSED_SRC2);
+        }
+        if (k64 && cfg == CONV_256x256) return use(K64_FUSED);
+        return use(cfg == CONV_128x256 || cfg == CONV_256x256 ? WG128_FUSED : DMA128_FUSED);
+    }
+    if (g.sub && dma_ok && !narrow && !lin && (a.Cm & 7) == 0) {        // a parity class of a stride-2 data gradient (EPI = 4)
+        if (k64 && cfg == CONV_256x256) return use(K64_CLS);
+        return use(cfg == CONV_128x256 || cfg == CONV_256x256 ? WG128_CLS : DMA128_CLS);
+    }
+    if (cfg == CONV_256x320) return use(K64_320);
+    if (k64 && cfg == CONV_256x256) return use(a.X2 ? K64_SRC2 : lin ? K64_LIN : K64);
+    if (k64 && cfg == CONV_128x256) return use(a.X2 ? K64S_SRC2 : lin ? K64S_LIN : K64S);
+    if (narrow_k64 && !lin && halo64_ok(a)) return use(HALO64);
+    if (narrow_k64) return use(K64S64);
+    if (narrow) return use(in_bn ? CONV64_BN : !dma_ok ? CONV64 : a.X2 ? DMA64_SRC2 : DMA64);
+    if (dma_ok && cfg == CONV_256x256) return use(WG256);
+    if (dma_ok && cfg == CONV_128x256) return use(lin ? WG128_LIN : WG128);
+    return use(in_bn ? CONV128_BN : !dma_ok ? CONV128 : a.X2 ? DMA128_SRC2 : lin ? DMA128_LIN : DMA128);
+}
+
+static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
+    IGemmArgs args = a;
+    args.g.lw = ilog2_exact(a.g.Wout);
+    args.g.lhw = ilog2_exact(a.g.Hout * a.g.Wout);
+    const GemmChoice c = conv_choose(args, f1_cu_count());
+    if (c.rc == DALI_ERR_LIMIT) return c.refuse();      // (refused before the launch is profiled)
+    const int K = a.g.nr * a.g.ns * a.g.Ck;
+    char what[160] = "";
+    if (g_prof)
+        snprintf(what, sizeof what, "%s,Cm=%d,K=%d,P=%d,taps=%d,stride=%d,sub=%d,fused=%d,stats=%d,res=%d,mask=%d,lin=%d", a.g.mode ? "dgrad" : "fwd", a.Cm, K, a.P,
+                 a.g.R * a.g.S, a.g.stride, a.g.sub, a.out_scale ? 1 : 0, a.stats ? 1 : 0, a.Res ? 1 : 0, (a.res_mask || a.out_mask) ? 1 : 0,
+                 (a.bias || a.row_scale || a.act) ? 1 : 0);
+    ProfScope prof_scope(st, 0, a.g.sub == 2 ? 2.0 * a.Cm * (double)a.P * a.g.R * a.g.S * a.g.Ck : 2.0 * a.Cm * (double)a.P * K, what);
+    if (!c.k) return c.refuse();
+    const int stat_tiles = a.stats ? igemm_conv_stat_tiles(a.Cm, a.P, K, a.in_scale != nullptr) : c.tiles_n;      // the slab the caller sized
+    if (stat_tiles != c.tiles_n) {
+        set_error("conv: the statistics slab has %d pixel tiles, the chosen kernel %d", stat_tiles, c.tiles_n);
+        return DALI_ERR_UNSUPPORTED;
+    }
+    if (c.k->grid == GRID_CLASSES) args.g.class_grid = c.class_grid;
+    return gemm_launch(st, c, args);
+}
 
 // Stride-2 data gradients are split by output parity: output position (2h'+ph, 2w'+pw) only receives the taps
 // kr = (ph+pad) mod 2 + 2i, ks likewise, so each of the four classes is a dense stride-1-like problem on a quarter of
@@ -2625,9 +2935,7 @@ int launch_igemm_conv(hipStream_t st, const IGemmArgs& a) {
     GatherGeom& g = args.g;
     g.sub = 0; g.oph = g.opw = 0; g.Hfull = g.Hout; g.Wfull = g.Wout;
     g.r0 = 0; g.rstep = 1; g.nr = g.R; g.s0 = 0; g.sstep = 1; g.ns = g.S;
-    const long long x_bytes = (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
-    const bool dma_ok = !a.in_scale && x_bytes < 0x7ff00000ll && (long long)a.Cm * g.R * g.S * g.Ck * 2 < 0x7ff00000ll;
-    if (g.mode == 1 && g.stride == 2 && dma_ok && !a.stats && (g.Hout % 2) == 0 && (g.Wout % 2) == 0 &&
+    if (g.mode == 1 && g.stride == 2 && conv_dma_ok(args) && !a.stats && (g.Hout % 2) == 0 && (g.Wout % 2) == 0 &&
         ilog2_exact(g.Wout / 2) >= 0 && ilog2_exact((g.Hout / 2) * (g.Wout / 2)) >= 0) {
         int nr[2], ns[2];
         for (int ph = 0; ph < 2; ++ph) {
@@ -2638,7 +2946,7 @@ int launch_igemm_conv(hipStream_t st, const IGemmArgs& a) {
         const bool all_have = nr[0] && nr[1] && ns[0] && ns[1];
         // every class has taps (3x3): ONE launch, the workgroups of the four classes interleaved (parity_block); the four separate launches
         // of a quarter of the pixels each ran one after the other with a short-K tail each (layer2 / layer3 conv2: 96 -> 72 us, 85 -> 53 us)
-        if (all_have && !narrow_cm(a.Cm) && (a.Cm & 7) == 0) {
+        if (all_have && a.Cm > 64 && (a.Cm & 7) == 0) {
             IGemmArgs s = args;
             s.g.sub = 2; s.g.oph = s.g.opw = 0; s.g.Hfull = g.Hout; s.g.Wfull = g.Wout;
             s.g.Hout = g.Hout / 2; s.g.Wout = g.Wout / 2; s.P = a.P / 4;
@@ -2664,291 +2972,6 @@ int launch_igemm_conv(hipStream_t st, const IGemmArgs& a) {
     return launch_igemm_conv_one(st, args);
 }
 
-// CUs of the current device rounded down to a multiple of 8 (the persistent streaming kernel's grid: one workgroup per CU, whole XCD groups)
-static int f1_cu_count() {
-    static int n_cus = 0;
-    if (!n_cus) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { set_error("conv: device query failed"); return -1; }
-        n_cus = v > 8 ? v & ~7 : 8;
-    }
-    return n_cus;
-}
-// does launch_igemm_conv take [X | X2] (c1 + c2 = K channels, plain rows) with the scale / shift / ReLU output stage at this size?  (dali_conv1x1_cat_act;
-// the net plan asks before it folds a downsample branch into conv3)
-bool conv_cat_act_supported(int Cm, int c1, int c2, int P, int parts) {
-    const int K = parts * (c1 + c2);
-    if (parts != 1 && parts != 2) return false;
-    if ((c1 & 63) || (c2 & 63) || (Cm % 128) || (long long)P * Cm * 2 >= 0x7ff00000ll || (long long)P * K * 2 >= 0x7ff00000ll) return false;
-    if (K <= F1_KMAX) {
-        const int n_cus = f1_cu_count(), tiles_m = Cm / 128, tiles_n = (P + 127) / 128;
-        return n_cus > 0 && (long long)tiles_m * tiles_n >= 2ll * n_cus && (n_cus / 8) % tiles_m == 0;
-    }
-    return parts == 1 && K >= 1024 && Cm >= 512 && P >= 16384;
-}
-
-static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
-    const bool in_bn = a.in_scale != nullptr;
-    const bool narrow = a.Cm <= 64;
-    IGemmArgs args = a;
-    args.g.lw = ilog2_exact(a.g.Wout);
-    args.g.lhw = ilog2_exact(a.g.Hout * a.g.Wout);
-    // the LDS-DMA kernel addresses both tensors with 32-bit byte offsets through buffer descriptors
-    const long long x_bytes = (long long)a.g.img_pitch * 2 * ((a.P + a.g.Hout * a.g.Wout - 1) / (a.g.Hout * a.g.Wout));
-    const bool dma_ok = !in_bn && x_bytes < 0x7ff00000ll && (long long)a.Cm * a.g.R * a.g.S * a.g.Ck * 2 < 0x7ff00000ll;
-    const int K = a.g.nr * a.g.ns * a.g.Ck;               // reduction length actually visited
-    int cfg = conv_pick_cfg(a.Cm, a.P, K);
-    const bool fused_out = a.out_scale || a.out_shift || a.out_relu || a.bits_out || a.out_mask || a.res_scale;
-    if (!in_bn && dma_ok && !a.stats && !fused_out && !a.g.sub && a.g.Ck % 64 == 0 && (a.Cm & 7) == 0 && conv_prefers_320(a.Cm, a.P, K))
-        cfg = CONV_256x320;
-    if (!dma_ok && !in_bn && a.stats && (cfg == CONV_128x256 || cfg == CONV_256x256)) {
-        set_error("conv: tensors beyond 2 GiB are not supported together with the BatchNorm statistics epilogue");
-        return DALI_ERR_LIMIT;
-    }
-    {
-    char what[160] = "";
-    if (g_prof)
-        snprintf(what, sizeof what, "%s,Cm=%d,K=%d,P=%d,taps=%d,stride=%d,sub=%d,fused=%d,stats=%d,res=%d,mask=%d,lin=%d", a.g.mode ? "dgrad" : "fwd", a.Cm, K, a.P,
-                 a.g.R * a.g.S, a.g.stride, a.g.sub, a.out_scale ? 1 : 0, a.stats ? 1 : 0, a.Res ? 1 : 0, (a.res_mask || a.out_mask) ? 1 : 0,
-                 (a.bias || a.row_scale || a.act) ? 1 : 0);
-    ProfScope prof_scope(st, 0, a.g.sub == 2 ? 2.0 * a.Cm * (double)a.P * a.g.R * a.g.S * a.g.Ck : 2.0 * a.Cm * (double)a.P * K, what);
-    // k-tile 64 pays where the main loop dominates (K >= 1024); with a short K or the 128 x 128 tile the smaller k-tile's 2-3
-    // co-resident workgroups overlap their epilogues better (measured per layer: 256 x 256 -12..-15 %; 128 x 256 wave-specialised
-    // -18..-26 % on the 3x3 layers, -10 % on the K = 1024 1x1 layers; K = 512 layers +12..+20 % with either k-tile-64 kernel)
-    const bool lin = a.act != 0 || a.O2 != nullptr || a.dact_pre != nullptr || a.row_scale != nullptr;      // linear-layer epilogue extras: the LIN kernel instantiations
-    bool k64 = !in_bn && dma_ok && !narrow && a.g.Ck % 64 == 0;
-    bool narrow_k64 = !in_bn && dma_ok && narrow && a.g.Ck % 64 == 0 && K >= 512;   // layer1's 3x3 (Cin = 64: a pixel is one line)
-    if (a.X2) {                                         // two operand tensors (IGemmArgs::X2): the SRC2 instantiations of the 128 x 128 / 64 x 256 LDS-DMA kernel
-        // a fused output stage beside X2: shift (+ scale) and ReLU only (the inference forward's conv3 + downsample branch as one GEMM), on the two
-        // kernels that have that instantiation: the persistent streaming kernel (K <= 256) and the 256 x 256 k-tile-64 kernel
-        const bool fo_simple = !a.bits_out && !a.out_mask && !a.res_scale && !a.Res && (a.out_scale || a.out_shift || a.out_relu);
-        const bool fo = (a.out_scale || a.out_shift || a.out_relu || a.bits_out || a.out_mask || a.res_scale) && !fo_simple;
-        const int xr = a.x_rep > 1 ? a.x_rep : 1;
-        if (xr > 1 && !(fo_simple && a.g.Ck % xr == 0 && conv_cat_act_supported(a.Cm, a.Ck1, a.g.Ck / xr - a.Ck1, a.P, xr) && a.g.Ck <= F1_KMAX)) {
-            set_error("conv: split weight images (x_rep = %d) are served by the persistent streaming kernel only (K <= 256, >= 2 tiles per CU)", xr);
-            return DALI_ERR_INVALID;
-        }
-        if (fo_simple && ((a.Ck1 & 63) || ((a.g.Ck / xr - a.Ck1) & 63) || (a.Cm % 128))) {
-            set_error("conv: two operand tensors with a fused output stage need channel counts that are multiples of 64 and Cm %% 128 == 0");
-            return DALI_ERR_INVALID;
-        }
-        if (in_bn || !dma_ok || a.stats || fo || lin || a.g.sub || a.g.R != 1 || a.g.S != 1 || a.g.stride != 1 || a.g.pad != 0 || a.Ck1 <= 0 || a.Ck1 >= a.g.Ck / xr ||
-            (a.Ck1 & 31) || ((a.g.Ck / xr - a.Ck1) & 31) || (a.Cm & 7)) {
-            set_error("conv: a second operand tensor needs a plain 1x1 / stride 1 problem with both channel counts multiples of 32");
-            return DALI_ERR_INVALID;
-        }
-        narrow_k64 = false;
-        if ((a.Ck1 & 63) || ((a.g.Ck / xr - a.Ck1) & 63)) k64 = false;
-        if (!(k64 && (cfg == CONV_256x256 || cfg == CONV_128x256)) && !narrow) { cfg = CONV_128; k64 = false; }
-    }
-    if (k64 && cfg != CONV_256x320 && !((K >= 1024 && (cfg == CONV_256x256 || cfg == CONV_128x256)) || (K >= 768 && cfg == CONV_256x256))) k64 = false;
-    // a second operand tensor is only read by the SRC2 instantiations: the two k-tile-64 kernels above (k64 still set) or, for every other
-    // choice -- including a k64 that the K gate has just cleared -- the 128 x 128 / 64 x 256 LDS-DMA kernel
-    if (a.X2 && !narrow && !(k64 && (cfg == CONV_256x256 || cfg == CONV_128x256))) { cfg = CONV_128; k64 = false; }
-    // fused output stage (IGemmArgs::out_scale ... out_mask): its own instantiations of three kernels, so that the convolutions' hot
-    // instantiations compile none of it (code that is never executed still cost their register allocation 0.4-0.8 ms per step)
-    const bool fused = a.out_scale || a.out_shift || a.out_relu || a.bits_out || a.out_mask || a.res_scale;
-    if (fused) {
-        // (measured, round 4: the 128 x 128 tile for the short-K fused launches instead of 128 x 256: 15.87-15.90 against 15.82-15.84 ms per step)
-        if (in_bn || !dma_ok || (a.Cm & 7) || lin) {
-            set_error("conv: the fused output stage needs Cm %% 8 == 0, tensors below 2 GiB, no operand transform and no linear-layer extras");
-            return DALI_ERR_INVALID;
-        }
-        DALI_ONCE_PER_DEVICE({
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (256 + 256) * 64 * 2 * 2));
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_wg_kernel<2, 4, 3, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (128 + 256) * 32 * 2 * 3));
-        });
-        // the inference forward (dali_resnet_forward, training = 0) folds every BatchNorm + ReLU into its convolution's output stage, so the
-        // 3x3 kernels and the narrow 1x1 kernel have fused instantiations too (the train step never reaches them: its fused launches are the
-        // 1x1 conv3 forwards and the masked conv1 data gradients, Cm >= 256 and K <= 512)
-        // short-K 1x1 with a residual / mask stream: the persistent streaming kernel (fused1x1.h).  K <= 256: at K = 512 (layer4) its four ring
-        // producers cannot issue the 32 DMA pieces of a k-step as fast as the consumers multiply it (141 against 125 us; the block is capped at 16 waves)
-        if (a.g.R == 1 && a.g.S == 1 && a.g.stride == 1 && a.g.pad == 0 && !a.g.sub && !a.res_mask &&
-            (a.Cm % F1_TM) == 0 && (a.g.Ck & 63) == 0 && a.g.Ck <= F1_KMAX && a.g.pix_pitch == a.g.Ck && a.g.row_pitch == a.g.Win * a.g.Ck &&
-            a.g.img_pitch == (long long)a.g.Hin * a.g.Win * a.g.Ck && a.g.Hin == a.g.Hout && a.g.Win == a.g.Wout &&
-            (long long)a.P * a.Cm * 2 < 0x7ff00000ll && (a.Res || a.out_mask || a.bits_out || a.X2)) {
-            const int n_cus = f1_cu_count();
-            if (n_cus <= 0) return DALI_ERR_HIP;
-            const int tiles_m = a.Cm / F1_TM, tiles_n = (a.P + F1_TN - 1) / F1_TN;
-            if ((long long)tiles_m * tiles_n >= 2ll * n_cus && (n_cus / 8) % tiles_m == 0) {     // (every workgroup keeps one channel tile)
-                const dim3 f1_block((F1_NC + F1_NP + F1_NR) * 64);
-#define DALI_F1_LAUNCH(RES, OM, BITS)                                                                                                                     \
-    do {                                                                                                                                                  \
-        DALI_ONCE_PER_DEVICE({                                                                                                                            \
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 2, RES, OM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 2, 128))); \
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 1, RES, OM, BITS>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 1, 256))); \
-        });                                                                                                                                               \
-        const int kk = a.g.Ck;                                                                                                                            \
-        if (kk <= 128) hipLaunchKernelGGL((fused1x1_persist_kernel<3, 2, RES, OM, BITS>), dim3(n_cus), f1_block, f1_lds_bytes(3, 2, kk), st, args, tiles_m, tiles_n); \
-        else hipLaunchKernelGGL((fused1x1_persist_kernel<3, 1, RES, OM, BITS>), dim3(n_cus), f1_block, f1_lds_bytes(3, 1, kk), st, args, tiles_m, tiles_n); \
-    } while (0)
-                const bool f_res = a.Res != nullptr, f_om = a.out_mask != nullptr, f_bits = a.bits_out != nullptr;
-                if (a.X2) {                                                               // [X | X2] against one weight image, shift + ReLU (inference)
-                    DALI_ONCE_PER_DEVICE({
-                        DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 2, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 2, 128)));
-                        DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fused1x1_persist_kernel<3, 1, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, f1_lds_bytes(3, 1, 256)));
-                    });
-                    if (a.g.Ck <= 128) hipLaunchKernelGGL((fused1x1_persist_kernel<3, 2, false, false, false, true>), dim3(n_cus), f1_block, f1_lds_bytes(3, 2, a.g.Ck), st, args, tiles_m, tiles_n);
-                    else hipLaunchKernelGGL((fused1x1_persist_kernel<3, 1, false, false, false, true>), dim3(n_cus), f1_block, f1_lds_bytes(3, 1, a.g.Ck), st, args, tiles_m, tiles_n);
-                } else if (f_res && !f_om && f_bits) DALI_F1_LAUNCH(true, false, true);          // conv3 forward of the train step
-                else if (f_res && !f_om && !f_bits) DALI_F1_LAUNCH(true, false, false);   // conv3 forward, inference
-                else if (f_res && f_om && !f_bits) DALI_F1_LAUNCH(true, true, false);     // conv1 data gradient + identity gradient, masked
-                else if (!f_res && f_om && !f_bits) DALI_F1_LAUNCH(false, true, false);   // masked data gradient without a residual
-                else if (f_res && f_om && f_bits) DALI_F1_LAUNCH(true, true, true);
-                else if (!f_res && f_om && f_bits) DALI_F1_LAUNCH(false, true, true);
-                else DALI_F1_LAUNCH(false, false, true);
-#undef DALI_F1_LAUNCH
-                DALI_LAUNCH_CHECK();
-                return DALI_OK;
-            }
-        }
-        const bool halo_ok = narrow_k64 && a.Cm == 64 && a.g.Ck == 64 && a.g.R == 3 && a.g.S == 3 && a.g.stride == 1 && a.g.pad == 1 && !a.g.sub &&
-                             (a.g.Wout == 16 || a.g.Wout == 32) && args.g.lhw >= 8 && a.g.Hin == a.g.Hout && a.g.Win == a.g.Wout && a.g.pix_pitch == 64 &&
-                             a.g.row_pitch == a.g.Win * 64 && a.g.img_pitch == (long long)a.g.Hin * a.g.Win * 64 && a.P % 256 == 0;
-        const bool lean = !a.Res && !a.out_mask && !a.bits_out && !a.res_mask && !a.res_scale && !a.X2;      // scale / shift / bias / ReLU only: the EPI = 5 instantiations
-        if (halo_ok && lean) {
-            const int lds = (3 * 64 * 64 + HALO64_PX * 64) * 2;
-            DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_halo64_kernel<3, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-            const int tiles_n = a.P / 256;
-            hipLaunchKernelGGL((igemm_conv_halo64_kernel<3, 5>), dim3(tiles_n), dim3(512), lds, st, args, tiles_n);
-        } else if (narrow && lean) {
-            using Cfg = GemmCfg<64, 256, 1, 1, 1>;
-            const int tiles_m = (a.Cm + 63) / 64, tiles_n = (a.P + 255) / 256;
-            hipLaunchKernelGGL((igemm_conv_dma_kernel<64, 256, 3, 5>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        } else if (lean && k64 && cfg == CONV_128x256 && !a.g.sub) {
-            const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 255) / 256;
-            const int lds = (128 + 256) * 64 * 2 * 3;
-            DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-            hipLaunchKernelGGL((igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 5>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-        } else if (a.X2) {
-            // two operand tensors + fused output: the 256 x 256 k-tile-64 kernel only (the dispatch above sends the short-K case to fused1x1)
-            if (!(k64 && cfg == CONV_256x256)) {
-                set_error("conv: two operand tensors with a fused output stage need K <= 256 or a 256 x 256 k-tile-64 problem (K >= 1024, Cm >= 512, >= 16384 pixels)");
-                return DALI_ERR_INVALID;
-            }
-            const int tiles_m = (a.Cm + 255) / 256, tiles_n = (a.P + 255) / 256;
-            DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (256 + 256) * 64 * 2 * 2)));
-            hipLaunchKernelGGL((igemm_conv_k64_kernel<4, 4, 2, 4, 4, 3, true>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), (256 + 256) * 64 * 2 * 2, st, args, tiles_m, tiles_n);
-        } else if (k64 && cfg == CONV_256x256) {
-            const int tiles_m = (a.Cm + 255) / 256, tiles_n = (a.P + 255) / 256;
-            hipLaunchKernelGGL((igemm_conv_k64_kernel<4, 4, 2, 4, 4, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), (256 + 256) * 64 * 2 * 2, st, args, tiles_m, tiles_n);
-        } else if (cfg == CONV_128x256 || cfg == CONV_256x256) {
-            const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 255) / 256;
-            hipLaunchKernelGGL((igemm_conv_wg_kernel<2, 4, 3, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(512), (128 + 256) * 32 * 2 * 3, st, args, tiles_m, tiles_n);
-        } else {
-            using Cfg = GemmCfg<128, 128, 1, 1, 1>;
-            const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 127) / 128;
-            hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 3, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        }
-    } else if (a.g.sub && !in_bn && dma_ok && !narrow && !lin && (a.Cm & 7) == 0) {
-        // a parity class of a stride-2 data gradient: the staged store with scattered pixel rows (EPI = 4)
-        DALI_ONCE_PER_DEVICE({
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (256 + 256) * 64 * 2 * 2));
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_wg_kernel<2, 4, 3, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (128 + 256) * 32 * 2 * 3));
-        });
-        const int ncls = a.g.sub == 2 ? 4 : 1;          // sub == 2: the four classes in one launch, class_grid workgroups each (parity_block)
-        if (k64 && cfg == CONV_256x256) {
-            const int tiles_m = (a.Cm + 255) / 256, tiles_n = (a.P + 255) / 256;
-            args.g.class_grid = xcd_tile_grid(tiles_m, tiles_n);
-            hipLaunchKernelGGL((igemm_conv_k64_kernel<4, 4, 2, 4, 4, 4>), dim3(ncls * args.g.class_grid), dim3(1024), (256 + 256) * 64 * 2 * 2, st, args, tiles_m, tiles_n);
-        } else if (cfg == CONV_128x256 || cfg == CONV_256x256) {
-            const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 255) / 256;
-            args.g.class_grid = xcd_tile_grid(tiles_m, tiles_n);
-            hipLaunchKernelGGL((igemm_conv_wg_kernel<2, 4, 3, 4>), dim3(ncls * args.g.class_grid), dim3(512), (128 + 256) * 32 * 2 * 3, st, args, tiles_m, tiles_n);
-        } else {
-            using Cfg = GemmCfg<128, 128, 1, 1, 1>;
-            const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 127) / 128;
-            args.g.class_grid = xcd_tile_grid(tiles_m, tiles_n);
-            hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 3, 4>), dim3(ncls * args.g.class_grid), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        }
-    } else if (cfg == CONV_256x320) {
-        const int tiles_m = (a.Cm + 255) / 256, tiles_n = (a.P + 319) / 320;
-        const int lds = (256 + 320) * 64 * 2 * 2;
-        DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<4, 4, 2, 4, 5, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-        hipLaunchKernelGGL((igemm_conv_k64_kernel<4, 4, 2, 4, 5, 1>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-    } else if (k64 && cfg == CONV_256x256) {
-        const int tiles_m = (a.Cm + 255) / 256, tiles_n = (a.P + 255) / 256;
-        const int lds = (256 + 256) * 64 * 2 * 2;
-        // (8 waves with 128 x 64 per wave, 25 % fewer LDS fragment bytes, 192 VGPRs: measured 3-5 % slower than 16 waves of 64 x 64)
-        // and the wave-specialised form (8 consumers of 128 x 64 + 4 producers, 168 VGPRs, 2-stage ring): -2 % on layer4's 3x3, +14 % on
-        // the stride-2 downsample dgrad -- a 256 x 256 tile has no room for producers beside 16 consumers (1024 threads per workgroup)
-        DALI_ONCE_PER_DEVICE({
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<4, 4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        });
-        if (a.X2) {
-            DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-            hipLaunchKernelGGL((igemm_conv_k64_kernel<4, 4, 2, 4, 4, 0, true>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-        } else if (lin) hipLaunchKernelGGL((igemm_conv_k64_kernel<4, 4, 2, 4, 4, true>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-        else hipLaunchKernelGGL((igemm_conv_k64_kernel<4, 4, 2>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-    } else if (k64 && cfg == CONV_128x256) {
-        const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 255) / 256;
-        const int lds = (128 + 256) * 64 * 2 * 3;
-        DALI_ONCE_PER_DEVICE({
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64s_kernel<2, 4, 8, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        });
-        if (a.X2) {
-            DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-            hipLaunchKernelGGL((igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 0, true>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-        } else if (lin) hipLaunchKernelGGL((igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 1>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-        else hipLaunchKernelGGL((igemm_conv_k64s_kernel<2, 4, 8, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-    } else if (narrow_k64 && a.Cm == 64 && a.g.Ck == 64 && a.g.R == 3 && a.g.S == 3 && a.g.stride == 1 && a.g.pad == 1 && !a.g.sub && !lin &&
-               (a.g.Wout == 16 || a.g.Wout == 32) && args.g.lhw >= 8 && a.g.Hin == a.g.Hout && a.g.Win == a.g.Wout && a.g.pix_pitch == 64 &&
-               a.g.row_pitch == a.g.Win * 64 && a.g.img_pitch == (long long)a.g.Hin * a.g.Win * 64 && a.P % 256 == 0) {
-        // layer1's 3x3 (64 -> 64): the halo patch of a 256-pixel tile fetched once, taps read it at shifted pixels (igemm_conv_halo64_kernel)
-        const int lds = (3 * 64 * 64 + HALO64_PX * 64) * 2;
-        DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_halo64_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-        const int tiles_n = a.P / 256;
-        hipLaunchKernelGGL((igemm_conv_halo64_kernel<3>), dim3(tiles_n), dim3(512), lds, st, args, tiles_n);
-    } else if (narrow_k64) {
-        // layer1's 3x3 (Cm = Cin = 64, K = 576): k-tile 64 = one full line per pixel and tap, 4 MFMA waves + 4 DMA waves, 2-stage ring,
-        // two workgroups per CU: 94 -> 77 us forward, 90 -> 73 us data gradient (unspecialised k-tile 64: 84 / 79; 3-stage ring, one
-        // workgroup per CU: 122 / 118)
-        const int tiles_m = (a.Cm + 63) / 64, tiles_n = (a.P + 255) / 256;
-        const int lds = (64 + 256) * 64 * 2 * 2;
-        // (8 producer waves instead of 4: 74 -> 78 us; the L2 -> LDS feed, 9 taps per pixel, bounds it, not the issue of the DMA pieces)
-        DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_k64s_kernel<1, 4, 4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-        hipLaunchKernelGGL((igemm_conv_k64s_kernel<1, 4, 4, 2>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(512), lds, st, args, tiles_m, tiles_n);
-    } else if (narrow) {
-        using Cfg = GemmCfg<64, 256, 1, 1, 1>;
-        const int tiles_m = (a.Cm + 63) / 64, tiles_n = (a.P + 255) / 256;
-        const int grid = xcd_tile_grid(tiles_m, tiles_n);
-        if (in_bn) hipLaunchKernelGGL((igemm_conv_kernel<64, 256, true>), dim3(grid), dim3(256), Cfg::LDS_BYTES, st, args, tiles_m, tiles_n);
-        else if (dma_ok && a.X2) hipLaunchKernelGGL((igemm_conv_dma_kernel<64, 256, 3, 0, true>), dim3(grid), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        else if (dma_ok) hipLaunchKernelGGL((igemm_conv_dma_kernel<64, 256, 3>), dim3(grid), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        else hipLaunchKernelGGL((igemm_conv_kernel<64, 256, false>), dim3(grid), dim3(256), Cfg::LDS_BYTES, st, args, tiles_m, tiles_n);
-    } else if (!in_bn && dma_ok && cfg == CONV_256x256) {
-        const int tiles_m = (a.Cm + 255) / 256, tiles_n = (a.P + 255) / 256;
-        const int lds = (256 + 256) * 32 * 2 * 4;
-        DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_wg_kernel<4, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-        hipLaunchKernelGGL((igemm_conv_wg_kernel<4, 4, 4>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(1024), lds, st, args, tiles_m, tiles_n);
-    } else if (!in_bn && dma_ok && cfg == CONV_128x256) {
-        const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 255) / 256;
-        const int lds = (128 + 256) * 32 * 2 * 3;
-        DALI_ONCE_PER_DEVICE({
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_wg_kernel<2, 4, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_conv_wg_kernel<2, 4, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        });
-        if (lin) hipLaunchKernelGGL((igemm_conv_wg_kernel<2, 4, 3, true>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(512), lds, st, args, tiles_m, tiles_n);
-        else hipLaunchKernelGGL((igemm_conv_wg_kernel<2, 4, 3>), dim3(xcd_tile_grid(tiles_m, tiles_n)), dim3(512), lds, st, args, tiles_m, tiles_n);
-    } else {
-        using Cfg = GemmCfg<128, 128, 1, 1, 1>;
-        const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.P + 127) / 128;
-        const int grid = xcd_tile_grid(tiles_m, tiles_n);
-        if (in_bn) hipLaunchKernelGGL((igemm_conv_kernel<128, 128, true>), dim3(grid), dim3(256), Cfg::LDS_BYTES, st, args, tiles_m, tiles_n);
-        else if (dma_ok && a.X2) hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 3, 0, true>), dim3(grid), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        else if (dma_ok && lin) hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 3, true>), dim3(grid), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        else if (dma_ok) hipLaunchKernelGGL((igemm_conv_dma_kernel<128, 128, 3>), dim3(grid), dim3(256), Cfg::LDS_BYTES / 2 * 3, st, args, tiles_m, tiles_n);
-        else hipLaunchKernelGGL((igemm_conv_kernel<128, 128, false>), dim3(grid), dim3(256), Cfg::LDS_BYTES, st, args, tiles_m, tiles_n);
-    }
-    }
-    DALI_LAUNCH_CHECK();
-    return DALI_OK;
-}
-
-// Chooses the split count so that the grid has ~target blocks; returns slab bytes through *ws_bytes.
-// 0: 128x128 (4 waves); 1: 256x256 (16 waves, 4-deep ring) for the large weight matrices
 // Tile shape of the weight-gradient GEMM (measured per layer, scripts/bench_convs.py): 0 = 128 x 128 / 4 waves,
 // 1 = 256 x 256 / 16 waves, 2 = 128 x 256 / 8 waves.  The wider tiles cut the L2 -> LDS operand bytes per FLOP and win
 // on the 1x1 layers with a long pixel (K) dimension; on 3x3 layers (each 128-column group of N is one tap's gather)
@@ -2964,12 +2987,26 @@ int wgrad_pick_cfg(int Cm, int Ntot, int taps, int P, int halo_w) {
     if (taps == 7 && Ntot == 224 && P >= 16384) return 2;         // the stem (7 tap rows of 32): one 256-wide n tile, dY read once (187 -> ~155 us)
     return (taps == 1 && Ntot >= 256 && P >= 16384) ? 2 : 0;      // incl. the ViT linears (P = 25216)
 }
+// The kernel of wgrad_pick_cfg's choice cfg.  An operand transform or a tensor beyond the descriptors' reach takes a register-staged 128 x 128
+// kernel whatever the choice (on the split wgrad_plan made for cfg); flat: plain_rows operands.
+static const GemmKernel& wgrad_kernel(int cfg, int Cm, int Ntot, bool in_bn, bool dma_ok, bool colsum, bool flat) {
+    if (in_bn) return WG_BN;
+    if (!dma_ok) return WG_PLAIN;
+    if (cfg == 3) return WG_3X3;
+    if (cfg == 2) return wgrad_spec(Cm, Ntot) ? WG_P[flat][colsum] : WG_WG[colsum];
+    return WG_DMA[colsum];
+}
+// column sums (WGradArgs::colsum) ride on the LDS-DMA 128 x 128 and 128 x 256 kernels
+static bool wgrad_colsum_ok(int cfg, bool in_bn, bool dma_ok) { return cfg != 3 && !in_bn && dma_ok; }
+// rows of the column-sum partial slab [rows][Cm] kernel k leaves: one per split from the 128 x 128 kernel (its n-tile-0 workgroups), one per
+// (split, n tile) from the 128 x 256 kernels (every n tile takes a share)
+static int colsum_rows_of(const GemmKernel& k, int Ntot, int splits) { return k.tn == 128 ? splits : splits * ((Ntot + k.tn - 1) / k.tn); }
+
+// Chooses the split count so that the grid has ~target blocks; returns slab bytes through *ws_bytes.
 void wgrad_plan(int Cm, int Ntot, int P, int target_blocks, int* splits, int* pix_per_split, size_t* ws_bytes, int taps, int halo_w) {
-    const int cfg = wgrad_pick_cfg(Cm, Ntot, taps, P, halo_w);
-    const int TMc = 128, TNc = cfg == 0 ? 128 : (cfg == 3 ? 9 * 64 : 256);
-    if (cfg == 3) target_blocks = 256;              // one 8-wave block per CU
-    if (cfg == 2) target_blocks = wgrad_spec(Cm, Ntot) ? 256 : 512;     // one 16-wave (specialised) / two 8-wave blocks per CU
-    const int tiles = ((Cm + TMc - 1) / TMc) * ((Ntot + TNc - 1) / TNc);
+    const GemmKernel& k = wgrad_kernel(wgrad_pick_cfg(Cm, Ntot, taps, P, halo_w), Cm, Ntot, false, true, false, true);
+    if (k.plan_wgs) target_blocks = k.plan_wgs;
+    const int tiles = ((Cm + k.tm - 1) / k.tm) * ((Ntot + k.tn - 1) / k.tn);
     int sp = (target_blocks + tiles - 1) / tiles;
     const int max_sp = (P + 255) / 256;              // at least 8 k-steps per block
     if (sp > max_sp) sp = max_sp;
@@ -2992,88 +3029,48 @@ void wgrad_plan(int Cm, int Ntot, int P, int target_blocks, int* splits, int* pi
     *ws_bytes = (size_t)sp * Cm * Ntot * sizeof(float);
 }
 
+// The kernel, tiles and grid of one weight-gradient GEMM, or the refusal; no HIP calls
+static GemmChoice wgrad_choose(const WGradArgs& a) {
+    const GatherGeom& g = a.g;
+    const bool dma_ok = gather_dma_ok(g, a.P, (long long)a.P * a.Cm * 2);
+    const bool halo = g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.mode == 0 && g.lw >= 0 && g.lhw >= 7 && g.Hin == g.Hout && g.Win == g.Wout &&
+                      g.pix_pitch == g.Ck && g.row_pitch == g.Win * g.Ck;
+    const int cfg = wgrad_pick_cfg(a.Cm, a.Ntot, g.R * g.S, a.P, halo ? g.Wout : 0);
+    if (a.colsum && !wgrad_colsum_ok(cfg, a.in_scale != nullptr, dma_ok))
+        return GemmChoice(DALI_ERR_INVALID, "wgrad: column sums ride on the 128 x 128 and 128 x 256 LDS-DMA kernels only (wgrad_colsum_supported)");
+    return gemm_place(wgrad_kernel(cfg, a.Cm, a.Ntot, a.in_scale != nullptr, dma_ok, a.colsum != nullptr, plain_rows(g)), a.Cm, a.Ntot, a.splits, g.Ck);
+}
+
 int launch_igemm_wgrad(hipStream_t st, const WGradArgs& a, float* out, int accumulate, float* colsum_out, int colsum_rows) {
     WGradArgs args = a;
     args.stamps = g_conv_stamps;
     args.g.lw = ilog2_exact(a.g.Wout);
     args.g.lhw = ilog2_exact(a.g.Hout * a.g.Wout);
-    const int tiles_m = (a.Cm + 127) / 128, tiles_n = (a.Ntot + 127) / 128;
-    const int grid = tiles_m * tiles_n * a.splits;
-    const long long x_bytes = (long long)a.g.img_pitch * 2 * ((a.P + a.g.Hout * a.g.Wout - 1) / (a.g.Hout * a.g.Wout));
-    const bool dma_ok = x_bytes < 0x7ff00000ll && (long long)a.P * a.Cm * 2 < 0x7ff00000ll;
+    const GemmChoice c = wgrad_choose(args);
     {
     char what[160] = "";
     if (g_prof)
         snprintf(what, sizeof what, "wgrad,Cm=%d,K=%d,P=%d,taps=%d,stride=%d,sub=0,fused=%d,stats=0,res=0,mask=0,lin=%d", a.Cm, a.Ntot, a.P, a.g.R * a.g.S, a.g.stride,
                  a.in_scale ? 1 : 0, a.colsum ? 1 : 0);
     ProfScope prof_scope(st, 1, 2.0 * a.Cm * (double)a.Ntot * a.P, what);
-    const bool halo_ok = a.g.R == 3 && a.g.S == 3 && a.g.stride == 1 && a.g.pad == 1 && a.g.mode == 0 && args.g.lw >= 0 && args.g.lhw >= 7 &&
-                         a.g.Hin == a.g.Hout && a.g.Win == a.g.Wout && a.g.pix_pitch == a.g.Ck && a.g.row_pitch == a.g.Win * a.g.Ck;
-    const int wcfg = wgrad_pick_cfg(a.Cm, a.Ntot, a.g.R * a.g.S, a.P, halo_ok ? a.g.Wout : 0);
-    if (a.colsum && !((wcfg == 0 || wcfg == 2) && dma_ok && !a.in_scale)) {
-        set_error("wgrad: column sums ride on the 128 x 128 and 128 x 256 LDS-DMA kernels only (wgrad_colsum_supported)");
-        return DALI_ERR_INVALID;
+    if (!c.k) return c.refuse();
+    if (a.colsum && colsum_out && colsum_rows != colsum_rows_of(*c.k, a.Ntot, a.splits)) {      // the caller sized them with wgrad_colsum_rows
+        set_error("wgrad: %d column-sum rows passed, the chosen kernel leaves %d", colsum_rows, colsum_rows_of(*c.k, a.Ntot, a.splits));
+        return DALI_ERR_UNSUPPORTED;
     }
-    if (!a.in_scale && dma_ok && wcfg == 3) {
-        const int tm3 = (a.Cm + 127) / 128, tn3 = a.g.Ck / 64;
-        const int lds = 3 * W3_STAGE * 2;            // 3 stages x 24 KiB (4 and 5 measured the same, before and after the inline-asm reads: the
-                                                     // k-step is bound by its 26 transposing reads + 36 MFMAs per wave, two waves per SIMD)
-        DALI_ONCE_PER_DEVICE(DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad3x3_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-        // (measured and removed, round 3: the same kernel software-pipelined -- layer4 conv2 161 us against 152 -- and as two wave groups half a
-        //  k-step apart, 195 us.  PMC on this kernel at the layer4 shape: matrix pipe busy 45 % of the SIMD cycles, LDS active 23 % (28 % of that bank
-        //  conflicts), waves parked at s_waitcnt / barriers 26 % of their cycles: neither the issue order nor the LDS bounds it.)
-        const dim3 grid3(((tm3 * tn3 * a.splits + 7) / 8) * 8);
-        hipLaunchKernelGGL(igemm_wgrad3x3_kernel<3>, grid3, dim3(512), lds, st, args, tm3, tn3);
-    } else if (!a.in_scale && dma_ok && wcfg == 2) {
-        const int tm2 = (a.Cm + 127) / 128, tn2 = (a.Ntot + 255) / 256;
-        const int lds = 3 * 3 * 32 * 128 * 2;       // 3 stages x 3 images x 8 KiB
-        DALI_ONCE_PER_DEVICE({
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_wg_kernel<2, 4, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_wg_kernel<2, 4, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        });
-        const dim3 grid2(((tm2 * tn2 * a.splits + 7) / 8) * 8);
-        if (wgrad_spec(a.Cm, a.Ntot)) {                 // few output tiles: the pipelined wave-specialised kernel, one workgroup per CU
-            constexpr int lds_p = 6 * 3 * 32 * 128 * 2;   // 6 stages x 3 images x 8 KiB
-            DALI_ONCE_PER_DEVICE({
-                DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_p));
-                DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_p));
-                DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_p));
-                DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_p));
-            });
-            // (measured, interleaved: plain [P][C] operands 92 us with 4 consumers of 128 x 64 + 4 producers against 94 with 8 + 8 and 105 before;
-            //  strided / gathered operands 83 us with 4 producers of 6 pieces, 75 with 8 of 3)
-            const GatherGeom& gg = a.g;
-            const bool flat = gg.R == 1 && gg.S == 1 && gg.stride == 1 && gg.pad == 0 && gg.pix_pitch == gg.Ck && gg.row_pitch == gg.Win * gg.Ck &&
-                              gg.img_pitch == (long long)gg.Hin * gg.Win * gg.Ck && gg.Hin == gg.Hout && gg.Win == gg.Wout;
-            if (a.colsum) {                                     // bias gradients of the linear layers / the Gram scheme's column sums ride on the GEMM
-                if (!flat) hipLaunchKernelGGL((igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6, true>), grid2, dim3(1024), lds_p, st, args, tm2, tn2);
-                else hipLaunchKernelGGL((igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6, true>), grid2, dim3(512), lds_p, st, args, tm2, tn2);
-            } else if (!flat) hipLaunchKernelGGL((igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6>), grid2, dim3(1024), lds_p, st, args, tm2, tn2);
-            else hipLaunchKernelGGL((igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6>), grid2, dim3(512), lds_p, st, args, tm2, tn2);
-        } else {
-            if (a.colsum) hipLaunchKernelGGL((igemm_wgrad_wg_kernel<2, 4, 3, true>), grid2, dim3(512), lds, st, args, tm2, tn2);
-            else hipLaunchKernelGGL((igemm_wgrad_wg_kernel<2, 4, 3>), grid2, dim3(512), lds, st, args, tm2, tn2);
-        }
-    } else if (a.in_scale) hipLaunchKernelGGL((igemm_wgrad_kernel<true>), dim3(grid), dim3(256), 0, st, args, tiles_m, tiles_n);
-    else if (dma_ok && a.colsum) hipLaunchKernelGGL(igemm_wgrad_dma_kernel<true>, dim3(((tiles_m * tiles_n * a.splits + 7) / 8) * 8), dim3(256), 0, st, args, tiles_m, tiles_n);
-    else if (dma_ok) hipLaunchKernelGGL(igemm_wgrad_dma_kernel<false>, dim3(((tiles_m * tiles_n * a.splits + 7) / 8) * 8), dim3(256), 0, st, args, tiles_m, tiles_n);
-    else hipLaunchKernelGGL((igemm_wgrad_kernel<false>), dim3(grid), dim3(256), 0, st, args, tiles_m, tiles_n);
+    if (int rc = gemm_launch(st, c, args)) return rc;
     }
-    DALI_LAUNCH_CHECK();
     if (!out) return DALI_OK;                       // the caller reduces the slabs itself
     // the column sums that rode on the GEMM (a.colsum, colsum_rows partial rows of Cm) are reduced in the same launch
     return launch_splitk_reduce2(st, a.partial, out, (size_t)a.Cm * a.Ntot, a.splits, accumulate, (a.colsum && colsum_out) ? a.colsum : nullptr, colsum_out,
                                  (size_t)a.Cm, colsum_rows);
 }
 
-// rows of the column-sum partial slab [rows][Cm] a weight-gradient launch with WGradArgs::colsum leaves: one per split from the
-// 128 x 128 kernel (its n-tile-0 workgroups), one per (split, n tile) from the 128 x 256 kernels (every n tile takes a share)
 int wgrad_colsum_rows(int Cm, int Ntot, int taps, int P, int splits) {
-    return wgrad_pick_cfg(Cm, Ntot, taps, P, 0) == 2 ? splits * ((Ntot + 255) / 256) : splits;
+    return colsum_rows_of(wgrad_kernel(wgrad_pick_cfg(Cm, Ntot, taps, P, 0), Cm, Ntot, false, true, true, true), Ntot, splits);
 }
 bool wgrad_colsum_supported(int Cm, int Ntot, int taps, int P) {
-    const int cfg = wgrad_pick_cfg(Cm, Ntot, taps, P, 0);
-    return (cfg == 0 || cfg == 2) && (long long)P * Cm * 2 < 0x7ff00000ll && (long long)P * Ntot * 2 < 0x7ff00000ll;
+    return wgrad_colsum_ok(wgrad_pick_cfg(Cm, Ntot, taps, P, 0), false, dma_addressable((long long)P * Cm * 2) && dma_addressable((long long)P * Ntot * 2));
 }
 
 int launch_splitk_reduce(hipStream_t st, const float* partial, float* out, size_t elems, int splits, int accumulate) {
@@ -3206,10 +3203,8 @@ static int halo_width(int r, int s, int stride, int pad, int ho, int wo) {
     return (r == 3 && s == 3 && stride == 1 && pad == 1 && ilog2_exact(wo) >= 0 && ilog2_exact(ho * wo) >= 0 && ho * wo >= 128) ? wo : 0;
 }
 extern "C" int dali_conv2d_stat_tiles(int cout, int cin, int r, int s, int stride, int pad, int n, int ho, int wo, int fused_operand) {
-    // the fused-operand (register-staged) kernels always use 128-pixel tiles for cout > 64
-    if (fused_operand && cout > 64) return (n * ho * wo + 127) / 128;
     (void)stride; (void)pad;
-    return igemm_conv_stat_tiles(cout, n * ho * wo, r * s * cin);
+    return igemm_conv_stat_tiles(cout, n * ho * wo, r * s * cin, fused_operand != 0);
 }
 
 extern "C" int dali_conv2d_dgrad(dali_ctx* ctx, void* stream, const uint16_t* dy, const uint16_t* wt, uint16_t* dx,

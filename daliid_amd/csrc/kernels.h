@@ -90,7 +90,7 @@ int launch_igemm_conv(hipStream_t st, const IGemmArgs& a);
 // per-launch event bracket of the GEMM profile steps (dali_gemm_profile_*), for GEMM launches outside conv.hip; cls 0 = forward / data gradient
 int gemm_profile_begin(hipStream_t st, int cls, double flops, const char* what);
 void gemm_profile_end(hipStream_t st, int slot);
-int igemm_conv_stat_tiles(int Cm, int P, int K);
+int igemm_conv_stat_tiles(int Cm, int P, int K, bool operand_transform = false);
 bool conv_cat_act_supported(int Cm, int c1, int c2, int P, int parts = 1);      // [X | X2] GEMM with the scale / shift / ReLU output stage at this size?
 // taps = R*S of the convolution (1 for 1x1 convolutions and linear layers): selects the tile shape
 // halo_w = output width of a 3x3 / stride 1 / pad 1 convolution whose H*W is a power of two (0 otherwise): enables the halo kernel

@@ -212,3 +212,23 @@ def test_conv1x1_two_operand_tensors_with_output_stage_exact_integers(nn, P, c1,
         y3 = nn.conv1x1_cat_act(x1.to(bf16), x2.to(bf16), w4, shift, relu=True, parts=2)
         ref3 = torch.relu((torch.cat((x1, x2), 1).double() @ wf.double().T).float() + shift).to(bf16)
         assert torch.equal(y3, ref3)
+
+
+# refusals of the two-operand output-stage entry that no other test reaches: a split weight image (weight_parts = 2) needs the persistent
+# kernel's >= 2 tiles per CU (here 2 x 8), and a one-image K = 384 lies between the persistent kernel's 256 and the 256 x 256 kernel's 1024
+@pytest.mark.parametrize("parts,c1,c2,cout", [(2, 64, 64, 256), (1, 256, 128, 256)])
+def test_conv1x1_cat_act_refuses_and_leaves_output(nn, parts, c1, c2, cout):
+    """dali_conv1x1_cat_act returns DALI_ERR_INVALID (-1) at 1000 pixels and writes nothing to y."""
+    from daliid_amd import _lib
+    P, dev = 1000, "cuda"
+    x1 = torch.ones(P, c1, dtype=bf16, device=dev)
+    x2 = torch.ones(P, c2, dtype=bf16, device=dev)
+    w = torch.ones(cout, parts * (c1 + c2), dtype=bf16, device=dev)
+    shift = torch.zeros(cout, device=dev)
+    y = torch.full((P, cout), 7.0, dtype=bf16, device=dev)
+    before = y.clone()
+    rc = _lib.lib().dali_conv1x1_cat_act(_lib.ctx(x1.device), _lib.stream_ptr(), _lib.ptr(x1, bf16, "x1"), c1, _lib.ptr(x2, bf16, "x2"), c2,
+                                         _lib.ptr(w, bf16, "w"), parts, _lib.ptr(None), _lib.ptr(shift, torch.float32, "out_shift"), 1, _lib.ptr(y), P, cout)
+    torch.cuda.synchronize()
+    assert rc == -1, (rc, _lib.last_error())
+    assert torch.equal(y, before)
