@@ -1,5 +1,8 @@
-"""GPU parity: loss heads, Adam and EMA kernels through the C ABI against the golden vectors produced by the
-reference's own losses.py (tests/golden/losses.npz) and against torch.optim.Adam."""
+"""GPU parity, end to end: the loss heads (similarity GEMM + head kernels + backward) against the golden vectors produced by the reference's
+own losses.py (tests/golden/losses.npz, triplet.npz), and FusedAdam / ema_update on a width-32 net against torch.optim.Adam.  The goldens have
+rows of at most 80 proxies (and one of 5120), unique center labels and no ties, and the net is smaller than one pass of Adam's grid: the
+kernels themselves, at real sizes and at their edges, are compared with fp64 in tests/test_gpu_loss_kernels.py and
+tests/test_gpu_optim_kernels.py."""
 import numpy as np
 import pytest
 import torch
