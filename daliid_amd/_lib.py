@@ -46,6 +46,10 @@ _SIGNATURES = {
     "dali_roc_scratch_bytes": [c_int, c_int],
     "dali_roc_build": [c_void_p] * 5 + [c_int, c_int, c_void_p, c_size_t, c_void_p],
     "dali_roc_emit": [c_void_p] * 3 + [c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p],
+    "dali_topk_rows": [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, c_int, c_int, c_int, c_int, c_void_p],
+    "dali_topk_decode": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "dali_pairdist_topk_scratch_bytes": [c_int] * 7,
+    "dali_pairdist_topk": [c_void_p] * 6 + [c_int] * 9 + [c_void_p] + [c_int] * 3 + [c_void_p],
     "dali_conv2d_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_int, c_void_p],
     "dali_conv2d_bn_act": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_int],
     "dali_stem_fused_supported": [c_int, c_int, c_int],
@@ -122,7 +126,8 @@ _SIGNATURES = {
     "dali_vit_backward_stages": [c_void_p, c_void_p, c_void_p, c_int, c_int],
     "dali_vit_set_drop_path": [c_void_p, c_void_p],
 }
-_RESTYPES = {"dali_last_error": ctypes.c_char_p, "dali_pairdist_operand_bytes": ctypes.c_size_t, "dali_roc_scratch_bytes": ctypes.c_size_t}
+_RESTYPES = {"dali_last_error": ctypes.c_char_p, "dali_pairdist_operand_bytes": ctypes.c_size_t, "dali_roc_scratch_bytes": ctypes.c_size_t,
+             "dali_pairdist_topk_scratch_bytes": ctypes.c_size_t}
 
 _lock = threading.Lock()
 _lib = None

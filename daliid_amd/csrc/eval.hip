@@ -2,7 +2,9 @@
 //   row L2 normalisation (:41-42), distmat = 1 - q @ g.T (:47) on MFMA, and the market1501 CMC/mAP
 //   arithmetic of torchreid.metrics.evaluate_rank (:68) without a full row sort.
 #include "gemm_tile.h"
+#include "topk_key.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace dali {
 
@@ -317,6 +319,47 @@ __device__ __forceinline__ void pairdist_epilogue_lines(f32x4_t (&acc)[4][4], in
     }
 }
 
+// Selecting epilogue (PairTopk, topk_key.h): the metric arithmetic of pairdist_epilogue, then one compare of the ordered value bits against
+// the query's threshold rejects almost every element; a survivor takes a slot of its query's candidate list.  Nothing of the tile is stored.
+// Edge tiles take the same bounds checks as pairdist_epilogue.
+__device__ __forceinline__ void pairdist_epilogue_topk(f32x4_t (&acc)[4][4], int g_tile0, int q_tile0, int mb, int nb, const float* __restrict__ gsq,
+                                                       const float* __restrict__ qsq, int ng, int nq, int metric, const PairTopk& t) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int q = q_tile0 + nb + j * 16;
+        if (q >= nq) continue;
+        const float qq = (metric == DALI_METRIC_L2SQ) ? qsq[q] : 0.f;
+        const unsigned long long thr = t.keys[(size_t)q * t.k + t.k - 1];
+        const unsigned int thr_hi = (unsigned int)(thr >> 32);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int g0 = g_tile0 + mb + i * 16;
+            if (g0 >= ng) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (g0 + r >= ng) continue;
+                const float dot = acc[i][j][r];
+                float v;
+                if (metric == DALI_METRIC_L2SQ) {
+                    const float gg = gsq[g0 + r];
+                    v = qq + gg - 2.0f * dot;
+                } else if (metric == DALI_METRIC_DOT) {
+                    v = dot;
+                } else {
+                    v = 1.0f - dot;
+                }
+                const unsigned int hi = topk_ordered_bits(v, t.largest);
+                if (hi > thr_hi) continue;
+                const unsigned long long key = ((unsigned long long)hi << 32) | (unsigned int)(t.g_offset + g0 + r);
+                if (key >= thr) continue;
+                const int slot = atomicAdd(&t.cnt[q], 1);
+                if (slot < t.cap) t.cand[(size_t)q * t.cap + slot] = key;
+                else *t.flag = 1;
+            }
+        }
+    }
+}
+
 // LDS-DMA version (what the launcher uses when the operands fit 32-bit buffer offsets): 128 gallery rows x 256 query
 // rows per 8-wave block (wave (wm, wn) of the 2 x 4 grid owns 64 x 64).  A k-step takes one 128-byte line of every operand
 // row ([hi 32 | lo 32] for NPROD = 3, 64 consecutive k for NPROD = 1) by buffer_load_dwordx4 ... lds (a DMA piece = 8 rows,
@@ -340,11 +383,17 @@ __device__ __forceinline__ void pairdist_epilogue_lines(f32x4_t (&acc)[4][4], in
 // columns kept in 48 registers and handed to the store path one (column, half) block every ktiles / 6 k-steps of the NEXT tile, so that
 // the stores run under its MFMAs: 9.41 ms (+5 %; bf16 3.64 against 3.51) -- stores issued inside the k-loop delay the LDS-DMA loads of the
 // same CU by more than the exposed burst costs; (c) start phases per XCD (blockIdx.x & 7) instead of per workgroup: 8.69-8.73 against 8.72.
-template <int NPROD>
+// EPI, the type of the last argument, is what a finished tile does: PairBlend (the default) stores it, blended or not; PairGate stores it
+// if the launch's gate word is set and ends the launch at once otherwise; PairTopk selects from it and stores nothing
+// (pairdist_epilogue_topk).  Resolved with if constexpr: the PairBlend instantiations are the kernels they were before the policy existed.
+template <int NPROD, class EPI = PairBlend>
 __global__ __launch_bounds__(1024) void pairdist_dma_kernel(const uint16_t* __restrict__ G, const uint16_t* __restrict__ Q,
                                                             const float* __restrict__ gsq, const float* __restrict__ qsq,
                                                             int ng, int nq, int pitch, int ktiles, int metric, float* out,
-                                                            int tiles_m, int tiles_n, int vgrid, PairBlend blend) {
+                                                            int tiles_m, int tiles_n, int vgrid, EPI blend) {
+    if constexpr (std::is_same_v<EPI, PairGate>) {
+        if (blend.gate[0] == 0) return;
+    }
     constexpr int TM = 128, TN = 256;
     constexpr int A_ELEMS = TM * 64, B_ELEMS = TN * 64, STAGE = A_ELEMS + B_ELEMS;
     constexpr int A_PIECES = TM / 8, NDMA = (TM + TN) / 8 / 8;                   // 1 KiB DMA pieces: 16 of A, 6 per producer wave
@@ -447,11 +496,22 @@ __global__ __launch_bounds__(1024) void pairdist_dma_kernel(const uint16_t* __re
             __builtin_amdgcn_s_barrier();
             st_cur = (st_cur == 2) ? 0 : st_cur + 1;
         }
-        if (!blend.on && (ng & 31) == 0 && (tm + 1) * TM <= ng && (tn + 1) * TN <= nq)
-            pairdist_epilogue_lines(acc, tm * TM + wm * 64, tn * TN + wn * 64, lane, gsq, qsq, ng, metric, out,
-                                    reinterpret_cast<char*>(smem + 3 * STAGE) + wave * PAIR_STRIP_BYTES);
-        else
-            pairdist_epilogue<4, 4>(acc, tm * TM, tn * TN, wm * 64 + (lane >> 4) * 4, wn * 64 + (lane & 15), gsq, qsq, ng, nq, metric, out, blend);
+        if constexpr (std::is_same_v<EPI, PairTopk>) {
+            pairdist_epilogue_topk(acc, tm * TM, tn * TN, wm * 64 + (lane >> 4) * 4, wn * 64 + (lane & 15), gsq, qsq, ng, nq, metric, blend);
+        } else if constexpr (std::is_same_v<EPI, PairGate>) {
+            if ((ng & 31) == 0 && (tm + 1) * TM <= ng && (tn + 1) * TN <= nq)
+                pairdist_epilogue_lines(acc, tm * TM + wm * 64, tn * TN + wn * 64, lane, gsq, qsq, ng, metric, out,
+                                        reinterpret_cast<char*>(smem + 3 * STAGE) + wave * PAIR_STRIP_BYTES);
+            else
+                pairdist_epilogue<4, 4>(acc, tm * TM, tn * TN, wm * 64 + (lane >> 4) * 4, wn * 64 + (lane & 15), gsq, qsq, ng, nq, metric, out,
+                                        PairBlend{nullptr, nullptr, nullptr, nullptr, 0});
+        } else {
+            if (!blend.on && (ng & 31) == 0 && (tm + 1) * TM <= ng && (tn + 1) * TN <= nq)
+                pairdist_epilogue_lines(acc, tm * TM + wm * 64, tn * TN + wn * 64, lane, gsq, qsq, ng, metric, out,
+                                        reinterpret_cast<char*>(smem + 3 * STAGE) + wave * PAIR_STRIP_BYTES);
+            else
+                pairdist_epilogue<4, 4>(acc, tm * TM, tn * TN, wm * 64 + (lane >> 4) * 4, wn * 64 + (lane & 15), gsq, qsq, ng, nq, metric, out, blend);
+        }
     }
 }
 
@@ -904,24 +964,34 @@ extern "C" int dali_l2norm_rows_bwd(dali_ctx* ctx, void* stream, const float* x,
 static inline int pair_kp(int d, bool split) { return split ? (d + 31) & ~31 : (d + 63) & ~63; }
 static inline int pair_pitch(int d, bool split) { return split ? 2 * pair_kp(d, true) : pair_kp(d, false); }
 
+// rows of an operand image the DMA kernel addresses with its 32-bit buffer offsets
+static inline bool pair_dma_fits(int n, int pitch) { return (long long)n * pitch * 2 < 0x7ff00000ll; }
+
+// epi: what the DMA kernel does with a finished tile (PairBlend: store; PairGate: store if the gate word is set; PairTopk: select)
+template <class EPI>
+static int launch_pairdist_dma(int num_cus, hipStream_t st, const uint16_t* g_img, const float* gsq, const uint16_t* q_img, const float* qsq, int nq, int ng,
+                               int d, int metric, bool split, float* out, EPI epi) {
+    const int Kp = pair_kp(d, split), pitch = pair_pitch(d, split);
+    const int tm2 = (ng + 127) / 128, tn2 = (nq + 255) / 256;
+    const int grid2 = xcd_tile_grid(tm2, tn2);
+    const int lds = 3 * (128 + 256) * 64 * 2 + 8 * PAIR_STRIP_BYTES;         // 3 stages x 48 KiB + the consumers' store strips = 160 KiB
+    DALI_ONCE_PER_DEVICE({
+        DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pairdist_dma_kernel<3, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pairdist_dma_kernel<1, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    });
+    const int cap = num_cus / 8 * 8, grid = grid2 < cap ? grid2 : cap;          // persistent: one workgroup per CU (144 KiB of LDS each)
+    const int kt = split ? Kp / 32 : Kp / 64;
+    if (split) hipLaunchKernelGGL((pairdist_dma_kernel<3, EPI>), dim3(grid), dim3(1024), lds, st, g_img, q_img, gsq, qsq, ng, nq, pitch, kt, metric, out, tm2, tn2, grid2, epi);
+    else hipLaunchKernelGGL((pairdist_dma_kernel<1, EPI>), dim3(grid), dim3(1024), lds, st, g_img, q_img, gsq, qsq, ng, nq, pitch, kt, metric, out, tm2, tn2, grid2, epi);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+
 static int launch_pairdist(int num_cus, hipStream_t st, const uint16_t* g_img, const float* gsq, const uint16_t* q_img, const float* qsq, int nq, int ng,
                            int d, int metric, bool split, float* out, PairBlend blend = PairBlend{nullptr, nullptr, nullptr, nullptr, 0}) {
     const int Kp = pair_kp(d, split), pitch = pair_pitch(d, split);
-    if ((long long)ng * pitch * 2 < 0x7ff00000ll && (long long)nq * pitch * 2 < 0x7ff00000ll) {
-        const int tm2 = (ng + 127) / 128, tn2 = (nq + 255) / 256;
-        const int grid2 = xcd_tile_grid(tm2, tn2);
-        const int lds = 3 * (128 + 256) * 64 * 2 + 8 * PAIR_STRIP_BYTES;         // 3 stages x 48 KiB + the consumers' store strips = 160 KiB
-        DALI_ONCE_PER_DEVICE({
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pairdist_dma_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&pairdist_dma_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        });
-        const int cap = num_cus / 8 * 8, grid = grid2 < cap ? grid2 : cap;          // persistent: one workgroup per CU (144 KiB of LDS each)
-        const int kt = split ? Kp / 32 : Kp / 64;
-        if (split) hipLaunchKernelGGL(pairdist_dma_kernel<3>, dim3(grid), dim3(1024), lds, st, g_img, q_img, gsq, qsq, ng, nq, pitch, kt, metric, out, tm2, tn2, grid2, blend);
-        else hipLaunchKernelGGL(pairdist_dma_kernel<1>, dim3(grid), dim3(1024), lds, st, g_img, q_img, gsq, qsq, ng, nq, pitch, kt, metric, out, tm2, tn2, grid2, blend);
-        DALI_LAUNCH_CHECK();
-        return DALI_OK;
-    }
+    if (pair_dma_fits(ng, pitch) && pair_dma_fits(nq, pitch))
+        return launch_pairdist_dma(num_cus, st, g_img, gsq, q_img, qsq, nq, ng, d, metric, split, out, blend);
     const int tiles_m = (ng + 127) / 128, tiles_n = (nq + 127) / 128;
     const int grid = xcd_tile_grid(tiles_m, tiles_n);
     if (split) {
@@ -967,6 +1037,20 @@ extern "C" int dali_pairdist_prepared(dali_ctx* ctx, void* stream, const void* q
     return launch_pairdist(ctx->num_cus, (hipStream_t)stream, static_cast<const uint16_t*>(g_image), g_sq, static_cast<const uint16_t*>(q_image), q_sq, nq, ng, d,
                            metric, precision == DALI_PREC_BF16X3, out);
 }
+
+// The distance kernel as topk.hip drives it (kernels.h): operand images whose row counts fit the DMA kernel's offsets (pairdist_dma_max_rows).
+namespace dali {
+int pairdist_dma_max_rows(int d, bool split) { return (int)((0x7ff00000ll - 1) / ((long long)pair_pitch(d, split) * 2)); }
+int launch_pairdist_matrix(int num_cus, hipStream_t st, const uint16_t* g_img, const float* gsq, const uint16_t* q_img, const float* qsq, int nq, int ng,
+                           int d, int metric, bool split, float* out, const int* gate) {
+    if (!gate) return launch_pairdist(num_cus, st, g_img, gsq, q_img, qsq, nq, ng, d, metric, split, out);
+    return launch_pairdist_dma(num_cus, st, g_img, gsq, q_img, qsq, nq, ng, d, metric, split, out, PairGate{gate});
+}
+int launch_pairdist_select(int num_cus, hipStream_t st, const uint16_t* g_img, const float* gsq, const uint16_t* q_img, const float* qsq, int nq, int ng,
+                           int d, int metric, bool split, const PairTopk& sel) {
+    return launch_pairdist_dma(num_cus, st, g_img, gsq, q_img, qsq, nq, ng, d, metric, split, (float*)nullptr, sel);
+}
+}  // namespace dali
 
 // ------------------------------------------------------------------------------------------------
 // Small similarity GEMMs (the loss heads' fn @ centers^T, fn @ proxies^T, dS @ centers: 256 x 751 .. 2253 x 2048, losses.py:62, :277) on the fp32

@@ -196,4 +196,13 @@ int launch_attention_fwd(hipStream_t st, const uint16_t* qkv, int B, int T, int 
 int launch_attention_bwd(hipStream_t st, const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, int B, int T, int H,
                          float scale, uint16_t* dqkv);
 
+// eval.hip: the distance kernel as topk.hip drives it.  Both operand images must have at most pairdist_dma_max_rows rows when a gate or a
+// selection is passed (the LDS-DMA kernel's 32-bit offsets); gate (nullable): the launch runs only if gate[0] != 0, decided on the device.
+struct PairTopk;
+int pairdist_dma_max_rows(int d, bool split);
+int launch_pairdist_matrix(int num_cus, hipStream_t st, const uint16_t* g_img, const float* gsq, const uint16_t* q_img, const float* qsq, int nq, int ng,
+                           int d, int metric, bool split, float* out, const int* gate);
+int launch_pairdist_select(int num_cus, hipStream_t st, const uint16_t* g_img, const float* gsq, const uint16_t* q_img, const float* qsq, int nq, int ng,
+                           int d, int metric, bool split, const PairTopk& sel);
+
 }  // namespace dali

@@ -70,6 +70,99 @@ def pairdist_prepared(qp, gp, metric="cosine", out=None):
     return out
 
 
+TOPK_K_MAX = 128          # keys per row the selection kernels keep (include/daliid.h, dali_topk_rows)
+
+
+def _topk_k(k, avail, running, who):
+    """k as the C entries take it: refused beyond the documented cap, clamped to the columns available when no list is being continued."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("%s: k=%d" % (who, k))
+    if k > TOPK_K_MAX:
+        raise _lib.DaliError("%s: k=%d above the documented cap %d" % (who, k, TOPK_K_MAX))
+    if running is not None:
+        if running.dim() != 2 or running.shape[1] != k or running.dtype != torch.int64:
+            raise ValueError("%s: running must be the int64 [nq, %d] keys of an earlier call" % (who, k))
+        return k
+    return min(k, int(avail))
+
+
+def topk_decode(keys, largest=False):
+    """keys int64 [nq, k] (topk_rows / pairdist_topk, return_keys=True) -> (values fp32 [nq, k], indices int32 [nq, k])."""
+    nq, k = keys.shape
+    values = torch.empty(nq, k, device=keys.device, dtype=torch.float32)
+    indices = torch.empty(nq, k, device=keys.device, dtype=torch.int32)
+    if nq and k:
+        _lib.check(_lib.lib().dali_topk_decode(_lib.ctx(keys.device), _lib.stream_ptr(), _lib.ptr(keys, torch.int64, "keys"), nq, k,
+                                               int(bool(largest)), _lib.ptr(values), _lib.ptr(indices)), "dali_topk_decode")
+    return values, indices
+
+
+def topk_rows(distmat, k, largest=False, col_offset=0, running=None, return_keys=False):
+    """The k best entries of every row of a CUDA fp32 matrix in the order of include/daliid.h (dali_topk_rows): ascending values
+    (descending for ``largest``), exact ties by ascending index, -0.0 == +0.0, NaN last.  -> (values fp32 [nq, k], indices int32 [nq, k]
+    [, keys int64 [nq, k]]) on the device, enqueued on the current stream.  ``distmat`` may be a column slice of a contiguous matrix
+    (read by its pitch); its column j has index ``col_offset + j``.  ``running``: the keys of an earlier call on other columns of the
+    same rows; the result is then the selection over both (the tensor passed in is left unchanged).  Without ``running`` k is clamped to
+    the number of columns."""
+    if distmat.dim() != 2:
+        raise ValueError("topk_rows: distmat must be 2-D")
+    nq, ncols = distmat.shape
+    k = _topk_k(k, ncols, running, "topk_rows")
+    if distmat.dtype != torch.float32 or not distmat.is_cuda:
+        raise _lib.DaliError("topk_rows: distmat must be a CUDA float32 tensor")
+    if ncols > 0 and nq > 0 and not (distmat.stride(1) == 1 and (nq == 1 or distmat.stride(0) >= ncols)):
+        distmat = distmat.contiguous()
+    ld = max(int(distmat.stride(0)), ncols) if nq > 1 else ncols
+    dev = distmat.device
+    if running is not None:
+        if running.shape[0] != nq:
+            raise ValueError("topk_rows: running has %d rows, distmat %d" % (running.shape[0], nq))
+        keys = running.to(dev).contiguous().clone()
+    else:
+        keys = torch.empty(nq, k, device=dev, dtype=torch.int64)
+    if nq > 0 and k > 0:
+        _lib.check(_lib.lib().dali_topk_rows(_lib.ctx(dev), _lib.stream_ptr(), _lib.c_void_p(distmat.data_ptr()), nq, ncols, ld, int(col_offset), k,
+                                             int(bool(largest)), int(running is not None), _lib.ptr(keys)), "dali_topk_rows")
+    out = topk_decode(keys, largest)
+    return out + (keys,) if return_keys else out
+
+
+def pairdist_topk(q, g, k, metric="cosine", precision="bf16x3", normalize=False, largest=False, g_offset=0, running=None, return_keys=False,
+                  return_stats=False, _tuning=None):
+    """The k nearest gallery rows of every query WITHOUT the [nq, ng] matrix (include/daliid.h, dali_pairdist_topk): exactly
+    ``topk_rows(pairdist_prepared(q, g, metric), k, largest, col_offset=g_offset)``, values bitwise those of the matrix, computed by the
+    same distance kernel with a selecting epilogue.  q, g: fp32 feature tensors (prepared here with ``normalize`` / ``precision``) or
+    ``PreparedRows``.  ``g_offset`` / ``running``: a gallery fed in slices (or held in shards) gives the lists of the whole.
+    -> (values fp32 [nq, k], indices int32 [nq, k] [, keys int64] [, stats int32 [3] on the device: gallery rows selected in the
+    epilogue, rows taken through the matrix block, overflow events]).  ``_tuning`` = (boot_cols, chunk_cols, cand_cap) is for tests."""
+    qp = q if isinstance(q, PreparedRows) else PreparedRows(q.contiguous(), normalize=normalize, precision=precision)
+    gp = g if isinstance(g, PreparedRows) else PreparedRows(g.contiguous(), normalize=normalize, precision=precision)
+    assert qp.d == gp.d and qp.precision == gp.precision
+    nq, ng = qp.n, gp.n
+    k = _topk_k(k, ng, running, "pairdist_topk")
+    dev = qp.image.device
+    boot, chunk, cap = (int(v) for v in _tuning) if _tuning is not None else (0, 0, 0)
+    if running is not None:
+        if running.shape[0] != nq:
+            raise ValueError("pairdist_topk: running has %d rows for %d queries" % (running.shape[0], nq))
+        keys = running.to(dev).contiguous().clone()
+    else:
+        keys = torch.empty(nq, k, device=dev, dtype=torch.int64)
+    stats = torch.zeros(3, device=dev, dtype=torch.int32)
+    if nq > 0 and k > 0:
+        _lib.check(_lib.lib().dali_pairdist_topk(_lib.ctx(dev), _lib.stream_ptr(), _lib.ptr(qp.image), _lib.ptr(qp.sq), _lib.ptr(gp.image),
+                                                 _lib.ptr(gp.sq), nq, ng, qp.d, _METRIC[metric], _PREC[qp.precision], k, int(bool(largest)),
+                                                 int(g_offset), int(running is not None), _lib.ptr(keys), boot, chunk, cap, _lib.ptr(stats)),
+                   "dali_pairdist_topk")
+    out = topk_decode(keys, largest)
+    if return_keys:
+        out += (keys,)
+    if return_stats:
+        out += (stats,)
+    return out
+
+
 def factorize_ids(*arrays):
     """Shared int32 codes for id columns (the reference carries pids / camids as numpy strings)."""
     flat = np.concatenate([np.asarray(a).ravel() for a in arrays])

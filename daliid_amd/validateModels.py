@@ -72,6 +72,20 @@ class validateModels:
         """validateModels.py:41-47: q/|q|, g/|g|, 1 - q @ g.T (fused)."""
         return ops_eval.pairdist(queries_fvs.contiguous(), gallery_fvs.contiguous(), metric="cosine", precision=self.precision, normalize=True)
 
+    def retrieve(self, queries, gallery, model, k=50):
+        """The k nearest gallery images of every query under ``validate``'s distance, without the [Nq, Ng] matrix
+        (ops_eval.pairdist_topk): -> (indices int32 [Nq, k] into ``gallery``, distances fp32 [Nq, k]) on the device, nearest first, exact
+        ties by ascending gallery index.  The distances are bitwise the entries ``validate`` would return in its matrix."""
+        model.eval()
+        queries_fvs = extractFeatures(queries, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
+        gallery_fvs = extractFeatures(gallery, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
+        return self.retrieve_features(queries_fvs, gallery_fvs, k)
+
+    def retrieve_features(self, queries_fvs, gallery_fvs, k=50):
+        distances, indices = ops_eval.pairdist_topk(queries_fvs.contiguous(), gallery_fvs.contiguous(), k, metric="cosine",
+                                                    precision=self.precision, normalize=True)
+        return indices, distances
+
     def calculateMetrics(self, distmat, queries, gallery):
         """validateModels.py:61-76 -> torchreid.metrics.evaluate_rank(distmat, q_pids, g_pids, q_camids, g_camids,
         use_metric_cuhk03=False)."""
@@ -90,6 +104,34 @@ class validateModels:
         return cmc, mAP
 
 
+class validateBRIAR(validateModels):
+    """validateModels.validateBRIAR (validateModels.py:79-105): closed-set identification without camera filtering."""
+
+    def calculateMetrics(self, distmat, queries, gallery):
+        """validateModels.py:84-105: Rank-1/5/10/20 = the share of queries whose identity is among the identities of their 1/5/10/20
+        nearest gallery entries; -> (list of the four rank values, 0).  The 20 nearest come from ops_eval.topk_rows instead of a full
+        ``torch.argsort(distmat, dim=1)[:, :20]``.  Exactly equal distances are ordered by ascending gallery index here; torch.argsort is
+        not stable by default and leaves that order unspecified, so on such ties the reference's own result is not defined either."""
+        if not isinstance(distmat, torch.Tensor):
+            distmat = torch.as_tensor(np.asarray(distmat))
+        distmat = distmat.to(torch.device("cuda", getattr(self, "gpu_index", 0)), dtype=torch.float32)
+        nq = queries.shape[0]
+        gt = queries[:, 1].reshape(nq, 1)
+        cmc = []
+        ranks = [1, 5, 10, 20]
+        print('Computing CMC and mAP ...')
+        _, ranked_idx = ops_eval.topk_rows(distmat, 20)
+        predicted = gallery[:, 1][ranked_idx.cpu().numpy()]
+        matching = gt == predicted
+        print('** Results **')
+        print('Ranks:')
+        for r in ranks:
+            rank_value = np.mean(np.sum(matching[:, :r], axis=1) > 0)
+            print('Rank-{:<3}: {:.2%}'.format(r, rank_value))
+            cmc.append(rank_value)
+        return cmc, 0
+
+
 class MSMT17_validator:
     """validateModels.MSMT17_validator (validateModels.py:120-190): MSMT17's train/val balanced-accuracy validation.  mainKIT.main only
     builds it when ``dataset == 'MSMT17'`` (mainKIT.py:122-124); that dataset branch is outside the scope table.  The
@@ -103,7 +145,9 @@ class validationManager:
 
     @staticmethod
     def getValidator(name):
-        """validateModels.py:108-118: the BRIAR / MSMT17 validators are outside the scope table."""
-        if name in ("BRIAR", "MSMT17"):
+        """validateModels.py:108-118; the MSMT17 validator is outside the scope table."""
+        if name == "MSMT17":
             raise NotImplementedError("validator for %s is out of scope of this build (SURVEY.md 2.1)" % name)
+        if name == "BRIAR":
+            return validateBRIAR()
         return validateModels()

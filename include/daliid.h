@@ -172,6 +172,44 @@ int dali_roc_build(dali_ctx* ctx, void* stream, const float* distmat, const int3
 int dali_roc_emit(dali_ctx* ctx, void* stream, const void* scratch, int nq, int ng, int drop_intermediate, int64_t n_points,
                   float* thresholds, int64_t* fps, int64_t* tps);
 
+/* Exact top-k retrieval: the k best entries of every row, the question behind validateBRIAR.calculateMetrics (validateModels.py:79-105,
+ * argsort[:, :20]), MSMT17_validator (:179-180, torch.topk) and get_subset_one_encoder (getFeatures.py:337-348).
+ * THE ORDER (everything below uses it): ascending by value, exact ties by ascending index; -0.0 equals +0.0; a NaN of either sign comes
+ * after +inf, as numpy and torch sort it.  largest != 0 reverses the value order only: ties still go by ascending index and NaN still
+ * comes last.  A list is kept as k int64 keys per row, best first: (ordered value bits << 32) | global column index, compared as
+ * unsigned; a slot that no column has filled yet (k larger than the columns seen) holds the all-ones key.
+ *   dali_topk_rows   x [nq][ncols] fp32 with row pitch ld >= ncols elements (a column slice of a wider matrix; 4-byte alignment is
+ *                    enough, 16-byte aligned rows are read faster); column j has global index col_offset + j (< 2^31).  accumulate == 0
+ *                    starts keys [nq][k]; accumulate != 0 merges the block into the lists an earlier call left there, so a matrix may
+ *                    be fed in column blocks of any widths and gives the lists of the whole.  One read of the block.
+ *   dali_topk_decode keys -> values [nq][k] fp32, indices [nq][k] int32.  Values are the selected entries' bits, except -0.0 -> +0.0
+ *                    and every NaN -> the quiet NaN 0x7fc00000; an unfilled slot gives index -1 and value +inf (-inf for largest).
+ *   dali_pairdist_topk  the same lists for the rows of D = dali_pairdist_prepared(q_image, g_image, metric, precision) WITHOUT the
+ *                    matrix: gallery row g has global index g_offset + g, values are bitwise those of D (same kernel, same
+ *                    accumulators, same metric arithmetic; its epilogue selects instead of storing).  accumulate as above, so a
+ *                    gallery may be fed in slices; slices and images of any size are accepted (images beyond the kernel's 32-bit
+ *                    offsets are walked in row ranges).  Method: the first boot_cols gallery rows go through a [nq][boot_cols] block
+ *                    of D and dali_topk_rows, which gives every query a threshold (its k-th key); the rest is walked in rounds of
+ *                    chunk_cols, 2 chunk_cols, 4 chunk_cols, ... rows, never more than the rows already seen (so that a gallery in
+ *                    random order leaves at most k survivors per query and round on average), whose distances are compared with the thresholds in the
+ *                    distance kernel's epilogue; the survivors (a fraction k / rows_seen of a gallery in random order) are appended
+ *                    to per-query candidate lists of cand_cap keys and merged after the round.  A round in which a list overflows is
+ *                    dropped and redone through the block, on the device, so any gallery order gives the exact result.
+ *                    boot_cols / chunk_cols (rounded up to multiples of 128) / cand_cap: 0 = defaults (4096, 4096, max(64, 4 k)).
+ *                    stats [3] int32 (device, written by this call): gallery rows selected in the epilogue, gallery rows taken through
+ *                    the block (the bootstrap included), overflow events.
+ *   dali_pairdist_topk_scratch_bytes  the workspace the call takes from the context: the block, the candidate lists and counters;
+ *                    independent of ng (its argument is kept for symmetry); 0 for an unsupported shape.
+ * Limits: 1 <= k <= 128 and cand_cap <= 1920 (DALI_ERR_LIMIT); indices < 2^31.  Nothing synchronises.  The only atomics are integer slot
+ * counters whose order of arrival cannot reach a result (lists are sorted by unique keys): bitwise identical results run to run. */
+int dali_topk_rows(dali_ctx* ctx, void* stream, const float* x, int nq, int ncols, int64_t ld, int col_offset, int k, int largest,
+                   int accumulate, int64_t* keys);
+int dali_topk_decode(dali_ctx* ctx, void* stream, const int64_t* keys, int nq, int k, int largest, float* values, int32_t* indices);
+size_t dali_pairdist_topk_scratch_bytes(int nq, int ng, int d, int k, int boot_cols, int chunk_cols, int cand_cap);
+int dali_pairdist_topk(dali_ctx* ctx, void* stream, const void* q_image, const float* q_sq, const void* g_image, const float* g_sq,
+                       int nq, int ng, int d, int metric, int precision, int k, int largest, int g_offset, int accumulate,
+                       int64_t* keys, int boot_cols, int chunk_cols, int cand_cap, int32_t* stats);
+
 /* ---- training path: Encoders.ResNet50ReID trunk (Encoders.py:330-339) ----------------------------- *
  * Single-op entry points (the parity tests call these; the net plan below chains the same kernels).
  * Layouts: activations NHWC bf16; forward weights [cout][r][s][cin] bf16; dgrad weights
