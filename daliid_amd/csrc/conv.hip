@@ -99,6 +99,27 @@ __device__ __forceinline__ int parity_block(IGemmArgs& a) {
     return b;
 }
 
+// Diagnostic timeline (dali_debug_set_conv_stamps; IGemmArgs / WGradArgs::stamps, 12 slots per workgroup, s_memrealtime ticks; read by
+// scripts/conv_block_timeline.py).  Slots: 0 start, 1 first tile landed, 2 main loop done, 3 stores acknowledged, 4 stores issued,
+// 5 statistics done, 6 / 8 half staged, 7 / 9 half's stores issued, 10 HW_ID (igemm_conv_k64_kernel).
+// (igemm_conv_dma_kernel and igemm_conv_k64_kernel write their slots 0 - 2 out instead of calling conv_stamp: with the call their linear-layer
+// instantiations, which sit at the 128-register limit, spilled 3 and 2 more registers in the epilogue.)
+template <class Args>
+__device__ __forceinline__ void conv_stamp(const Args& a, int slot) {
+    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + slot] = __builtin_amdgcn_s_memrealtime();
+}
+template <class Args>
+__device__ __forceinline__ void conv_stamp_stores(const Args& a) {
+    if (a.stamps) {
+        const unsigned long long t_issued = __builtin_amdgcn_s_memrealtime();   // all stores issued (not yet acknowledged)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's stores have been acknowledged
+        if (threadIdx.x == 0) {
+            a.stamps[(size_t)blockIdx.x * 12 + 3] = __builtin_amdgcn_s_memrealtime();
+            a.stamps[(size_t)blockIdx.x * 12 + 4] = t_issued;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // forward / dgrad
 // ------------------------------------------------------------------------------------------------
@@ -364,7 +385,7 @@ __device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&ac
         }
         // no barrier: the staged store below does not touch `red`
     }
-    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 5] = __builtin_amdgcn_s_memrealtime();     // stats done
+    conv_stamp(a, 5);     // stats done
 
     // ---- lean path: plain convolution (optionally + residual), interior tile, natural output addressing ----
     // LIN == 4: the lean path with the output addressing of a stride-2 data gradient's parity class (GatherGeom::sub): the pixel rows of
@@ -440,7 +461,7 @@ __device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&ac
                 }
             }
             lds_barrier();
-            if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 6 + 2 * h] = __builtin_amdgcn_s_memrealtime();   // half staged
+            conv_stamp(a, 6 + 2 * h);   // half staged
 #pragma unroll
             for (int it = 0; it < ITERS; ++it) {
                 const int lp = lp0 + it * (NT / CPR);
@@ -448,7 +469,7 @@ __device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&ac
                 *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + row_bytes(q)) =
                     *reinterpret_cast<const uint4*>(stage + lp * ROWB + ch * 16);
             }
-            if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 7 + 2 * h] = __builtin_amdgcn_s_memrealtime();   // half's stores issued
+            conv_stamp(a, 7 + 2 * h);   // half's stores issued
             if (h == 0) lds_barrier();                          // the LDS reads are done before the second half overwrites them
         }
         return;
@@ -539,9 +560,9 @@ __device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&ac
                 }
             }
             lds_barrier();
-            if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 6 + 2 * h] = __builtin_amdgcn_s_memrealtime();   // half staged
+            conv_stamp(a, 6 + 2 * h);   // half staged
             store_half(a.O, gbase);
-            if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 7 + 2 * h] = __builtin_amdgcn_s_memrealtime();   // half's stores issued
+            conv_stamp(a, 7 + 2 * h);   // half's stores issued
             if (h == 0) lds_barrier();                          // the LDS reads are done before the second half overwrites them
         }
         return;
@@ -785,218 +806,96 @@ __global__ __launch_bounds__(256) void igemm_conv_kernel(IGemmArgs a, int tiles_
 // ------------------------------------------------------------------------------------------------
 // (lds_void_ptr, DMA_OOB, dma_wait<N> live in gemm_tile.h: shared with eval.hip)
 
+// The gather of every LDS-DMA forward / data-gradient kernel: one issuing wave's share of a k-tile, fetched as 1 KiB pieces
+// (ROWS rows of KT bf16) into a stage's weight image `sa` ([TM][KT]) and pixel image `sb` ([TN][KT]).  Piece q = wave + NW * i holds
+// rows ROWS * q .. ROWS * q + ROWS - 1.  The kernels around it own the ring schedule, the wave roles and the epilogue.
 // SRC2: K = the channels of X followed by the channels of a second plain [P][channels] tensor X2 (IGemmArgs::X2 / Ck1; 1x1, stride 1): its own
 // instantiations, so that the hot ones carry none of it.
-template <int TM, int TN, int NSTAGE, int EPI = 0, bool SRC2 = false>        // EPI: 0 convolution, 1 linear-layer extras, 3 fused output stage (conv_epilogue_g)
-__global__ __launch_bounds__(256, (TM >= 128 ? (EPI == 3 ? 3 : 4) : 2)) void igemm_conv_dma_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
-    // 128 x 128: <= 128 VGPRs (4 waves per SIMD); the 64 x 256 shape carries twice the per-lane gather state and would spill
-    using Cfg = GemmCfg<TM, TN, 1, 1, 1>;
-    constexpr int FM = Cfg::FM, FN = Cfg::FN;
-    constexpr int A_BLK = TM / 16 / 4, B_BLK = TN / 16 / 4;      // 1 KiB DMA blocks (16 rows x 64 B) per wave per k-tile
-    extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
-    int tm, tn;
-    if (!xcd_tile_map(parity_block(a), tiles_m, tiles_n, tm, tn)) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12] = __builtin_amdgcn_s_memrealtime();
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const GatherGeom g = a.g;
-    const int K = g.R * g.S * g.Ck;                    // weight row length
-    const int ktiles = (g.nr * g.ns * g.Ck) >> 5;      // taps actually visited (all of them unless g.sub)
+template <int KT, int TM, int TN, int NW, bool SRC2>
+struct ConvGather {
+    static_assert(KT == 32 || KT == 64, "k-tile depth");
+    static constexpr int ROWS = 512 / KT;                                              // rows per piece
+    static constexpr int A_BLK = TM / ROWS / NW, B_BLK = (TN / ROWS + NW - 1) / NW;    // pieces per wave per k-tile
+    static constexpr bool B_RAGGED = (TN / ROWS) % NW != 0;     // 320 pixels: 40 pieces over 16 waves, the waves of the upper half skip their third
+    static constexpr int NDMA = A_BLK + B_BLK;                                         // what dma_wait<> counts for one k-tile
+    static_assert(TM % (ROWS * NW) == 0 && TN % ROWS == 0, "DMA pieces: whole pieces, the weight pieces evenly over the waves");
+    static_assert(KT == 64 || !B_RAGGED, "k-tile 32: the pixel pieces must divide evenly over the waves");
+    static_assert(KT == 32 || NW % 2 == 0, "k-tile 64: an even number of issuing waves (piece wave + NW * i keeps the wave's parity)");
+    static_assert(!(SRC2 && B_RAGGED), "the two-tensor branch has no ragged skip");
 
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.W), 0, a.Cm * K * 2, 0x00020000);
-    const long long x_bytes = SRC2 ? (long long)a.P * a.Ck1 * 2 : (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000);
-    const int Ck2 = g.Ck - a.Ck1;                                   // (SRC2) channels of the second tensor
-    const __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(SRC2 ? a.X2 : a.X), 0, SRC2 ? (int)((long long)a.P * Ck2 * 2) : (int)x_bytes, 0x00020000);
-
-    // lane-constant part of the source swizzle: LDS slot `lane` of a block = row lane>>2, physical chunk lane&3
-    const int r_in = lane >> 2;
-    const int kc = (lane & 3) ^ lds_swz(r_in);                     // logical 16-byte chunk this lane fetches
-    // A (weights): rows m0 + 16*(wave + 4*i) + r_in
+    const GatherGeom& g;
+    int wave, Ck1, Ck2;                       // (SRC2) channels of the first / second tensor
+    __amdgpu_buffer_rsrc_t rs_w, rs_x, rs_x2;
+    int kc;                                   // logical 16-byte chunk this lane fetches
     uint32_t a_off[A_BLK];
-#pragma unroll
-    for (int i = 0; i < A_BLK; ++i) {
-        const int m = tm * TM + 16 * (wave + 4 * i) + r_in;
-        a_off[i] = (m < a.Cm) ? (uint32_t)(m * K + kc * 8) * 2u : DMA_OOB;
-    }
-    // B (pixels): rows p0 + 16*(wave + 4*i) + r_in
     int b_pix[B_BLK], b_h0[B_BLK], b_w0[B_BLK];
-#pragma unroll
-    for (int i = 0; i < B_BLK; ++i) {
-        const int p = tn * TN + 16 * (wave + 4 * i) + r_in;
-        int n = 0, ho = 0, wo = 0;
-        const bool ok = p < a.P;
-        if (ok) decode_pixel(g, p, n, ho, wo);
-        if (g.sub) { ho = 2 * ho + g.oph; wo = 2 * wo + g.opw; }
-        if (g.mode == 0) { b_h0[i] = ho * g.stride - g.pad; b_w0[i] = wo * g.stride - g.pad; }
-        else { b_h0[i] = ho + g.pad; b_w0[i] = wo + g.pad; }
-        if (!ok) b_h0[i] = -0x40000000;                             // never in range
-        b_pix[i] = (int)((long long)n * g.img_pitch) + kc * 8;      // element offset of the image (+ this lane's chunk)
-        if constexpr (SRC2) b_pix[i] = ok ? p : -1;                  // plain rows: the pixel index itself (row pitch differs between the two tensors)
-    }
+    int kr, ks, kc0, ks_end, kr_end;          // wave-uniform k position
 
-    // wave-uniform k position
-    int kr = g.r0, ks = g.s0, kc0 = 0;
-    const int ks_end = g.s0 + g.sstep * g.ns, kr_end = g.r0 + g.rstep * g.nr;
-    auto issue = [&](int stage) {
-        uint16_t* sa = smem + stage * Cfg::STAGE_ELEMS;
-        uint16_t* sb = sa + Cfg::A_ELEMS;
-        const int kbase = ((kr * g.S + ks) * g.Ck + kc0) * 2;      // byte offset of this k-tile inside a weight row
+    __device__ __forceinline__ ConvGather(const IGemmArgs& a, const GatherGeom& g_, int tm, int tn, int wave_, int lane) : g(g_) {
+        wave = wave_;
+        const int K = g.R * g.S * g.Ck;                    // weight row length
+        rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.W), 0, a.Cm * K * 2, 0x00020000);
+        const long long x_bytes = SRC2 ? (long long)a.P * a.Ck1 * 2 : (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
+        rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000);
+        Ck1 = a.Ck1; Ck2 = g.Ck - a.Ck1;
+        rs_x2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(SRC2 ? a.X2 : a.X), 0, SRC2 ? (int)((long long)a.P * Ck2 * 2) : (int)x_bytes, 0x00020000);
+        // The source-side swizzle.  An LDS-DMA wave-instruction writes lane-linear, so the XOR swizzle of the LDS image is applied to the
+        // chunk each lane fetches; the lane-constant part:
+        //   KT 32: LDS slot `lane` of a piece = row lane >> 2, physical chunk lane & 3, swizzle lds_swz(row) (gemm_tile.h);
+        //   KT 64: LDS slot `lane` of piece q = row 8q + (lane >> 3), physical chunk lane & 7, swizzle (row >> 1) & 7; q = wave + NW * i has
+        //          the parity of the wave, so the logical chunk this lane fetches is the same for all of its pieces.
+        int r_in;
+        if constexpr (KT == 32) { r_in = lane >> 2; kc = (lane & 3) ^ lds_swz(r_in); }
+        else { r_in = lane >> 3; kc = (lane & 7) ^ (((wave & 1) << 2) | (r_in >> 1)); }
+        // A (weights): rows m0 + ROWS * (wave + NW * i) + r_in
 #pragma unroll
         for (int i = 0; i < A_BLK; ++i) {
-            const uint32_t off = (a_off[i] == DMA_OOB) ? DMA_OOB : a_off[i] + (uint32_t)kbase;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_ptr)(sa + (wave + 4 * i) * 512), 16, off, 0, 0, 0);
+            const int m = tm * TM + ROWS * (wave + NW * i) + r_in;
+            a_off[i] = (m < a.Cm) ? (uint32_t)(m * K + kc * 8) * 2u : DMA_OOB;
         }
-        if constexpr (SRC2) {
-            // K position kc0 lies in X (< Ck1) or in X2: a wave-uniform choice per k-tile
-            const bool second = kc0 >= a.Ck1;
-            const int pitch = second ? Ck2 : a.Ck1, cbase = (second ? kc0 - a.Ck1 : kc0) + kc * 8;
-#pragma unroll
-            for (int i = 0; i < B_BLK; ++i) {
-                const uint32_t off = b_pix[i] >= 0 ? (uint32_t)(b_pix[i] * pitch + cbase) * 2u : DMA_OOB;
-                if (second) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x2, (lds_void_ptr)(sb + (wave + 4 * i) * 512), 16, off, 0, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(sb + (wave + 4 * i) * 512), 16, off, 0, 0, 0);
-            }
-            kc0 += 32;
-            return;
-        }
+        // B (pixels): rows p0 + ROWS * (wave + NW * i) + r_in
 #pragma unroll
         for (int i = 0; i < B_BLK; ++i) {
-            int hi, wi;
-            bool ok;
-            if (g.mode == 0) {
-                hi = b_h0[i] + kr; wi = b_w0[i] + ks;
-                ok = true;
-            } else {
-                const int th = b_h0[i] - kr, tw = b_w0[i] - ks;
-                ok = (th >= 0) && (tw >= 0);
-                if (g.stride == 2) { ok = ok && (((th | tw) & 1) == 0); hi = th >> 1; wi = tw >> 1; }
-                else { hi = th; wi = tw; }
-            }
-            ok = ok && ((unsigned)hi < (unsigned)g.Hin) && ((unsigned)wi < (unsigned)g.Win);
-            const uint32_t off = ok ? (uint32_t)(b_pix[i] + hi * g.row_pitch + wi * g.pix_pitch + kc0) * 2u : DMA_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(sb + (wave + 4 * i) * 512), 16, off, 0, 0, 0);
+            const int p = tn * TN + ROWS * (wave + NW * i) + r_in;
+            int n = 0, ho = 0, wo = 0;
+            const bool ok = p < a.P;
+            if (ok) decode_pixel(g, p, n, ho, wo);
+            if (g.sub) { ho = 2 * ho + g.oph; wo = 2 * wo + g.opw; }
+            if (g.mode == 0) { b_h0[i] = ho * g.stride - g.pad; b_w0[i] = wo * g.stride - g.pad; }
+            else { b_h0[i] = ho + g.pad; b_w0[i] = wo + g.pad; }
+            if (!ok) b_h0[i] = -0x40000000;                             // never in range
+            b_pix[i] = (int)((long long)n * g.img_pitch) + kc * 8;      // element offset of the image (+ this lane's chunk)
+            if constexpr (SRC2) b_pix[i] = ok ? p : -1;                  // plain rows: the pixel index itself (row pitch differs between the two tensors)
         }
-        // advance (channel block fastest, then s, then r)
-        // taps fastest, channel block outermost: the R*S taps of one channel block are fetched in consecutive k-steps, so the
-        // shifted re-reads of the same pixels hit the XCD's L2 (channels-fastest order spaced them Ck/32 steps apart: with
-        // Ck >= 128 the line had left the 4 MiB L2 and came back from the Infinity Cache at HBM-like bandwidth, 9 times)
-        ks += g.sstep;
-        if (ks >= ks_end) { ks = g.s0; kr += g.rstep; if (kr >= kr_end) { kr = g.r0; kc0 += 32; } }
-    };
-
-    f32x4_t acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int frag_off = (lane & 15) * 32 + (((lane >> 4) ^ lds_swz(lane & 15)) << 3);
-    const int a_row0 = wm * (TM / 2), b_row0 = wn * (TN / 2);
-
-    // 3-stage ring: the DMA of tile t+2 is issued before tile t is multiplied; the wait at the end of iteration t retires
-    // tile t+1 only (counted vmcnt leaves tile t+2's A_BLK+B_BLK DMAs in flight ACROSS the barrier, so a raw s_barrier is
-    // used: __syncthreads() would drain them).  A stage is read one iteration after the wait+barrier that retired it, and
-    // re-filled two barriers after its last read.
-    constexpr int NDMA = A_BLK + B_BLK;
-    constexpr int AHEAD = NSTAGE - 1;                   // tiles in flight beyond the one being multiplied
-    issue(0);
-    if (AHEAD == 2 && ktiles > 1) issue(1);
-    if (AHEAD == 2 && ktiles > 1) dma_wait<NDMA>(); else dma_wait<0>();
-    __builtin_amdgcn_s_barrier();
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
-    int st_cur = 0, st_nxt2 = AHEAD;
-    for (int kt = 0; kt < ktiles; ++kt) {
-        if (kt + AHEAD < ktiles) issue(st_nxt2);
-        const uint16_t* sa = smem + st_cur * Cfg::STAGE_ELEMS;
-        const uint16_t* sb = sa + Cfg::A_ELEMS;
-        bf16x8_t fa[FM];
-#pragma unroll
-        for (int i = 0; i < FM; ++i) fa[i] = *reinterpret_cast<const bf16x8_t*>(sa + (a_row0 + i * 16) * 32 + frag_off);
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-            const bf16x8_t fb = *reinterpret_cast<const bf16x8_t*>(sb + (b_row0 + j * 16) * 32 + frag_off);
-#pragma unroll
-            for (int i = 0; i < FM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
-        }
-        if (AHEAD == 2 && kt + 2 < ktiles) dma_wait<NDMA>(); else dma_wait<0>();
-        __builtin_amdgcn_s_barrier();
-        st_cur = (st_cur == NSTAGE - 1) ? 0 : st_cur + 1;
-        st_nxt2 = (st_nxt2 == NSTAGE - 1) ? 0 : st_nxt2 + 1;
+        kr = g.r0; ks = g.s0; kc0 = 0;
+        ks_end = g.s0 + g.sstep * g.ns; kr_end = g.r0 + g.rstep * g.nr;
     }
-    __syncthreads();
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
 
-    conv_epilogue<Cfg, ((TM == 128 && TN == 128 && NSTAGE == 3) || EPI == 3 || EPI == 5) ? EPI : 2>(a, acc, tm, tn, smem);
-    if (a.stamps) {
-        const unsigned long long t_issued = __builtin_amdgcn_s_memrealtime();   // all stores issued (not yet acknowledged)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's stores have been acknowledged
-        if (tid == 0) {
-            a.stamps[(size_t)blockIdx.x * 12 + 3] = __builtin_amdgcn_s_memrealtime();
-            a.stamps[(size_t)blockIdx.x * 12 + 4] = t_issued;
-        }
-    }
-}
-
-// Wave-grid variant for the large layers: WM x WN waves, each owning a 64 x 64 sub-tile (same per-wave code and register
-// budget as the 128 x 128 kernel), block tile (64*WM) x (64*WN).  256 x 256 with 16 waves halves the L2->LDS bytes per
-// FLOP (measured limiter of the 128 x 128 kernel: ~47 GB/s per CU of operand traffic at 0.8 PFLOP/s) and leaves room
-// for a 4-deep LDS ring (3 k-tiles in flight) at one block per CU.
-// (launch bounds: 4 waves per SIMD.  The 8-wave shapes are meant to run two workgroups per CU; their linear-layer instantiation compiled
-// to 130 VGPRs = 3 waves per SIMD = ONE workgroup of 8 waves per CU, and fc1 forward / fc2 data gradient ran at 440 TFLOP/s for it.)
-template <int WM, int WN, int NSTAGE, int EPI = 0>
-__global__ __launch_bounds__(WM * WN * 64, 4) void igemm_conv_wg_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
-    constexpr int TM = 64 * WM, TN = 64 * WN, NW = WM * WN, NT = NW * 64;
-    constexpr int A_BLK = TM / 16 / NW, B_BLK = TN / 16 / NW, NDMA = A_BLK + B_BLK;
-    constexpr int A_ELEMS = TM * 32, B_ELEMS = TN * 32, STAGE_ELEMS = A_ELEMS + B_ELEMS;
-    constexpr int AHEAD = NSTAGE - 1;
-    static_assert(TM % (16 * NW) == 0 && TN % (16 * NW) == 0, "DMA blocks must divide evenly over the waves");
-    extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
-    int tm, tn;
-    if (!xcd_tile_map(parity_block(a), tiles_m, tiles_n, tm, tn)) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const GatherGeom g = a.g;
-    const int K = g.R * g.S * g.Ck;                    // weight row length
-    const int ktiles = (g.nr * g.ns * g.Ck) >> 5;      // taps actually visited (all of them unless g.sub)
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.W), 0, a.Cm * K * 2, 0x00020000);
-    const long long x_bytes = (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000);
-    const int r_in = lane >> 2;
-    const int kc = (lane & 3) ^ lds_swz(r_in);
-    uint32_t a_off[A_BLK];
-#pragma unroll
-    for (int i = 0; i < A_BLK; ++i) {
-        const int m = tm * TM + 16 * (wave + NW * i) + r_in;
-        a_off[i] = (m < a.Cm) ? (uint32_t)(m * K + kc * 8) * 2u : DMA_OOB;
-    }
-    int b_pix[B_BLK], b_h0[B_BLK], b_w0[B_BLK];
-#pragma unroll
-    for (int i = 0; i < B_BLK; ++i) {
-        const int p = tn * TN + 16 * (wave + NW * i) + r_in;
-        int n = 0, ho = 0, wo = 0;
-        const bool ok = p < a.P;
-        if (ok) decode_pixel(g, p, n, ho, wo);
-        if (g.sub) { ho = 2 * ho + g.oph; wo = 2 * wo + g.opw; }
-        if (g.mode == 0) { b_h0[i] = ho * g.stride - g.pad; b_w0[i] = wo * g.stride - g.pad; }
-        else { b_h0[i] = ho + g.pad; b_w0[i] = wo + g.pad; }
-        if (!ok) b_h0[i] = -0x40000000;
-        b_pix[i] = (int)((long long)n * g.img_pitch) + kc * 8;
-    }
-    int kr = g.r0, ks = g.s0, kc0 = 0;
-    const int ks_end = g.s0 + g.sstep * g.ns, kr_end = g.r0 + g.rstep * g.nr;
-    auto issue = [&](int stage) {
-        uint16_t* sa = smem + stage * STAGE_ELEMS;
-        uint16_t* sb = sa + A_ELEMS;
-        const int kbase = ((kr * g.S + ks) * g.Ck + kc0) * 2;
+    // fetches the current k-tile into the stage images sa / sb and advances to the next.  Rows past Cm / P and taps outside the image get the
+    // offset DMA_OOB, past num_records of every descriptor: the buffer range check then makes the DMA write zeros.
+    __device__ __forceinline__ void issue(uint16_t* sa, uint16_t* sb) {
+        const int kbase = ((kr * g.S + ks) * g.Ck + kc0) * 2;      // byte offset of this k-tile inside a weight row
 #pragma unroll
         for (int i = 0; i < A_BLK; ++i) {
             const uint32_t off = (a_off[i] == DMA_OOB) ? DMA_OOB : a_off[i] + (uint32_t)kbase;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_ptr)(sa + (wave + NW * i) * 512), 16, off, 0, 0, 0);
         }
+        if constexpr (SRC2) {
+            // K position kc0 lies in X (< Ck1) or in X2: a wave-uniform choice per k-tile
+            const bool second = kc0 >= Ck1;
+            const int pitch = second ? Ck2 : Ck1, cbase = (second ? kc0 - Ck1 : kc0) + kc * 8;
+#pragma unroll
+            for (int i = 0; i < B_BLK; ++i) {
+                const uint32_t off = b_pix[i] >= 0 ? (uint32_t)(b_pix[i] * pitch + cbase) * 2u : DMA_OOB;
+                if (second) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x2, (lds_void_ptr)(sb + (wave + NW * i) * 512), 16, off, 0, 0, 0);
+                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(sb + (wave + NW * i) * 512), 16, off, 0, 0, 0);
+            }
+            kc0 += KT;
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < B_BLK; ++i) {
+            if (B_RAGGED && wave + NW * i >= TN / ROWS) continue;       // (wave-uniform)
             int hi, wi;
             bool ok = true;
             if (g.mode == 0) { hi = b_h0[i] + kr; wi = b_w0[i] + ks; }
@@ -1014,14 +913,116 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_conv_wg_kernel(IGemmArg
         // shifted re-reads of the same pixels hit the XCD's L2 (channels-fastest order spaced them Ck/32 steps apart: with
         // Ck >= 128 the line had left the 4 MiB L2 and came back from the Infinity Cache at HBM-like bandwidth, 9 times)
         ks += g.sstep;
-        if (ks >= ks_end) { ks = g.s0; kr += g.rstep; if (kr >= kr_end) { kr = g.r0; kc0 += 32; } }
-    };
+        if (ks >= ks_end) { ks = g.s0; kr += g.rstep; if (kr >= kr_end) { kr = g.r0; kc0 += KT; } }
+    }
+};
+
+// element offset of this lane's 16-byte MFMA fragment chunk inside a 16-row block of a [rows][KT] stage image: row lane & 15, logical chunk
+// lane >> 4, swizzled as the gather wrote it.  KT 64: the second 32 k are chunk + 4 = physical chunk ^ 4 = offset ^ 32.
+template <int KT>
+__device__ __forceinline__ int frag_offset(int lane) {
+    if constexpr (KT == 32) return (lane & 15) * 32 + (((lane >> 4) ^ lds_swz(lane & 15)) << 3);
+    else return (lane & 15) * 64 + (((lane >> 4) ^ ((lane & 15) >> 1)) << 3);
+}
+// one k-tile of a wave's (16 FM) x (16 FN) sub-tile: fragment reads of rows a_row0 .. / b_row0 .. and KT / 32 MFMA k-steps
+template <int KT, int FM, int FN>
+__device__ __forceinline__ void mma_ktile(const uint16_t* sa, const uint16_t* sb, int a_row0, int b_row0, int lane, f32x4_t (&acc)[FM][FN]) {
+    const int frag_off = frag_offset<KT>(lane);
+#pragma unroll
+    for (int h = 0; h < KT / 32; ++h) {
+        const int fo = frag_off ^ (h << 5);
+        bf16x8_t fa[FM];
+#pragma unroll
+        for (int i = 0; i < FM; ++i) fa[i] = *reinterpret_cast<const bf16x8_t*>(sa + (a_row0 + i * 16) * KT + fo);
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+            const bf16x8_t fb = *reinterpret_cast<const bf16x8_t*>(sb + (b_row0 + j * 16) * KT + fo);
+#pragma unroll
+            for (int i = 0; i < FM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
+        }
+    }
+}
+
+template <int TM, int TN, int NSTAGE, int EPI = 0, bool SRC2 = false>        // EPI: 0 convolution, 1 linear-layer extras, 3 fused output stage (conv_epilogue_g)
+__global__ __launch_bounds__(256, (TM >= 128 ? (EPI == 3 ? 3 : 4) : 2)) void igemm_conv_dma_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
+    // 128 x 128: <= 128 VGPRs (4 waves per SIMD); the 64 x 256 shape carries twice the per-lane gather state and would spill
+    using Cfg = GemmCfg<TM, TN, 1, 1, 1>;
+    using Gather = ConvGather<32, TM, TN, 4, SRC2>;
+    constexpr int FM = Cfg::FM, FN = Cfg::FN, NDMA = Gather::NDMA;
+    extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
+    int tm, tn;
+    if (!xcd_tile_map(parity_block(a), tiles_m, tiles_n, tm, tn)) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 0] = __builtin_amdgcn_s_memrealtime();   // (written out: see conv_stamp)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const GatherGeom g = a.g;                          // (after parity_block, which rewrites a.g)
+    const int ktiles = (g.nr * g.ns * g.Ck) >> 5;      // taps actually visited (all of them unless g.sub)
+    Gather gather(a, g, tm, tn, wave, lane);
+    auto issue = [&](int stage) { uint16_t* sa = smem + stage * Cfg::STAGE_ELEMS; gather.issue(sa, sa + Cfg::A_ELEMS); };
+
+    f32x4_t acc[FM][FN];
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const int a_row0 = wm * (TM / 2), b_row0 = wn * (TN / 2);
+
+    // 3-stage ring: the DMA of tile t+2 is issued before tile t is multiplied; the wait at the end of iteration t retires
+    // tile t+1 only (counted vmcnt leaves tile t+2's NDMA DMAs in flight ACROSS the barrier, so a raw s_barrier is
+    // used: __syncthreads() would drain them).  A stage is read one iteration after the wait+barrier that retired it, and
+    // re-filled two barriers after its last read.
+    constexpr int AHEAD = NSTAGE - 1;                   // tiles in flight beyond the one being multiplied
+    issue(0);
+    if (AHEAD == 2 && ktiles > 1) issue(1);
+    if (AHEAD == 2 && ktiles > 1) dma_wait<NDMA>(); else dma_wait<0>();
+    __builtin_amdgcn_s_barrier();
+    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
+    int st_cur = 0, st_nxt2 = AHEAD;
+    for (int kt = 0; kt < ktiles; ++kt) {
+        if (kt + AHEAD < ktiles) issue(st_nxt2);
+        const uint16_t* sa = smem + st_cur * Cfg::STAGE_ELEMS;
+        mma_ktile<32>(sa, sa + Cfg::A_ELEMS, a_row0, b_row0, lane, acc);
+        if (AHEAD == 2 && kt + 2 < ktiles) dma_wait<NDMA>(); else dma_wait<0>();
+        __builtin_amdgcn_s_barrier();
+        st_cur = (st_cur == NSTAGE - 1) ? 0 : st_cur + 1;
+        st_nxt2 = (st_nxt2 == NSTAGE - 1) ? 0 : st_nxt2 + 1;
+    }
+    __syncthreads();
+    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
+
+    conv_epilogue<Cfg, ((TM == 128 && TN == 128 && NSTAGE == 3) || EPI == 3 || EPI == 5) ? EPI : 2>(a, acc, tm, tn, smem);
+    conv_stamp_stores(a);
+}
+
+// Wave-grid variant for the large layers: WM x WN waves, each owning a 64 x 64 sub-tile (same per-wave code and register
+// budget as the 128 x 128 kernel), block tile (64*WM) x (64*WN).  256 x 256 with 16 waves halves the L2->LDS bytes per
+// FLOP (measured limiter of the 128 x 128 kernel: ~47 GB/s per CU of operand traffic at 0.8 PFLOP/s) and leaves room
+// for a 4-deep LDS ring (3 k-tiles in flight) at one block per CU.
+// (launch bounds: 4 waves per SIMD.  The 8-wave shapes are meant to run two workgroups per CU; their linear-layer instantiation compiled
+// to 130 VGPRs = 3 waves per SIMD = ONE workgroup of 8 waves per CU, and fc1 forward / fc2 data gradient ran at 440 TFLOP/s for it.)
+template <int WM, int WN, int NSTAGE, int EPI = 0>
+__global__ __launch_bounds__(WM * WN * 64, 4) void igemm_conv_wg_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
+    constexpr int TM = 64 * WM, TN = 64 * WN, NW = WM * WN, NT = NW * 64;
+    using Gather = ConvGather<32, TM, TN, NW, false>;
+    constexpr int NDMA = Gather::NDMA;
+    constexpr int A_ELEMS = TM * 32, B_ELEMS = TN * 32, STAGE_ELEMS = A_ELEMS + B_ELEMS;
+    constexpr int AHEAD = NSTAGE - 1;
+    extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
+    int tm, tn;
+    if (!xcd_tile_map(parity_block(a), tiles_m, tiles_n, tm, tn)) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const GatherGeom g = a.g;                          // (after parity_block, which rewrites a.g)
+    const int ktiles = (g.nr * g.ns * g.Ck) >> 5;      // taps actually visited (all of them unless g.sub)
+    Gather gather(a, g, tm, tn, wave, lane);
+    auto issue = [&](int stage) { uint16_t* sa = smem + stage * STAGE_ELEMS; gather.issue(sa, sa + A_ELEMS); };
     f32x4_t acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int frag_off = (lane & 15) * 32 + (((lane >> 4) ^ lds_swz(lane & 15)) << 3);
     const int a_row0 = wm * 64, b_row0 = wn * 64;
     // prologue: AHEAD tiles in flight, wait for the first
     int issued = 0;
@@ -1035,16 +1036,7 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_conv_wg_kernel(IGemmArg
         const bool more = kt + AHEAD < ktiles;
         if (more) issue(st_fill);
         const uint16_t* sa = smem + st_cur * STAGE_ELEMS;
-        const uint16_t* sb = sa + A_ELEMS;
-        bf16x8_t fa[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const bf16x8_t*>(sa + (a_row0 + i * 16) * 32 + frag_off);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bf16x8_t fb = *reinterpret_cast<const bf16x8_t*>(sb + (b_row0 + j * 16) * 32 + frag_off);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
-        }
+        mma_ktile<32>(sa, sa + A_ELEMS, a_row0, b_row0, lane, acc);
         // retire tile kt+1: everything but the youngest min(AHEAD-1, remaining) tiles must have landed
         const int left = ktiles - 1 - kt;                    // tiles after this one
         int inflight_after = left < AHEAD ? left : AHEAD;      // tiles issued and not yet multiplied (excl. current)
@@ -1073,12 +1065,11 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_conv_wg_kernel(IGemmArg
 template <int WM, int WN, int NSTAGE, int FM = 4, int FN = 4, int EPI = 0, bool SRC2 = false>
 __global__ __launch_bounds__(WM * WN * 64) void igemm_conv_k64_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
     constexpr int TM = 16 * FM * WM, TN = 16 * FN * WN, NW = WM * WN, NT = NW * 64;     // per-wave sub-tile 16 FM x 16 FN
-    constexpr int A_BLK = TM / 8 / NW, B_BLK = (TN / 8 + NW - 1) / NW, NDMA = A_BLK + B_BLK;
-    constexpr bool B_RAGGED = (TN / 8) % NW != 0;        // 320 pixels: 40 pieces over 16 waves, the waves of the upper half skip their third
+    using Gather = ConvGather<64, TM, TN, NW, SRC2>;
+    constexpr int NDMA = Gather::NDMA;
     constexpr int A_ELEMS = TM * 64, B_ELEMS = TN * 64, STAGE_ELEMS = A_ELEMS + B_ELEMS;
     constexpr int AHEAD = NSTAGE - 1;
-    static_assert(NW % 2 == 0 && TM % (8 * NW) == 0 && TN % 8 == 0, "DMA pieces: whole 8-row pieces over an even number of waves");
-    static_assert(!B_RAGGED || NSTAGE == 2, "a ragged piece count needs the wait-for-all of the 2-stage ring (dma_wait<NDMA> counts pieces per wave)");
+    static_assert(!Gather::B_RAGGED || NSTAGE == 2, "a ragged piece count needs the wait-for-all of the 2-stage ring (dma_wait<NDMA> counts pieces per wave)");
     static_assert(NSTAGE == 2 || NSTAGE == 3, "ring depth");
     extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
     int tm, tn;
@@ -1086,118 +1077,33 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_conv_k64_kernel(IGemmArgs 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
+    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 0] = __builtin_amdgcn_s_memrealtime();   // (written out: see conv_stamp)
     if (a.stamps && tid == 0) {
-        a.stamps[(size_t)blockIdx.x * 12] = __builtin_amdgcn_s_memrealtime();
         unsigned hw, xcc;                              // where this workgroup sits (slot 10: HW_ID | XCC_ID << 32)
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         a.stamps[(size_t)blockIdx.x * 12 + 10] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
     }
-    const GatherGeom g = a.g;
-    const int K = g.R * g.S * g.Ck;                    // weight row length
+    const GatherGeom g = a.g;                          // (after parity_block, which rewrites a.g)
     const int ktiles = (g.nr * g.ns * g.Ck) >> 6;      // taps actually visited (all of them unless g.sub)
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.W), 0, a.Cm * K * 2, 0x00020000);
-    const long long x_bytes = SRC2 ? (long long)a.P * a.Ck1 * 2 : (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000);
-    const int Ck2 = g.Ck - a.Ck1;                                   // (SRC2) channels of the second tensor
-    const __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(SRC2 ? a.X2 : a.X), 0, SRC2 ? (int)((long long)a.P * Ck2 * 2) : (int)x_bytes, 0x00020000);
-    // LDS slot `lane` of piece q (rows 8q .. 8q+7) = row 8q + (lane >> 3), physical chunk lane & 7; q = wave + NW * i has the
-    // parity of the wave, so the logical chunk this lane fetches is the same for all of its pieces
-    const int r_in = lane >> 3;
-    const int kc = (lane & 7) ^ (((wave & 1) << 2) | (r_in >> 1));
-    uint32_t a_off[A_BLK];
-#pragma unroll
-    for (int i = 0; i < A_BLK; ++i) {
-        const int m = tm * TM + 8 * (wave + NW * i) + r_in;
-        a_off[i] = (m < a.Cm) ? (uint32_t)(m * K + kc * 8) * 2u : DMA_OOB;
-    }
-    int b_pix[B_BLK], b_h0[B_BLK], b_w0[B_BLK];
-#pragma unroll
-    for (int i = 0; i < B_BLK; ++i) {
-        const int p = tn * TN + 8 * (wave + NW * i) + r_in;
-        int n = 0, ho = 0, wo = 0;
-        const bool ok = p < a.P;
-        if (ok) decode_pixel(g, p, n, ho, wo);
-        if (g.sub) { ho = 2 * ho + g.oph; wo = 2 * wo + g.opw; }
-        if (g.mode == 0) { b_h0[i] = ho * g.stride - g.pad; b_w0[i] = wo * g.stride - g.pad; }
-        else { b_h0[i] = ho + g.pad; b_w0[i] = wo + g.pad; }
-        if (!ok) b_h0[i] = -0x40000000;
-        b_pix[i] = (int)((long long)n * g.img_pitch) + kc * 8;
-        if constexpr (SRC2) b_pix[i] = ok ? p : -1;                  // plain rows: the pixel index itself
-    }
-    int kr = g.r0, ks = g.s0, kc0 = 0;
-    const int ks_end = g.s0 + g.sstep * g.ns, kr_end = g.r0 + g.rstep * g.nr;
-    auto issue = [&](int stage) {
-        uint16_t* sa = smem + stage * STAGE_ELEMS;
-        uint16_t* sb = sa + A_ELEMS;
-        const int kbase = ((kr * g.S + ks) * g.Ck + kc0) * 2;
-#pragma unroll
-        for (int i = 0; i < A_BLK; ++i) {
-            const uint32_t off = (a_off[i] == DMA_OOB) ? DMA_OOB : a_off[i] + (uint32_t)kbase;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_ptr)(sa + (wave + NW * i) * 512), 16, off, 0, 0, 0);
-        }
-        if constexpr (SRC2) {                             // K position kc0 lies in X (< Ck1) or in X2: a wave-uniform choice per k-tile
-            const bool second = kc0 >= a.Ck1;
-            const int pitch = second ? Ck2 : a.Ck1, cbase = (second ? kc0 - a.Ck1 : kc0) + kc * 8;
-#pragma unroll
-            for (int i = 0; i < B_BLK; ++i) {
-                const uint32_t off = b_pix[i] >= 0 ? (uint32_t)(b_pix[i] * pitch + cbase) * 2u : DMA_OOB;
-                if (second) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x2, (lds_void_ptr)(sb + (wave + NW * i) * 512), 16, off, 0, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(sb + (wave + NW * i) * 512), 16, off, 0, 0, 0);
-            }
-            kc0 += 64;
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < B_BLK; ++i) {
-            if (B_RAGGED && wave + NW * i >= TN / 8) continue;          // (wave-uniform)
-            int hi, wi;
-            bool ok = true;
-            if (g.mode == 0) { hi = b_h0[i] + kr; wi = b_w0[i] + ks; }
-            else {
-                const int th = b_h0[i] - kr, tw = b_w0[i] - ks;
-                ok = (th >= 0) && (tw >= 0);
-                if (g.stride == 2) { ok = ok && (((th | tw) & 1) == 0); hi = th >> 1; wi = tw >> 1; }
-                else { hi = th; wi = tw; }
-            }
-            ok = ok && ((unsigned)hi < (unsigned)g.Hin) && ((unsigned)wi < (unsigned)g.Win);
-            const uint32_t off = ok ? (uint32_t)(b_pix[i] + hi * g.row_pitch + wi * g.pix_pitch + kc0) * 2u : DMA_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(sb + (wave + NW * i) * 512), 16, off, 0, 0, 0);
-        }
-        ks += g.sstep;                                   // taps fastest, channel block outermost (see igemm_conv_dma_kernel)
-        if (ks >= ks_end) { ks = g.s0; kr += g.rstep; if (kr >= kr_end) { kr = g.r0; kc0 += 64; } }
-    };
+    Gather gather(a, g, tm, tn, wave, lane);
+    auto issue = [&](int stage) { uint16_t* sa = smem + stage * STAGE_ELEMS; gather.issue(sa, sa + A_ELEMS); };
     f32x4_t acc[FM][FN];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    // fragment of the first 32 k: row lane & 15, logical chunk lane >> 4; the second 32 k are chunk + 4 = physical chunk ^ 4
-    const int frag_off = (lane & 15) * 64 + (((lane >> 4) ^ ((lane & 15) >> 1)) << 3);
     const int a_row0 = wm * (16 * FM), b_row0 = wn * (16 * FN);
     int issued = 0;
     for (; issued < AHEAD && issued < ktiles; ++issued) issue(issued);
     if (issued == 2) dma_wait<NDMA>(); else dma_wait<0>();
     __builtin_amdgcn_s_barrier();
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
+    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
     int st_cur = 0, st_fill = AHEAD % NSTAGE;
     for (int kt = 0; kt < ktiles; ++kt) {
         if (kt + AHEAD < ktiles) issue(st_fill);
         const uint16_t* sa = smem + st_cur * STAGE_ELEMS;
-        const uint16_t* sb = sa + A_ELEMS;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int fo = frag_off ^ (h << 5);
-            bf16x8_t fa[FM];
-#pragma unroll
-            for (int i = 0; i < FM; ++i) fa[i] = *reinterpret_cast<const bf16x8_t*>(sa + (a_row0 + i * 16) * 64 + fo);
-#pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                const bf16x8_t fb = *reinterpret_cast<const bf16x8_t*>(sb + (b_row0 + j * 16) * 64 + fo);
-#pragma unroll
-                for (int i = 0; i < FM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
-            }
-        }
+        mma_ktile<64>(sa, sa + A_ELEMS, a_row0, b_row0, lane, acc);
         // retire tile kt+1: only the youngest tile (if any beyond kt+1) may still be in flight
         const int left = ktiles - 1 - kt;
         if (AHEAD == 2 && left >= 2) dma_wait<NDMA>(); else dma_wait<0>();
@@ -1206,16 +1112,9 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_conv_k64_kernel(IGemmArgs 
         st_fill = (st_fill == NSTAGE - 1) ? 0 : st_fill + 1;
     }
     __syncthreads();
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
+    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
     conv_epilogue_g<TM, TN, FM, FN, WN, NT, (WM == 4 && WN == 4 && NSTAGE == 2 && FM == 4) ? EPI : 2>(a, acc, tm, tn, smem, wm, wn);
-    if (a.stamps) {
-        const unsigned long long t_issued = __builtin_amdgcn_s_memrealtime();   // all stores issued (not yet acknowledged)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) {
-            a.stamps[(size_t)blockIdx.x * 12 + 3] = __builtin_amdgcn_s_memrealtime();
-            a.stamps[(size_t)blockIdx.x * 12 + 4] = t_issued;
-        }
-    }
+    conv_stamp_stores(a);
 }
 
 // Wave-specialised k-tile-64 kernel: WM x WN consumer waves (64 x 64 sub-tiles: fragment reads + MFMAs + epilogue) and NP
@@ -1226,10 +1125,11 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_conv_k64_kernel(IGemmArgs 
 template <int WM, int WN, int NP, int NSTAGE, int FM = 4, int FN = 4, int EPI = 0, bool SRC2 = false>      // EPI: as igemm_conv_dma_kernel
 __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_conv_k64s_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
     constexpr int TM = 16 * FM * WM, TN = 16 * FN * WN, NC = WM * WN, NT = NC * 64;       // consumer sub-tile 16 FM x 16 FN
-    constexpr int A_BLK = TM / 8 / NP, B_BLK = TN / 8 / NP, NDMA = A_BLK + B_BLK;
+    using Gather = ConvGather<64, TM, TN, NP, SRC2>;
+    constexpr int NDMA = Gather::NDMA;
     constexpr int A_ELEMS = TM * 64, B_ELEMS = TN * 64, STAGE_ELEMS = A_ELEMS + B_ELEMS;
     constexpr int AHEAD = NSTAGE - 1;
-    static_assert(NP % 2 == 0 && TM % (8 * NP) == 0 && TN % (8 * NP) == 0, "DMA pieces must divide evenly over an even number of producers");
+    static_assert(!Gather::B_RAGGED, "DMA pieces must divide evenly over the producers (the waits below count NDMA per producer)");
     static_assert(NSTAGE == 2 || NSTAGE == 3, "ring depth");
     extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
     int tm, tn;
@@ -1240,76 +1140,8 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_conv_k64s_kernel(IG
     const int ktiles = (g.nr * g.ns * g.Ck) >> 6;      // taps actually visited (all of them unless g.sub)
     if (wave >= NC) {
         // ---------------- producers ----------------
-        const int pw = wave - NC;
-        const int K = g.R * g.S * g.Ck;                // weight row length
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.W), 0, a.Cm * K * 2, 0x00020000);
-        const long long x_bytes = SRC2 ? (long long)a.P * a.Ck1 * 2 : (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
-        const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000);
-        const int Ck2 = g.Ck - a.Ck1;                                   // (SRC2) channels of the second tensor
-        const __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(SRC2 ? a.X2 : a.X), 0, SRC2 ? (int)((long long)a.P * Ck2 * 2) : (int)x_bytes, 0x00020000);
-        const int r_in = lane >> 3;
-        const int kc = (lane & 7) ^ (((pw & 1) << 2) | (r_in >> 1));      // see igemm_conv_k64_kernel
-        uint32_t a_off[A_BLK];
-#pragma unroll
-        for (int i = 0; i < A_BLK; ++i) {
-            const int m = tm * TM + 8 * (pw + NP * i) + r_in;
-            a_off[i] = (m < a.Cm) ? (uint32_t)(m * K + kc * 8) * 2u : DMA_OOB;
-        }
-        int b_pix[B_BLK], b_h0[B_BLK], b_w0[B_BLK];
-#pragma unroll
-        for (int i = 0; i < B_BLK; ++i) {
-            const int p = tn * TN + 8 * (pw + NP * i) + r_in;
-            int n = 0, ho = 0, wo = 0;
-            const bool ok = p < a.P;
-            if (ok) decode_pixel(g, p, n, ho, wo);
-            if (g.sub) { ho = 2 * ho + g.oph; wo = 2 * wo + g.opw; }
-            if (g.mode == 0) { b_h0[i] = ho * g.stride - g.pad; b_w0[i] = wo * g.stride - g.pad; }
-            else { b_h0[i] = ho + g.pad; b_w0[i] = wo + g.pad; }
-            if (!ok) b_h0[i] = -0x40000000;
-            b_pix[i] = (int)((long long)n * g.img_pitch) + kc * 8;
-            if constexpr (SRC2) b_pix[i] = ok ? p : -1;                  // plain rows: the pixel index itself
-        }
-        int kr = g.r0, ks = g.s0, kc0 = 0;
-        const int ks_end = g.s0 + g.sstep * g.ns, kr_end = g.r0 + g.rstep * g.nr;
-        auto issue = [&](int stage) {
-            uint16_t* sa = smem + stage * STAGE_ELEMS;
-            uint16_t* sb = sa + A_ELEMS;
-            const int kbase = ((kr * g.S + ks) * g.Ck + kc0) * 2;
-#pragma unroll
-            for (int i = 0; i < A_BLK; ++i) {
-                const uint32_t off = (a_off[i] == DMA_OOB) ? DMA_OOB : a_off[i] + (uint32_t)kbase;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_ptr)(sa + (pw + NP * i) * 512), 16, off, 0, 0, 0);
-            }
-            if constexpr (SRC2) {                             // K position kc0 lies in X (< Ck1) or in X2: a wave-uniform choice per k-tile
-                const bool second = kc0 >= a.Ck1;
-                const int pitch = second ? Ck2 : a.Ck1, cbase = (second ? kc0 - a.Ck1 : kc0) + kc * 8;
-#pragma unroll
-                for (int i = 0; i < B_BLK; ++i) {
-                    const uint32_t off = b_pix[i] >= 0 ? (uint32_t)(b_pix[i] * pitch + cbase) * 2u : DMA_OOB;
-                    if (second) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x2, (lds_void_ptr)(sb + (pw + NP * i) * 512), 16, off, 0, 0, 0);
-                    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(sb + (pw + NP * i) * 512), 16, off, 0, 0, 0);
-                }
-                kc0 += 64;
-                return;
-            }
-#pragma unroll
-            for (int i = 0; i < B_BLK; ++i) {
-                int hi, wi;
-                bool ok = true;
-                if (g.mode == 0) { hi = b_h0[i] + kr; wi = b_w0[i] + ks; }
-                else {
-                    const int th = b_h0[i] - kr, tw = b_w0[i] - ks;
-                    ok = (th >= 0) && (tw >= 0);
-                    if (g.stride == 2) { ok = ok && (((th | tw) & 1) == 0); hi = th >> 1; wi = tw >> 1; }
-                    else { hi = th; wi = tw; }
-                }
-                ok = ok && ((unsigned)hi < (unsigned)g.Hin) && ((unsigned)wi < (unsigned)g.Win);
-                const uint32_t off = ok ? (uint32_t)(b_pix[i] + hi * g.row_pitch + wi * g.pix_pitch + kc0) * 2u : DMA_OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(sb + (pw + NP * i) * 512), 16, off, 0, 0, 0);
-            }
-            ks += g.sstep;                                   // taps fastest, channel block outermost (see igemm_conv_dma_kernel)
-            if (ks >= ks_end) { ks = g.s0; kr += g.rstep; if (kr >= kr_end) { kr = g.r0; kc0 += 64; } }
-        };
+        Gather gather(a, g, tm, tn, wave - NC, lane);
+        auto issue = [&](int stage) { uint16_t* sa = smem + stage * STAGE_ELEMS; gather.issue(sa, sa + A_ELEMS); };
         issue(0);
         if constexpr (AHEAD == 2) { if (ktiles > 1) { issue(1); dma_wait<NDMA>(); } else dma_wait<0>(); }
         else dma_wait<0>();
@@ -1333,39 +1165,21 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_conv_k64s_kernel(IG
     for (int i = 0; i < FM; ++i)
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int frag_off = (lane & 15) * 64 + (((lane >> 4) ^ ((lane & 15) >> 1)) << 3);
     const int a_row0 = wm * (16 * FM), b_row0 = wn * (16 * FN);
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12] = __builtin_amdgcn_s_memrealtime();
+    conv_stamp(a, 0);
     __builtin_amdgcn_s_barrier();
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
+    conv_stamp(a, 1);
     int st_cur = 0;
     for (int kt = 0; kt < ktiles; ++kt) {
         const uint16_t* sa = smem + st_cur * STAGE_ELEMS;
-        const uint16_t* sb = sa + A_ELEMS;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int fo = frag_off ^ (h << 5);
-            bf16x8_t fa[FM];
-#pragma unroll
-            for (int i = 0; i < FM; ++i) fa[i] = *reinterpret_cast<const bf16x8_t*>(sa + (a_row0 + i * 16) * 64 + fo);
-#pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                const bf16x8_t fb = *reinterpret_cast<const bf16x8_t*>(sb + (b_row0 + j * 16) * 64 + fo);
-#pragma unroll
-                for (int i = 0; i < FM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
-            }
-        }
+        mma_ktile<64>(sa, sa + A_ELEMS, a_row0, b_row0, lane, acc);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // my reads of this stage are complete before it can be refilled
         __builtin_amdgcn_s_barrier();
         st_cur = (st_cur == NSTAGE - 1) ? 0 : st_cur + 1;
     }
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
+    conv_stamp(a, 2);
     conv_epilogue_g<TM, TN, FM, FN, WN, NT, (WM == 2 && WN == 4 && NP == 8 && NSTAGE == 3) ? EPI : 2>(a, acc, tm, tn, smem, wm, wn);
-    if (a.stamps) {
-        const unsigned long long t_issued = __builtin_amdgcn_s_memrealtime();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) { a.stamps[(size_t)blockIdx.x * 12 + 3] = __builtin_amdgcn_s_memrealtime(); a.stamps[(size_t)blockIdx.x * 12 + 4] = t_issued; }
-    }
+    conv_stamp_stores(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1419,7 +1233,7 @@ __global__ __launch_bounds__(512, 4) void igemm_conv_halo64_kernel(IGemmArgs a, 
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(patch + q * 512), 16, off, 0, 0, 0);
             }
         }
-        // weight tap kt: rows m = 8 (pw + 4 i) + lane >> 3 of the [64][64] stage image, k-tile-64 swizzle (see igemm_conv_k64_kernel)
+        // weight tap kt: rows m = 8 (pw + 4 i) + lane >> 3 of the [64][64] stage image, k-tile-64 swizzle (see ConvGather)
         const int r_in = lane >> 3;
         const int kc = (lane & 7) ^ (((pw & 1) << 2) | (r_in >> 1));
         uint32_t a_off[2];
@@ -1449,7 +1263,7 @@ __global__ __launch_bounds__(512, 4) void igemm_conv_halo64_kernel(IGemmArgs a, 
     for (int i = 0; i < FM; ++i)
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int frag_off = (lane & 15) * 64 + (((lane >> 4) ^ ((lane & 15) >> 1)) << 3);       // weights: as igemm_conv_k64s_kernel
+    const int frag_off = frag_offset<64>(lane);                    // weights: the k-tile-64 stage image of mma_ktile
     int hp_base[FN];                                               // halo pixel of tap (0, 0) [mode 0] for this lane's pixel of fragment j
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
@@ -1707,7 +1521,7 @@ __global__ __launch_bounds__(256) void igemm_wgrad_dma_kernel(WGradArgs a, int t
     const int ks = item / tiles, tile = item - ks * tiles;
     const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
     const int m0 = tm * 128, n0 = tn * 128;
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12] = __builtin_amdgcn_s_memrealtime();
+    conv_stamp(a, 0);
     const GatherGeom g = a.g;
     const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.dY), 0, a.P * a.Cm * 2, 0x00020000);
     const long long x_bytes = (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
@@ -1770,7 +1584,7 @@ __global__ __launch_bounds__(256) void igemm_wgrad_dma_kernel(WGradArgs a, int t
         if (ksteps > 1) issue(1, 1);
         if (ksteps > 1) dma_wait<4>(); else dma_wait<0>();
         __builtin_amdgcn_s_barrier();
-        if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
+        conv_stamp(a, 1);
         int st_cur = 0, st_nxt2 = 2;
         for (int kt = 0; kt < ksteps; ++kt) {
             if (kt + 2 < ksteps) issue(kt + 2, st_nxt2);
@@ -1803,7 +1617,7 @@ __global__ __launch_bounds__(256) void igemm_wgrad_dma_kernel(WGradArgs a, int t
             st_nxt2 = (st_nxt2 == 2) ? 0 : st_nxt2 + 1;
         }
     }
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
+    conv_stamp(a, 2);
     float* slab = a.partial + (size_t)ks * a.Cm * a.Ntot;
     store_slab_tiles<4, 4>(slab, acc, m0 + wm * 64, n0 + wn * 64, a.Cm, a.Ntot, lane);
     if constexpr (COLSUM) if (do_cs && (lane & 15) == 0) {
@@ -1815,11 +1629,7 @@ __global__ __launch_bounds__(256) void igemm_wgrad_dma_kernel(WGradArgs a, int t
                 if (m < a.Cm) a.colsum[(size_t)ks * a.Cm + m] = cs[i][rr];
             }
     }
-    if (a.stamps) {
-        const unsigned long long t_issued = __builtin_amdgcn_s_memrealtime();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) { a.stamps[(size_t)blockIdx.x * 12 + 3] = __builtin_amdgcn_s_memrealtime(); a.stamps[(size_t)blockIdx.x * 12 + 4] = t_issued; }
-    }
+    conv_stamp_stores(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1852,7 +1662,7 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
     const int ks = item / tiles, tile = item - ks * tiles;
     const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
     const int m0 = tm * 128, ci0 = tn * 64;
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12] = __builtin_amdgcn_s_memrealtime();
+    conv_stamp(a, 0);
     const bool m_active = m0 + wm * 64 < a.Cm;          // Cout = 64: the upper half of the co tile is padding, its waves only help with the DMA
     const GatherGeom g = a.g;
     const int W = g.Wout, H = g.Hout, Cin = g.Ck, lw = g.lw, lhw = g.lhw;
@@ -1937,7 +1747,7 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
         for (; issued < AHEAD && issued < ksteps; ++issued) issue(issued, issued);
         wait_inflight(issued - 1 > 4 ? 4 : issued - 1);
         __builtin_amdgcn_s_barrier();
-        if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
+        conv_stamp(a, 1);
         int st_cur = 0, st_fill = AHEAD % NSTAGE;
         for (int kt = 0; kt < ksteps; ++kt) {
             if (kt + AHEAD < ksteps) issue(kt + AHEAD, st_fill);
@@ -1981,7 +1791,7 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
             st_fill = (st_fill == NSTAGE - 1) ? 0 : st_fill + 1;
         }
     }
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
+    conv_stamp(a, 2);
     float* slab = a.partial + (size_t)ks * a.Cm * a.Ntot;
     if (m_active) {                                      // one row pointer per (i, r), the nine taps Cin columns apart
         float* row = slab + (size_t)(m0 + wm * 64 + (lane >> 4) * 4) * a.Ntot + ci0 + wn * 16 + (lane & 15);
@@ -1994,11 +1804,7 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
                 for (int t = 0; t < 9; ++t) p[t * Cin] = acc[t][i][rr];
             }
     }
-    if (a.stamps) {
-        const unsigned long long t_issued = __builtin_amdgcn_s_memrealtime();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) { a.stamps[(size_t)blockIdx.x * 12 + 3] = __builtin_amdgcn_s_memrealtime(); a.stamps[(size_t)blockIdx.x * 12 + 4] = t_issued; }
-    }
+    conv_stamp_stores(a);
 }
 
 // wgrad, wave-grid variant: WM x WN waves of 64 x 64 sub-tiles; the (64*WM) x (64*WN) block tile is held as (TM+TN)/128
@@ -2316,7 +2122,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_wgrad_p_kernel(WGra
     const int p_begin = ks * a.pix_per_split;
     const int p_end = min(a.P, p_begin + a.pix_per_split);
     const int ksteps = (p_end > p_begin) ? (p_end - p_begin + 31) >> 5 : 0;
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12] = __builtin_amdgcn_s_memrealtime();
+    conv_stamp(a, 0);
     if (wave >= NC) {
         // ---------------- producers ---------------- (a __device__ function: see wgrad_p_produce)
         if (ksteps > 0) wgrad_p_produce<TM, TN, NP, NSTAGE>(a, smem, wave - NC, m0, n0, p_begin, p_end, ksteps);
@@ -2413,7 +2219,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_wgrad_p_kernel(WGra
     if (ksteps > 0) {
         bf16x8_t fa0[FM], fb0[FN], fa1[FM], fb1[FN];
         __builtin_amdgcn_s_barrier();                              // P0: k-steps 0 and 1 have landed
-        if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
+        conv_stamp(a, 1);
         load_frags(fa0, fb0, 0);
         int t = 0, st1 = 1 % NSTAGE;                               // st1 = stage of k-step t + 1
         // two k-steps per trip, no branch inside: the last trip's second request re-reads the last k-step's stage (landed, unused)
@@ -2439,7 +2245,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_wgrad_p_kernel(WGra
             __builtin_amdgcn_s_barrier();                          // E_{ksteps-1}
         }
     }
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
+    conv_stamp(a, 2);
     float* slab = a.partial + (size_t)ks * a.Cm * a.Ntot;
     store_slab_tiles<FM, FN>(slab, acc, m0 + wm * 16 * FM, n0 + wn * 16 * FN, a.Cm, a.Ntot, lane);
     if constexpr (COLSUM) if (do_cs && (lane & 3) == 0 && cs_col < CSF) {
@@ -2449,11 +2255,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_wgrad_p_kernel(WGra
             if (m < a.Cm) a.colsum[((size_t)ks * tiles_n + tn) * a.Cm + m] = cs[rr];
         }
     }
-    if (a.stamps) {
-        const unsigned long long t_issued = __builtin_amdgcn_s_memrealtime();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) { a.stamps[(size_t)blockIdx.x * 12 + 3] = __builtin_amdgcn_s_memrealtime(); a.stamps[(size_t)blockIdx.x * 12 + 4] = t_issued; }
-    }
+    conv_stamp_stores(a);
 }
 
 // Split-K reduce: out[e] (+)= sum_k partial[k][e] in a fixed order (deterministic).  One block covers 64 float4 chunks (1 KiB contiguous

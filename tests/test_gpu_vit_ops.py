@@ -28,8 +28,9 @@ def close(got, ref, rel=2.0 ** -7, abs_frac=4e-3):
 # residual epilogue, wave-specialised 128 x 256, specialised weight gradient), ragged row count
 # (25216, 1024, 768): ViT-B's row count with 768 outputs = the 256 x 320 tile (297 tiles of 256 x 256 would be 2 rounds of 256 CUs) and
 # its column-block epilogue, ragged last tile (25216 = 78 * 320 + 256) through the general path
+# (16448, 512, 256): K and N at the 128 x 256 tile's gates with K < 1024 = the k-tile-32 8-wave kernel with the linear-layer epilogue
 @pytest.mark.parametrize("rows,K,N", [(197 * 2, 768, 2304), (100, 3072, 768), (333, 768, 3072), (64, 64, 36), (16500, 3072, 768), (16500, 1024, 384),
-                                      (25216, 1024, 768)])
+                                      (25216, 1024, 768), (16448, 512, 256)])
 def test_linear_fwd_dgrad_wgrad(V, rows, K, N):
     g = torch.Generator().manual_seed(rows + K + N)
     x = torch.randn(rows, K, generator=g).to(bf16)
