@@ -13,7 +13,8 @@
 //     the L image, L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.
 // The augmentation kernel keeps one whole image in LDS (256 x 128 x 3 bytes = 96 KiB of the CU's 160 KiB): crop + flip
 // on load, the three enhancers in their random order with a block-wide reduction for the contrast mean, erase + normalise
-// on store.  HBM-bound: 3 bytes read + 12 written per output pixel.
+// on store.  HBM-bound: 3 bytes read + 12 written per output pixel.  With a row-index array the image is picked from a store of resized
+// images that stays in HBM (dali_augment_gather; transforms.ImageStore).
 #include "common.h"
 
 namespace dali {
@@ -83,29 +84,35 @@ __device__ __forceinline__ int luma8(int r, int g, int b) { return (19595 * r + 
 //   [11] brightness factor (float bits)  [12] contrast  [13] saturation  [14] pad  [15] augment (0: eval path = normalise only)
 constexpr int AUG_WORDS = 16;
 
-__global__ __launch_bounds__(1024) void augment_kernel(const uint8_t* __restrict__ img, const int32_t* __restrict__ params, int H, int W,
+// rows == nullptr: image n is img[n] (dali_augment_batch).  Otherwise img is a store of store_rows images and image n is img[rows[n]]
+// (dali_augment_gather): rows is device data nobody has checked, so a row outside [0, store_rows) is never dereferenced -- it loads as an
+// all-black image and the rest of the pipeline runs on it.
+__global__ __launch_bounds__(1024) void augment_kernel(const uint8_t* __restrict__ img, const int32_t* __restrict__ rows, int64_t store_rows,
+                                                        const int32_t* __restrict__ params, int H, int W,
                                                         float m0, float m1, float m2, float s0, float s1, float s2, float* __restrict__ out) {
     extern __shared__ uint8_t px[];                 // [H][W][3]
     __shared__ unsigned long long red[16];
     __shared__ int mean_l;
     const int n = blockIdx.x, tid = threadIdx.x;
     const int32_t* p = params + (size_t)n * AUG_WORDS;
-    const uint8_t* src = img + (size_t)n * H * W * 3;
+    const int64_t row = rows ? (int64_t)rows[n] : (int64_t)n;
+    const bool present = !rows || (row >= 0 && row < store_rows);
+    const uint8_t* src = img + (present ? (size_t)row : (size_t)0) * H * W * 3;          // 64-bit: row 21,846 of 256 x 128 lies past 2^31 bytes
     const int npix = H * W;
     const bool aug = p[15] != 0;
     const int top = p[0], left = p[1], flip = p[2], pad = p[14];
     // ---- load: zero-padded crop + horizontal flip ----
     for (int i = tid; i < npix; i += 1024) {
         const int h = i / W, w = i - h * W;
-        int r = 0, g = 0, b = 0;
-        if (aug) {
+        int r = 0, g = 0, b = 0;                    // padding, and every pixel of an out-of-range row
+        if (present && aug) {
             const int ws = flip ? W - 1 - w : w;
             const int sh = h + top - pad, sw = ws + left - pad;
             if ((unsigned)sh < (unsigned)H && (unsigned)sw < (unsigned)W) {
                 const uint8_t* q = src + ((size_t)sh * W + sw) * 3;
                 r = q[0]; g = q[1]; b = q[2];
             }
-        } else {
+        } else if (present) {
             const uint8_t* q = src + (size_t)i * 3;
             r = q[0]; g = q[1]; b = q[2];
         }
@@ -184,20 +191,33 @@ extern "C" int dali_resize_bicubic_u8(dali_ctx* ctx, void* stream, const uint8_t
     return DALI_OK;
 }
 
-extern "C" int dali_augment_batch(dali_ctx* ctx, void* stream, const uint8_t* images, const int32_t* params, int n, int h, int w,
-                                  const float* mean3, const float* std3, float* out) {
-    DALI_REQUIRE(ctx && images && params && mean3 && std3 && out, "dali_augment_batch: null argument");
-    DALI_REQUIRE(n >= 0 && h > 0 && w > 0, "dali_augment_batch: bad sizes");
+// the two entries' shared size guards + launch; rows == nullptr: images are taken in order (dali_augment_batch)
+static int launch_augment(const char* who, void* stream, const uint8_t* store, const int32_t* rows, int64_t store_rows, const int32_t* params,
+                          int n, int h, int w, const float* mean3, const float* std3, float* out) {
+    DALI_REQUIRE(n >= 0 && h > 0 && w > 0, "%s: bad sizes", who);
     const size_t lds = (size_t)h * w * 3;
-    DALI_REQUIRE(lds <= 150 * 1024, "dali_augment_batch: an image of %d x %d does not fit the 160 KiB LDS (limit 150 KiB)", h, w);
+    DALI_REQUIRE(lds <= 150 * 1024, "%s: an image of %d x %d does not fit the 160 KiB LDS (limit 150 KiB)", who, h, w);
     if (n == 0) return DALI_OK;
     static size_t lds_set = 0;
     if (lds > lds_set) {
         DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&augment_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_set = lds;
     }
-    hipLaunchKernelGGL(augment_kernel, dim3(n), dim3(1024), lds, (hipStream_t)stream, images, params, h, w, mean3[0], mean3[1], mean3[2],
-                       std3[0], std3[1], std3[2], out);
+    hipLaunchKernelGGL(augment_kernel, dim3(n), dim3(1024), lds, (hipStream_t)stream, store, rows, store_rows, params, h, w, mean3[0], mean3[1],
+                       mean3[2], std3[0], std3[1], std3[2], out);
     DALI_LAUNCH_CHECK();
     return DALI_OK;
+}
+
+extern "C" int dali_augment_batch(dali_ctx* ctx, void* stream, const uint8_t* images, const int32_t* params, int n, int h, int w,
+                                  const float* mean3, const float* std3, float* out) {
+    DALI_REQUIRE(ctx && images && params && mean3 && std3 && out, "dali_augment_batch: null argument");
+    return launch_augment("dali_augment_batch", stream, images, nullptr, 0, params, n, h, w, mean3, std3, out);
+}
+
+extern "C" int dali_augment_gather(dali_ctx* ctx, void* stream, const uint8_t* store, int64_t store_rows, const int32_t* rows,
+                                   const int32_t* params, int n, int h, int w, const float* mean3, const float* std3, float* out) {
+    DALI_REQUIRE(ctx && store && rows && params && mean3 && std3 && out, "dali_augment_gather: null argument");
+    DALI_REQUIRE(store_rows >= 1, "dali_augment_gather: store_rows=%lld must be >= 1", (long long)store_rows);
+    return launch_augment("dali_augment_gather", stream, store, rows, store_rows, params, n, h, w, mean3, std3, out);
 }

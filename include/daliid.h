@@ -456,6 +456,14 @@ int dali_resize_bicubic_u8(dali_ctx* ctx, void* stream, const uint8_t* src, cons
  * to 3 floats; out = fp32 [n][3][h][w].  One workgroup per image, the image lives in LDS (h*w*3 <= 150 KiB). */
 int dali_augment_batch(dali_ctx* ctx, void* stream, const uint8_t* images, const int32_t* params, int n, int h, int w,
                        const float* mean3, const float* std3, float* out);
+/* The same transform, by the same kernel, on images picked from a device-resident store (transforms.ImageStore): store =
+ * [store_rows][h][w][3] uint8, rows [n] int32 DEVICE array, image i of out = dali_augment_batch applied to store[rows[i]]
+ * with params[i], bit for bit.  rows may come in any order and may repeat; byte offsets into the store are 64-bit (the
+ * store may exceed 2 GiB).  rows is device data this entry cannot inspect: whatever it holds, the kernel does not read
+ * outside the store -- a row outside [0, store_rows) is treated as an ALL-BLACK image (every byte 0) and the rest of the
+ * pipeline (crop, flip, jitter, erase, normalise) runs on it.  Same limits as dali_augment_batch, and store_rows >= 1. */
+int dali_augment_gather(dali_ctx* ctx, void* stream, const uint8_t* store, int64_t store_rows, const int32_t* rows,
+                        const int32_t* params, int n, int h, int w, const float* mean3, const float* std3, float* out);
 
 /* ---- measurement aid (bench.py roofline leg; no reference counterpart) ------------------------------- *
  * Between _begin and _end every MFMA GEMM kernel launch of the conv / linear path (class 0: igemm_conv_*
