@@ -1315,18 +1315,18 @@ __device__ __forceinline__ int wg_swz(int row) { return (row & 3) | (((row >> 3)
 
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
+// element offset of a lane's first (half 0) or second (half 1) transposing read of 32-byte chunk chunk32 of a [32 px][128 ch] image: row 8g+q
+// resp. 8g+4+q, g = lane>>4, q = (lane&15)>>2, columns 4*(lane&3)..+3
+__device__ __forceinline__ int tr_frag_off(int chunk32, int lane, int half) {
+    const int row = 8 * (lane >> 4) + ((lane & 15) >> 2) + 4 * half;
+    return row * 128 + ((chunk32 ^ wg_swz(row)) << 4) + 4 * (lane & 3);
+}
+typedef short s16x8_t __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ bf16x8_t tr_frag(const uint16_t* tile, int chunk32, int lane) {
-    // rows 8g+q (first read) and 8g+4+q (second read), g = lane>>4, q = (lane&15)>>2, columns 4*(lane&3)..+3
-    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const int row0 = 8 * g + q, row1 = row0 + 4;
-    const int off0 = row0 * 128 + ((chunk32 ^ wg_swz(row0)) << 4) + 4 * p;      // in bf16 elements
-    const int off1 = row1 * 128 + ((chunk32 ^ wg_swz(row1)) << 4) + 4 * p;
     typedef __attribute__((address_space(3))) s16x4_t* lds_ptr_t;
-    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr_t)(tile + off0));
-    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr_t)(tile + off1));
-    typedef short s16x8_t __attribute__((ext_vector_type(8)));
-    const s16x8_t v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8_t, v);
+    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr_t)(tile + tr_frag_off(chunk32, lane, 0)));
+    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr_t)(tile + tr_frag_off(chunk32, lane, 1)));
+    return __builtin_bit_cast(bf16x8_t, s16x8_t{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]});
 }
 
 // The same reads through inline asm.  With LDS-DMA writes in flight the compiler puts `s_waitcnt vmcnt(0)` in front of the first
@@ -1343,26 +1343,17 @@ __device__ __forceinline__ s16x4_t ds_read_tr_raw(const uint16_t* p) {
     return v;
 }
 __device__ __forceinline__ TrPair tr_frag_raw(const uint16_t* tile, int chunk32, int lane) {
-    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const int row0 = 8 * g + q, row1 = row0 + 4;
-    const int off0 = row0 * 128 + ((chunk32 ^ wg_swz(row0)) << 4) + 4 * p;
-    const int off1 = row1 * 128 + ((chunk32 ^ wg_swz(row1)) << 4) + 4 * p;
-    return TrPair{ds_read_tr_raw(tile + off0), ds_read_tr_raw(tile + off1)};
+    return TrPair{ds_read_tr_raw(tile + tr_frag_off(chunk32, lane, 0)), ds_read_tr_raw(tile + tr_frag_off(chunk32, lane, 1))};
 }
 __device__ __forceinline__ bf16x8_t tr_join(const TrPair& t) {
-    typedef short s16x8_t __attribute__((ext_vector_type(8)));
-    const s16x8_t v = {t.lo[0], t.lo[1], t.lo[2], t.lo[3], t.hi[0], t.hi[1], t.hi[2], t.hi[3]};
-    return __builtin_bit_cast(bf16x8_t, v);
+    return __builtin_bit_cast(bf16x8_t, s16x8_t{t.lo[0], t.lo[1], t.lo[2], t.lo[3], t.hi[0], t.hi[1], t.hi[2], t.hi[3]});
 }
-// wait until at most N LDS reads of this wave are outstanding; the four pairs are "used and redefined" by the wait
+// wait until at most N LDS reads of this wave are outstanding (the counter holds 15 at the most: a larger N waits for 15); the four pairs are
+// "used and redefined" by the wait
 template <int N>
 __device__ __forceinline__ void tr_settle(TrPair& a, TrPair& b, TrPair& c, TrPair& d) {
     static_assert(N == 0 || N == 8 || N == 10 || N == 16 || N == 18, "lgkmcnt immediates used by the callers");
-    if constexpr (N == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi), "+v"(c.lo), "+v"(c.hi), "+v"(d.lo), "+v"(d.hi));
-    else if constexpr (N == 8) asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi), "+v"(c.lo), "+v"(c.hi), "+v"(d.lo), "+v"(d.hi));
-    else if constexpr (N == 10) asm volatile("s_waitcnt lgkmcnt(10)" : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi), "+v"(c.lo), "+v"(c.hi), "+v"(d.lo), "+v"(d.hi));
-    else if constexpr (N == 16) asm volatile("s_waitcnt lgkmcnt(15)" : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi), "+v"(c.lo), "+v"(c.hi), "+v"(d.lo), "+v"(d.hi));
-    else asm volatile("s_waitcnt lgkmcnt(15)" : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi), "+v"(c.lo), "+v"(c.hi), "+v"(d.lo), "+v"(d.hi));
+    asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(a.lo), "+v"(a.hi), "+v"(b.lo), "+v"(b.hi), "+v"(c.lo), "+v"(c.hi), "+v"(d.lo), "+v"(d.hi) : "n"(N > 15 ? 15 : N));
 }
 
 __device__ __forceinline__ void tr_settle_all(TrPair& a) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a.lo), "+v"(a.hi)); }
@@ -1398,16 +1389,151 @@ __device__ __forceinline__ void store_slab_tiles(float* slab, const f32x4_t (&ac
         }
 }
 
+// ---- pieces shared by the weight-gradient kernels; a kernel body spells out its ring and schedule, its wave roles, its read / MFMA interleave
+// and its column sums ----
+
+// A workgroup's work item: split ks of output tile (tm, tn), i.e. pixels [p_begin, p_end) in ksteps k-steps of 32.
+struct WGradWork {
+    int ks, tm, tn, p_begin, p_end, ksteps;
+    // item ks * tiles + tile of the slice-major order
+    __device__ __forceinline__ void set(const WGradArgs& a, unsigned item, int tiles_m, int tiles_n) {
+        const unsigned tiles = tiles_m * tiles_n;
+        ks = item / tiles;
+        const int tile = item - ks * tiles;
+        tm = tile / tiles_n; tn = tile - tm * tiles_n;
+        p_begin = ks * a.pix_per_split;
+        p_end = min(a.P, p_begin + a.pix_per_split);
+        ksteps = (p_end > p_begin) ? (p_end - p_begin + 31) >> 5 : 0;
+    }
+    // XCD-aware (k-slice, tile) map: blocks are dealt round-robin to the 8 XCDs; XCD x owns items [x*W/8, (x+1)*W/8) of the slice-major order:
+    // the tiles_n (resp. tiles_m) blocks that re-read the same dY (resp. X) pixel range share ONE L2 instead of
+    // missing in eight (measured before this map: 20 GB of L2-miss traffic per step in igemm_wgrad_dma_kernel alone).
+    // false: this block has no work (the grid is rounded up to the XCDs).
+    __device__ __forceinline__ bool map_xcd(const WGradArgs& a, int tiles_m, int tiles_n) {
+        const int work = tiles_m * tiles_n * a.splits, per_xcd = (work + 7) >> 3;
+        const int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);     // each XCD owns a contiguous, slice-major run of (ks, tile)
+        if ((int)(blockIdx.x >> 3) >= per_xcd || item >= work) return false;
+        set(a, item, tiles_m, tiles_n);
+        return true;
+    }
+};
+
+// buffer descriptors of dY ([P][Cm]) and of X (whole images: the rounded-up image count of P pixels)
+struct WGradRsrc { __amdgpu_buffer_rsrc_t y, x; };
+__device__ __forceinline__ WGradRsrc wgrad_rsrc(const WGradArgs& a) {
+    const GatherGeom& g = a.g;
+    const long long x_bytes = (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
+    return WGradRsrc{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.dY), 0, a.P * a.Cm * 2, 0x00020000),
+                     __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000)};
+}
+
+// The general LDS-DMA gather of the 128-wide-image kernels: issuing wave w of NW fetches, per k-step, the 1 KiB pieces q = w + NW * i of a stage of
+// NIMG swizzled [32 px][128 ch] images (NIMG_A of dY, then X): image q >> 3, piece row q & 7 = pixels 4 * (q & 7) + (lane >> 4) of the k-step.
+// wg_swz(4 * blk + r) is the same for blk and blk + 4, so the lane's source chunk is one constant for all of its pieces; w < NW and NW divides 8,
+// so the image of piece i, (NW * i) >> 3, does not depend on the wave.
+template <int NIMG_A_, int NIMG_, int NW>
+struct WGradGather {
+    static constexpr int IMG = 32 * 128, NIMG_A = NIMG_A_, NIMG = NIMG_, STAGE = NIMG * IMG;
+    static constexpr int NDMA = NIMG * 8 / NW;          // pieces per issuing wave per k-step: what dma_wait<> / vm_wait<> count
+    static constexpr int NB = NW >= 8 ? 1 : 8 / NW;     // distinct piece rows (q & 7) a wave serves
+    static_assert((NIMG * 8) % NW == 0 && (NW == 4 || NW == 8), "DMA pieces: evenly over the issuing waves, q & 7 periodic in i");
+
+    const WGradArgs& a;                                 // (references to the kernel's own argument: a gather must not outlive it)
+    const GatherGeom& g;
+    WGradRsrc rs;
+    int w, r_in, p_begin, p_end;
+    bool col_ok[NDMA];                                  // per piece: the lane's 8 columns are inside Cm / Ntot
+    int col[NDMA], tap_r[NDMA], tap_s[NDMA];            // dY channel, or channel of X and the tap
+    static constexpr int img_of(int i) { return NW * i / 8; }
+    static constexpr bool is_a(int i) { return img_of(i) < NIMG_A; }
+
+    __device__ __forceinline__ WGradGather(const WGradArgs& a_, int w_, int m0, int n0, int p_begin_, int p_end_, int lane) : a(a_), g(a_.g) {
+        rs = wgrad_rsrc(a);
+        w = w_; p_begin = p_begin_; p_end = p_end_;
+        r_in = lane >> 4;
+        const int ps = lane & 15;
+        const int c16 = ((((ps >> 1) ^ wg_swz(4 * (w & 7) + r_in)) << 1) | (ps & 1));
+#pragma unroll
+        for (int i = 0; i < NDMA; ++i) {
+            const int img = img_of(i);
+            if (is_a(i)) {
+                col[i] = m0 + img * 128 + c16 * 8;
+                col_ok[i] = col[i] < a.Cm;
+                tap_r[i] = tap_s[i] = 0;
+            } else {
+                const int bn = n0 + (img - NIMG_A) * 128 + c16 * 8;
+                col_ok[i] = bn < a.Ntot;
+                const int tap = col_ok[i] ? bn / g.Ck : 0;
+                col[i] = bn - tap * g.Ck;
+                tap_r[i] = tap / g.S; tap_s[i] = tap - tap_r[i] * g.S;
+            }
+        }
+    }
+    __device__ __forceinline__ uint16_t* piece(uint16_t* base, int i) const { return base + img_of(i) * IMG + ((w + NW * i) & 7) * 512; }
+    __device__ __forceinline__ void load(uint16_t* dst, int i, uint32_t off) const {
+        if (is_a(i)) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.y, (lds_void_ptr)dst, 16, off, 0, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.x, (lds_void_ptr)dst, 16, off, 0, 0, 0);
+    }
+    // fetches k-step kt of the split into the stage at `base`.  Pixels past p_end, columns past Cm / Ntot and taps outside the image get the offset
+    // DMA_OOB, past num_records of both descriptors: the buffer range check then makes the DMA write zeros.
+    __device__ __forceinline__ void issue(int kt, uint16_t* base) const {
+        int pn[NB], pho[NB], pwo[NB], pp[NB];
+        bool pok[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            pp[j] = p_begin + kt * 32 + 4 * ((w + NW * j) & 7) + r_in;
+            pok[j] = pp[j] < p_end;
+            int n = 0, ho = 0, wo = 0;
+            if (pok[j]) decode_pixel(g, pp[j], n, ho, wo);
+            pn[j] = (int)((long long)n * g.img_pitch); pho[j] = ho; pwo[j] = wo;
+        }
+#pragma unroll
+        for (int i = 0; i < NDMA; ++i) {
+            const int j = i % NB;
+            uint32_t off = DMA_OOB;
+            if (pok[j] && col_ok[i]) {
+                if (is_a(i)) off = (uint32_t)(pp[j] * a.Cm + col[i]) * 2u;
+                else {
+                    const int hi = pho[j] * g.stride - g.pad + tap_r[i], wi = pwo[j] * g.stride - g.pad + tap_s[i];
+                    if ((unsigned)hi < (unsigned)g.Hin && (unsigned)wi < (unsigned)g.Win)
+                        off = (uint32_t)(pn[j] + hi * g.row_pitch + wi * g.pix_pitch + col[i]) * 2u;
+                }
+            }
+            load(piece(base, i), i, off);
+        }
+    }
+};
+
+// One k-step of a 64 x 64 wave tile: the fragments at 32-byte chunks ca .. ca + 3 of image sa and cb .. cb + 3 of image sb through inline-asm
+// transposing reads (see ds_read_tr_raw), 16 reads in order, A (8) then B (8); 16 MFMAs.  fa stays with the caller for the column sums.
+__device__ __forceinline__ void wgrad_tr_kstep(const uint16_t* sa, int ca, const uint16_t* sb, int cb, int lane, f32x4_t (&acc)[4][4], bf16x8_t (&fa)[4]) {
+    TrPair ra[4], rb[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ra[i] = tr_frag_raw(sa, ca + i, lane);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rb[j] = tr_frag_raw(sb, cb + j, lane);
+    tr_settle<8>(ra[0], ra[1], ra[2], ra[3]);
+    tr_settle<0>(rb[0], rb[1], rb[2], rb[3]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fa[i] = tr_join(ra[i]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bf16x8_t fb = tr_join(rb[j]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
+    }
+}
+
 template <bool IN_BN>
 __global__ __launch_bounds__(256) void igemm_wgrad_kernel(WGradArgs a, int tiles_m, int tiles_n) {
     constexpr int TILE = 32 * 128;                       // elements per operand per stage
     __shared__ __attribute__((aligned(16))) uint16_t smem[2 * 2 * TILE];   // 32 KiB
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int tiles = tiles_m * tiles_n;
-    const int tile = blockIdx.x % tiles, ks = blockIdx.x / tiles;
-    const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
-    const int m0 = tm * 128, n0 = tn * 128;
+    WGradWork wk;
+    wk.set(a, blockIdx.x, tiles_m, tiles_n);            // (plain map: GRID_SPLITS)
+    const int ks = wk.ks, m0 = wk.tm * 128, n0 = wk.tn * 128;
+    const int p_begin = wk.p_begin, p_end = wk.p_end, ksteps = wk.ksteps;
     const GatherGeom g = a.g;
 
     // this thread's fixed 16-byte column chunk (same for both of its rows): 16 chunks per 128-wide row
@@ -1419,10 +1545,6 @@ __global__ __launch_bounds__(256) void igemm_wgrad_kernel(WGradArgs a, int tiles
     const int tap = b_ok ? bn / g.Ck : 0;
     const int ci = bn - tap * g.Ck;
     const int r = tap / g.S, s = tap - r * g.S;
-
-    const int p_begin = ks * a.pix_per_split;
-    const int p_end = min(a.P, p_begin + a.pix_per_split);
-    const int ksteps = (p_end > p_begin) ? (p_end - p_begin + 31) >> 5 : 0;
 
     uint4 ra[2], rb[2];
     auto gload = [&](int kt) {
@@ -1489,17 +1611,7 @@ __global__ __launch_bounds__(256) void igemm_wgrad_kernel(WGradArgs a, int tiles
     }
     // epilogue: fp32 slab
     float* slab = a.partial + (size_t)ks * a.Cm * a.Ntot;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + j * 16 + (lane & 15);
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + rr;
-                if (m < a.Cm && n < a.Ntot) slab[(size_t)m * a.Ntot + n] = acc[i][j][rr];
-            }
-        }
+    store_slab_tiles<4, 4>(slab, acc, m0 + wm * 64, n0 + wn * 64, a.Cm, a.Ntot, lane);
 }
 
 // wgrad, LDS-DMA version (the one the net plan uses): same tile / fragment scheme as igemm_wgrad_kernel, operands
@@ -1511,21 +1623,12 @@ __global__ __launch_bounds__(256) void igemm_wgrad_dma_kernel(WGradArgs a, int t
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware (k-slice, tile) map: blocks are dealt round-robin to the 8 XCDs; XCD x owns items [x*W/8, (x+1)*W/8) of the slice-major order:
-    // the tiles_n (resp. tiles_m) blocks that re-read the same dY (resp. X) pixel range share ONE L2 instead of
-    // missing in eight (measured before this map: 20 GB of L2-miss traffic per step in this kernel alone).
-    const int tiles = tiles_m * tiles_n;
-    const int work = tiles * a.splits, per_xcd = (work + 7) >> 3;
-    const int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);     // each XCD owns a contiguous, slice-major run of (ks, tile)
-    if ((int)(blockIdx.x >> 3) >= per_xcd || item >= work) return;
-    const int ks = item / tiles, tile = item - ks * tiles;
-    const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
-    const int m0 = tm * 128, n0 = tn * 128;
+    WGradWork wk;
+    if (!wk.map_xcd(a, tiles_m, tiles_n)) return;
+    const int ks = wk.ks, tn = wk.tn, m0 = wk.tm * 128, n0 = tn * 128;
     conv_stamp(a, 0);
     const GatherGeom g = a.g;
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.dY), 0, a.P * a.Cm * 2, 0x00020000);
-    const long long x_bytes = (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000);
+    const WGradRsrc rs = wgrad_rsrc(a);
 
     // lane-constant source chunk: slot lane&15 of row (4*block + lane>>4); swz(row) is the same for blocks w and w+4
     const int r_in = lane >> 4, ps = lane & 15;
@@ -1537,11 +1640,9 @@ __global__ __launch_bounds__(256) void igemm_wgrad_dma_kernel(WGradArgs a, int t
     const int tap = b_ok ? bn / g.Ck : 0;
     const int ci = bn - tap * g.Ck;
     const int r = tap / g.S, s = tap - r * g.S;
+    const int p_begin = wk.p_begin, p_end = wk.p_end, ksteps = wk.ksteps;
 
-    const int p_begin = ks * a.pix_per_split;
-    const int p_end = min(a.P, p_begin + a.pix_per_split);
-    const int ksteps = (p_end > p_begin) ? (p_end - p_begin + 31) >> 5 : 0;
-
+    // (written out, not WGradGather: the two images' loads alternate A, B, A, B)
     auto issue = [&](int kt, int stage) {
         uint16_t* sa = smem + stage * 2 * TILE;
         uint16_t* sb = sa + TILE;
@@ -1560,8 +1661,8 @@ __global__ __launch_bounds__(256) void igemm_wgrad_dma_kernel(WGradArgs a, int t
                         ob = (uint32_t)((int)((long long)n * g.img_pitch) + hi * g.row_pitch + wi * g.pix_pitch + ci) * 2u;
                 }
             }
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void_ptr)(sa + blk * 512), 16, oa, 0, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(sb + blk * 512), 16, ob, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.y, (lds_void_ptr)(sa + blk * 512), 16, oa, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.x, (lds_void_ptr)(sb + blk * 512), 16, ob, 0, 0, 0);
         }
     };
 
@@ -1590,23 +1691,8 @@ __global__ __launch_bounds__(256) void igemm_wgrad_dma_kernel(WGradArgs a, int t
             if (kt + 2 < ksteps) issue(kt + 2, st_nxt2);
             const uint16_t* sa = smem + st_cur * 2 * TILE;
             const uint16_t* sb = sa + TILE;
-            // transposing reads through inline asm (see ds_read_tr_raw): 16 reads in order, A (8) then B (8)
-            TrPair ra[4], rb[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ra[i] = tr_frag_raw(sa, wm * 4 + i, lane);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rb[j] = tr_frag_raw(sb, wn * 4 + j, lane);
-            tr_settle<8>(ra[0], ra[1], ra[2], ra[3]);
-            tr_settle<0>(rb[0], rb[1], rb[2], rb[3]);
             bf16x8_t fa[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fa[i] = tr_join(ra[i]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bf16x8_t fb = tr_join(rb[j]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
-            }
+            wgrad_tr_kstep(sa, wm * 4, sb, wn * 4, lane, acc, fa);
             if constexpr (COLSUM) if (do_cs) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) cs[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], ones, cs[i], 0, 0, 0);
@@ -1655,21 +1741,15 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    const int tiles = tiles_m * tiles_n;
-    const int work = tiles * a.splits, per_xcd = (work + 7) >> 3;
-    const int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per_xcd || item >= work) return;
-    const int ks = item / tiles, tile = item - ks * tiles;
-    const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
-    const int m0 = tm * 128, ci0 = tn * 64;
+    WGradWork wk;
+    if (!wk.map_xcd(a, tiles_m, tiles_n)) return;
+    const int ks = wk.ks, m0 = wk.tm * 128, ci0 = wk.tn * 64;
     conv_stamp(a, 0);
     const bool m_active = m0 + wm * 64 < a.Cm;          // Cout = 64: the upper half of the co tile is padding, its waves only help with the DMA
     const GatherGeom g = a.g;
     const int W = g.Wout, H = g.Hout, Cin = g.Ck, lw = g.lw, lhw = g.lhw;
     const int RW = 32 >> lw, HC = W + 2, HP = (RW + 2) * HC;
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.dY), 0, a.P * a.Cm * 2, 0x00020000);
-    const long long x_bytes = (long long)g.img_pitch * 2 * (a.P >> lhw);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000);
+    const WGradRsrc rs = wgrad_rsrc(a);                  // (P is whole images of 2^lhw pixels here)
 
     // dY DMA (block = wave): row 4*wave + lane>>4 of the [32][128] image, swizzled 16-byte slot as in igemm_wgrad_dma_kernel
     const int r_in = lane >> 4, ps = lane & 15;
@@ -1688,9 +1768,7 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
         hb_ok[i] = hp < HP && (unsigned)(hc - 1) < (unsigned)W && ci0 + lc * 8 < Cin;
         hb_off[i] = ((hc - 1) * Cin + ci0 + lc * 8) * 2;                   // bytes inside an image row (+ row / image part per k-step)
     }
-    const int p_begin = ks * a.pix_per_split;
-    const int p_end = min(a.P, p_begin + a.pix_per_split);
-    const int ksteps = (p_end > p_begin) ? (p_end - p_begin + 31) >> 5 : 0;
+    const int p_begin = wk.p_begin, p_end = wk.p_end, ksteps = wk.ksteps;
 
     auto issue = [&](int kt, int stage) {
         uint16_t* sa = smem + stage * W3_STAGE;
@@ -1698,7 +1776,7 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
         const int p0 = p_begin + kt * 32;
         const int p = p0 + 4 * wave + r_in;
         const uint32_t oa = (p < p_end && a_ok) ? (uint32_t)(p * a.Cm + am) * 2u : DMA_OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void_ptr)(sa + wave * 512), 16, oa, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.y, (lds_void_ptr)(sa + wave * 512), 16, oa, 0, 0, 0);
         const int n = p0 >> lhw, h_base = (p0 & ((1 << lhw) - 1)) >> lw;       // wave-uniform: first image row of this k-step
         const int row_bytes = W * Cin * 2;
         const int img_base = (int)((long long)n * g.img_pitch * 2);
@@ -1707,7 +1785,7 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
             const int h = h_base - 1 + hb_hr[i];
             const bool ok = hb_ok[i] && (unsigned)h < (unsigned)H && p0 < p_end;
             const uint32_t ob = ok ? (uint32_t)(img_base + h * row_bytes + hb_off[i]) : DMA_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)(sb + (wave + 8 * i) * 512), 16, ob, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.x, (lds_void_ptr)(sb + (wave + 8 * i) * 512), 16, ob, 0, 0, 0);
         }
     };
 
@@ -1812,76 +1890,18 @@ __global__ __launch_bounds__(512) void igemm_wgrad3x3_kernel(WGradArgs a, int ti
 template <int WM, int WN, int NSTAGE, bool COLSUM = false>
 __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_wgrad_wg_kernel(WGradArgs a, int tiles_m, int tiles_n) {      // (4 waves per SIMD = two 8-wave workgroups per CU: the column-sum variant allocated 136 registers without the bound)
     constexpr int TM = 64 * WM, TN = 64 * WN, NW = WM * WN;
-    constexpr int IMG = 32 * 128, NIMG_A = TM / 128, NIMG = (TM + TN) / 128;
-    constexpr int NBLK = NIMG * 8 / NW;                 // 1 KiB DMA blocks per wave per k-step
+    using Gather = WGradGather<TM / 128, (TM + TN) / 128, NW>;
+    constexpr int IMG = Gather::IMG, NIMG_A = Gather::NIMG_A, STAGE = Gather::STAGE, NDMA = Gather::NDMA;
     constexpr int AHEAD = NSTAGE - 1;
-    static_assert((NIMG * 8) % NW == 0 && TM % 128 == 0 && TN % 128 == 0, "unsupported wave grid");
+    static_assert(TM % 128 == 0 && TN % 128 == 0, "unsupported wave grid");
     extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const int tiles = tiles_m * tiles_n;
-    const int work = tiles * a.splits, per_xcd = (work + 7) >> 3;
-    const int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if ((int)(blockIdx.x >> 3) >= per_xcd || item >= work) return;
-    const int ks = item / tiles, tile = item - ks * tiles;
-    const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
-    const int m0 = tm * TM, n0 = tn * TN;
-    const GatherGeom g = a.g;
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.dY), 0, a.P * a.Cm * 2, 0x00020000);
-    const long long x_bytes = (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000);
-    // this wave's DMA blocks: q = wave + NW*i -> image q>>3, block q&7 (rows 4*(q&7) + lane>>4); (q&7) is the same for every i
-    const int r_in = lane >> 4, ps = lane & 15;
-    const int blk = wave & 7;
-    const int c16 = ((((ps >> 1) ^ wg_swz(4 * blk + r_in)) << 1) | (ps & 1));
-    // per-block operand column state
-    bool is_a[NBLK], col_ok[NBLK];
-    int col[NBLK], tap_r[NBLK], tap_s[NBLK], img_of[NBLK];
-#pragma unroll
-    for (int i = 0; i < NBLK; ++i) {
-        const int q = wave + NW * i, img = q >> 3;
-        img_of[i] = img;
-        is_a[i] = img < NIMG_A;
-        if (is_a[i]) {
-            col[i] = m0 + img * 128 + c16 * 8;
-            col_ok[i] = col[i] < a.Cm;
-            tap_r[i] = tap_s[i] = 0;
-        } else {
-            const int bn = n0 + (img - NIMG_A) * 128 + c16 * 8;
-            col_ok[i] = bn < a.Ntot;
-            const int tap = col_ok[i] ? bn / g.Ck : 0;
-            col[i] = bn - tap * g.Ck;
-            tap_r[i] = tap / g.S; tap_s[i] = tap - tap_r[i] * g.S;
-        }
-    }
-    const int p_begin = ks * a.pix_per_split;
-    const int p_end = min(a.P, p_begin + a.pix_per_split);
-    const int ksteps = (p_end > p_begin) ? (p_end - p_begin + 31) >> 5 : 0;
-
-    auto issue = [&](int kt, int stage) {
-        uint16_t* base = smem + stage * NIMG * IMG;
-        const int p = p_begin + kt * 32 + 4 * blk + r_in;
-        int n = 0, ho = 0, wo = 0;
-        const bool pok = p < p_end;
-        if (pok) decode_pixel(g, p, n, ho, wo);
-        const int pix_base = (int)((long long)n * g.img_pitch);
-#pragma unroll
-        for (int i = 0; i < NBLK; ++i) {
-            uint32_t off = DMA_OOB;
-            if (pok && col_ok[i]) {
-                if (is_a[i]) off = (uint32_t)(p * a.Cm + col[i]) * 2u;
-                else {
-                    const int hi = ho * g.stride - g.pad + tap_r[i], wi = wo * g.stride - g.pad + tap_s[i];
-                    if ((unsigned)hi < (unsigned)g.Hin && (unsigned)wi < (unsigned)g.Win)
-                        off = (uint32_t)(pix_base + hi * g.row_pitch + wi * g.pix_pitch + col[i]) * 2u;
-                }
-            }
-            uint16_t* dst = base + img_of[i] * IMG + blk * 512;
-            if (is_a[i]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void_ptr)dst, 16, off, 0, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)dst, 16, off, 0, 0, 0);
-        }
-    };
+    WGradWork wk;
+    if (!wk.map_xcd(a, tiles_m, tiles_n)) return;
+    const int m0 = wk.tm * TM, n0 = wk.tn * TN, ksteps = wk.ksteps;
+    const Gather gather(a, wave, m0, n0, wk.p_begin, wk.p_end, lane);
 
     // COLSUM: column sums of dY over this split's pixels ride on the GEMM as one more MFMA per A fragment against an all-ones operand
     // (see igemm_wgrad_dma_kernel), in the wn-0 waves, whose A fragments cover each channel of the m tile exactly once.  All n tiles of an
@@ -1891,7 +1911,7 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_wgrad_wg_kernel(WGradAr
     // elsewhere, so column 4i of the 16 x 16 result carries fragment i's row sums (16 accumulator registers for the four sums spilled
     // inside the main loop of the 128-register kernel).
     const bool do_cs = COLSUM && wn == 0;
-    int cs_turn = tn;                                    // k-steps until this workgroup's next turn
+    int cs_turn = wk.tn;                                   // k-steps until this workgroup's next turn
     f32x4_t cs = f32x4_t{0.f, 0.f, 0.f, 0.f};
     typedef unsigned sel_vec_t __attribute__((ext_vector_type(4)));
     const int cs_col = (lane & 15) >> 2;                 // the fragment whose sums this lane's result column carries
@@ -1902,32 +1922,18 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_wgrad_wg_kernel(WGradAr
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     if (ksteps > 0) {
         int issued = 0;
-        for (; issued < AHEAD && issued < ksteps; ++issued) issue(issued, issued);
+        for (; issued < AHEAD && issued < ksteps; ++issued) gather.issue(issued, smem + issued * STAGE);
         if (issued == 1) dma_wait<0>();
-        else if (issued == 2) dma_wait<NBLK>();
-        else dma_wait<2 * NBLK>();
+        else if (issued == 2) dma_wait<NDMA>();
+        else dma_wait<2 * NDMA>();
         __builtin_amdgcn_s_barrier();
         int st_cur = 0, st_fill = AHEAD % NSTAGE;
         for (int kt = 0; kt < ksteps; ++kt) {
-            if (kt + AHEAD < ksteps) issue(kt + AHEAD, st_fill);
-            const uint16_t* sa = smem + st_cur * NIMG * IMG + (wm >> 1) * IMG;
-            const uint16_t* sb = smem + st_cur * NIMG * IMG + (NIMG_A + (wn >> 1)) * IMG;
-            TrPair ra[4], rb[4];                                     // inline-asm transposing reads, see ds_read_tr_raw
-#pragma unroll
-            for (int i = 0; i < 4; ++i) ra[i] = tr_frag_raw(sa, (wm & 1) * 4 + i, lane);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rb[j] = tr_frag_raw(sb, (wn & 1) * 4 + j, lane);
-            tr_settle<8>(ra[0], ra[1], ra[2], ra[3]);
-            tr_settle<0>(rb[0], rb[1], rb[2], rb[3]);
+            if (kt + AHEAD < ksteps) gather.issue(kt + AHEAD, smem + st_fill * STAGE);
+            const uint16_t* sa = smem + st_cur * STAGE + (wm >> 1) * IMG;
+            const uint16_t* sb = smem + st_cur * STAGE + (NIMG_A + (wn >> 1)) * IMG;
             bf16x8_t fa[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fa[i] = tr_join(ra[i]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bf16x8_t fb = tr_join(rb[j]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
-            }
+            wgrad_tr_kstep(sa, (wm & 1) * 4, sb, (wn & 1) * 4, lane, acc, fa);
             if constexpr (COLSUM) if (do_cs) {
                 if (cs_turn == 0) {
                     int opaque;                          // the select operands are built here, per use: hoisted out of the loop they cost 16 registers
@@ -1944,30 +1950,20 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_wgrad_wg_kernel(WGradAr
             const int left = ksteps - 1 - kt;
             const int inflight_after = left < AHEAD ? left : AHEAD;
             if (inflight_after <= 1) dma_wait<0>();
-            else if (inflight_after == 2) dma_wait<NBLK>();
-            else dma_wait<2 * NBLK>();
+            else if (inflight_after == 2) dma_wait<NDMA>();
+            else dma_wait<2 * NDMA>();
             __builtin_amdgcn_s_barrier();
             st_cur = (st_cur == NSTAGE - 1) ? 0 : st_cur + 1;
             st_fill = (st_fill == NSTAGE - 1) ? 0 : st_fill + 1;
         }
     }
-    float* slab = a.partial + (size_t)ks * a.Cm * a.Ntot;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + j * 16 + (lane & 15);
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + rr;
-                if (m < a.Cm && n < a.Ntot) slab[(size_t)m * a.Ntot + n] = acc[i][j][rr];
-            }
-        }
+    float* slab = a.partial + (size_t)wk.ks * a.Cm * a.Ntot;
+    store_slab_tiles<4, 4>(slab, acc, m0 + wm * 64, n0 + wn * 64, a.Cm, a.Ntot, lane);
     if constexpr (COLSUM) if (do_cs && (lane & 3) == 0) {
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int m = m0 + wm * 64 + cs_col * 16 + (lane >> 4) * 4 + rr;
-            if (m < a.Cm) a.colsum[((size_t)ks * tiles_n + tn) * a.Cm + m] = cs[rr];
+            if (m < a.Cm) a.colsum[((size_t)wk.ks * tiles_n + wk.tn) * a.Cm + m] = cs[rr];
         }
     }
 }
@@ -1985,44 +1981,27 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_wgrad_wg_kernel(WGradAr
 // Wave grid: WM x WN consumers of (16 FM) x (16 FN), NP producers.  1 x 4 consumers of 128 x 64 + 4 producers = 8 waves at <= 256 registers
 // (one MFMA stream per SIMD, 12 fragments = 24 reads per 32 MFMAs); 2 x 4 consumers of 64 x 64 + 4 producers = 12 waves at <= 168.
 // ------------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// tile, ring and piece constants of igemm_wgrad_p_kernel and its producers
+template <int TM, int TN, int NP, int NSTAGE>
+struct WGradPCfg {
+    using Gather = WGradGather<TM / 128, (TM + TN) / 128, NP>;
+    static constexpr int IMG = Gather::IMG, NIMG_A = Gather::NIMG_A, STAGE = Gather::STAGE;
+    static constexpr int NBLK = Gather::NDMA;           // 1 KiB DMA pieces per producer per k-step
+    static constexpr int LEAD = NSTAGE - 3;             // k-steps that may still be in flight at the barrier (beyond the one that must have landed)
+    static_assert(TM % 128 == 0 && TN % 128 == 0, "unsupported wave grid");
+    static_assert(NSTAGE >= 4 && LEAD * NBLK <= 63, "ring depth / vmcnt range");
+};
 
 // Producer wave pw of igemm_wgrad_p_kernel.  A __device__ function of its own rather than a branch of the kernel body: lambdas inside a
 // __global__ function are compiled for the host too, and with this code inside the kernel hipcc 7.2 dropped the kernel's HOST stub
 // without a diagnostic (the library then failed to load with an undefined symbol).
 template <int TM, int TN, int NP, int NSTAGE>
-__device__ __forceinline__ void wgrad_p_produce(const WGradArgs& a, uint16_t* smem, int pw, int m0, int n0, int p_begin, int p_end, int ksteps) {
-    constexpr int IMG = 32 * 128, NIMG_A = TM / 128, NIMG = (TM + TN) / 128, STAGE = NIMG * IMG;
-    constexpr int NBLK = NIMG * 8 / NP;                 // 1 KiB DMA pieces per producer per k-step
-    constexpr int NB = NP >= 8 ? 1 : 8 / NP;            // distinct piece rows (q & 7) a producer serves
-    constexpr int LEAD = NSTAGE - 3;                    // k-steps that may still be in flight at the barrier (beyond the one that must have landed)
-    const int lane = threadIdx.x & 63;
-    const GatherGeom g = a.g;
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.dY), 0, a.P * a.Cm * 2, 0x00020000);
-    const long long x_bytes = (long long)g.img_pitch * 2 * ((a.P + g.Hout * g.Wout - 1) / (g.Hout * g.Wout));
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)x_bytes, 0x00020000);
-    // pieces q = pw + NP*i -> image q >> 3, piece row q & 7 (pixels 4*(q&7) + lane>>4 of the k-step); wg_swz(4*blk + r) is the same for blk and blk + 4
-    const int r_in = lane >> 4, ps = lane & 15;
-    const int c16 = ((((ps >> 1) ^ wg_swz(4 * (pw & 7) + r_in)) << 1) | (ps & 1));
-    bool is_a[NBLK], col_ok[NBLK];
-    int col[NBLK], tap_r[NBLK], tap_s[NBLK];
-#pragma unroll
-    for (int i = 0; i < NBLK; ++i) {
-        const int img = (pw + NP * i) >> 3;
-        is_a[i] = img < NIMG_A;
-        if (is_a[i]) {
-            col[i] = m0 + img * 128 + c16 * 8;
-            col_ok[i] = col[i] < a.Cm;
-            tap_r[i] = tap_s[i] = 0;
-        } else {
-            const int bn = n0 + (img - NIMG_A) * 128 + c16 * 8;
-            col_ok[i] = bn < a.Ntot;
-            const int tap = col_ok[i] ? bn / g.Ck : 0;
-            col[i] = bn - tap * g.Ck;
-            tap_r[i] = tap / g.S; tap_s[i] = tap - tap_r[i] * g.S;
-        }
-    }
+__device__ __forceinline__ void wgrad_p_produce(const WGradArgs& a, uint16_t* smem, int pw, int m0, int n0, const WGradWork& wk) {
+    using Cfg = WGradPCfg<TM, TN, NP, NSTAGE>;
+    constexpr int STAGE = Cfg::STAGE, NBLK = Cfg::NBLK, LEAD = Cfg::LEAD;
+    const int lane = threadIdx.x & 63, ksteps = wk.ksteps;
+    const GatherGeom& g = a.g;
+    const typename Cfg::Gather gather(a, pw, m0, n0, wk.p_begin, wk.p_end, lane);
     // 1x1 / stride 1 convolutions and linear layers: both operands are plain [P][ld] matrices, so a piece's source offset is a base
     // plus kt * 32 rows -- one add per piece instead of the pixel decode / tap arithmetic / bounds tests of the general gather (with four
     // producers of six pieces each, that arithmetic, not the matrix pipe, set the k-step: 126 us against 94 for layer4's conv1).
@@ -2033,50 +2012,19 @@ __device__ __forceinline__ void wgrad_p_produce(const WGradArgs& a, uint16_t* sm
     uint32_t off0[NBLK];
 #pragma unroll
     for (int i = 0; i < NBLK; ++i) {
-        const int row = p_begin + 4 * ((pw + NP * i) & 7) + r_in;
-        off0[i] = col_ok[i] ? (uint32_t)(row * (is_a[i] ? a.Cm : g.Ck) + col[i]) * 2u : DMA_OOB;
+        const int row = wk.p_begin + 4 * ((pw + NP * i) & 7) + gather.r_in;
+        off0[i] = gather.col_ok[i] ? (uint32_t)(row * (gather.is_a(i) ? a.Cm : g.Ck) + gather.col[i]) * 2u : DMA_OOB;
     }
     const uint32_t step_a = 32u * (uint32_t)a.Cm * 2u, step_b = 32u * (uint32_t)g.Ck * 2u;
     auto issue = [&](int kt) {
         uint16_t* base = smem + (kt % NSTAGE) * STAGE;
         if (flat) {
 #pragma unroll
-            for (int i = 0; i < NBLK; ++i) {
-                const int q = pw + NP * i;
-                uint16_t* dst = base + (q >> 3) * IMG + (q & 7) * 512;
-                // (DMA_OOB + kt * step stays below 2^32 and above every num_records: the tensors are below 0x7ff00000 bytes)
-                const uint32_t off = off0[i] + (uint32_t)kt * (is_a[i] ? step_a : step_b);
-                if (is_a[i]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void_ptr)dst, 16, off, 0, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)dst, 16, off, 0, 0, 0);
-            }
+            for (int i = 0; i < NBLK; ++i)      // (DMA_OOB + kt * step stays below 2^32 and above every num_records: the tensors are below 0x7ff00000 bytes)
+                gather.load(gather.piece(base, i), i, off0[i] + (uint32_t)kt * (gather.is_a(i) ? step_a : step_b));
             return;
         }
-        int pn[NB], pho[NB], pwo[NB], pp[NB];
-        bool pok[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            pp[j] = p_begin + kt * 32 + 4 * ((pw + NP * j) & 7) + r_in;
-            pok[j] = pp[j] < p_end;
-            int n = 0, ho = 0, wo = 0;
-            if (pok[j]) decode_pixel(g, pp[j], n, ho, wo);
-            pn[j] = (int)((long long)n * g.img_pitch); pho[j] = ho; pwo[j] = wo;
-        }
-#pragma unroll
-        for (int i = 0; i < NBLK; ++i) {
-            const int j = i % NB, q = pw + NP * i;
-            uint32_t off = DMA_OOB;
-            if (pok[j] && col_ok[i]) {
-                if (is_a[i]) off = (uint32_t)(pp[j] * a.Cm + col[i]) * 2u;
-                else {
-                    const int hi = pho[j] * g.stride - g.pad + tap_r[i], wi = pwo[j] * g.stride - g.pad + tap_s[i];
-                    if ((unsigned)hi < (unsigned)g.Hin && (unsigned)wi < (unsigned)g.Win)
-                        off = (uint32_t)(pn[j] + hi * g.row_pitch + wi * g.pix_pitch + col[i]) * 2u;
-                }
-            }
-            uint16_t* dst = base + (q >> 3) * IMG + (q & 7) * 512;
-            if (is_a[i]) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void_ptr)dst, 16, off, 0, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_void_ptr)dst, 16, off, 0, 0, 0);
-        }
+        gather.issue(kt, base);
     };
     auto wait_all_but = [&](int n) {                           // all but the youngest n k-steps of this wave's pieces have landed
         if (n <= 0) vm_wait<0>();
@@ -2104,28 +2052,24 @@ __device__ __forceinline__ void wgrad_p_produce(const WGradArgs& a, uint16_t* sm
 template <int WM, int WN, int FM, int FN, int NP, int NSTAGE, bool COLSUM = false>
 __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_wgrad_p_kernel(WGradArgs a, int tiles_m, int tiles_n) {
     constexpr int TM = 16 * FM * WM, TN = 16 * FN * WN, NC = WM * WN;
-    constexpr int IMG = 32 * 128, NIMG_A = TM / 128, NIMG = (TM + TN) / 128, STAGE = NIMG * IMG;
-    constexpr int NBLK = NIMG * 8 / NP;                 // 1 KiB DMA pieces per producer per k-step
-    constexpr int LEAD = NSTAGE - 3;                    // k-steps that may still be in flight at the barrier (beyond the one that must have landed)
-    static_assert((NIMG * 8) % NP == 0 && (NP == 4 || NP == 8) && TM % 128 == 0 && TN % 128 == 0, "unsupported wave grid");
-    static_assert(NSTAGE >= 4 && LEAD * NBLK <= 63, "ring depth / vmcnt range");
+    using Cfg = WGradPCfg<TM, TN, NP, NSTAGE>;
+    constexpr int IMG = Cfg::IMG, NIMG_A = Cfg::NIMG_A, STAGE = Cfg::STAGE;
     extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the item of WGradWork::map_xcd written out, WGradWork::set for the rest (through map_xcd itself the ViT's weight gradients measured 1.5 - 2 % slower,
+    // 4.52 against 4.45 ms for the 48 of them, with the same main loops: the cause was not found in the assembly; this form measures as the parent)
     const int tiles = tiles_m * tiles_n;
     const int work = tiles * a.splits, per_xcd = (work + 7) >> 3;
     const int item = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     if ((int)(blockIdx.x >> 3) >= per_xcd || item >= work) return;
-    const int ks = item / tiles, tile = item - ks * tiles;
-    const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
-    const int m0 = tm * TM, n0 = tn * TN;
-    const int p_begin = ks * a.pix_per_split;
-    const int p_end = min(a.P, p_begin + a.pix_per_split);
-    const int ksteps = (p_end > p_begin) ? (p_end - p_begin + 31) >> 5 : 0;
+    WGradWork wk;
+    wk.set(a, item, tiles_m, tiles_n);
+    const int ks = wk.ks, tn = wk.tn, m0 = wk.tm * TM, n0 = tn * TN, ksteps = wk.ksteps;
     conv_stamp(a, 0);
     if (wave >= NC) {
         // ---------------- producers ---------------- (a __device__ function: see wgrad_p_produce)
-        if (ksteps > 0) wgrad_p_produce<TM, TN, NP, NSTAGE>(a, smem, wave - NC, m0, n0, p_begin, p_end, ksteps);
+        if (ksteps > 0) wgrad_p_produce<TM, TN, NP, NSTAGE>(a, smem, wave - NC, m0, n0, wk);
         return;
     }
     // ---------------- consumers ----------------
@@ -2147,7 +2091,6 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_wgrad_p_kernel(WGra
     const uint32_t base_a = (uint32_t)((ca >> 3) * IMG * 2 + row0 * 256 + 8 * p4 + (((ca & 7) ^ swz0) << 5));
     const uint32_t base_b = (uint32_t)((NIMG_A + (cb >> 3)) * IMG * 2 + row0 * 256 + 8 * p4 + (((cb & 7) ^ swz0) << 5));
     typedef __attribute__((address_space(3))) s16x4_t* lds_ptr_t;
-    typedef short s16x8_t __attribute__((ext_vector_type(8)));
     auto frag_at = [&](uint32_t addr) -> bf16x8_t {
         const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr_t)(uintptr_t)addr);
         const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr_t)(uintptr_t)(addr + 1024));
@@ -2184,6 +2127,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_wgrad_p_kernel(WGra
     // against a column-select operand (fragment i' of a wave's share lands in result column 4 i'), the n tiles of an (m tile, split) taking the k-steps
     // in turn.  The WN waves of a consumer row hold the same FM A fragments: each sums FM / WN of them (all on the wn-0 wave, 8 extra MFMAs in its turn
     // steps while the other three waited at the barrier: 4.76 ms for the ViT's 48 weight gradients against 4.67 shared).
+    // (written out, as is igemm_wgrad_wg_kernel's: through a shared struct this kernel's column-sum variant, the ViT plan's own, measured 1.5 % slower)
     constexpr int CSF = FM / WN;
     static_assert(!COLSUM || (FM % WN == 0 && CSF <= 4), "column sums: the fragments must divide over the waves of a row");
     const bool do_cs = COLSUM;
@@ -2246,7 +2190,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_wgrad_p_kernel(WGra
         }
     }
     conv_stamp(a, 2);
-    float* slab = a.partial + (size_t)ks * a.Cm * a.Ntot;
+    float* slab = a.partial + (size_t)wk.ks * a.Cm * a.Ntot;
     store_slab_tiles<FM, FN>(slab, acc, m0 + wm * 16 * FM, n0 + wn * 16 * FN, a.Cm, a.Ntot, lane);
     if constexpr (COLSUM) if (do_cs && (lane & 3) == 0 && cs_col < CSF) {
 #pragma unroll

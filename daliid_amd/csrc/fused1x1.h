@@ -38,48 +38,47 @@ __device__ __forceinline__ unsigned f1_pos_bits(uint32_t w) {
     return ((p >> 15) | (p >> 30)) & 3u;
 }
 
-template <int N> __device__ __forceinline__ void f1_vm_wait_imm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // wave-uniform n; anything beyond the table waits for everything (stricter = safe)
 __device__ __forceinline__ void f1_vm_wait(int n) {
     switch (n) {
-        case 1: f1_vm_wait_imm<1>(); break;
-        case 2: f1_vm_wait_imm<2>(); break;
-        case 3: f1_vm_wait_imm<3>(); break;
-        case 4: f1_vm_wait_imm<4>(); break;
-        case 5: f1_vm_wait_imm<5>(); break;
-        case 6: f1_vm_wait_imm<6>(); break;
-        case 7: f1_vm_wait_imm<7>(); break;
-        case 8: f1_vm_wait_imm<8>(); break;
-        case 9: f1_vm_wait_imm<9>(); break;
-        case 10: f1_vm_wait_imm<10>(); break;
-        case 11: f1_vm_wait_imm<11>(); break;
-        case 12: f1_vm_wait_imm<12>(); break;
-        case 13: f1_vm_wait_imm<13>(); break;
-        case 14: f1_vm_wait_imm<14>(); break;
-        case 15: f1_vm_wait_imm<15>(); break;
-        case 16: f1_vm_wait_imm<16>(); break;
-        case 17: f1_vm_wait_imm<17>(); break;
-        case 18: f1_vm_wait_imm<18>(); break;
-        case 19: f1_vm_wait_imm<19>(); break;
-        case 20: f1_vm_wait_imm<20>(); break;
-        case 21: f1_vm_wait_imm<21>(); break;
-        case 22: f1_vm_wait_imm<22>(); break;
-        case 23: f1_vm_wait_imm<23>(); break;
-        case 24: f1_vm_wait_imm<24>(); break;
-        case 25: f1_vm_wait_imm<25>(); break;
-        case 26: f1_vm_wait_imm<26>(); break;
-        case 27: f1_vm_wait_imm<27>(); break;
-        case 28: f1_vm_wait_imm<28>(); break;
-        default: f1_vm_wait_imm<0>(); break;
+        case 1: vm_wait<1>(); break;
+        case 2: vm_wait<2>(); break;
+        case 3: vm_wait<3>(); break;
+        case 4: vm_wait<4>(); break;
+        case 5: vm_wait<5>(); break;
+        case 6: vm_wait<6>(); break;
+        case 7: vm_wait<7>(); break;
+        case 8: vm_wait<8>(); break;
+        case 9: vm_wait<9>(); break;
+        case 10: vm_wait<10>(); break;
+        case 11: vm_wait<11>(); break;
+        case 12: vm_wait<12>(); break;
+        case 13: vm_wait<13>(); break;
+        case 14: vm_wait<14>(); break;
+        case 15: vm_wait<15>(); break;
+        case 16: vm_wait<16>(); break;
+        case 17: vm_wait<17>(); break;
+        case 18: vm_wait<18>(); break;
+        case 19: vm_wait<19>(); break;
+        case 20: vm_wait<20>(); break;
+        case 21: vm_wait<21>(); break;
+        case 22: vm_wait<22>(); break;
+        case 23: vm_wait<23>(); break;
+        case 24: vm_wait<24>(); break;
+        case 25: vm_wait<25>(); break;
+        case 26: vm_wait<26>(); break;
+        case 27: vm_wait<27>(); break;
+        case 28: vm_wait<28>(); break;
+        default: vm_wait<0>(); break;
     }
 }
 
 // the residual producers' counts: 0, 1 (mask only), 16 (residual only), 17 (both)
 __device__ __forceinline__ void f1_vm_wait_pieces(int n) {
-    if (n == 17) f1_vm_wait_imm<17>();
-    else if (n == 16) f1_vm_wait_imm<16>();
-    else if (n == 1) f1_vm_wait_imm<1>();
-    else f1_vm_wait_imm<0>();
+    if (n == 17) vm_wait<17>();
+    else if (n == 16) vm_wait<16>();
+    else if (n == 1) vm_wait<1>();
+    else vm_wait<0>();
 }
 
 constexpr int F1_TM = 128, F1_TN = 128, F1_NC = 8, F1_NP = 4, F1_NR = 2;
@@ -253,10 +252,10 @@ __global__ __launch_bounds__((F1_NC + F1_NP + F1_NR) * 64) void fused1x1_persist
                 if constexpr (F1_RB == 2) {
                     if (k == 0 && t + 1 < T) issue_rm(t + 1);
                     // last main beat: tile t's pieces (requested one tile ago) have landed; only tile t + 1's may still be in flight
-                    if (k == KT - 1) { if (t + 1 < T) f1_vm_wait_pieces(pieces); else f1_vm_wait_imm<0>(); }
+                    if (k == KT - 1) { if (t + 1 < T) f1_vm_wait_pieces(pieces); else vm_wait<0>(); }
                 } else {                                              // one buffer: free since the previous tile's output stage; lands under this main loop
                     if (k == 0 && t > 0) issue_rm(t);
-                    if (k == KT - 1) f1_vm_wait_imm<0>();
+                    if (k == KT - 1) vm_wait<0>();
                 }
                 __builtin_amdgcn_s_barrier();
             }

@@ -134,23 +134,18 @@ __device__ __forceinline__ void acc_coords(int& m_base, int& n_base) {
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 constexpr uint32_t DMA_OOB = 0x7ffffff0u;
 
-// wait until at most N of this wave's vector-memory operations (the LDS-DMA loads) are still in flight; also drains
-// this wave's LDS reads so the following barrier orders them against the next refill
+// wait until at most N of this wave's vector-memory operations are still in flight (the count is an immediate of the instruction)
+template <int N>
+__device__ __forceinline__ void vm_wait() {
+    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// the same for the LDS-DMA loads of a ring; also drains this wave's LDS reads so the following barrier orders them against the next refill
 template <int N>
 __device__ __forceinline__ void dma_wait() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
-    else static_assert(N == 0, "unsupported DMA count");
+    static_assert(N == 0 || N == 2 || N == 3 || N == 4 || N == 5 || N == 6 || N == 8 || N == 9 || N == 10 || N == 12, "DMA piece counts of the rings in use");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
 }
-
 
 // XCD-aware block -> tile map.  Blocks are dealt round-robin to the 8 XCDs (b % 8 labels the XCD group); each group
 // walks 64-tile "super-tiles" of SM x SN tiles so the 64 blocks resident on one XCD share SM A panels and SN B panels

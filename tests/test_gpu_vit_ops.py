@@ -67,6 +67,35 @@ def test_linear_fwd_dgrad_wgrad(V, rows, K, N):
         np.testing.assert_allclose(db.cpu().numpy(), dpre.float().sum(0).numpy(), rtol=1e-4, atol=1e-3)
 
 
+@pytest.fixture(scope="module")
+def wide_wgrad_case(V):
+    """rows = 16400, K = 2056, N = 1608 on small integers (x in [-2, 2], dy at density 0.5), with torch's own fp32 products as the reference: every
+    partial sum is an integer of magnitude <= 16400 * 4 < 2^24, exact in fp32 in any order."""
+    rows, K, N = 16400, 2056, 1608
+    g = torch.Generator().manual_seed(rows + K + N)
+    x = torch.randint(-2, 3, (rows, K), generator=g).float()
+    dy = torch.randint(-2, 3, (rows, N), generator=g).float() * (torch.rand((rows, N), generator=g) < 0.5).float()
+    xc, dyc = x.cuda(), dy.cuda()
+    return xc.to(bf16), dyc.to(bf16), dyc.t() @ xc, dyc.sum(0)
+
+
+@pytest.mark.parametrize("want_bias", [True, False])
+def test_linear_wgrad_two_workgroup_kernel_exact_integers(V, wide_wgrad_case, want_bias):
+    """117 output tiles of 128 x 256 (13 x 9, both dimensions ragged) are more than the pipelined kernel takes: the plain 8-wave 128 x 256
+    weight-gradient kernel (igemm_wgrad_wg_kernel<2, 4, 3>), with and without the column sums that its nine n tiles share round-robin; the last
+    split ends in a half-filled k-step."""
+    # (wgrad_plan: 512 places / 117 tiles -> 4 splits of 4128 pixels, the last one 16400 - 3 * 4128 = 4016 = 125.5 k-steps of 32)
+    x, dy, ref_dw, ref_db = wide_wgrad_case
+    out = V.linear_wgrad(x, dy, want_bias=want_bias)
+    again = V.linear_wgrad(x, dy, want_bias=want_bias)
+    dw, dw2 = (out[0], again[0]) if want_bias else (out, again)
+    assert torch.equal(dw, ref_dw), (dw - ref_dw).abs().max()
+    assert torch.equal(dw, dw2)                                   # bit-reproducible
+    if want_bias:
+        assert torch.equal(out[1], ref_db), (out[1] - ref_db).abs().max()
+        assert torch.equal(out[1], again[1])
+
+
 def test_linear_256x320_tile_bit_exact_on_integers(V):
     """Small integers: every product and fp32 partial sum is exact, so the 256 x 320 kernel (k-tile 64, ragged DMA pieces, transpose-staged
     store) must equal the fp32 matmul bit for bit, bias and residual included -- interior tiles and the ragged last one."""
