@@ -80,9 +80,14 @@ _SIGNATURES = {
     "dali_vit_patchify": [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
     "dali_vit_assemble_tokens": [c_void_p] * 5 + [c_int] * 3 + [c_void_p],
     "dali_vit_assemble_tokens_bwd": [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 3,
+    "dali_vit_assemble_tokens_sie": [c_void_p] * 7 + [c_int, c_float] + [c_int] * 3 + [c_void_p],
+    "dali_vit_sie_grad": [c_void_p] * 4 + [c_int] * 4 + [c_float, c_void_p],
+    "dali_vit_jpm_gather": [c_void_p] * 4 + [c_int] * 5 + [c_void_p],
+    "dali_vit_jpm_head": [c_void_p] * 8 + [c_int] * 3 + [c_void_p],
     "dali_layernorm_fwd": [c_void_p] * 5 + [c_int, c_int, c_float] + [c_void_p] * 3,
     "dali_layernorm_bwd": [c_void_p] * 8 + [c_int, c_int] + [c_void_p] * 3,
     "dali_attention_fwd": [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p],
+    "dali_attention_fwd_short": [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p],
     "dali_attention_bwd": [c_void_p] * 6 + [c_int] * 4 + [c_float, c_void_p],
     "dali_center_loss_fwd": [c_void_p] * 6 + [c_float, c_int, c_int, c_void_p, c_void_p],
     "dali_center_loss_bwd": [c_void_p] * 6 + [c_float, c_int, c_int, c_void_p, c_float, c_void_p],
@@ -116,12 +121,14 @@ _SIGNATURES = {
     "dali_resnet_backward": [c_void_p, c_void_p, c_void_p, c_int, c_int],
     "dali_resnet_debug_tensor": [c_void_p, ctypes.c_char_p, c_void_p, c_void_p],
     "dali_vit_create": [c_void_p, c_void_p, ctypes.POINTER(c_void_p)],
+    "dali_vit_create_ex": [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p)],
     "dali_vit_destroy": [c_void_p],
     "dali_vit_sizes": [c_void_p] + [c_void_p] * 6,
     "dali_vit_tensor_info": [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "dali_vit_bind": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t],
     "dali_vit_refresh_weights": [c_void_p, c_void_p],
     "dali_vit_forward": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "dali_vit_forward_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "dali_vit_backward": [c_void_p, c_void_p, c_void_p],
     "dali_vit_num_stages": [c_void_p],
     "dali_vit_stage_param_range": [c_void_p, c_int, c_void_p, c_void_p],

@@ -193,6 +193,16 @@ int launch_rowscale_add(hipStream_t st, const uint16_t* branch, const float* sca
                         uint16_t* out);
 int launch_expand_rowscale(hipStream_t st, const float* scale, int n_vec, int B, int T, float* out);
 int launch_attention_fwd(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse);
+// T <= 64 (the JPM local sequences): the 4-tile instance of the forward kernel
+int launch_attention_fwd_short(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse);
+// SIE / JPM (vit_pytorch.py:316-331, 382-396; make_models.py:221-377)
+int launch_assemble_tokens_sie(hipStream_t st, const uint16_t* pe, const float* cls, const float* pos, const float* sie, const int32_t* idx, int n_sie,
+                               float coef, int B, int T, int C, uint16_t* x);
+int launch_sie_grad(hipStream_t st, const uint16_t* dx, const int32_t* idx, int B, int T, int C, int n_sie, float coef, float* dsie);
+int launch_jpm_gather(hipStream_t st, const uint16_t* feat, const int32_t* map, int B, int T, int C, int G, int L, uint16_t* out);
+struct JpmNecks { const float *gamma[5], *beta[5], *rm[5], *rv[5]; };       // bottleneck, bottleneck_1 .. _4
+int launch_jpm_head(hipStream_t st, const float* glob, const float* loc, const JpmNecks& nk, int B, int C, int after, float eps, float* out);
+int launch_tokens_f32(hipStream_t st, const uint16_t* x, size_t elems, float* y);
 int launch_attention_bwd(hipStream_t st, const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, int B, int T, int H,
                          float scale, uint16_t* dqkv);
 

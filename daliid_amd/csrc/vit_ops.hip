@@ -335,6 +335,117 @@ __global__ __launch_bounds__(256) void expand_rowscale_kernel(const float* __res
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) out[i] = scale[i / T];
 }
 
+// ------------------------------------------------------------------------------------------------
+// SIE (side information embeddings, vit_pytorch.py:316-331, 382-387): one learned vector per camera and / or view, added to every token of
+// the sample.  x[b,t,:] = (tok + pos[t]) + coef * sie[idx[b]] in fp32, in the reference's order, rounded once to bf16.  An idx[b] outside
+// [0, n_sie) is never dereferenced and adds nothing (the Python side validates the labels on the host).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void assemble_tokens_sie_kernel(const uint16_t* __restrict__ pe, const float* __restrict__ cls,
+                                                                   const float* __restrict__ pos, const float* __restrict__ sie,
+                                                                   const int32_t* __restrict__ idx, int n_sie, float coef, int B, int T, int C,
+                                                                   uint16_t* __restrict__ x) {
+    const int cpr = C >> 3;
+    const size_t total = (size_t)B * T * cpr;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % cpr) * 8;
+        const size_t row = i / cpr;
+        const int t = (int)(row % T), b = (int)(row / T);
+        float v[8];
+        if (t == 0) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = cls[c + q];
+        } else {
+            unpack8v(*reinterpret_cast<const uint4*>(pe + ((size_t)b * (T - 1) + t - 1) * C + c), v);
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] += pos[(size_t)t * C + c + q];
+        const int si = idx[b];
+        if (si >= 0 && si < n_sie) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] += coef * sie[(size_t)si * C + c + q];
+        }
+        *reinterpret_cast<uint4*>(x + row * C + c) = pack8v(v);
+    }
+}
+// dsie[i][c] = coef * sum over the samples b with idx[b] == i and their tokens t of dx[b,t,c], fp32.  One workgroup per (embedding row,
+// 64-channel block): thread (slice, chunk) walks the matching samples in ascending b and the tokens t = slice, slice + 32, ...; the 32 slices
+// are then summed in ascending order through LDS.  No atomics: the order is fixed, a row no sample uses gets exactly 0.
+__global__ __launch_bounds__(256) void sie_grad_kernel(const uint16_t* __restrict__ dx, const int32_t* __restrict__ idx, int B, int T, int C,
+                                                        float coef, float* __restrict__ dsie) {
+    __shared__ float red[32][64];
+    const int i = blockIdx.x, sub = threadIdx.x & 7, slice = threadIdx.x >> 3;
+    const int c = (blockIdx.y * 8 + sub) * 8;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c < C) {
+        for (int b = 0; b < B; ++b) {
+            if (idx[b] != i) continue;
+            for (int t = slice; t < T; t += 32) {
+                float v[8];
+                unpack8v(*reinterpret_cast<const uint4*>(dx + ((size_t)b * T + t) * C + c), v);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc[q] += v[q];
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) red[slice][sub * 8 + q] = acc[q];
+    __syncthreads();
+    const int co = blockIdx.y * 64 + threadIdx.x;
+    if (threadIdx.x < 64 && co < C) {
+        float s = 0.f;
+        for (int r = 0; r < 32; ++r) s += red[r][threadIdx.x];
+        dsie[(size_t)i * C + co] = coef * s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// JPM (jigsaw patch module, make_models.py:314-349): the local branch's G sequences of every sample, out [G*B][1+L][C] (sequence g*B + b):
+// row 0 = the sample's cls token (features[b,0]), row 1+j = features[b, map[g][j]].  map [G][L] int32 holds TOKEN indices (1 .. T-1), computed
+// once on the host (shift + group shuffle, shuffle_unit make_models.py:8-25); an index outside [0, T) writes zeros.  16 bytes per lane.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void jpm_gather_kernel(const uint16_t* __restrict__ feat, const int32_t* __restrict__ map, int B, int T, int C,
+                                                          int G, int L, uint16_t* __restrict__ out) {
+    const int cpr = C >> 3;
+    const size_t total = (size_t)G * B * (1 + L) * cpr;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int ch = (int)(i % cpr);
+        const size_t row = i / cpr;
+        const int r = (int)(row % (1 + L));
+        const size_t seq = row / (1 + L);
+        const int b = (int)(seq % B), g = (int)(seq / B);
+        const int tok = r == 0 ? 0 : map[(size_t)g * L + r - 1];
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (tok >= 0 && tok < T) v = *reinterpret_cast<const uint4*>(feat + ((size_t)b * T + tok) * C + ch * 8);
+        *reinterpret_cast<uint4*>(out + i * 8) = v;
+    }
+}
+// The JPM eval output (make_models.py:351-377): out [B][5C] = cat(global, local_1 / 4, .., local_4 / 4), each branch through its own
+// BatchNorm1d by running statistics when `after` (TEST.NECK_FEAT == 'after'), raw otherwise.  glob [B][C], loc [4*B][C] (sequence g*B + b), fp32.
+// The neck arithmetic is bn1d_fwd_kernel's (x * scale + shift): the global slice is bitwise what the plain net's neck returns.
+__global__ __launch_bounds__(256) void jpm_head_kernel(const float* __restrict__ glob, const float* __restrict__ loc, JpmNecks nk, int B, int C,
+                                                        int after, float eps, float* __restrict__ out) {
+    const size_t total = (size_t)B * 5 * C;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const int c = (int)(e % C), br = (int)((e / C) % 5), b = (int)(e / ((size_t)5 * C));
+        float x = br == 0 ? glob[(size_t)b * C + c] : loc[((size_t)(br - 1) * B + b) * C + c];
+        if (after) {
+            const float invstd = 1.0f / sqrtf(nk.rv[br][c] + eps);
+            const float sc = nk.gamma[br][c] * invstd, sh = nk.beta[br][c] - nk.rm[br][c] * sc;
+            x = x * sc + sh;
+        }
+        out[e] = br == 0 ? x : x * 0.25f;
+    }
+}
+// tokens bf16 -> fp32 (the local_feature tokens handed back to the caller)
+__global__ __launch_bounds__(256) void tokens_f32_kernel(const uint16_t* __restrict__ x, size_t chunks, float* __restrict__ y) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (size_t)gridDim.x * 256) {
+        float v[8];
+        unpack8v(*reinterpret_cast<const uint4*>(x + i * 8), v);
+        *reinterpret_cast<float4*>(y + i * 8) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(y + i * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    }
+}
+
 static inline int vgrid(size_t items, int cap = 16384) {
     size_t b = (items + 255) / 256;
     if (b > (size_t)cap) b = cap;
@@ -355,6 +466,32 @@ int launch_assemble_tokens(hipStream_t st, const uint16_t* pe, const float* cls,
 }
 int launch_assemble_tokens_bwd(hipStream_t st, const uint16_t* dx, int B, int T, int C, float* dpos, float* dcls, uint16_t* dpe) {
     hipLaunchKernelGGL(assemble_tokens_bwd_kernel, dim3((T * (C / 8) + 255) / 256), dim3(256), 0, st, dx, B, T, C, dpos, dcls, dpe);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+int launch_assemble_tokens_sie(hipStream_t st, const uint16_t* pe, const float* cls, const float* pos, const float* sie, const int32_t* idx, int n_sie,
+                               float coef, int B, int T, int C, uint16_t* x) {
+    hipLaunchKernelGGL(assemble_tokens_sie_kernel, dim3(vgrid((size_t)B * T * (C / 8))), dim3(256), 0, st, pe, cls, pos, sie, idx, n_sie, coef, B, T, C, x);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+int launch_sie_grad(hipStream_t st, const uint16_t* dx, const int32_t* idx, int B, int T, int C, int n_sie, float coef, float* dsie) {
+    hipLaunchKernelGGL(sie_grad_kernel, dim3(n_sie, (C + 63) / 64), dim3(256), 0, st, dx, idx, B, T, C, coef, dsie);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+int launch_jpm_gather(hipStream_t st, const uint16_t* feat, const int32_t* map, int B, int T, int C, int G, int L, uint16_t* out) {
+    hipLaunchKernelGGL(jpm_gather_kernel, dim3(vgrid((size_t)G * B * (1 + L) * (C / 8))), dim3(256), 0, st, feat, map, B, T, C, G, L, out);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+int launch_jpm_head(hipStream_t st, const float* glob, const float* loc, const JpmNecks& nk, int B, int C, int after, float eps, float* out) {
+    hipLaunchKernelGGL(jpm_head_kernel, dim3(vgrid((size_t)B * 5 * C, 4096)), dim3(256), 0, st, glob, loc, nk, B, C, after, eps, out);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+int launch_tokens_f32(hipStream_t st, const uint16_t* x, size_t elems, float* y) {
+    hipLaunchKernelGGL(tokens_f32_kernel, dim3(vgrid(elems / 8, 4096)), dim3(256), 0, st, x, elems / 8, y);
     DALI_LAUNCH_CHECK();
     return DALI_OK;
 }
@@ -727,6 +864,14 @@ int launch_attention_fwd(hipStream_t st, const uint16_t* qkv, int B, int T, int 
     set_error("attention: %d tokens exceed the limit of %d", T, ATT_MAX_T);
     return DALI_ERR_LIMIT;
 }
+// The JPM local branch runs 4 B sequences of 1 + L tokens (33 at 256x128 / stride 16, 53 at stride 12, 50 at 224x224): a 4-tile instance of the
+// same kernel, four waves, 16 tile pairs per head where the 13-tile instance walks 169.  launch_attention_fwd's routing is unchanged.
+constexpr int ATT_SHORT_T = 64;
+int launch_attention_fwd_short(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse) {
+    if (T <= ATT_SHORT_T) return att2_fwd_launch<4, 4>(st, qkv, B, T, H, scale, out, lse);
+    set_error("attention (short): %d tokens exceed the limit of %d", T, ATT_SHORT_T);
+    return DALI_ERR_LIMIT;
+}
 int launch_attention_bwd(hipStream_t st, const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, int B, int T, int H,
                          float scale, uint16_t* dqkv) {
     if (T <= 208) return att2_bwd_launch<13, 7>(st, qkv, o, d_o, lse, B, T, H, scale, dqkv);
@@ -756,6 +901,33 @@ extern "C" int dali_vit_assemble_tokens_bwd(dali_ctx* ctx, void* stream, const u
     DALI_REQUIRE(ctx && dx && dpos && dcls && C % 8 == 0, "dali_vit_assemble_tokens_bwd: bad argument");
     return launch_assemble_tokens_bwd((hipStream_t)stream, dx, B, T, C, dpos, dcls, dpatch_emb);
 }
+extern "C" int dali_vit_assemble_tokens_sie(dali_ctx* ctx, void* stream, const uint16_t* patch_emb, const float* cls, const float* pos, const float* sie,
+                                            const int32_t* idx, int n_sie, float coef, int B, int T, int C, uint16_t* x) {
+    DALI_REQUIRE(ctx && patch_emb && cls && pos && sie && idx && x && C % 8 == 0 && n_sie > 0 && B > 0 && T > 1, "dali_vit_assemble_tokens_sie: bad argument");
+    return launch_assemble_tokens_sie((hipStream_t)stream, patch_emb, cls, pos, sie, idx, n_sie, coef, B, T, C, x);
+}
+extern "C" int dali_vit_sie_grad(dali_ctx* ctx, void* stream, const uint16_t* dx, const int32_t* idx, int B, int T, int C, int n_sie, float coef,
+                                 float* dsie) {
+    DALI_REQUIRE(ctx && dx && idx && dsie && C % 8 == 0 && n_sie > 0 && B > 0 && T > 0, "dali_vit_sie_grad: bad argument");
+    return launch_sie_grad((hipStream_t)stream, dx, idx, B, T, C, n_sie, coef, dsie);
+}
+extern "C" int dali_vit_jpm_gather(dali_ctx* ctx, void* stream, const uint16_t* features, const int32_t* map, int B, int T, int C, int G, int L,
+                                   uint16_t* out) {
+    DALI_REQUIRE(ctx && features && map && out && B > 0 && T > 0 && G > 0 && L > 0, "dali_vit_jpm_gather: bad argument");
+    DALI_REQUIRE(C > 0 && C % 8 == 0, "dali_vit_jpm_gather: C must be a multiple of 8 (C=%d)", C);
+    return launch_jpm_gather((hipStream_t)stream, features, map, B, T, C, G, L, out);
+}
+extern "C" int dali_vit_jpm_head(dali_ctx* ctx, void* stream, const float* global_feat, const float* local_feat, const float* gamma, const float* beta,
+                                 const float* running_mean, const float* running_var, int B, int C, int after, float* out) {
+    DALI_REQUIRE(ctx && global_feat && local_feat && out && B > 0 && C > 0, "dali_vit_jpm_head: bad argument");
+    DALI_REQUIRE(!after || (gamma && beta && running_mean && running_var), "dali_vit_jpm_head: the 'after' flavour needs the five necks' [5][C] parameters");
+    JpmNecks nk{};
+    for (int i = 0; i < 5 && after; ++i) {
+        nk.gamma[i] = gamma + (size_t)i * C; nk.beta[i] = beta + (size_t)i * C;
+        nk.rm[i] = running_mean + (size_t)i * C; nk.rv[i] = running_var + (size_t)i * C;
+    }
+    return launch_jpm_head((hipStream_t)stream, global_feat, local_feat, nk, B, C, after, 1e-5f, out);
+}
 extern "C" int dali_layernorm_fwd(dali_ctx* ctx, void* stream, const uint16_t* x, const float* gamma, const float* beta, int rows, int C,
                                   float eps, uint16_t* y, float* mean, float* rstd) {
     DALI_REQUIRE(ctx && x && gamma && beta && y && mean && rstd, "dali_layernorm_fwd: null argument");
@@ -777,6 +949,12 @@ extern "C" int dali_attention_fwd(dali_ctx* ctx, void* stream, const uint16_t* q
     DALI_REQUIRE(ctx && qkv && out, "dali_attention_fwd: null argument");
     DALI_REQUIRE(head_dim == ATT_HD && T > 0 && T <= ATT_MAX_T, "dali_attention_fwd: head_dim must be %d and T <= %d (got %d, %d)", ATT_HD, ATT_MAX_T, head_dim, T);
     return launch_attention_fwd((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
+}
+extern "C" int dali_attention_fwd_short(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
+                                        uint16_t* out, float* lse) {
+    DALI_REQUIRE(ctx && qkv && out, "dali_attention_fwd_short: null argument");
+    DALI_REQUIRE(head_dim == ATT_HD && T > 0 && T <= ATT_SHORT_T, "dali_attention_fwd_short: head_dim must be %d and T <= %d (got %d, %d)", ATT_HD, ATT_SHORT_T, head_dim, T);
+    return launch_attention_fwd_short((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
 }
 extern "C" int dali_attention_bwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out, const float* lse,
                                   int B, int T, int H, int head_dim, float scale, uint16_t* dqkv) {

@@ -6,6 +6,13 @@
 // buffers and one byte arena.  Parameter names / order follow the reference state_dict ("base.cls_token",
 // "base.pos_embed", "base.patch_embed.proj.weight", "base.blocks.N....", "base.norm.*", "base.fc.*", "bottleneck.*").
 // `base.fc` (vit_pytorch.py:349) is never used by forward(): it is carried as parameters with zero gradient.
+// dali_vit_ext adds what a TransReID checkpoint normally contains (dali_vit_create_ex; all zero = the plan above, byte for byte):
+//   SIE (vit_pytorch.py:316-331, 382-387): "base.sie_embed" [n_sie,1,C] right after pos_embed, added to every token as coef * sie[idx[b]];
+//   local_feature (vit_pytorch.py:393-396): blocks[:-1] only, all tokens, no final norm; blocks[depth-1], norm and fc stay as unused parameters;
+//   JPM (make_models.build_transformer_local, make_models.py:221-377), eval mode only: b1 / b2 = block + norm copies, the shifted and
+//   shuffled patch tokens cut into four runs that share b2, five BatchNorm1d necks, output [B][5C].
+// A local_feature / JPM plan never runs a backward, so it reserves none of the backward's buffers (dgrad weight images, weight-gradient slab,
+// reduction partials, DropPath rows, gradient buffers) and its refresh_weights only casts.
 #include "kernels.h"
 #include <cstdio>
 #include <new>
@@ -23,6 +30,7 @@ struct VBlock {
     uint16_t *x_in, *h1, *qkv_o, *att, *x_mid, *h2, *pre1, *act1, *x_out;
     float* lse;
 };
+struct Neck { int64_t g, b, rm, rv; };
 struct VArena { size_t used = 0; size_t take(size_t b) { size_t o = used; used = align_up(used + b, 256); return o; } };
 }  // namespace
 
@@ -47,6 +55,17 @@ struct dali_vit {
     bool fwd_training = false;
     const float* dp_scale = nullptr;      // device [2*depth][B]: row 2i = attention branch of block i, 2i+1 = its MLP branch; null = no DropPath
     const float* dp_used = nullptr;       // what the last training forward applied (the backward mirrors it)
+    // ---- SIE / local_feature / JPM (dali_vit_ext) ----
+    dali_vit_ext ext{};
+    int64_t sie_off = -1;
+    const int32_t* sie_used = nullptr;    // the indices of the last training forward (the backward's sie_grad reads them)
+    int L = 0, Tl = 0, rows2 = 0;         // JPM: tokens per run, 1 + L, and the local branch's row count divide * B * Tl
+    VBlock b1, b2; Ln fin1, fin2;
+    Neck necks[5];                        // bottleneck, bottleneck_1 .. _4 (necks[0] = neck_g .. neck_rv)
+    std::vector<int32_t> map_host;        // [divide][L] token indices, copied from dali_vit_ext::token_map
+    int32_t* map_dev = nullptr;
+    uint16_t *jseq = nullptr, *cls2 = nullptr;
+    float *gf2 = nullptr, *fin2_mean = nullptr, *fin2_rstd = nullptr;
     int n_stages = 1;
     std::vector<int> stage_first_block;   // backward stage s runs blocks [stage_first_block[s+1], stage_first_block[s]) downwards
 };
@@ -71,45 +90,77 @@ void add_ln(dali_vit* n, Ln& l, const std::string& name, int C) {
     l.g_off = addt(n->params, n->param_elems, name + ".weight", {C});
     l.b_off = addt(n->params, n->param_elems, name + ".bias", {C});
 }
+void add_block(dali_vit* n, VBlock& b, const std::string& pre) {
+    const int C = n->C;
+    add_ln(n, b.n1, pre + ".norm1", C);
+    add_lin(n, b.qkv, pre + ".attn.qkv", C, 3 * C);
+    add_lin(n, b.proj, pre + ".attn.proj", C, C);
+    add_ln(n, b.n2, pre + ".norm2", C);
+    add_lin(n, b.fc1, pre + ".mlp.fc1", C, n->cfg.mlp_hidden);
+    add_lin(n, b.fc2, pre + ".mlp.fc2", n->cfg.mlp_hidden, C);
+}
 template <class T> void rsv(dali_vit* n, VArena& a, T*& p, size_t bytes) { n->fixups.emplace_back(reinterpret_cast<void**>(&p), a.take(bytes)); }
 }  // namespace
 
 extern "C" int dali_vit_create(dali_ctx* ctx, const dali_vit_cfg* cfg, dali_vit** out) {
-    DALI_REQUIRE(ctx && cfg && out, "dali_vit_create: null argument");
+    const dali_vit_ext none{};
+    return dali_vit_create_ex(ctx, cfg, &none, out);
+}
+
+extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const dali_vit_ext* ext, dali_vit** out) {
+    DALI_REQUIRE(ctx && cfg && ext && out, "dali_vit_create: null argument");
     DALI_REQUIRE(cfg->batch > 0 && cfg->patch % 8 == 0 && cfg->stride > 0 && cfg->height >= cfg->patch && cfg->width >= cfg->patch,
                  "dali_vit_create: bad geometry");
     DALI_REQUIRE(cfg->dim % 64 == 0 && cfg->heads * 64 == cfg->dim && cfg->dim <= 2048, "dali_vit_create: head_dim must be 64 (dim=%d heads=%d)", cfg->dim, cfg->heads);
     DALI_REQUIRE(cfg->depth >= 1 && cfg->mlp_hidden % 32 == 0 && cfg->mlp_hidden > 0, "dali_vit_create: bad depth / mlp_hidden");
     dali_vit* n = new (std::nothrow) dali_vit();
     if (!n) { set_error("dali_vit_create: out of host memory"); return DALI_ERR_NOMEM; }
-    n->ctx = ctx; n->cfg = *cfg;
+    n->ctx = ctx; n->cfg = *cfg; n->ext = *ext;
+    if (n->ext.jpm) n->ext.local_feature = 1;            // make_models.py:243: the JPM base is built with local_feature = cfg.MODEL.JPM
     const int ny = (cfg->height - cfg->patch) / cfg->stride + 1, nx = (cfg->width - cfg->patch) / cfg->stride + 1;
     n->B = cfg->batch; n->np = ny * nx; n->T = n->np + 1; n->C = cfg->dim; n->H = cfg->heads; n->rows = n->B * n->T;
     if (n->T > 256) { set_error("dali_vit_create: %d tokens exceed the attention kernel's limit of 256", n->T); delete n; return DALI_ERR_LIMIT; }
     const int C = n->C, Kp = 3 * cfg->patch * cfg->patch;
     n->cls_off = addt(n->params, n->param_elems, "base.cls_token", {1, 1, C});
     n->pos_off = addt(n->params, n->param_elems, "base.pos_embed", {1, n->T, C});
+    if (ext->n_sie < 0) { set_error("dali_vit_create: n_sie = %d", ext->n_sie); delete n; return DALI_ERR_INVALID; }
+    if (ext->n_sie > 0) n->sie_off = addt(n->params, n->param_elems, "base.sie_embed", {ext->n_sie, 1, C});      // vit_pytorch.py:316-331
     n->patch.K = Kp; n->patch.N = C;
     n->patch.w_off = addt(n->params, n->param_elems, "base.patch_embed.proj.weight", {C, 3, cfg->patch, cfg->patch});
     n->patch.b_off = addt(n->params, n->param_elems, "base.patch_embed.proj.bias", {C});
     n->blocks.resize(cfg->depth);
-    for (int i = 0; i < cfg->depth; ++i) {
-        VBlock& b = n->blocks[i];
-        const std::string pre = "base.blocks." + std::to_string(i);
-        add_ln(n, b.n1, pre + ".norm1", C);
-        add_lin(n, b.qkv, pre + ".attn.qkv", C, 3 * C);
-        add_lin(n, b.proj, pre + ".attn.proj", C, C);
-        add_ln(n, b.n2, pre + ".norm2", C);
-        add_lin(n, b.fc1, pre + ".mlp.fc1", C, cfg->mlp_hidden);
-        add_lin(n, b.fc2, pre + ".mlp.fc2", cfg->mlp_hidden, C);
-    }
+    for (int i = 0; i < cfg->depth; ++i) add_block(n, n->blocks[i], "base.blocks." + std::to_string(i));
     add_ln(n, n->fin, "base.norm", C);
     n->fcw_off = addt(n->params, n->param_elems, "base.fc.weight", {cfg->num_classes, C});
     n->fcb_off = addt(n->params, n->param_elems, "base.fc.bias", {cfg->num_classes});
-    n->neck_g = addt(n->params, n->param_elems, "bottleneck.weight", {C});
-    n->neck_b = addt(n->params, n->param_elems, "bottleneck.bias", {C});
-    n->neck_rm = addt(n->buffers, n->buffer_elems, "bottleneck.running_mean", {C});
-    n->neck_rv = addt(n->buffers, n->buffer_elems, "bottleneck.running_var", {C});
+    if (n->ext.jpm) {
+        // make_models.py:249-258, 279-288: b1 / b2 = (block, norm) copies, then the five unused classifiers, in the state dict's order
+        if (n->ext.id_classes < 1) { set_error("dali_vit_create: JPM needs id_classes >= 1 (the classifiers' rows)"); delete n; return DALI_ERR_INVALID; }
+        if (n->ext.divide != 4) { set_error("dali_vit_create: JPM needs divide = 4, the reference's forward cuts four runs (got %d)", n->ext.divide); delete n; return DALI_ERR_INVALID; }
+        // the token map (shift + group shuffle, make_models.jpm_token_map) is the caller's: [divide][L] token indices, each a patch token 1 .. np
+        n->L = n->np / n->ext.divide;
+        bool map_ok = n->ext.token_map != nullptr && n->L >= 1;
+        for (int i = 0; map_ok && i < n->ext.divide * n->L; ++i) map_ok = n->ext.token_map[i] >= 1 && n->ext.token_map[i] <= n->np;
+        if (!map_ok) {
+            set_error("dali_vit_create: JPM needs token_map [%d][%d] with entries in 1 .. %d", n->ext.divide, n->L, n->np);
+            delete n; return DALI_ERR_INVALID;
+        }
+        n->map_host.assign(n->ext.token_map, n->ext.token_map + (size_t)n->ext.divide * n->L);
+        n->ext.token_map = nullptr;                      // copied: the caller's array need not outlive this call
+        n->Tl = 1 + n->L; n->rows2 = n->ext.divide * n->B * n->Tl;
+        add_block(n, n->b1, "b1.0"); add_ln(n, n->fin1, "b1.1", C);
+        add_block(n, n->b2, "b2.0"); add_ln(n, n->fin2, "b2.1", C);
+        for (int i = 0; i < 5; ++i) addt(n->params, n->param_elems, i ? "classifier_" + std::to_string(i) + ".weight" : std::string("classifier.weight"), {n->ext.id_classes, C});
+    }
+    for (int i = 0; i < (n->ext.jpm ? 5 : 1); ++i) {
+        const std::string nm = i ? "bottleneck_" + std::to_string(i) : std::string("bottleneck");
+        Neck& k = n->necks[i];
+        k.g = addt(n->params, n->param_elems, nm + ".weight", {C});
+        k.b = addt(n->params, n->param_elems, nm + ".bias", {C});
+        k.rm = addt(n->buffers, n->buffer_elems, nm + ".running_mean", {C});
+        k.rv = addt(n->buffers, n->buffer_elems, nm + ".running_var", {C});
+    }
+    n->neck_g = n->necks[0].g; n->neck_b = n->necks[0].b; n->neck_rm = n->necks[0].rm; n->neck_rv = n->necks[0].rv;
     // backward stages = gradient buckets of the data-parallel reducer: up to 4 groups of consecutive blocks, last blocks first
     n->n_stages = cfg->depth >= 4 ? 4 : cfg->depth;
     n->stage_first_block.resize(n->n_stages + 1);
@@ -121,7 +172,8 @@ extern "C" int dali_vit_create(dali_ctx* ctx, const dali_vit_cfg* cfg, dali_vit*
     rsv(n, a, n->patches, (size_t)n->B * n->np * Kp * 2);
     rsv(n, a, n->pe, (size_t)n->B * n->np * C * 2);
     rsv(n, a, n->x0, rows * C * 2);
-    rsv(n, a, n->patch.wt, (size_t)Kp * C * 2);          // unused (images need no gradient) but keeps Lin uniform
+    const bool eval_only = n->ext.local_feature != 0;
+    if (!eval_only) rsv(n, a, n->patch.wt, (size_t)Kp * C * 2);          // unused (images need no gradient) but keeps Lin uniform
     size_t slab = linear_wgrad_slab_bytes(n->B * n->np, Kp, C);
     size_t part = std::max(layernorm_bwd_partial_floats((int)rows, C), colsum_partial_floats((int)rows, (int)std::max<size_t>(Hd, 3 * C))) * 4;
     for (auto& b : n->blocks) {
@@ -132,7 +184,7 @@ extern "C" int dali_vit_create(dali_ctx* ctx, const dali_vit_cfg* cfg, dali_vit*
         rsv(n, a, b.n1.mean, rows * 4); rsv(n, a, b.n1.rstd, rows * 4); rsv(n, a, b.n2.mean, rows * 4); rsv(n, a, b.n2.rstd, rows * 4);
         Lin* ls[4] = {&b.qkv, &b.proj, &b.fc1, &b.fc2};
         for (Lin* l : ls) {
-            rsv(n, a, l->wt, (size_t)l->K * l->N * 2);
+            if (!eval_only) rsv(n, a, l->wt, (size_t)l->K * l->N * 2);
             slab = std::max(slab, linear_wgrad_slab_bytes((int)rows, l->K, l->N));
         }
     }
@@ -140,10 +192,26 @@ extern "C" int dali_vit_create(dali_ctx* ctx, const dali_vit_cfg* cfg, dali_vit*
     rsv(n, a, n->gf, (size_t)n->B * C * 4); rsv(n, a, n->dgf, (size_t)n->B * C * 4);
     rsv(n, a, n->neck_mean, C * 4); rsv(n, a, n->neck_invstd, C * 4);
     rsv(n, a, n->fin_mean, n->B * 4); rsv(n, a, n->fin_rstd, n->B * 4);
-    rsv(n, a, n->slab, slab); rsv(n, a, n->partial, part);
-    rsv(n, a, n->dp_rows, (size_t)2 * cfg->depth * rows * 4);
+    if (!eval_only) {
+        rsv(n, a, n->slab, slab); rsv(n, a, n->partial, part);
+        rsv(n, a, n->dp_rows, (size_t)2 * cfg->depth * rows * 4);
+    }
     rsv(n, a, n->scratch, reduce_scratch_bytes((int)std::max<size_t>(Hd, 3 * C), 2));
-    for (int i = 0; i < 4; ++i) rsv(n, a, n->gbuf[i], rows * std::max<size_t>(Hd, 3 * C) * 2);
+    for (int i = 0; i < 4 && !eval_only; ++i) rsv(n, a, n->gbuf[i], rows * std::max<size_t>(Hd, 3 * C) * 2);
+    if (n->ext.jpm) {
+        // b1 runs on the B*T rows in the buffers of the idle blocks[depth-1] (bind); b2 gets its own for the divide * B sequences of 1 + L tokens
+        VBlock& b = n->b2;
+        const size_t r2 = n->rows2, seqs = (size_t)n->ext.divide * n->B;
+        rsv(n, a, n->jseq, r2 * C * 2);
+        rsv(n, a, b.h1, r2 * C * 2); rsv(n, a, b.qkv_o, r2 * 3 * C * 2); rsv(n, a, b.att, r2 * C * 2);
+        rsv(n, a, b.x_mid, r2 * C * 2); rsv(n, a, b.h2, r2 * C * 2); rsv(n, a, b.pre1, r2 * Hd * 2);
+        rsv(n, a, b.act1, r2 * Hd * 2); rsv(n, a, b.x_out, r2 * C * 2);
+        rsv(n, a, b.lse, seqs * n->H * n->Tl * 4);
+        rsv(n, a, b.n1.mean, r2 * 4); rsv(n, a, b.n1.rstd, r2 * 4); rsv(n, a, b.n2.mean, r2 * 4); rsv(n, a, b.n2.rstd, r2 * 4);
+        rsv(n, a, n->cls2, seqs * C * 2); rsv(n, a, n->gf2, seqs * C * 4);
+        rsv(n, a, n->fin2_mean, seqs * 4); rsv(n, a, n->fin2_rstd, seqs * 4);
+        rsv(n, a, n->map_dev, n->map_host.size() * 4);
+    }
     n->arena_bytes = a.used;
     *out = n;
     return DALI_OK;
@@ -157,7 +225,7 @@ extern "C" int dali_vit_sizes(const dali_vit* n, int64_t* param_elems, int64_t* 
     if (param_elems) *param_elems = n->param_elems;
     if (buffer_elems) *buffer_elems = n->buffer_elems;
     if (arena_bytes) *arena_bytes = (int64_t)n->arena_bytes;
-    if (feat_dim) *feat_dim = n->C;
+    if (feat_dim) *feat_dim = n->ext.jpm ? 5 * n->C : n->C;
     if (n_params) *n_params = (int)n->params.size();
     if (n_buffers) *n_buffers = (int)n->buffers.size();
     return DALI_OK;
@@ -179,6 +247,14 @@ extern "C" int dali_vit_bind(dali_vit* n, float* params, float* grads, float* bu
     for (auto& f : n->fixups) *f.first = n->arena + f.second;
     n->patch.w = n->wbf16 + n->patch.w_off;
     for (auto& b : n->blocks) { b.qkv.w = n->wbf16 + b.qkv.w_off; b.proj.w = n->wbf16 + b.proj.w_off; b.fc1.w = n->wbf16 + b.fc1.w_off; b.fc2.w = n->wbf16 + b.fc2.w_off; }
+    if (n->ext.jpm) {
+        const VBlock& idle = n->blocks.back();           // local_feature never runs it: b1, its copy, works in its buffers
+        VBlock& b = n->b1;
+        b.h1 = idle.h1; b.qkv_o = idle.qkv_o; b.att = idle.att; b.x_mid = idle.x_mid; b.h2 = idle.h2; b.pre1 = idle.pre1; b.act1 = idle.act1;
+        b.x_out = idle.x_out; b.lse = idle.lse;
+        b.n1.mean = idle.n1.mean; b.n1.rstd = idle.n1.rstd; b.n2.mean = idle.n2.mean; b.n2.rstd = idle.n2.rstd;
+        for (VBlock* v : {&n->b1, &n->b2}) { v->qkv.w = n->wbf16 + v->qkv.w_off; v->proj.w = n->wbf16 + v->proj.w_off; v->fc1.w = n->wbf16 + v->fc1.w_off; v->fc2.w = n->wbf16 + v->fc2.w_off; }
+    }
     return DALI_OK;
 }
 extern "C" int dali_vit_refresh_weights(dali_vit* n, void* stream) {
@@ -186,6 +262,9 @@ extern "C" int dali_vit_refresh_weights(dali_vit* n, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     int rc = launch_cast_bf16(st, n->P, (size_t)n->param_elems, n->wbf16);
     if (rc) return rc;
+    // b1 / b2 read their bf16 weights from the same image (the cast above covers them)
+    if (n->ext.jpm) DALI_HIP(hipMemcpyAsync(n->map_dev, n->map_host.data(), n->map_host.size() * 4, hipMemcpyHostToDevice, st));
+    if (n->ext.local_feature) return DALI_OK;            // eval only: no dgrad images
     std::vector<TransposeJob> jobs;                      // every linear's dgrad image [K][N], batched launches (48 single launches cost 0.3 ms)
     for (auto& b : n->blocks) {
         Lin* ls[4] = {&b.qkv, &b.proj, &b.fc1, &b.fc2};
@@ -194,34 +273,82 @@ extern "C" int dali_vit_refresh_weights(dali_vit* n, void* stream) {
     return launch_weight_transpose_batched(st, jobs.data(), (int)jobs.size());
 }
 
-extern "C" int dali_vit_forward(dali_vit* n, void* stream, const float* images, int training, float* feat, float* global_feat) {
-    DALI_REQUIRE(n && n->P && images && feat, "dali_vit_forward: null argument or net not bound");
-    hipStream_t st = (hipStream_t)stream;
-    const int C = n->C, rows = n->rows, Hd = n->cfg.mlp_hidden;
+namespace {
+// one transformer block (vit_pytorch.py:166-184) on `rows` = seqs * T token rows; dp_att / dp_mlp: DropPath factors per row or null
+int run_block(dali_vit* n, hipStream_t st, VBlock& b, const uint16_t* x, int rows, int seqs, int T, const float* dp_att, const float* dp_mlp, bool short_att) {
+    const int C = n->C, Hd = n->cfg.mlp_hidden;
     const float eps = 1e-6f, scale = 0.125f;           // head_dim 64 -> 64^-0.5
+    int rc;
+    b.x_in = const_cast<uint16_t*>(x);
+    if ((rc = launch_layernorm_fwd(st, x, n->P + b.n1.g_off, n->P + b.n1.b_off, rows, C, eps, b.h1, b.n1.mean, b.n1.rstd, nullptr))) return rc;
+    if ((rc = launch_linear_fwd(st, b.h1, b.qkv.w, n->P + b.qkv.b_off, 0, nullptr, b.qkv_o, nullptr, nullptr, rows, C, 3 * C))) return rc;
+    if ((rc = short_att ? launch_attention_fwd_short(st, b.qkv_o, seqs, T, n->H, scale, b.att, b.lse)
+                        : launch_attention_fwd(st, b.qkv_o, seqs, T, n->H, scale, b.att, b.lse))) return rc;
+    // x_mid = x + s[b] * proj(...): the per-row factor rides in the GEMM's epilogue (IGemmArgs::row_scale)
+    if ((rc = launch_linear_fwd(st, b.att, b.proj.w, n->P + b.proj.b_off, 0, x, b.x_mid, nullptr, nullptr, rows, C, C, dp_att))) return rc;
+    if ((rc = launch_layernorm_fwd(st, b.x_mid, n->P + b.n2.g_off, n->P + b.n2.b_off, rows, C, eps, b.h2, b.n2.mean, b.n2.rstd, nullptr))) return rc;
+    if ((rc = launch_linear_fwd(st, b.h2, b.fc1.w, n->P + b.fc1.b_off, 1, nullptr, b.act1, b.pre1, nullptr, rows, C, Hd))) return rc;
+    return launch_linear_fwd(st, b.act1, b.fc2.w, n->P + b.fc2.b_off, 0, b.x_mid, b.x_out, nullptr, nullptr, rows, Hd, C, dp_mlp);
+}
+}  // namespace
+
+extern "C" int dali_vit_forward(dali_vit* n, void* stream, const float* images, int training, float* feat, float* global_feat) {
+    return dali_vit_forward_ex(n, stream, images, nullptr, training, feat, global_feat, nullptr);
+}
+
+extern "C" int dali_vit_forward_ex(dali_vit* n, void* stream, const float* images, const int32_t* sie_idx, int training, float* feat, float* global_feat,
+                                   float* tokens_out) {
+    DALI_REQUIRE(n && n->P && images, "dali_vit_forward: null argument or net not bound");
+    const bool local = n->ext.local_feature != 0, jpm = n->ext.jpm != 0;
+    if (local && !jpm) {
+        // vit_pytorch.py:393-396 returns the tokens and nothing else: there is no cls feature and no neck output to write
+        DALI_REQUIRE(tokens_out && !feat && !global_feat, "dali_vit_forward: a local_feature net without JPM writes only tokens_out (feat and global_feat must be null)");
+    } else {
+        DALI_REQUIRE(feat, "dali_vit_forward: null argument or net not bound");
+    }
+    DALI_REQUIRE(!tokens_out || local, "dali_vit_forward: tokens_out needs a local_feature net");
+    DALI_REQUIRE(!(local && training), "dali_vit_forward: a local_feature / JPM net runs in eval mode only");
+    DALI_REQUIRE(n->ext.n_sie == 0 || sie_idx, "dali_vit_forward: this net has SIE embeddings and needs the per-sample indices");
+    hipStream_t st = (hipStream_t)stream;
+    const int C = n->C, rows = n->rows;
+    const float eps = 1e-6f;
     n->fwd_training = training != 0;
     int rc;
     if ((rc = launch_patchify(st, images, n->B, n->cfg.height, n->cfg.width, n->cfg.patch, n->cfg.stride, n->patches))) return rc;
     if ((rc = launch_linear_fwd(st, n->patches, n->patch.w, n->P + n->patch.b_off, 0, nullptr, n->pe, nullptr, nullptr, n->B * n->np, n->patch.K, C))) return rc;
-    if ((rc = launch_assemble_tokens(st, n->pe, n->P + n->cls_off, n->P + n->pos_off, n->B, n->T, C, n->x0))) return rc;
+    if (n->ext.n_sie > 0) {
+        if ((rc = launch_assemble_tokens_sie(st, n->pe, n->P + n->cls_off, n->P + n->pos_off, n->P + n->sie_off, sie_idx, n->ext.n_sie, n->ext.sie_coef,
+                                             n->B, n->T, C, n->x0))) return rc;
+        if (training) n->sie_used = sie_idx;
+    } else if ((rc = launch_assemble_tokens(st, n->pe, n->P + n->cls_off, n->P + n->pos_off, n->B, n->T, C, n->x0))) return rc;
     const uint16_t* x = n->x0;
     const float* dp = training ? n->dp_scale : nullptr;        // DropPath is the identity in eval mode (vit_pytorch.py:58)
     n->dp_used = dp;
     if (dp && (rc = launch_expand_rowscale(st, dp, 2 * (int)n->blocks.size(), n->B, n->T, n->dp_rows))) return rc;
-    for (int bi = 0; bi < (int)n->blocks.size(); ++bi) {
+    const int n_run = (int)n->blocks.size() - (local ? 1 : 0);          // local_feature: blocks[:-1] (vit_pytorch.py:393-396)
+    for (int bi = 0; bi < n_run; ++bi) {
         VBlock& b = n->blocks[bi];
-        b.x_in = const_cast<uint16_t*>(x);
-        if ((rc = launch_layernorm_fwd(st, x, n->P + b.n1.g_off, n->P + b.n1.b_off, rows, C, eps, b.h1, b.n1.mean, b.n1.rstd, nullptr))) return rc;
-        if ((rc = launch_linear_fwd(st, b.h1, b.qkv.w, n->P + b.qkv.b_off, 0, nullptr, b.qkv_o, nullptr, nullptr, rows, C, 3 * C))) return rc;
-        if ((rc = launch_attention_fwd(st, b.qkv_o, n->B, n->T, n->H, scale, b.att, b.lse))) return rc;
-        // x_mid = x + s[b] * proj(...): the per-row factor rides in the GEMM's epilogue (IGemmArgs::row_scale)
-        if ((rc = launch_linear_fwd(st, b.att, b.proj.w, n->P + b.proj.b_off, 0, x, b.x_mid, nullptr, nullptr, rows, C, C,
-                                    dp ? n->dp_rows + (size_t)(2 * bi) * rows : nullptr))) return rc;
-        if ((rc = launch_layernorm_fwd(st, b.x_mid, n->P + b.n2.g_off, n->P + b.n2.b_off, rows, C, eps, b.h2, b.n2.mean, b.n2.rstd, nullptr))) return rc;
-        if ((rc = launch_linear_fwd(st, b.h2, b.fc1.w, n->P + b.fc1.b_off, 1, nullptr, b.act1, b.pre1, nullptr, rows, C, Hd))) return rc;
-        if ((rc = launch_linear_fwd(st, b.act1, b.fc2.w, n->P + b.fc2.b_off, 0, b.x_mid, b.x_out, nullptr, nullptr, rows, Hd, C,
-                                    dp ? n->dp_rows + (size_t)(2 * bi + 1) * rows : nullptr))) return rc;
+        if ((rc = run_block(n, st, b, x, rows, n->B, n->T, dp ? n->dp_rows + (size_t)(2 * bi) * rows : nullptr,
+                            dp ? n->dp_rows + (size_t)(2 * bi + 1) * rows : nullptr, false))) return rc;
         x = b.x_out;
+    }
+    if (tokens_out && (rc = launch_tokens_f32(st, x, (size_t)rows * C, tokens_out))) return rc;
+    if (local && !jpm) return DALI_OK;
+    if (jpm) {
+        // global branch (make_models.py:318-320): b1 on all tokens, its norm on the cls rows only
+        if ((rc = run_block(n, st, n->b1, x, rows, n->B, n->T, nullptr, nullptr, false))) return rc;
+        DALI_HIP(hipMemcpy2DAsync(n->cls_rows, (size_t)C * 2, n->b1.x_out, (size_t)n->T * C * 2, (size_t)C * 2, n->B, hipMemcpyDeviceToDevice, st));
+        if ((rc = launch_layernorm_fwd(st, n->cls_rows, n->P + n->fin1.g_off, n->P + n->fin1.b_off, n->B, C, eps, nullptr, n->fin_mean, n->fin_rstd, n->gf))) return rc;
+        if (global_feat) DALI_HIP(hipMemcpyAsync(global_feat, n->gf, (size_t)n->B * C * 4, hipMemcpyDeviceToDevice, st));
+        // local branch (make_models.py:322-349): cls + each of the four runs of shuffled patch tokens through the shared b2
+        const int seqs = n->ext.divide * n->B;
+        if ((rc = launch_jpm_gather(st, x, n->map_dev, n->B, n->T, C, n->ext.divide, n->L, n->jseq))) return rc;
+        if ((rc = run_block(n, st, n->b2, n->jseq, n->rows2, seqs, n->Tl, nullptr, nullptr, n->Tl <= 64))) return rc;
+        DALI_HIP(hipMemcpy2DAsync(n->cls2, (size_t)C * 2, n->b2.x_out, (size_t)n->Tl * C * 2, (size_t)C * 2, seqs, hipMemcpyDeviceToDevice, st));
+        if ((rc = launch_layernorm_fwd(st, n->cls2, n->P + n->fin2.g_off, n->P + n->fin2.b_off, seqs, C, eps, nullptr, n->fin2_mean, n->fin2_rstd, n->gf2))) return rc;
+        JpmNecks nk;
+        for (int i = 0; i < 5; ++i) { nk.gamma[i] = n->P + n->necks[i].g; nk.beta[i] = n->P + n->necks[i].b; nk.rm[i] = n->Bf + n->necks[i].rm; nk.rv[i] = n->Bf + n->necks[i].rv; }
+        return launch_jpm_head(st, n->gf, n->gf2, nk, n->B, C, n->ext.neck_after, 1e-5f, feat);       // make_models.py:351-377
     }
     // final LayerNorm on the cls rows only (x[:, 0], vit_pytorch.py:401-403), then the BN neck (make_models.py:187)
     DALI_HIP(hipMemcpy2DAsync(n->cls_rows, (size_t)C * 2, x, (size_t)n->T * C * 2, (size_t)C * 2, n->B, hipMemcpyDeviceToDevice, st));
@@ -262,6 +389,7 @@ extern "C" int dali_vit_stage_param_range(const dali_vit* n, int stage, int64_t*
 
 extern "C" int dali_vit_backward_stages(dali_vit* n, void* stream, const float* d_feat, int stage_begin, int stage_end) {
     DALI_REQUIRE(n && n->P && n->G, "dali_vit_backward: null argument or net not bound");
+    DALI_REQUIRE(!n->ext.local_feature, "dali_vit_backward: a local_feature / JPM net is eval only (its train-mode forward feeds an ID loss that is out of scope)");
     DALI_REQUIRE(n->fwd_training, "dali_vit_backward: the last forward was not in training mode");
     DALI_REQUIRE(stage_begin >= 0 && stage_end < n->n_stages && stage_begin <= stage_end, "dali_vit_backward: bad stage range %d..%d", stage_begin, stage_end);
     hipStream_t st = (hipStream_t)stream;
@@ -304,6 +432,11 @@ extern "C" int dali_vit_backward_stages(dali_vit* n, void* stream, const float* 
             // tokens: d pos_embed, d cls_token, d patch embedding
             if ((rc = launch_assemble_tokens_bwd(st, dx, n->B, n->T, C, n->G + n->pos_off, n->G + n->cls_off, n->gbuf[1]))) return rc;
             if ((rc = lin_bwd(n, st, n->patch, n->patches, n->gbuf[1], nullptr, nullptr, n->B * n->np))) return rc;
+            // d sie_embed from the same dx (every token of sample b carries coef * sie[idx[b]], vit_pytorch.py:382-387)
+            if (n->ext.n_sie > 0) {
+                DALI_REQUIRE(n->sie_used != nullptr, "dali_vit_backward: no SIE indices from the last training forward");
+                if ((rc = launch_sie_grad(st, dx, n->sie_used, n->B, n->T, C, n->ext.n_sie, n->ext.sie_coef, n->G + n->sie_off))) return rc;
+            }
         }
     }
     return DALI_OK;

@@ -55,9 +55,11 @@ def get_image_loader():
 
 
 def extractFeatures(subset, img_height, img_width, model, batch_size, gpu_index=0, dataset=None, turbulance_dir_path=None,
-                    turb_strength=None, keep_on_device=False, verbose=True):
+                    turb_strength=None, keep_on_device=False, verbose=True, cam_labels=None, view_labels=None):
     """-> fp32 [N, D] features in dataset order; on the CPU like the reference (getFeatures.py:62) unless
-    ``keep_on_device`` (the in-tree callers keep them on the GPU and skip the D2H/H2D round trip)."""
+    ``keep_on_device`` (the in-tree callers keep them on the GPU and skip the D2H/H2D round trip).
+    ``cam_labels`` / ``view_labels``: integer arrays aligned with ``subset`` for a model with SIE embeddings (make_models.py:184-185); each
+    batch's slice is handed to the model as ``cam_label`` / ``view_label``."""
     model.eval()
     dev = torch.device("cuda", gpu_index)
     paths = [row[0] for row in subset]
@@ -65,6 +67,15 @@ def extractFeatures(subset, img_height, img_width, model, batch_size, gpu_index=
     chunks = []
     turb = None if not turbulance_dir_path else (turbulance_dir_path, turb_strength, dataset)
     starts = list(range(0, len(paths), batch_size))
+    side = {}
+    if cam_labels is not None:
+        side["cam_label"] = np.asarray(cam_labels).reshape(-1)
+    if view_labels is not None:
+        side["view_label"] = np.asarray(view_labels).reshape(-1)
+    for k, v in side.items():
+        if len(v) != len(paths):
+            raise ValueError("%ss must have one entry per row of subset (%d != %d)" % (k, len(v), len(paths)))
+    labels = lambda b: {k: v[b:b + batch_size] for k, v in side.items()}
     batched = all(hasattr(_loader, a) for a in ("plan", "submit", "finish"))        # transforms.gpu_eval_loader: decode pool + one launch per batch
     with torch.no_grad():
         if batched:
@@ -74,11 +85,11 @@ def extractFeatures(subset, img_height, img_width, model, batch_size, gpu_index=
                 if i + 1 < len(starts):
                     b = starts[i + 1]
                     ahead.append(_loader.submit(_loader.plan(paths[b:b + batch_size], img_height, img_width, turb)))
-                chunks.append(model(_loader.finish(ahead.pop(0), dev)))
+                chunks.append(model(_loader.finish(ahead.pop(0), dev), **labels(starts[i])))
         else:
             for b in starts:
                 batch = _loader(paths[b:b + batch_size], img_height, img_width, turb)
-                chunks.append(model(batch.to(dev, non_blocking=True)))
+                chunks.append(model(batch.to(dev, non_blocking=True), **labels(b)))
     fvs = torch.cat(chunks, 0) if chunks else torch.empty(0, 0, device=dev)
     if not keep_on_device:
         fvs = fvs.cpu()

@@ -113,3 +113,55 @@ def attention_bwd(qkv, out, d_out, lse, B, T, H, scale=None):
                                               _lib.ptr(d_out, bf16), _lib.ptr(lse, torch.float32), B, T, H, hd, float(scale), _lib.ptr(dqkv)),
                "dali_attention_bwd")
     return dqkv
+
+
+def assemble_tokens_sie(pe, cls, pos, sie, idx, coef, B, T):
+    """x[b,t] = (tok + pos[t]) + coef * sie[idx[b]] (vit_pytorch.py:382-387); sie fp32 [n_sie, C], idx int32 [B]."""
+    C = pe.shape[1]
+    x = torch.empty(B * T, C, device=pe.device, dtype=bf16)
+    _lib.check(_lib.lib().dali_vit_assemble_tokens_sie(_lib.ctx(pe.device), _lib.stream_ptr(), _lib.ptr(pe, bf16), _lib.ptr(cls, torch.float32),
+                                                        _lib.ptr(pos, torch.float32), _lib.ptr(sie, torch.float32), _lib.ptr(idx, torch.int32),
+                                                        sie.shape[0], float(coef), B, T, C, _lib.ptr(x)), "dali_vit_assemble_tokens_sie")
+    return x
+
+
+def sie_grad(dx, idx, n_sie, coef, B, T):
+    """dsie [n_sie, C] fp32 = coef * sum of dx over the tokens of the samples that use each row; fixed order."""
+    C = dx.shape[1]
+    dsie = torch.empty(n_sie, C, device=dx.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dali_vit_sie_grad(_lib.ctx(dx.device), _lib.stream_ptr(), _lib.ptr(dx, bf16), _lib.ptr(idx, torch.int32), B, T, C, n_sie,
+                                             float(coef), _lib.ptr(dsie)), "dali_vit_sie_grad")
+    return dsie
+
+
+def jpm_gather(features, token_map, B, T):
+    """features bf16 [B*T, C], token_map int32 [G, L] (device) -> [G*B*(1+L), C]: sequence g*B + b = cls of b, then features[b, token_map[g]]."""
+    C = features.shape[1]
+    G, L = token_map.shape
+    out = torch.empty(G * B * (1 + L), C, device=features.device, dtype=bf16)
+    _lib.check(_lib.lib().dali_vit_jpm_gather(_lib.ctx(features.device), _lib.stream_ptr(), _lib.ptr(features, bf16), _lib.ptr(token_map, torch.int32),
+                                               B, T, C, G, L, _lib.ptr(out)), "dali_vit_jpm_gather")
+    return out
+
+
+def attention_fwd_short(qkv, B, T, H, scale=None):
+    """attention_fwd for T <= 64 (the JPM local sequences)."""
+    hd = qkv.shape[1] // (3 * H)
+    scale = hd ** -0.5 if scale is None else scale
+    out = torch.empty(B * T, H * hd, device=qkv.device, dtype=bf16)
+    lse = torch.empty(B * H, T, device=qkv.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dali_attention_fwd_short(_lib.ctx(qkv.device), _lib.stream_ptr(), _lib.ptr(qkv, bf16, "qkv"), B, T, H, hd, float(scale),
+                                                    _lib.ptr(out), _lib.ptr(lse)), "dali_attention_fwd_short")
+    return out, lse
+
+
+def jpm_head(glob, loc, necks=None):
+    """glob fp32 [B, C], loc fp32 [4*B, C] -> [B, 5C] (make_models.py:351-377).  necks = (gamma, beta, running_mean, running_var), each fp32
+    [5, C]: the 'after' flavour; None: the raw features ('before')."""
+    B, C = glob.shape
+    out = torch.empty(B, 5 * C, device=glob.device, dtype=torch.float32)
+    g, b, rm, rv = necks if necks is not None else (None, None, None, None)
+    _lib.check(_lib.lib().dali_vit_jpm_head(_lib.ctx(glob.device), _lib.stream_ptr(), _lib.ptr(glob, torch.float32), _lib.ptr(loc, torch.float32),
+                                             _lib.ptr(g, torch.float32), _lib.ptr(b, torch.float32), _lib.ptr(rm, torch.float32),
+                                             _lib.ptr(rv, torch.float32), B, C, int(necks is not None), _lib.ptr(out)), "dali_vit_jpm_head")
+    return out

@@ -13,6 +13,7 @@ class validateModels:
 
     precision = "bf16x3"          # "bf16" trades ~1e-4 absolute distance error for ~2x distance throughput
     distmat_on_cpu = False        # the reference returns a CPU tensor (validateModels.py:58); 4 GB at config-5 size
+    cam_label_of = view_label_of = None      # setSIE
 
     def setParameters(self, img_height, img_width, rerank, gpu_index):
         self.img_height = img_height
@@ -20,10 +21,23 @@ class validateModels:
         self.rerank = rerank
         self.gpu_index = gpu_index
 
+    def setSIE(self, cam_label_of=None, view_label_of=None):
+        """For a model with SIE embeddings: callables from a subset (the rows handed to ``validate`` / ``validate_sharded`` / ``retrieve``) to the integer camera /
+        view label of every row.  Without this call nothing changes."""
+        self.cam_label_of, self.view_label_of = cam_label_of, view_label_of
+
+    def _features(self, subset, model):
+        side = {}
+        if self.cam_label_of is not None:
+            side["cam_labels"] = self.cam_label_of(subset)
+        if self.view_label_of is not None:
+            side["view_labels"] = self.view_label_of(subset)
+        return extractFeatures(subset, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True, **side)
+
     def validate(self, queries, gallery, model):
         model.eval()
-        queries_fvs = extractFeatures(queries, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
-        gallery_fvs = extractFeatures(gallery, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
+        queries_fvs = self._features(queries, model)
+        gallery_fvs = self._features(gallery, model)
         distmat = self.distance(queries_fvs, gallery_fvs)
         if getattr(self, "rerank", False):
             # validateModels.py:49-53 (commented out in the reference): every block is the same cosine distance, so the three agree
@@ -57,9 +71,9 @@ class validateModels:
             raise _lib.DaliError("validate_sharded: BatchNorm running statistics differ between ranks "
                                  "(call parallel.sync_buffers_from_rank0 or load the same checkpoint on every rank)")
         lo, hi = ops_eval.shard_bounds(len(gallery), world)[rank:rank + 2]
-        queries_fvs = extractFeatures(queries, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
+        queries_fvs = self._features(queries, model)
         if hi > lo:
-            gallery_fvs = extractFeatures(gallery[lo:hi], self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
+            gallery_fvs = self._features(gallery[lo:hi], model)
         else:                  # trailing ranks of a small gallery hold no rows (128-row aligned slices): an empty block, same collectives
             gallery_fvs = queries_fvs.new_zeros(0, queries_fvs.shape[1])
         block = self.distance(queries_fvs, gallery_fvs)
@@ -77,8 +91,8 @@ class validateModels:
         (ops_eval.pairdist_topk): -> (indices int32 [Nq, k] into ``gallery``, distances fp32 [Nq, k]) on the device, nearest first, exact
         ties by ascending gallery index.  The distances are bitwise the entries ``validate`` would return in its matrix."""
         model.eval()
-        queries_fvs = extractFeatures(queries, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
-        gallery_fvs = extractFeatures(gallery, self.img_height, self.img_width, model, 500, self.gpu_index, keep_on_device=True)
+        queries_fvs = self._features(queries, model)
+        gallery_fvs = self._features(gallery, model)
         return self.retrieve_features(queries_fvs, gallery_fvs, k)
 
     def retrieve_features(self, queries_fvs, gallery_fvs, k=50):

@@ -5,8 +5,9 @@ make_models.py:121-205) is the module that owns the plan; ``TransReID`` here is 
 feature so the reference's key names (``cls_token``, ``pos_embed``, ``patch_embed.proj.*``, ``blocks.N.*``, ``norm.*``,
 ``fc.*``) and call signature ``forward(x, cam_label=None, view_label=None)`` are kept.
 
-Supported (everything the reference's callers use, evaluate.py:179-183): camera = view = 0 (no SIE embedding),
-local_feature = False, drop / attn_drop = 0.  DropPath (vit_pytorch.py:45-62; per-block rate
+Supported: drop / attn_drop = 0; SIE camera / view embeddings (vit_pytorch.py:316-331, 382-387: ``sie_embed`` added to every token as
+``sie_xishu * sie_embed[index]``, trained through ``dali_vit_sie_grad``); ``local_feature=True`` (:393-396: ``blocks[:-1]``, all tokens, no
+final norm; eval mode only).  ``make_models.build_transformer_local`` puts the JPM head on the same plan.  DropPath (vit_pytorch.py:45-62; per-block rate
 ``linspace(0, drop_path_rate, depth)``, :338) is applied in training mode: one uniform draw per (branch, sample) on the
 device per step, scale = floor(keep + u) / keep; ``drop_path_uniform`` can be set to inject the draws (parity tests hand
 the same ones to the oracle).  In eval mode it is the identity, as in the reference.
@@ -14,6 +15,7 @@ the same ones to the oracle).  In eval mode it is the identity, as in the refere
 import ctypes
 import math
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -24,11 +26,22 @@ class _VitCfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("batch", "height", "width", "patch", "stride", "dim", "depth", "heads", "mlp_hidden", "num_classes")]
 
 
+class _VitExt(ctypes.Structure):
+    _fields_ = [("n_sie", ctypes.c_int), ("sie_coef", ctypes.c_float), ("local_feature", ctypes.c_int), ("jpm", ctypes.c_int),
+                ("divide", ctypes.c_int), ("token_map", ctypes.c_void_p), ("neck_after", ctypes.c_int), ("id_classes", ctypes.c_int)]
+
+
 class _VitPlan:
-    def __init__(self, device, cfg_tuple):
+    def __init__(self, device, cfg_tuple, ext=None):
         cfg = _VitCfg(*cfg_tuple)
+        ext = dict(ext or {})
+        token_map = ext.pop("token_map", None)           # int32 [divide, L] on the host; the plan copies it during the call
+        if token_map is not None:
+            token_map = np.ascontiguousarray(token_map, dtype=np.int32)
+            ext["divide"], ext["token_map"] = token_map.shape[0], token_map.ctypes.data
+        ext = _VitExt(**ext)
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib().dali_vit_create(_lib.ctx(device), ctypes.byref(cfg), ctypes.byref(h)), "dali_vit_create")
+        _lib.check(_lib.lib().dali_vit_create_ex(_lib.ctx(device), ctypes.byref(cfg), ctypes.byref(ext), ctypes.byref(h)), "dali_vit_create_ex")
         self.h = h
         pe, be, ab = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         fd, np_, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
@@ -62,23 +75,33 @@ class _VitPlan:
 
 class _VitFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, anchor, net):
+    def forward(ctx, x, anchor, net, sie_idx=None):
         ctx.net = net
-        return net._run_forward(x, True)
+        return net._run_forward(x, True, sie_idx=sie_idx)
 
     @staticmethod
     def backward(ctx, d_feat):
         ctx.net._run_backward(d_feat.contiguous())
-        return None, torch.zeros_like(ctx.net._anchor), None
+        return None, torch.zeros_like(ctx.net._anchor), None, None
 
 
 class ViTNeckNet(nn.Module):
     """TransReID encoder + BatchNorm1d neck on the HIP plan; state_dict keys as make_models.build_transformer
-    (``base.*``, ``bottleneck.*``)."""
+    (``base.*``, ``bottleneck.*``).  ``camera`` / ``view`` > 1 add the SIE parameter ``base.sie_embed`` (vit_pytorch.py:316-331);
+    ``jpm`` (a dict of dali_vit_ext's JPM fields: ``token_map``, ``neck_after``, ``id_classes``; set by make_models.build_transformer_local) adds ``b1.*``, ``b2.*``, ``classifier*`` and
+    ``bottleneck_1..4`` and makes the output [B, 5 * embed_dim]."""
 
     def __init__(self, img_size=(224, 224), patch_size=16, stride_size=16, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.0,
-                 num_classes=1000, drop_path_rate=0.0, device=None, seed=None):
+                 num_classes=1000, drop_path_rate=0.0, device=None, seed=None, camera=0, view=0, sie_xishu=1.0, local_feature=False, jpm=None):
         super().__init__()
+        self.cam_num, self.view_num, self.sie_xishu = int(camera), int(view), float(sie_xishu)
+        # vit_pytorch.py:317-331: one row per (camera, view) pair, per camera, or per view
+        n_sie = camera * view if camera > 1 and view > 1 else camera if camera > 1 else view if view > 1 else 0
+        self.local_feature = bool(local_feature or jpm)
+        self._ext = dict(n_sie=int(n_sie), sie_coef=float(sie_xishu), local_feature=int(self.local_feature))
+        if jpm:
+            self._ext.update(jpm=1, **jpm)
+        self._sie_idx = None
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
         if device is None:
@@ -96,7 +119,7 @@ class ViTNeckNet(nn.Module):
         self.flat_params = torch.zeros(probe.param_elems, device=dev)
         self.flat_grads = torch.zeros(probe.param_elems, device=dev)
         self.flat_buffers = torch.zeros(probe.buffer_elems, device=dev)
-        self.flat_nbt = torch.zeros(1, dtype=torch.long, device=dev)
+        self.flat_nbt = torch.zeros(sum(1 for t in probe.tensor_table(1) if t[0].endswith("running_var")), dtype=torch.long, device=dev)
         self._anchor = torch.zeros(1, device=dev, requires_grad=True)
         self._grad_views, self._param_names = {}, []
         for name, off, numel, shape in probe.tensor_table(0):
@@ -104,12 +127,16 @@ class ViTNeckNet(nn.Module):
             leaf.register_parameter(attr, nn.Parameter(self.flat_params[off:off + numel].view(*shape)))
             self._grad_views[name] = self.flat_grads[off:off + numel].view(*shape)
             self._param_names.append(name)
+        n_necks = 0
         for name, off, numel, shape in probe.tensor_table(1):
             leaf, attr = self._leaf(name)
             leaf.register_buffer(attr, self.flat_buffers[off:off + numel].view(*shape))
             if attr == "running_var":
-                leaf.register_buffer("num_batches_tracked", self.flat_nbt[0])
-        self.bottleneck.bias.requires_grad_(False)                                   # make_models.py:181
+                leaf.register_buffer("num_batches_tracked", self.flat_nbt[n_necks])
+                n_necks += 1
+        for name, p in self.named_parameters():
+            if name.startswith("bottleneck") and name.endswith(".bias"):
+                p.requires_grad_(False)                                              # make_models.py:181, :290-304
         # base.fc is built but never called (vit_pytorch.py:405-408 returns the cls feature): its grad stays None in the
         # reference, so torch.optim.Adam skips it (no weight decay either)
         self._no_grad_params = ("base.fc.weight", "base.fc.bias")
@@ -130,17 +157,28 @@ class ViTNeckNet(nn.Module):
         tn = lambda shape, std: torch.nn.init.trunc_normal_(torch.empty(shape), std=std, a=-2.0, b=2.0, generator=gen)
         with torch.no_grad():
             for name, p in self.named_parameters():
-                if name.endswith("cls_token") or name.endswith("pos_embed"):
+                if name.endswith("cls_token") or name.endswith("pos_embed") or name.endswith("sie_embed"):
                     p.copy_(tn(p.shape, 0.02).to(p.device))
                 elif "patch_embed.proj.weight" in name:
                     n = p.shape[2] * p.shape[3] * p.shape[0]
                     p.copy_((torch.randn(p.shape, generator=gen) * math.sqrt(2.0 / n)).to(p.device))
+                elif name.startswith("classifier"):
+                    p.copy_((torch.randn(p.shape, generator=gen) * 0.001).to(p.device))       # weights_init_classifier, make_models.py:42-47
                 elif name.endswith(".weight") and p.dim() == 2:
                     p.copy_(tn(p.shape, 0.02).to(p.device))
                 elif name.endswith(".weight"):
                     p.fill_(1.0)                       # LayerNorm / BatchNorm weights
                 else:
                     p.zero_()                          # every bias
+            if self._ext.get("jpm"):
+                # make_models.py:249-258: b1 and b2 start as deep copies of the last block and the final norm
+                sd = self.state_dict()
+                last = "base.blocks.%d." % (self._geom[3] - 1)
+                for name in self._param_names:
+                    if name.startswith(("b1.0.", "b2.0.")):
+                        sd[name].copy_(sd[last + name[5:]])
+                    elif name.startswith(("b1.1.", "b2.1.")):
+                        sd[name].copy_(sd["base.norm." + name[5:]])
             self.flat_buffers.zero_()
             for name, b in self.named_buffers():
                 if name.endswith("running_var"):
@@ -160,7 +198,7 @@ class ViTNeckNet(nn.Module):
         p = self._plans.get(batch)
         if p is None:
             ps, st, dim, depth, heads, hidden, ncls = self._geom
-            p = self._plans[batch] = _VitPlan(self._device, (batch, self.img_size[0], self.img_size[1], ps, st, dim, depth, heads, hidden, ncls))
+            p = self._plans[batch] = _VitPlan(self._device, (batch, self.img_size[0], self.img_size[1], ps, st, dim, depth, heads, hidden, ncls), self._ext)
         return p
 
     def _activate(self, plan):
@@ -179,7 +217,31 @@ class ViTNeckNet(nn.Module):
             _lib.check(L.dali_vit_refresh_weights(plan.h, _lib.stream_ptr()), "dali_vit_refresh_weights")
             self._refreshed = key
 
-    def _run_forward(self, x, training, want_global=False):
+    def sie_index(self, cam_label, view_label, batch):
+        """vit_pytorch.py:382-389: the row of ``sie_embed`` per sample, ``cam * view_num + view``, ``cam`` or ``view``, validated on the host
+        -> int32 [batch] on the device (None for a model without SIE).  Labels: an int, a numpy array or a tensor of length ``batch``."""
+        if self._ext["n_sie"] == 0:
+            return None
+
+        def host(lab, n, what):
+            if lab is None:
+                raise _lib.DaliError("this model has SIE %s embeddings: forward() needs %s_label" % (what, what if what == "view" else "cam"))
+            a = lab.detach().cpu().numpy() if isinstance(lab, torch.Tensor) else np.asarray(lab)
+            a = np.broadcast_to(a.reshape(-1), (batch,)) if a.size == 1 else a.reshape(-1)
+            if a.shape != (batch,) or a.dtype.kind not in "iu":
+                raise _lib.DaliError("%s labels must be %d integers" % (what, batch))
+            if a.min() < 0 or a.max() >= n:
+                raise _lib.DaliError("%s label out of range [0, %d)" % (what, n))
+            return a.astype(np.int64)
+        if self.cam_num > 1 and self.view_num > 1:
+            idx = host(cam_label, self.cam_num, "camera") * self.view_num + host(view_label, self.view_num, "view")
+        elif self.cam_num > 1:
+            idx = host(cam_label, self.cam_num, "camera")
+        else:
+            idx = host(view_label, self.view_num, "view")
+        return torch.from_numpy(idx.astype(np.int32)).to(self._device)
+
+    def _run_forward(self, x, training, want_global=False, sie_idx=None, want_tokens=False):
         if x.dim() != 4 or tuple(x.shape[1:]) != (3,) + self.img_size:
             raise _lib.DaliError("Input image size (%s) doesn't match model (%s)" % (tuple(x.shape[2:]), self.img_size))   # vit_pytorch.py:282-284
         x = x.to(device=self._device, dtype=torch.float32).contiguous()
@@ -187,9 +249,19 @@ class ViTNeckNet(nn.Module):
         self._activate(plan)
         self._dp_scales = self._draw_drop_path(x.shape[0]) if training else None
         _lib.check(_lib.lib().dali_vit_set_drop_path(plan.h, _lib.ptr(self._dp_scales)), "dali_vit_set_drop_path")
+        if self._ext["n_sie"] and sie_idx is None:
+            raise _lib.DaliError("this model has SIE embeddings: forward() needs cam_label / view_label")
+        if training:
+            self._sie_idx = sie_idx                  # the backward's sie_grad reads it
+        if want_tokens:
+            tokens = torch.empty(x.shape[0], self.base.pos_embed.shape[1], self.in_planes, device=self._device)
+            _lib.check(_lib.lib().dali_vit_forward_ex(plan.h, _lib.stream_ptr(), _lib.ptr(x), _lib.ptr(sie_idx), 0, None, None, _lib.ptr(tokens)),
+                       "dali_vit_forward_ex")
+            return tokens
         feat = torch.empty(x.shape[0], plan.feat_dim, device=self._device)
-        gf = torch.empty_like(feat) if want_global else None
-        _lib.check(_lib.lib().dali_vit_forward(plan.h, _lib.stream_ptr(), _lib.ptr(x), int(training), _lib.ptr(feat), _lib.ptr(gf)), "dali_vit_forward")
+        gf = torch.empty(x.shape[0], self.in_planes, device=self._device) if want_global else None
+        _lib.check(_lib.lib().dali_vit_forward_ex(plan.h, _lib.stream_ptr(), _lib.ptr(x), _lib.ptr(sie_idx), int(training), _lib.ptr(feat), _lib.ptr(gf),
+                                                  None), "dali_vit_forward_ex")
         if training:
             self.flat_nbt += 1
             self._bwd_plan = plan
@@ -231,13 +303,27 @@ class ViTNeckNet(nn.Module):
 
     def forward(self, x, label=None, cam_label=None, view_label=None):
         """make_models.py:184-205: returns the post-neck ``feat``."""
+        self._refuse_tokens_only("forward()")
+        idx = self.sie_index(cam_label, view_label, x.shape[0])
         if self.training and torch.is_grad_enabled():
-            return _VitFn.apply(x, self._anchor, self)
-        return self._run_forward(x, self.training)
+            return _VitFn.apply(x, self._anchor, self, idx)
+        return self._run_forward(x, self.training, sie_idx=idx)
 
-    def global_feat(self, x):
+    def global_feat(self, x, cam_label=None, view_label=None):
         """The pre-neck cls feature = ``TransReID.forward`` (vit_pytorch.py:405-408); eval-mode helper."""
-        return self._run_forward(x, False, want_global=True)[1]
+        self._refuse_tokens_only("global_feat()")
+        return self._run_forward(x, False, want_global=True, sie_idx=self.sie_index(cam_label, view_label, x.shape[0]))[1]
+
+    def _refuse_tokens_only(self, what):
+        if self.local_feature and not self._ext.get("jpm"):
+            raise _lib.DaliError("%s: a local_feature model without the JPM head has no cls feature and no neck output "
+                                 "(vit_pytorch.py:393-396 returns the tokens); call local_tokens()" % what)
+
+    def local_tokens(self, x, cam_label=None, view_label=None):
+        """``TransReID.forward`` with local_feature=True (vit_pytorch.py:393-396): the tokens after ``blocks[:-1]``, fp32 [B, T, C]; eval only."""
+        if not self.local_feature:
+            raise _lib.DaliError("local_tokens() needs a model built with local_feature=True")
+        return self._run_forward(x, False, sie_idx=self.sie_index(cam_label, view_label, x.shape[0]), want_tokens=True)
 
 
 class TransReID(nn.Module):
@@ -247,13 +333,13 @@ class TransReID(nn.Module):
                  mlp_ratio=4., qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., camera=0, view=0, drop_path_rate=0.,
                  hybrid_backbone=None, norm_layer=None, local_feature=False, sie_xishu=1.0, device=None, seed=None):
         super().__init__()
-        if in_chans != 3 or not qkv_bias or qk_scale is not None or hybrid_backbone is not None or local_feature:
-            raise NotImplementedError("TransReID: only in_chans=3, qkv_bias=True, default qk_scale, no hybrid backbone, local_feature=False are in scope")
-        if camera > 1 or view > 1:
-            raise NotImplementedError("TransReID: SIE camera/view embeddings are out of scope (camera = view = 0 in every reference caller)")
+        if in_chans != 3 or not qkv_bias or qk_scale is not None or hybrid_backbone is not None:
+            raise NotImplementedError("TransReID: only in_chans=3, qkv_bias=True, default qk_scale, no hybrid backbone are in scope")
         if drop_rate != 0. or attn_drop_rate != 0.:
             raise NotImplementedError("TransReID: dropout is not supported (the reference's callers use 0)")
-        self.net = ViTNeckNet(img_size, patch_size, stride_size, embed_dim, depth, num_heads, mlp_ratio, num_classes, drop_path_rate, device, seed)
+        self.net = ViTNeckNet(img_size, patch_size, stride_size, embed_dim, depth, num_heads, mlp_ratio, num_classes, drop_path_rate, device, seed,
+                              camera=camera, view=view, sie_xishu=sie_xishu, local_feature=local_feature)
+        self.local_feature, self.cam_num, self.view_num, self.sie_xishu = bool(local_feature), camera, view, sie_xishu
         self.num_features = self.embed_dim = embed_dim
         self.num_classes = num_classes
 
@@ -266,7 +352,11 @@ class TransReID(nn.Module):
         return self.net.load_state_dict(full, strict=strict)
 
     def forward(self, x, cam_label=None, view_label=None):
-        return self.net.global_feat(x)
+        if self.local_feature:
+            if self.training and torch.is_grad_enabled():
+                raise NotImplementedError("TransReID(local_feature=True) is eval only: call .eval() or run under torch.no_grad()")
+            return self.net.local_tokens(x, cam_label, view_label)
+        return self.net.global_feat(x, cam_label, view_label)
 
 
 def vit_base_patch16_224_TransReID(img_size=(256, 128), stride_size=16, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.1, camera=0, view=0,

@@ -355,6 +355,22 @@ int dali_vit_assemble_tokens(dali_ctx* ctx, void* stream, const uint16_t* patch_
                              int C, uint16_t* x);
 int dali_vit_assemble_tokens_bwd(dali_ctx* ctx, void* stream, const uint16_t* dx, int B, int T, int C, float* dpos, float* dcls,
                                  uint16_t* dpatch_emb);
+/* SIE (vit_pytorch.py:316-331, 382-387): the token assembly with the side-information term, x[b,t] = (tok + pos[t]) + coef * sie[idx[b]]
+ * (fp32, one rounding to bf16); sie fp32 [n_sie][C], idx int32 [B] on the device; an index outside [0, n_sie) adds nothing.
+ * sie_grad: dsie[i] = coef * sum over the samples with idx[b] == i (ascending b) and their tokens of dx[b,t], fp32, fixed order (no atomics:
+ * bit-identical run to run); unused rows get 0. */
+int dali_vit_assemble_tokens_sie(dali_ctx* ctx, void* stream, const uint16_t* patch_emb, const float* cls, const float* pos, const float* sie,
+                                 const int32_t* idx, int n_sie, float coef, int B, int T, int C, uint16_t* x);
+int dali_vit_sie_grad(dali_ctx* ctx, void* stream, const uint16_t* dx, const int32_t* idx, int B, int T, int C, int n_sie, float coef,
+                      float* dsie);
+/* JPM (make_models.py:314-377).  gather: features bf16 [B][T][C] + map int32 [G][L] of token indices (device) -> out [G*B][1+L][C], sequence
+ * g*B + b, row 0 = the sample's cls token; C % 8 == 0.  head: global fp32 [B][C] and local fp32 [4*B][C] (sequence g*B + b) ->
+ * out [B][5C] = cat(global, local_1 / 4, .., local_4 / 4); after != 0: every branch first through its BatchNorm1d by running statistics
+ * (gamma / beta / running_mean / running_var fp32 [5][C], eps 1e-5), after == 0: the raw features (the four arrays may be NULL). */
+int dali_vit_jpm_gather(dali_ctx* ctx, void* stream, const uint16_t* features, const int32_t* map, int B, int T, int C, int G, int L,
+                        uint16_t* out);
+int dali_vit_jpm_head(dali_ctx* ctx, void* stream, const float* global_feat, const float* local_feat, const float* gamma, const float* beta,
+                      const float* running_mean, const float* running_var, int B, int C, int after, float* out);
 /* nn.LayerNorm over C (eps 1e-6 in TransReID); backward optionally adds the residual-stream gradient `add`. */
 int dali_layernorm_fwd(dali_ctx* ctx, void* stream, const uint16_t* x, const float* gamma, const float* beta, int rows, int C,
                        float eps, uint16_t* y, float* mean, float* rstd);
@@ -366,6 +382,9 @@ int dali_attention_fwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, 
                        uint16_t* out, float* lse);
 int dali_attention_bwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out, const float* lse,
                        int B, int T, int H, int head_dim, float scale, uint16_t* dqkv);
+/* The forward for short sequences, T <= 64 (the JPM local runs: 33 / 53 / 50 tokens): a 4-tile instance of the same kernel. */
+int dali_attention_fwd_short(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
+                             uint16_t* out, float* lse);
 
 /* ---- loss heads (train_encodersKIT.py:200-208), fp32 --------------------------------------------------- *
  * S is the similarity matrix fn @ C^T (dali_pairdist with DALI_METRIC_DOT).  labels are int32 codes shared between
@@ -514,8 +533,8 @@ int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void** ptr, int
 
 /* ---- net plan: TransReID ViT + BN neck (make_models.build_transformer.forward, make_models.py:184-205) ----- *
  * Same storage contract as dali_resnet_*.  forward: images fp32 NCHW -> feat fp32 [batch, dim] (after the
- * BatchNorm1d neck); global_feat (nullable) receives the pre-neck cls feature.  DropPath / Dropout are identity
- * (rate 0).  Limits: head_dim 64, at most 208 tokens. */
+ * BatchNorm1d neck); global_feat (nullable) receives the pre-neck cls feature.  Dropout is the identity (rate 0).
+ * Limits: head_dim 64, at most 256 tokens. */
 typedef struct dali_vit dali_vit;
 typedef struct {
     int batch, height, width;   /* images fp32 NCHW [batch,3,height,width] */
@@ -524,7 +543,24 @@ typedef struct {
     int mlp_hidden;             /* 3072 */
     int num_classes;            /* size of the unused `base.fc` head kept for state_dict compatibility (1000) */
 } dali_vit_cfg;
+/* What a TransReID checkpoint normally carries on top of the baseline; all zero = dali_vit_create.
+ *   SIE: "base.sie_embed" [n_sie,1,dim] after pos_embed; forward_ex takes the per-sample index (cam*view_num + view, cam, or view).
+ *   local_feature (vit_pytorch.py:393-396): blocks[:-1], all tokens, no final norm; eval only.
+ *   jpm (make_models.build_transformer_local, make_models.py:221-377; implies local_feature; eval only): parameters "b1.0.*", "b1.1.*",
+ *   "b2.0.*", "b2.1.*", "classifier*.weight" [id_classes, dim] (unused), "bottleneck", "bottleneck_1..4"; feat is [batch, 5*dim].
+ *   The shift + group shuffle of the patch tokens (shuffle_unit, make_models.py:8-25) does not depend on the data: the caller computes it once
+ *   (daliid_amd.make_models.jpm_token_map) and hands it in as token_map; the plan copies it. */
+typedef struct {
+    int n_sie;                  /* rows of sie_embed; 0 = no SIE */
+    float sie_coef;             /* cfg.MODEL.SIE_COE */
+    int local_feature, jpm;
+    int divide;                 /* cfg.MODEL.DEVIDE_LENGTH (must be 4: the reference's forward cuts four runs) */
+    const int32_t* token_map;   /* jpm: host int32 [divide][L], L = n_patches / divide: the token (1 .. n_patches; 0 is cls) at place j of run i */
+    int neck_after;             /* cfg.TEST.NECK_FEAT == 'after' */
+    int id_classes;             /* rows of the unused classifier weights (the training set's identities) */
+} dali_vit_ext;
 int dali_vit_create(dali_ctx* ctx, const dali_vit_cfg* cfg, dali_vit** out);
+int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const dali_vit_ext* ext, dali_vit** out);
 int dali_vit_destroy(dali_vit* net);
 int dali_vit_sizes(const dali_vit* net, int64_t* param_elems, int64_t* buffer_elems, int64_t* arena_bytes, int* feat_dim,
                    int* n_params, int* n_buffers);
@@ -533,6 +569,11 @@ int dali_vit_tensor_info(const dali_vit* net, int kind, int index, char* name, i
 int dali_vit_bind(dali_vit* net, float* params, float* grads, float* buffers, void* arena, size_t arena_bytes);
 int dali_vit_refresh_weights(dali_vit* net, void* stream);
 int dali_vit_forward(dali_vit* net, void* stream, const float* images, int training, float* feat, float* global_feat);
+/* sie_idx: device int32 [batch] (required when n_sie > 0; must outlive the backward of a training forward); tokens_out (nullable, local_feature
+ * nets): the tokens after blocks[:-1] as fp32 [batch][T][dim].  A local_feature net without jpm writes only tokens_out: it requires
+ * tokens_out and refuses a non-null feat or global_feat (the reference has no cls feature or neck output for such a base). */
+int dali_vit_forward_ex(dali_vit* net, void* stream, const float* images, const int32_t* sie_idx, int training, float* feat, float* global_feat,
+                        float* tokens_out);
 int dali_vit_backward(dali_vit* net, void* stream, const float* d_feat);
 /* Backward in stages = gradient buckets of the data-parallel reducer (daliid_amd/parallel.py): stage 0 = neck + final norm + the
  * last group of blocks (consumes d_feat), ..., the last stage also holds cls / pos / patch embedding.  Replaces the autograd
