@@ -231,14 +231,34 @@ __device__ __forceinline__ float row16_reduce8(const float (&v)[8], int lane) {
 // __syncthreads() would wait for the global stores); and for interior tiles of the plain convolution a lean path that
 // stages the tile through LDS as [pixel][TM channels] bf16 and writes 16 bytes per lane, TM/8 adjacent lanes covering
 // one pixel's contiguous TM*2 bytes, without per-element predicates.  Values and rounding are identical on every path.
-template <int FM_, int FN_> struct EpiShape { static constexpr int FM = FM_, FN = FN_; };
 // Generic over the block shape: TM x TN tile, WNW waves along n, NT threads; this wave sits at (wm, wn) and owns an
 // (FM*16) x (FN*16) sub-tile.
+//
+// What an instantiation's output stage compiles in (conv_epilogue_g; the kernels' EPI parameter, the GemmKernel table).  Each mode is its own
+// instantiation so that the hot convolution kernels compile none of the others' code: code that is never executed still cost their register
+// allocation 0.4-0.8 ms per ResNet step.
+enum class Epi : int {
+    CONV = 0,        // convolution only: the lean staged store (+ residual, + residual mask); no linear-layer extras compiled in at all
+    LIN = 1,         // linear-layer extras (GELU, pre-activation copy O2, GELU' factor, DropPath row factor) in a staged block and in the general path
+    GENERAL = 2,     // the lean store, the extras in the general path only: kernels without a LIN variant
+    FUSED = 3,       // the fused output stage (IGemmArgs::out_scale ... out_mask) in a staged block and in the general path
+    PARITY = 4,      // the lean store with the output addressing of a stride-2 data gradient's parity class (GatherGeom::sub)
+    FUSED_LEAN = 5,  // the fused stage WITHOUT residual, masks and mask bits (scale / shift / bias / ReLU only): the inference forward's conv + BatchNorm
+                     // + ReLU launches on the 3x3 and narrow kernels, whose register budgets the full stage's residual prefetch overflowed
+};
+// the mode of one kernel instantiation: the shape that has a variant per mode (`own`) gets its own, every other one the extras in the general path only
+constexpr Epi epi_mode(bool own, Epi asked) { return own ? asked : Epi::GENERAL; }
+constexpr bool epi_fused(Epi m) { return m == Epi::FUSED || m == Epi::FUSED_LEAN; }
+
 // keep the bf16 halves of `w` whose mask bits (bit 0: low half, bit 1: high half) are set
 __device__ __forceinline__ uint32_t gate_bf16x2(uint32_t w, unsigned bits) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_sbfe((int)bits, 0, 1) & 0xffffu;      // 0 or 0x0000ffff
     const uint32_t hi = (uint32_t)__builtin_amdgcn_sbfe((int)bits, 1, 1) << 16;         // 0 or 0xffff0000
     return w & (lo | hi);
+}
+// the same for a 16-byte chunk: 8 channels = one mask byte
+__device__ __forceinline__ void gate_bf16x8(uint4& v, unsigned m) {
+    v.x = gate_bf16x2(v.x, m); v.y = gate_bf16x2(v.y, m >> 2); v.z = gate_bf16x2(v.z, m >> 4); v.w = gate_bf16x2(v.w, m >> 6);
 }
 // exact-erf GELU (vit_pytorch.py:120-136, nn.GELU) and its derivative.  erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7: three orders
 // below the bf16 rounding of the stored result) on v_rcp / v_exp: ocml's erff + expf were ~60 VALU instructions per element, a third of the
@@ -259,9 +279,23 @@ __device__ __forceinline__ void gelu_parts(float v, float& cdf, float& pdf) {
 }
 __device__ __forceinline__ float gelu_f(float v) { float c, p; gelu_parts(v, c, p); return v * c; }
 __device__ __forceinline__ float gelu_grad_f(float x) { float c, p; gelu_parts(x, c, p); return __builtin_fmaf(x, p, c); }
+__device__ __forceinline__ void unpack4(uint2 q, float (&f)[4]) {
+    f[0] = bf16_bits_to_f32(q.x & 0xffffu); f[1] = bf16_bits_to_f32(q.x >> 16); f[2] = bf16_bits_to_f32(q.y & 0xffffu); f[3] = bf16_bits_to_f32(q.y >> 16);
+}
 __device__ __forceinline__ void unpack8(const uint4& q, float (&f)[8]) {
     f[0] = bf16_bits_to_f32(q.x & 0xffffu); f[1] = bf16_bits_to_f32(q.x >> 16); f[2] = bf16_bits_to_f32(q.y & 0xffffu); f[3] = bf16_bits_to_f32(q.y >> 16);
     f[4] = bf16_bits_to_f32(q.z & 0xffffu); f[5] = bf16_bits_to_f32(q.z >> 16); f[6] = bf16_bits_to_f32(q.w & 0xffffu); f[7] = bf16_bits_to_f32(q.w >> 16);
+}
+// the one rounding to bf16 at the end of every path
+__device__ __forceinline__ uint2 pack4(const float (&v)[4]) { return make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])); }
+__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
+    return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+}
+// this lane's 4 channels of every 16-row block of a per-channel vector (bias, scale, shift); `vec` points at the lane's first channel
+template <int FM>
+__device__ __forceinline__ void load_rows4(float4 (&d)[FM], const float* vec) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i) d[i] = *reinterpret_cast<const float4*>(vec + i * 16);
 }
 // bit 0 / bit 1: the low / high bf16 half of w is > 0
 __device__ __forceinline__ unsigned pos_bits_bf16x2(uint32_t w) {
@@ -272,7 +306,7 @@ __device__ __forceinline__ unsigned pos_bits_bf16x2(uint32_t w) {
 // channels of a pixel back applies the whole output stage to them -- bias, pre-activation copy (O2), GELU, GELU' factor, DropPath row
 // factor, residual (+ mask) -- with its residual / GELU' argument chunk (16 bytes, requested before the staging so that the transpose
 // hides its latency) and stores 16 bytes.  One rounding to bf16 at the end, as on every other path; interior tiles, natural output
-// addressing, Cm % 8 == 0.
+// addressing, Cm % 8 == 0.  (Its own geometry: fp32 by column block, not the half tiles of EpiStage below.)
 template <int TM, int TN, int FM_, int FN_, int WNW, int NT>
 __device__ __forceinline__ void conv_epilogue_cols(const IGemmArgs& a, f32x4_t (&acc)[FM_][FN_], int tm, int tn, uint16_t* smem, int wm, int wn) {
     constexpr int ROWB = TM * 4 + 16, ROWS = WNW * 16, CPR = TM / 8, ITERS = ROWS * CPR / NT;       // +16: 16 rows of 16-byte writes cover all banks once
@@ -308,9 +342,7 @@ __device__ __forceinline__ void conv_epilogue_cols(const IGemmArgs& a, f32x4_t (
                 const float4 b0 = *reinterpret_cast<const float4*>(bias_c), b1 = *reinterpret_cast<const float4*>(bias_c + 4);
                 v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
             }
-            if (a.O2)
-                *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O2) + gofs[it]) =
-                    make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+            if (a.O2) *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O2) + gofs[it]) = pack8(v);
             if (a.act == 1) {
 #pragma unroll
                 for (int t = 0; t < 8; ++t) v[t] = gelu_f(v[t]);
@@ -328,387 +360,320 @@ __device__ __forceinline__ void conv_epilogue_cols(const IGemmArgs& a, f32x4_t (
             }
             if (a.Res) {
                 uint4 rv = tin[it];
-                if (a.res_mask) {
-                    const unsigned m = a.res_mask[gofs[it] >> 4];
-                    rv.x = gate_bf16x2(rv.x, m); rv.y = gate_bf16x2(rv.y, m >> 2); rv.z = gate_bf16x2(rv.z, m >> 4); rv.w = gate_bf16x2(rv.w, m >> 6);
-                }
+                // (reachable: dali_conv2d_dgrad with a masked residual at a shape conv_prefers_320 takes, e.g. 1x1 / stride 1, 512 channels, 32896 pixels)
+                if (a.res_mask) gate_bf16x8(rv, a.res_mask[gofs[it] >> 4]);
                 float r8[8];
                 unpack8(rv, r8);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) v[t] += r8[t];
             }
-            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + gofs[it]) =
-                make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + gofs[it]) = pack8(v);
         }
         if (j + 1 < FN_) lds_barrier();                  // the read-out is done before the next column block overwrites the stage
     }
 }
 
-// LIN: 3 = the fused output stage (IGemmArgs::out_scale ... out_mask) in a staged block and in the general path;
-// LIN: 0 = a convolution-only instantiation (no linear-layer extras compiled in at all), 1 = extras in the staged block and in the
-// general path (the LIN kernel variants), 2 = extras in the general path only (kernels without a LIN variant)
-template <int TM, int TN, int FM_, int FN_, int WNW, int NT, int LIN = 2>
-__device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&acc)[FM_][FN_], int tm, int tn, uint16_t* smem, int wm, int wn) {
-    using Cfg = EpiShape<FM_, FN_>;
-    constexpr bool EVEN = FN_ % 2 == 0;                  // the staged stores below split the tile's pixels in two halves; odd FN: conv_epilogue_cols
+// The staged half-tile store's geometry, shared by the lean, linear-extras and fused paths.  The tile's pixels leave in two halves (the first
+// FN / 2 of every wave's 16-pixel column blocks, then the rest).  A half goes through LDS as [pixel][TM channels] bf16: every lane puts its
+// accumulator quads into `slot(jj, i)`; after a barrier a thread owns the 16-byte chunk `ch` of rows row(0), row(1), ..., CPR adjacent lanes
+// covering one pixel's contiguous TM * 2 bytes.  An input tile (residual, GELU' argument) comes in the same way and is read back from the slots.
+constexpr int epi_stage_bytes(int TM, int TN) { return (TN / 2) * (TM * 2 + 32); }      // the LDS image of a half; the statistics' partial sums sit behind it
+template <bool SUB, int TM, int TN, int FM, int FN, int WNW, int NT>      // SUB: output rows through a parity class's scattered pixels (out_pixel)
+struct EpiStage {
+    static constexpr int ROWB = TM * 2 + 32;                    // LDS row pitch in bytes (+32: spreads the 8-byte accesses over banks)
+    static constexpr int HFN = FN / 2, WROWS = HFN * 16, ROWS = TN / 2, CPR = TM / 8, ITERS = ROWS * CPR / NT;
+    static_assert(ROWS * CPR % NT == 0 && NT % CPR == 0, "staged store: threads must tile the half evenly");
+    static_assert(ROWS * ROWB == epi_stage_bytes(TM, TN), "layout of the partial sums behind the staged tile");
+    char* stage;
+    char* my_stage;           // this lane's slots: + jj*16*ROWB + i*32
+    int ch, lp0, tm, tn;      // read-out: 16-byte chunk / first row; the tile
+    const IGemmArgs& a;
+    __device__ __forceinline__ EpiStage(const IGemmArgs& a_, int tm_, int tn_, uint16_t* smem, int wn, int mb) : tm(tm_), tn(tn_), a(a_) {
+        const int lane = threadIdx.x & 63;
+        stage = reinterpret_cast<char*>(smem);
+        my_stage = stage + (wn * WROWS + (lane & 15)) * ROWB + mb * 2;
+        ch = threadIdx.x % CPR; lp0 = threadIdx.x / CPR;
+    }
+    // the accumulator quad (column block jj of the half, row block i) of this lane
+    __device__ __forceinline__ uint2* slot(int jj, int i) const { return reinterpret_cast<uint2*>(my_stage + jj * 16 * ROWB + i * 32); }
+    // read-out iteration `it`: this thread's LDS row, the row's pixel inside the tile (minus h * WROWS), and its chunk in LDS
+    __device__ __forceinline__ int row(int it) const { return lp0 + it * (NT / CPR); }
+    __device__ __forceinline__ int pixel(int it) const { const int lp = row(it); return (lp / WROWS) * (FN * 16) + (lp % WROWS); }
+    __device__ __forceinline__ uint4* chunk(int it) const { return reinterpret_cast<uint4*>(stage + row(it) * ROWB + ch * 16); }
+    // byte offset of that chunk in a [pixels][Cm] tensor, half h
+    __device__ __forceinline__ size_t offset(int h, int it) const {
+        if constexpr (SUB) return (out_pixel(a.g, tn * TN + h * WROWS + pixel(it)) * a.Cm + tm * TM + ch * 8) * 2;
+        else return ((size_t)(tn * TN + h * WROWS) * a.Cm + tm * TM + ch * 8) * 2 + (size_t)pixel(it) * a.Cm * 2;
+    }
+    // that chunk of tensor `src`; the staged chunk -> `dst`.  (The loops over `it` stay in the store paths, inside their loop over the halves: a
+    // member holding the loop is unrolled before it is inlined, its chunk addresses are then hoisted out of the half loop and stay live across
+    // both halves: 105 -> 122 VGPRs for igemm_conv_dma_kernel<128, 128, 3>.)
+    __device__ __forceinline__ uint4 in(const uint16_t* src, int h, int it) const {
+        return *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(src) + offset(h, it));
+    }
+    __device__ __forceinline__ void out(uint16_t* dst, int h, int it) const {
+        *reinterpret_cast<uint4*>(reinterpret_cast<char*>(dst) + offset(h, it)) = *chunk(it);
+    }
+};
+
+// ---- BatchNorm partial statistics: per channel sum / sumsq over this tile's pixels ----
+template <int TM, int TN, int FM, int FN, int WNW, int NT>
+__device__ __forceinline__ void epi_stats(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wn, int mb) {
     const int lane = threadIdx.x & 63;
-    const int mb = wm * (FM_ * 16) + (lane >> 4) * 4, nb = wn * (FN_ * 16) + (lane & 15);
-    // Precondition: the caller has synchronised after its main loop (every kernel ends the loop with a barrier that follows
-    // each wave's last fragment read), so smem is free.
-    // ---- BatchNorm partial statistics: per channel sum / sumsq over this tile's pixels ----
-    constexpr int STAGE_BYTES = (TN / 2) * (TM * 2 + 32);      // the staged store's LDS image (below); the partial sums sit behind it
-    if (a.stats) {
-        float* red = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + STAGE_BYTES);   // [WNW (wn)][TM][2]
+    float* red = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + epi_stage_bytes(TM, TN));   // [WNW (wn)][TM][2]
 #pragma unroll
-        for (int i = 0; i < Cfg::FM; ++i) {
-            float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < FM; ++i) {
+        float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < Cfg::FN; ++j)
+        for (int j = 0; j < FN; ++j)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { const float v = acc[i][j][r]; s1[r] += v; s2[r] = __builtin_fmaf(v, v, s2[r]); }      // (explicit: the build has -ffp-contract=off)
-            const float v8[8] = {s1[0], s1[1], s1[2], s1[3], s2[0], s2[1], s2[2], s2[3]};
-            const float tot = row16_reduce8(v8, lane);   // lanes 0-7 of the row: sums, 8-15: sums of squares; channel r = 2 * ((l & 7) >= 4) + ((l & 2) != 0)
-            if ((lane & 1) == 0) {
-                const int r = ((lane & 4) >> 1) | ((lane & 2) >> 1);
-                red[(wn * TM + mb + i * 16 + r) * 2 + ((lane >> 3) & 1)] = tot;
+            for (int r = 0; r < 4; ++r) { const float v = acc[i][j][r]; s1[r] += v; s2[r] = __builtin_fmaf(v, v, s2[r]); }      // (explicit: the build has -ffp-contract=off)
+        const float v8[8] = {s1[0], s1[1], s1[2], s1[3], s2[0], s2[1], s2[2], s2[3]};
+        const float tot = row16_reduce8(v8, lane);   // lanes 0-7 of the row: sums, 8-15: sums of squares; channel r = 2 * ((l & 7) >= 4) + ((l & 2) != 0)
+        if ((lane & 1) == 0) {
+            const int r = ((lane & 4) >> 1) | ((lane & 2) >> 1);
+            red[(wn * TM + mb + i * 16 + r) * 2 + ((lane >> 3) & 1)] = tot;
+        }
+    }
+    lds_barrier();
+    for (int t = threadIdx.x; t < TM; t += NT) {
+        const int c = tm * TM + t;
+        if (c < a.Cm) {
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int w = 0; w < WNW; ++w) { const float2 v = *reinterpret_cast<const float2*>(red + (w * TM + t) * 2); s1 += v.x; s2 += v.y; }
+            *reinterpret_cast<float2*>(a.stats + ((size_t)tn * a.Cm + c) * 2) = make_float2(s1, s2);
+        }
+    }
+}       // no barrier: the staged stores do not touch `red`
+// ---- lean path: plain convolution (optionally + bias, + residual, + residual mask), interior tile ----
+// SUB (Epi::PARITY): the output addressing of a stride-2 data gradient's parity class: the pixel rows of the tile scatter to every second
+// position of every second image row, each still TM * 2 contiguous bytes.  Its own instantiations (the sub-problems went through the general
+// path before: 8-byte stores per lane, per-element residual loads; layer2's downsample data gradient 169 us against 71 us forward), so that
+// the hot convolution instantiations stay as they are.
+template <bool SUB, int TM, int TN, int FM, int FN, int WNW, int NT>
+__device__ __forceinline__ void epi_store_lean(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wn, int mb) {
+    using Stage = EpiStage<SUB, TM, TN, FM, FN, WNW, NT>;
+    constexpr int ITERS = Stage::ITERS;
+    const Stage st(a, tm, tn, smem, wn, mb);
+    float4 bias4[FM];                                           // this lane's 4 channels of every 16-row block (linear layers; folded in here)
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+        bias4[i] = a.bias ? *reinterpret_cast<const float4*>(a.bias + tm * TM + mb + i * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (a.Res) {
+            unsigned rm[ITERS];                                 // (mask bytes requested together: see the fused output stage below)
+            if (a.res_mask) {
+#pragma unroll
+                for (int it = 0; it < ITERS; ++it) rm[it] = a.res_mask[st.offset(h, it) >> 4];
+            }
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) {
+                uint4 rv = st.in(a.Res, h, it);
+                if (a.res_mask) gate_bf16x8(rv, rm[it]);
+                *st.chunk(it) = rv;
+            }
+            lds_barrier_vm();                                   // the loaded residual is visible to every wave
+        }
+#pragma unroll
+        for (int jj = 0; jj < Stage::HFN; ++jj) {
+            const int j = h * Stage::HFN + jj;
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                float v[4] = {acc[i][j][0] + bias4[i].x, acc[i][j][1] + bias4[i].y, acc[i][j][2] + bias4[i].z, acc[i][j][3] + bias4[i].w};
+                uint2* slot = st.slot(jj, i);
+                if (a.Res) {
+                    float r4[4];
+                    unpack4(*slot, r4);
+                    v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3];
+                }
+                *slot = pack4(v);
             }
         }
         lds_barrier();
-        for (int t = threadIdx.x; t < TM; t += NT) {
-            const int c = tm * TM + t;
-            if (c < a.Cm) {
-                float s1 = 0.f, s2 = 0.f;
+        conv_stamp(a, 6 + 2 * h);   // half staged
 #pragma unroll
-                for (int w = 0; w < WNW; ++w) { const float2 v = *reinterpret_cast<const float2*>(red + (w * TM + t) * 2); s1 += v.x; s2 += v.y; }
-                *reinterpret_cast<float2*>(a.stats + ((size_t)tn * a.Cm + c) * 2) = make_float2(s1, s2);
+        for (int it = 0; it < ITERS; ++it) st.out(a.O, h, it);
+        conv_stamp(a, 7 + 2 * h);   // half's stores issued
+        if (h == 0) lds_barrier();                              // the LDS reads are done before the second half overwrites them
+    }
+}
+// ---- linear-layer extras (Epi::LIN): GELU, pre-activation copy, GELU' factor, DropPath row factor; interior tile, natural addressing ----
+// A second staged block, kept apart so that the convolutions' path stays as lean as it was (folding them into one block cost the ResNet step
+// 0.8 ms), and only in the LIN instantiations of the kernels (compiled into every kernel it changed the convolutions' register allocation and
+// cost the ResNet step 0.4 ms even when never taken).  No residual mask: conv_choose refuses res_mask beside an extra.
+template <int TM, int TN, int FM, int FN, int WNW, int NT>
+__device__ __forceinline__ void epi_store_lin(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wn, int mb) {
+    using Stage = EpiStage<false, TM, TN, FM, FN, WNW, NT>;
+    constexpr int ITERS = Stage::ITERS;
+    const Stage st(a, tm, tn, smem, wn, mb);
+    const int lane = threadIdx.x & 63;
+    float4 bias4[FM];                                           // this lane's 4 channels of every 16-row block
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+        bias4[i] = a.bias ? *reinterpret_cast<const float4*>(a.bias + tm * TM + mb + i * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint16_t* in_tile = a.Res ? a.Res : a.dact_pre;       // optional input tile (residual / GELU' argument) staged through LDS in the output layout
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (a.O2) {                                             // pre-activation copy (kept for the backward) goes out first
+#pragma unroll
+            for (int jj = 0; jj < Stage::HFN; ++jj) {
+                const int j = h * Stage::HFN + jj;
+#pragma unroll
+                for (int i = 0; i < FM; ++i) {
+                    const float v[4] = {acc[i][j][0] + bias4[i].x, acc[i][j][1] + bias4[i].y, acc[i][j][2] + bias4[i].z, acc[i][j][3] + bias4[i].w};
+                    *st.slot(jj, i) = pack4(v);
+                }
             }
+            lds_barrier();
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) st.out(a.O2, h, it);
+            lds_barrier();
         }
-        // no barrier: the staged store below does not touch `red`
-    }
-    conv_stamp(a, 5);     // stats done
-
-    // ---- lean path: plain convolution (optionally + residual), interior tile, natural output addressing ----
-    // LIN == 4: the lean path with the output addressing of a stride-2 data gradient's parity class (GatherGeom::sub): the pixel rows of
-    // the tile scatter to every second position of every second image row, each still TM * 2 contiguous bytes.  Its own instantiations
-    // (the sub-problems went through the general path before: 8-byte stores per lane, per-element residual loads; layer2's downsample
-    // data gradient 169 us against 71 us forward), so that the hot convolution instantiations stay as they are.
-    constexpr bool SUB = LIN == 4;
-    const bool plain = LIN != 3 && LIN != 5 && !a.O2 && a.act == 0 && !a.dact_pre && !a.row_scale && (SUB || !a.g.sub) && (a.Cm & 7) == 0;   // bias (linear layers) is folded in below
-    // the linear layers' GELU / pre-activation copy (O2) / GELU' factor take a second staged block further down, kept apart so that the
-    // convolutions' path stays as lean as it was (folding them into one block cost the ResNet step 0.8 ms)
-    // (only in the LIN instantiations of the kernels: compiled into every kernel it changed the convolutions' register allocation and
-    // cost the ResNet step 0.4 ms even when never taken)
-    const bool plain_ext = LIN == 1 && !plain && !a.g.sub && (a.Cm & 7) == 0 && !(a.Res && a.dact_pre);
-    const bool interior = (tm + 1) * TM <= a.Cm && (tn + 1) * TN <= a.P;
-    if constexpr (!EVEN) {
-        if (interior && LIN != 3 && LIN != 5 && !a.g.sub && (a.Cm & 7) == 0 && !(a.Res && a.dact_pre) && (unsigned long long)a.P * a.Cm * 2ull < 0xffffffffull) { conv_epilogue_cols<TM, TN, FM_, FN_, WNW, NT>(a, acc, tm, tn, smem, wm, wn); return; }
-    }
-    if constexpr (EVEN) if (plain && interior) {
-        constexpr int ROWB = TM * 2 + 32;                       // LDS row pitch in bytes (+32: spreads the 8-byte accesses over banks)
-        constexpr int HFN = FN_ / 2, WROWS = HFN * 16, ROWS = TN / 2, CPR = TM / 8, ITERS = ROWS * CPR / NT;
-        static_assert(ROWS * CPR % NT == 0 && NT % CPR == 0, "staged store: threads must tile the half evenly");
-        char* stage = reinterpret_cast<char*>(smem);
-        char* my_stage = stage + (wn * WROWS + (lane & 15)) * ROWB + mb * 2;              // + jj*16*ROWB + i*32
-        const int ch = threadIdx.x % CPR, lp0 = threadIdx.x / CPR;                        // read-out: 16-byte chunk / first row
-        static_assert(ROWS * ROWB == STAGE_BYTES, "layout of the partial sums behind the staged tile");
-        float4 bias4[Cfg::FM];                                                            // this lane's 4 channels of every 16-row block
+        if (in_tile) {
 #pragma unroll
-        for (int i = 0; i < Cfg::FM; ++i)
-            bias4[i] = a.bias ? *reinterpret_cast<const float4*>(a.bias + tm * TM + mb + i * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int it = 0; it < ITERS; ++it) *st.chunk(it) = st.in(in_tile, h, it);
+            lds_barrier_vm();                                   // the loaded tile is visible to every wave
+        }
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const size_t gbase = ((size_t)(tn * TN + h * WROWS) * a.Cm + tm * TM + ch * 8) * 2;     // bytes; + pixel q * Cm * 2
-            auto row_bytes = [&](int q) -> size_t {             // byte offset of this thread's chunk of tile pixel q (of half h)
-                if constexpr (SUB) return (out_pixel(a.g, tn * TN + h * WROWS + q) * a.Cm + tm * TM + ch * 8) * 2;
-                else return gbase + (size_t)q * a.Cm * 2;
-            };
-            if (a.Res) {                                        // residual tile -> LDS with 16-byte loads, same layout as the output
-                unsigned rm[ITERS];                             // (mask bytes requested together: see the fused output stage below)
-                if (a.res_mask) {
+        for (int jj = 0; jj < Stage::HFN; ++jj) {
+            const int j = h * Stage::HFN + jj;
 #pragma unroll
-                    for (int it = 0; it < ITERS; ++it) {
-                        const int lp = lp0 + it * (NT / CPR);
-                        rm[it] = a.res_mask[row_bytes((lp / WROWS) * (FN_ * 16) + (lp % WROWS)) >> 4];
-                    }
+            for (int i = 0; i < FM; ++i) {
+                float v[4] = {acc[i][j][0] + bias4[i].x, acc[i][j][1] + bias4[i].y, acc[i][j][2] + bias4[i].z, acc[i][j][3] + bias4[i].w};
+                uint2* slot = st.slot(jj, i);
+                if (a.act == 1) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) v[t] = gelu_f(v[t]);
                 }
-#pragma unroll
-                for (int it = 0; it < ITERS; ++it) {
-                    const int lp = lp0 + it * (NT / CPR);
-                    const int q = (lp / WROWS) * (FN_ * 16) + (lp % WROWS);
-                    const size_t rb = row_bytes(q);
-                    uint4 rv = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.Res) + rb);
-                    if (a.res_mask) {                           // 16 bytes = 8 channels = one mask byte
-                        const unsigned m = rm[it];
-                        rv.x = gate_bf16x2(rv.x, m); rv.y = gate_bf16x2(rv.y, m >> 2); rv.z = gate_bf16x2(rv.z, m >> 4); rv.w = gate_bf16x2(rv.w, m >> 6);
-                    }
-                    *reinterpret_cast<uint4*>(stage + lp * ROWB + ch * 16) = rv;
+                if (a.row_scale) {                              // DropPath: the whole branch output (bias included) times its sample's factor
+                    const float rs = a.row_scale[tn * TN + h * Stage::WROWS + wn * (FN * 16) + jj * 16 + (lane & 15)];
+                    v[0] *= rs; v[1] *= rs; v[2] *= rs; v[3] *= rs;
                 }
-                lds_barrier_vm();                               // the loaded residual is visible to every wave
-            }
-#pragma unroll
-            for (int jj = 0; jj < HFN; ++jj) {
-                const int j = h * HFN + jj;
-#pragma unroll
-                for (int i = 0; i < Cfg::FM; ++i) {
-                    float v0 = acc[i][j][0] + bias4[i].x, v1 = acc[i][j][1] + bias4[i].y, v2 = acc[i][j][2] + bias4[i].z, v3 = acc[i][j][3] + bias4[i].w;
-                    uint2* slot = reinterpret_cast<uint2*>(my_stage + jj * 16 * ROWB + i * 32);
+                if (in_tile) {
+                    float x4[4];
+                    unpack4(*slot, x4);
                     if (a.Res) {
-                        const uint2 rv = *slot;
-                        v0 += bf16_bits_to_f32(rv.x & 0xffffu); v1 += bf16_bits_to_f32(rv.x >> 16);
-                        v2 += bf16_bits_to_f32(rv.y & 0xffffu); v3 += bf16_bits_to_f32(rv.y >> 16);
+                        v[0] += x4[0]; v[1] += x4[1]; v[2] += x4[2]; v[3] += x4[3];
+                    } else {
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) v[t] *= gelu_grad_f(x4[t]);
                     }
-                    *slot = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
                 }
+                *slot = pack4(v);
             }
-            lds_barrier();
-            conv_stamp(a, 6 + 2 * h);   // half staged
+        }
+        lds_barrier();
+        conv_stamp(a, 6 + 2 * h);   // half staged
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) st.out(a.O, h, it);
+        conv_stamp(a, 7 + 2 * h);   // half's stores issued
+        if (h == 0) lds_barrier();                              // the LDS reads are done before the second half overwrites them
+    }
+}
+// ---- fused output stage (see IGemmArgs; Epi::FUSED, and FULL = false: Epi::FUSED_LEAN), staged like the lean path; interior tile, natural
+// addressing.  No residual mask: conv_choose refuses res_mask beside a fused-stage field.
+template <bool FULL, int TM, int TN, int FM, int FN, int WNW, int NT>
+__device__ __forceinline__ void epi_store_fused(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wn, int mb) {
+    using Stage = EpiStage<false, TM, TN, FM, FN, WNW, NT>;
+    constexpr int ITERS = Stage::ITERS;
+    const Stage st(a, tm, tn, smem, wn, mb);
+    const uint16_t* const Res = FULL ? a.Res : nullptr;
+    const uint8_t* const out_mask = FULL ? a.out_mask : nullptr;
+    uint8_t* const bits_out = FULL ? a.bits_out : nullptr;
+    float4 sc4[FM], sh4[FM];
+#pragma unroll
+    for (int i = 0; i < FM; ++i) { sc4[i] = make_float4(1.f, 1.f, 1.f, 1.f); sh4[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
+    if (a.out_scale) load_rows4(sc4, a.out_scale + tm * TM + mb);        // one branch per batch of loads (as for the mask bytes below)
+    if (a.out_shift) load_rows4(sh4, a.out_shift + tm * TM + mb);
+    if (a.bias) {
+        float4 bi4[FM];
+        load_rows4(bi4, a.bias + tm * TM + mb);
+#pragma unroll
+        for (int i = 0; i < FM; ++i) { sh4[i].x += bi4[i].x; sh4[i].y += bi4[i].y; sh4[i].z += bi4[i].z; sh4[i].w += bi4[i].w; }
+    }
+    // the residual tile of BOTH halves is requested up front: the second half's loads fly while the first half is formed and stored
+    // (requested per half they exposed one HBM round trip per half: these kernels are short-K, their epilogue is most of their time)
+    constexpr bool PRE = FULL && NT == 256;          // (the 512-thread 128 x 256 kernel would leave its 128-register budget = two workgroups per CU)
+    uint4 rpre[2][PRE ? ITERS : 1];
+    if (PRE && Res) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) rpre[h][it] = st.in(Res, h, it);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        // the mask bytes of this half, requested together and early: "if (mask) m = mask[..]" inside the unrolled loops below compiled to a
+        // branch and a wait around every byte load (up to 16 dependent round trips per tile; MI355X guide, the per-element select trap)
+        unsigned om[ITERS];
+        if (out_mask) {
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) om[it] = out_mask[st.offset(h, it) >> 4];
+        }
+        if (Res) {
 #pragma unroll
             for (int it = 0; it < ITERS; ++it) {
-                const int lp = lp0 + it * (NT / CPR);
-                const int q = (lp / WROWS) * (FN_ * 16) + (lp % WROWS);                  // pixel inside the tile, minus h*WROWS
-                *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + row_bytes(q)) =
-                    *reinterpret_cast<const uint4*>(stage + lp * ROWB + ch * 16);
+                uint4 rv;
+                if constexpr (PRE) rv = rpre[h][it];
+                else rv = st.in(Res, h, it);
+                *st.chunk(it) = rv;
             }
-            conv_stamp(a, 7 + 2 * h);   // half's stores issued
-            if (h == 0) lds_barrier();                          // the LDS reads are done before the second half overwrites them
+            if constexpr (PRE) lds_barrier();                   // (the register dependence waits for the loads of this half only)
+            else lds_barrier_vm();
         }
-        return;
+#pragma unroll
+        for (int jj = 0; jj < Stage::HFN; ++jj) {
+            const int j = h * Stage::HFN + jj;
+#pragma unroll
+            for (int i = 0; i < FM; ++i) {
+                float v[4] = {acc[i][j][0] * sc4[i].x + sh4[i].x, acc[i][j][1] * sc4[i].y + sh4[i].y, acc[i][j][2] * sc4[i].z + sh4[i].z, acc[i][j][3] * sc4[i].w + sh4[i].w};
+                uint2* slot = st.slot(jj, i);
+                if (Res) {
+                    float r4[4];
+                    unpack4(*slot, r4);
+                    if (a.res_scale) {                          // (loaded per use: L1-resident; held across the tile it cost 16 registers and spills)
+                        const float4 rs = *reinterpret_cast<const float4*>(a.res_scale + tm * TM + mb + i * 16);
+                        v[0] += rs.x * r4[0]; v[1] += rs.y * r4[1]; v[2] += rs.z * r4[2]; v[3] += rs.w * r4[3];
+                    } else {
+                        v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3];
+                    }
+                }
+                if (a.out_relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                *slot = pack4(v);
+            }
+        }
+        lds_barrier();
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const size_t ob = st.offset(h, it);
+            uint4 v = *st.chunk(it);
+            if (out_mask) gate_bf16x8(v, om[it]);
+            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + ob) = v;
+            if (bits_out) bits_out[ob >> 4] = (uint8_t)(pos_bits_bf16x2(v.x) | (pos_bits_bf16x2(v.y) << 2) | (pos_bits_bf16x2(v.z) << 4) | (pos_bits_bf16x2(v.w) << 6));
+        }
+        if (h == 0) lds_barrier();
     }
-
-    if constexpr (LIN == 1 && EVEN) if (plain_ext && interior) {            // linear-layer extras: GELU, pre-activation copy, GELU' factor
-        constexpr int ROWB = TM * 2 + 32;                       // LDS row pitch in bytes (+32: spreads the 8-byte accesses over banks)
-        constexpr int HFN = FN_ / 2, WROWS = HFN * 16, ROWS = TN / 2, CPR = TM / 8, ITERS = ROWS * CPR / NT;
-        static_assert(ROWS * CPR % NT == 0 && NT % CPR == 0, "staged store: threads must tile the half evenly");
-        char* stage = reinterpret_cast<char*>(smem);
-        char* my_stage = stage + (wn * WROWS + (lane & 15)) * ROWB + mb * 2;              // + jj*16*ROWB + i*32
-        const int ch = threadIdx.x % CPR, lp0 = threadIdx.x / CPR;                        // read-out: 16-byte chunk / first row
-        static_assert(ROWS * ROWB == STAGE_BYTES, "layout of the partial sums behind the staged tile");
-        float4 bias4[Cfg::FM];                                                            // this lane's 4 channels of every 16-row block
+}
+// ---- general path: edge tiles, Cm % 8 != 0, parity sub-problems outside Epi::PARITY, the linear layers' extras outside Epi::LIN; 8-byte
+// stores with per-element predicates.  What MODE compiles in: the extras under LIN and GENERAL, the fused stage under FUSED, its scale / shift /
+// ReLU under FUSED_LEAN; the residual everywhere but FUSED_LEAN, its mask everywhere but FUSED (dali_conv2d_dgrad's edge tiles).
+template <Epi MODE, int TM, int TN, int FM, int FN>
+__device__ __forceinline__ void epi_store_general(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, int mb, int nb) {
+    const int lane = threadIdx.x & 63;
 #pragma unroll
-        for (int i = 0; i < Cfg::FM; ++i)
-            bias4[i] = a.bias ? *reinterpret_cast<const float4*>(a.bias + tm * TM + mb + i * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const uint16_t* in_tile = a.Res ? a.Res : a.dact_pre;       // optional input tile staged through LDS in the output layout
-        auto store_half = [&](uint16_t* dst, size_t gbase) {
-#pragma unroll
-            for (int it = 0; it < ITERS; ++it) {
-                const int lp = lp0 + it * (NT / CPR);
-                const int q = (lp / WROWS) * (FN_ * 16) + (lp % WROWS);                  // pixel inside the tile, minus h*WROWS
-                *reinterpret_cast<uint4*>(reinterpret_cast<char*>(dst) + gbase + (size_t)q * a.Cm * 2) =
-                    *reinterpret_cast<const uint4*>(stage + lp * ROWB + ch * 16);
-            }
-        };
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const size_t gbase = ((size_t)(tn * TN + h * WROWS) * a.Cm + tm * TM + ch * 8) * 2;     // bytes; + pixel q * Cm * 2
-            if (a.O2) {                                         // pre-activation copy (kept for the backward) goes out first
-#pragma unroll
-                for (int jj = 0; jj < HFN; ++jj) {
-                    const int j = h * HFN + jj;
-#pragma unroll
-                    for (int i = 0; i < Cfg::FM; ++i)
-                        *reinterpret_cast<uint2*>(my_stage + jj * 16 * ROWB + i * 32) =
-                            make_uint2(pack_bf16x2(acc[i][j][0] + bias4[i].x, acc[i][j][1] + bias4[i].y), pack_bf16x2(acc[i][j][2] + bias4[i].z, acc[i][j][3] + bias4[i].w));
-                }
-                lds_barrier();
-                store_half(a.O2, gbase);
-                lds_barrier();
-            }
-            if (in_tile) {                                      // residual / GELU' argument tile -> LDS with 16-byte loads
-#pragma unroll
-                for (int it = 0; it < ITERS; ++it) {
-                    const int lp = lp0 + it * (NT / CPR);
-                    const int q = (lp / WROWS) * (FN_ * 16) + (lp % WROWS);
-                    const size_t rb = gbase + (size_t)q * a.Cm * 2;
-                    uint4 rv = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(in_tile) + rb);
-                    if (a.Res && a.res_mask) {                  // 16 bytes = 8 channels = one mask byte
-                        const unsigned m = a.res_mask[rb >> 4];
-                        rv.x = gate_bf16x2(rv.x, m); rv.y = gate_bf16x2(rv.y, m >> 2); rv.z = gate_bf16x2(rv.z, m >> 4); rv.w = gate_bf16x2(rv.w, m >> 6);
-                    }
-                    *reinterpret_cast<uint4*>(stage + lp * ROWB + ch * 16) = rv;
-                }
-                lds_barrier_vm();                               // the loaded tile is visible to every wave
-            }
-#pragma unroll
-            for (int jj = 0; jj < HFN; ++jj) {
-                const int j = h * HFN + jj;
-#pragma unroll
-                for (int i = 0; i < Cfg::FM; ++i) {
-                    float v[4] = {acc[i][j][0] + bias4[i].x, acc[i][j][1] + bias4[i].y, acc[i][j][2] + bias4[i].z, acc[i][j][3] + bias4[i].w};
-                    uint2* slot = reinterpret_cast<uint2*>(my_stage + jj * 16 * ROWB + i * 32);
-                    if (a.act == 1) {
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) v[t] = gelu_f(v[t]);
-                    }
-                    if (a.row_scale) {                          // DropPath: the whole branch output (bias included) times its sample's factor
-                        const float rs = a.row_scale[tn * TN + h * WROWS + wn * (FN_ * 16) + jj * 16 + (lane & 15)];
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) v[t] *= rs;
-                    }
-                    if (in_tile) {
-                        const uint2 rv = *slot;
-                        const float x4[4] = {bf16_bits_to_f32(rv.x & 0xffffu), bf16_bits_to_f32(rv.x >> 16), bf16_bits_to_f32(rv.y & 0xffffu), bf16_bits_to_f32(rv.y >> 16)};
-                        if (a.Res) {
-#pragma unroll
-                            for (int t = 0; t < 4; ++t) v[t] += x4[t];
-                        } else {
-#pragma unroll
-                            for (int t = 0; t < 4; ++t)
-                                v[t] *= gelu_grad_f(x4[t]);
-                        }
-                    }
-                    *slot = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-                }
-            }
-            lds_barrier();
-            conv_stamp(a, 6 + 2 * h);   // half staged
-            store_half(a.O, gbase);
-            conv_stamp(a, 7 + 2 * h);   // half's stores issued
-            if (h == 0) lds_barrier();                          // the LDS reads are done before the second half overwrites them
-        }
-        return;
-    }
-
-    // LIN == 5: the fused output stage WITHOUT residual, masks and mask bits (scale / shift / bias / ReLU only): the inference forward's
-    // conv + BatchNorm + ReLU launches on the 3x3 and narrow kernels, whose register budgets the full stage's residual prefetch overflowed
-    if constexpr ((LIN == 3 || LIN == 5) && EVEN) if (interior && !a.g.sub && (a.Cm & 7) == 0) {     // fused output stage (see IGemmArgs): staged like the lean path
-        constexpr bool FULL = LIN == 3;
-        const uint16_t* const Res = FULL ? a.Res : nullptr;
-        const uint8_t* const out_mask = FULL ? a.out_mask : nullptr;
-        const uint8_t* const res_mask = FULL ? a.res_mask : nullptr;
-        uint8_t* const bits_out = FULL ? a.bits_out : nullptr;
-        constexpr int ROWB = TM * 2 + 32;
-        constexpr int HFN = FN_ / 2, WROWS = HFN * 16, ROWS = TN / 2, CPR = TM / 8, ITERS = ROWS * CPR / NT;
-        static_assert(ROWS * CPR % NT == 0 && NT % CPR == 0, "staged store: threads must tile the half evenly");
-        char* stage = reinterpret_cast<char*>(smem);
-        char* my_stage = stage + (wn * WROWS + (lane & 15)) * ROWB + mb * 2;
-        const int ch = threadIdx.x % CPR, lp0 = threadIdx.x / CPR;
-        float4 sc4[Cfg::FM], sh4[Cfg::FM];
-#pragma unroll
-        for (int i = 0; i < Cfg::FM; ++i) { sc4[i] = make_float4(1.f, 1.f, 1.f, 1.f); sh4[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
-        if (a.out_scale) {                                      // one branch per batch of loads (as for the mask bytes below)
-#pragma unroll
-            for (int i = 0; i < Cfg::FM; ++i) sc4[i] = *reinterpret_cast<const float4*>(a.out_scale + tm * TM + mb + i * 16);
-        }
-        if (a.out_shift) {
-#pragma unroll
-            for (int i = 0; i < Cfg::FM; ++i) sh4[i] = *reinterpret_cast<const float4*>(a.out_shift + tm * TM + mb + i * 16);
-        }
-        if (a.bias) {
-            float4 bi4[Cfg::FM];
-#pragma unroll
-            for (int i = 0; i < Cfg::FM; ++i) bi4[i] = *reinterpret_cast<const float4*>(a.bias + tm * TM + mb + i * 16);
-#pragma unroll
-            for (int i = 0; i < Cfg::FM; ++i) { sh4[i].x += bi4[i].x; sh4[i].y += bi4[i].y; sh4[i].z += bi4[i].z; sh4[i].w += bi4[i].w; }
-        }
-        // the residual tile of BOTH halves is requested up front: the second half's loads fly while the first half is formed and stored
-        // (requested per half they exposed one HBM round trip per half: these kernels are short-K, their epilogue is most of their time)
-        constexpr bool PRE = FULL && NT == 256;          // (the 512-thread 128 x 256 kernel would leave its 128-register budget = two workgroups per CU)
-        uint4 rpre[2][PRE ? ITERS : 1];
-        if (PRE && Res) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const size_t gbase = ((size_t)(tn * TN + h * WROWS) * a.Cm + tm * TM + ch * 8) * 2;
-#pragma unroll
-                for (int it = 0; it < ITERS; ++it) {
-                    const int lp = lp0 + it * (NT / CPR);
-                    const int q = (lp / WROWS) * (FN_ * 16) + (lp % WROWS);
-                    rpre[h][it] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Res) + gbase + (size_t)q * a.Cm * 2);
-                }
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const size_t gbase = ((size_t)(tn * TN + h * WROWS) * a.Cm + tm * TM + ch * 8) * 2;     // bytes; + pixel q * Cm * 2
-            // the mask bytes of this half, requested together and early: "if (mask) m = mask[..]" inside the unrolled loops below compiled to a
-            // branch and a wait around every byte load (up to 16 dependent round trips per tile; MI355X guide, the per-element select trap)
-            unsigned om[ITERS], rm[ITERS];
-            if (out_mask) {
-#pragma unroll
-                for (int it = 0; it < ITERS; ++it) {
-                    const int lp = lp0 + it * (NT / CPR);
-                    om[it] = out_mask[(gbase + (size_t)((lp / WROWS) * (FN_ * 16) + (lp % WROWS)) * a.Cm * 2) >> 4];
-                }
-            }
-            if (Res && res_mask) {
-#pragma unroll
-                for (int it = 0; it < ITERS; ++it) {
-                    const int lp = lp0 + it * (NT / CPR);
-                    rm[it] = res_mask[(gbase + (size_t)((lp / WROWS) * (FN_ * 16) + (lp % WROWS)) * a.Cm * 2) >> 4];
-                }
-            }
-            if (Res) {
-#pragma unroll
-                for (int it = 0; it < ITERS; ++it) {
-                    const int lp = lp0 + it * (NT / CPR);
-                    const int q = (lp / WROWS) * (FN_ * 16) + (lp % WROWS);
-                    const size_t rb = gbase + (size_t)q * a.Cm * 2;
-                    uint4 rv;
-                    if constexpr (PRE) rv = rpre[h][it];
-                    else rv = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Res) + rb);
-                    if (res_mask) {
-                        const unsigned m = rm[it];
-                        rv.x = gate_bf16x2(rv.x, m); rv.y = gate_bf16x2(rv.y, m >> 2); rv.z = gate_bf16x2(rv.z, m >> 4); rv.w = gate_bf16x2(rv.w, m >> 6);
-                    }
-                    *reinterpret_cast<uint4*>(stage + lp * ROWB + ch * 16) = rv;
-                }
-                if constexpr (PRE) lds_barrier();               // (the register dependence waits for the loads of this half only)
-                else lds_barrier_vm();
-            }
-#pragma unroll
-            for (int jj = 0; jj < HFN; ++jj) {
-                const int j = h * HFN + jj;
-#pragma unroll
-                for (int i = 0; i < Cfg::FM; ++i) {
-                    float v0 = acc[i][j][0] * sc4[i].x + sh4[i].x, v1 = acc[i][j][1] * sc4[i].y + sh4[i].y;
-                    float v2 = acc[i][j][2] * sc4[i].z + sh4[i].z, v3 = acc[i][j][3] * sc4[i].w + sh4[i].w;
-                    uint2* slot = reinterpret_cast<uint2*>(my_stage + jj * 16 * ROWB + i * 32);
-                    if (Res) {
-                        const uint2 rv = *slot;
-                        if (a.res_scale) {                      // (loaded per use: L1-resident; held across the tile it cost 16 registers and spills)
-                            const float4 rs = *reinterpret_cast<const float4*>(a.res_scale + tm * TM + mb + i * 16);
-                            v0 += rs.x * bf16_bits_to_f32(rv.x & 0xffffu); v1 += rs.y * bf16_bits_to_f32(rv.x >> 16);
-                            v2 += rs.z * bf16_bits_to_f32(rv.y & 0xffffu); v3 += rs.w * bf16_bits_to_f32(rv.y >> 16);
-                        } else {
-                            v0 += bf16_bits_to_f32(rv.x & 0xffffu); v1 += bf16_bits_to_f32(rv.x >> 16);
-                            v2 += bf16_bits_to_f32(rv.y & 0xffffu); v3 += bf16_bits_to_f32(rv.y >> 16);
-                        }
-                    }
-                    if (a.out_relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-                    *slot = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
-                }
-            }
-            lds_barrier();
-#pragma unroll
-            for (int it = 0; it < ITERS; ++it) {
-                const int lp = lp0 + it * (NT / CPR);
-                const int q = (lp / WROWS) * (FN_ * 16) + (lp % WROWS);
-                const size_t ob = gbase + (size_t)q * a.Cm * 2;
-                uint4 v = *reinterpret_cast<const uint4*>(stage + lp * ROWB + ch * 16);
-                if (out_mask) {
-                    const unsigned m = om[it];
-                    v.x = gate_bf16x2(v.x, m); v.y = gate_bf16x2(v.y, m >> 2); v.z = gate_bf16x2(v.z, m >> 4); v.w = gate_bf16x2(v.w, m >> 6);
-                }
-                *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + ob) = v;
-                if (bits_out) bits_out[ob >> 4] = (uint8_t)(pos_bits_bf16x2(v.x) | (pos_bits_bf16x2(v.y) << 2) | (pos_bits_bf16x2(v.z) << 4) | (pos_bits_bf16x2(v.w) << 6));
-            }
-            if (h == 0) lds_barrier();
-        }
-        return;
-    }
-
-    // ---- general path: edge tiles, linear-layer epilogues (bias / GELU / GELU' / second output), parity sub-problems ----
-#pragma unroll
-    for (int j = 0; j < Cfg::FN; ++j) {
+    for (int j = 0; j < FN; ++j) {
         const int p = tn * TN + nb + j * 16;
         const size_t opix = (p < a.P) ? out_pixel(a.g, p) : 0;
 #pragma unroll
-        for (int i = 0; i < Cfg::FM; ++i) {
+        for (int i = 0; i < FM; ++i) {
             const int c = tm * TM + mb + i * 16;
             unsigned nib = 0;
             if (p < a.P && c < a.Cm) {      // Cm is a multiple of 4: the 4 channels are all valid
                 float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
                 const size_t o = opix * a.Cm + c;
-                if constexpr (LIN == 3 || LIN == 5) {
+                if constexpr (epi_fused(MODE)) {
                     if (a.out_scale) { const float4 sv = *reinterpret_cast<const float4*>(a.out_scale + c); v[0] *= sv.x; v[1] *= sv.y; v[2] *= sv.z; v[3] *= sv.w; }
                     if (a.out_shift) { const float4 sv = *reinterpret_cast<const float4*>(a.out_shift + c); v[0] += sv.x; v[1] += sv.y; v[2] += sv.z; v[3] += sv.w; }
                 }
@@ -716,43 +681,40 @@ __device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&ac
                     const float4 bv = *reinterpret_cast<const float4*>(a.bias + c);
                     v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
                 }
-                if constexpr (LIN == 1 || LIN == 2) {
-                if (a.O2) *reinterpret_cast<uint2*>(a.O2 + o) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-                if (a.act == 1) {
+                if constexpr (MODE == Epi::LIN || MODE == Epi::GENERAL) {
+                    if (a.O2) *reinterpret_cast<uint2*>(a.O2 + o) = pack4(v);
+                    if (a.act == 1) {
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) v[t] = gelu_f(v[t]);
-                }
-                if (a.dact_pre) {
-                    const uint2 pv = *reinterpret_cast<const uint2*>(a.dact_pre + o);
-                    const float x4[4] = {bf16_bits_to_f32(pv.x & 0xffffu), bf16_bits_to_f32(pv.x >> 16), bf16_bits_to_f32(pv.y & 0xffffu),
-                                         bf16_bits_to_f32(pv.y >> 16)};
+                        for (int t = 0; t < 4; ++t) v[t] = gelu_f(v[t]);
+                    }
+                    if (a.dact_pre) {
+                        float x4[4];
+                        unpack4(*reinterpret_cast<const uint2*>(a.dact_pre + o), x4);
 #pragma unroll
-                    for (int t = 0; t < 4; ++t)
-                        v[t] *= gelu_grad_f(x4[t]);
+                        for (int t = 0; t < 4; ++t) v[t] *= gelu_grad_f(x4[t]);
+                    }
+                    if (a.row_scale) {
+                        const float rs = a.row_scale[p];
+                        v[0] *= rs; v[1] *= rs; v[2] *= rs; v[3] *= rs;
+                    }
                 }
-                if (a.row_scale) {
-                    const float rs = a.row_scale[p];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) v[t] *= rs;
-                }
-                }
-                if (LIN != 5 && a.Res) {
+                if (MODE != Epi::FUSED_LEAN && a.Res) {
                     uint2 rv = *reinterpret_cast<const uint2*>(a.Res + o);
-                    if (a.res_mask) {                           // o is a multiple of 4: this lane's nibble of the mask byte
+                    if constexpr (MODE != Epi::FUSED) if (a.res_mask) {         // o is a multiple of 4: this lane's nibble of the mask byte
                         const unsigned m = a.res_mask[o >> 3] >> (o & 4);
                         rv.x = gate_bf16x2(rv.x, m); rv.y = gate_bf16x2(rv.y, m >> 2);
                     }
-                    float r4[4] = {bf16_bits_to_f32(rv.x & 0xffffu), bf16_bits_to_f32(rv.x >> 16), bf16_bits_to_f32(rv.y & 0xffffu), bf16_bits_to_f32(rv.y >> 16)};
-                    if constexpr (LIN == 3) if (a.res_scale) {
+                    float r4[4];
+                    unpack4(rv, r4);
+                    if constexpr (MODE == Epi::FUSED) if (a.res_scale) {
                         const float4 rs = *reinterpret_cast<const float4*>(a.res_scale + c);
                         r4[0] *= rs.x; r4[1] *= rs.y; r4[2] *= rs.z; r4[3] *= rs.w;
                     }
                     v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3];
                 }
-                uint2 ov = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-                if constexpr (LIN == 5) { if (a.out_relu) ov = make_uint2(pack_bf16x2(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)), pack_bf16x2(fmaxf(v[2], 0.f), fmaxf(v[3], 0.f))); }
-                if constexpr (LIN == 3) {
-                    if (a.out_relu) ov = make_uint2(pack_bf16x2(fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)), pack_bf16x2(fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)));
+                if constexpr (epi_fused(MODE)) if (a.out_relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                uint2 ov = pack4(v);
+                if constexpr (MODE == Epi::FUSED) {
                     if (a.out_mask) {
                         const unsigned m = a.out_mask[o >> 3] >> (o & 4);
                         ov.x = gate_bf16x2(ov.x, m); ov.y = gate_bf16x2(ov.y, m >> 2);
@@ -761,7 +723,7 @@ __device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&ac
                 }
                 *reinterpret_cast<uint2*>(a.O + o) = ov;
             }
-            if constexpr (LIN == 3) {
+            if constexpr (MODE == Epi::FUSED) {
                 // this lane's 4 mask bits and those of lane ^ 16 (the other half of the same byte: Cm % 8 == 0 is required) -> one byte store
                 const unsigned other = __shfl_xor(nib, 16, 64);
                 if (a.bits_out && p < a.P && c < a.Cm && ((lane >> 4) & 1) == 0) a.bits_out[(opix * a.Cm + c) >> 3] = (uint8_t)(nib | (other << 4));
@@ -769,10 +731,39 @@ __device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&ac
         }
     }
 }
-template <class Cfg, int LIN = 2>
+
+// The output stage of every forward / data-gradient / linear-layer kernel: the statistics, then exactly one store path, in this order of
+// precedence.  Precondition: the caller has synchronised after its main loop (every kernel ends the loop with a barrier that follows each wave's
+// last fragment read), so smem is free.
+template <int TM, int TN, int FM, int FN, int WNW, int NT, Epi MODE = Epi::GENERAL>
+__device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wm, int wn) {
+    constexpr bool EVEN = FN % 2 == 0;       // the half-tile stores split every wave's column blocks in two; odd FN: conv_epilogue_cols
+    constexpr bool FUSED = epi_fused(MODE), SUB = MODE == Epi::PARITY;
+    const int lane = threadIdx.x & 63;
+    const int mb = wm * (FM * 16) + (lane >> 4) * 4, nb = wn * (FN * 16) + (lane & 15);      // this lane's first channel / pixel inside the tile
+    if (a.stats) epi_stats<TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
+    conv_stamp(a, 5);     // stats done
+    const bool interior = (tm + 1) * TM <= a.Cm && (tn + 1) * TN <= a.P;
+    const bool chunks = (a.Cm & 7) == 0;                                                    // a pixel's channels are whole 16-byte chunks
+    const bool extras = a.O2 || a.act != 0 || a.dact_pre || a.row_scale;                    // a linear layer's (bias alone is folded into the lean path)
+    const bool plain = !FUSED && !extras && (SUB || !a.g.sub) && chunks;
+    const bool in_once = !(a.Res && a.dact_pre);                                            // the staged extras take one input tile
+    if constexpr (!EVEN) {
+        if (interior && !FUSED && !a.g.sub && chunks && in_once && (unsigned long long)a.P * a.Cm * 2ull < 0xffffffffull)
+            return conv_epilogue_cols<TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wm, wn);
+    } else if constexpr (FUSED) {
+        if (interior && !a.g.sub && chunks) return epi_store_fused<MODE == Epi::FUSED, TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
+    } else {
+        if (interior && plain) return epi_store_lean<SUB, TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
+        if constexpr (MODE == Epi::LIN)
+            if (interior && !plain && !a.g.sub && chunks && in_once) return epi_store_lin<TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
+    }
+    epi_store_general<MODE, TM, TN, FM, FN>(a, acc, tm, tn, mb, nb);
+}
+template <class Cfg, Epi MODE = Epi::GENERAL>
 __device__ __forceinline__ void conv_epilogue(const IGemmArgs& a, f32x4_t (&acc)[Cfg::FM][Cfg::FN], int tm, int tn, uint16_t* smem) {
     const int wave = threadIdx.x >> 6;
-    conv_epilogue_g<Cfg::TM, Cfg::TN, Cfg::FM, Cfg::FN, 2, 256, LIN>(a, acc, tm, tn, smem, wave >> 1, wave & 1);
+    conv_epilogue_g<Cfg::TM, Cfg::TN, Cfg::FM, Cfg::FN, 2, 256, MODE>(a, acc, tm, tn, smem, wave >> 1, wave & 1);
 }
 
 template <int TM, int TN, bool IN_BN>
@@ -943,8 +934,8 @@ __device__ __forceinline__ void mma_ktile(const uint16_t* sa, const uint16_t* sb
     }
 }
 
-template <int TM, int TN, int NSTAGE, int EPI = 0, bool SRC2 = false>        // EPI: 0 convolution, 1 linear-layer extras, 3 fused output stage (conv_epilogue_g)
-__global__ __launch_bounds__(256, (TM >= 128 ? (EPI == 3 ? 3 : 4) : 2)) void igemm_conv_dma_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
+template <int TM, int TN, int NSTAGE, Epi EPI = Epi::CONV, bool SRC2 = false>
+__global__ __launch_bounds__(256, (TM >= 128 ? (EPI == Epi::FUSED ? 3 : 4) : 2)) void igemm_conv_dma_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
     // 128 x 128: <= 128 VGPRs (4 waves per SIMD); the 64 x 256 shape carries twice the per-lane gather state and would spill
     using Cfg = GemmCfg<TM, TN, 1, 1, 1>;
     using Gather = ConvGather<32, TM, TN, 4, SRC2>;
@@ -991,7 +982,7 @@ __global__ __launch_bounds__(256, (TM >= 128 ? (EPI == 3 ? 3 : 4) : 2)) void ige
     __syncthreads();
     if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
 
-    conv_epilogue<Cfg, ((TM == 128 && TN == 128 && NSTAGE == 3) || EPI == 3 || EPI == 5) ? EPI : 2>(a, acc, tm, tn, smem);
+    conv_epilogue<Cfg, epi_mode((TM == 128 && TN == 128 && NSTAGE == 3) || epi_fused(EPI), EPI)>(a, acc, tm, tn, smem);
     conv_stamp_stores(a);
 }
 
@@ -1001,7 +992,7 @@ __global__ __launch_bounds__(256, (TM >= 128 ? (EPI == 3 ? 3 : 4) : 2)) void ige
 // for a 4-deep LDS ring (3 k-tiles in flight) at one block per CU.
 // (launch bounds: 4 waves per SIMD.  The 8-wave shapes are meant to run two workgroups per CU; their linear-layer instantiation compiled
 // to 130 VGPRs = 3 waves per SIMD = ONE workgroup of 8 waves per CU, and fc1 forward / fc2 data gradient ran at 440 TFLOP/s for it.)
-template <int WM, int WN, int NSTAGE, int EPI = 0>
+template <int WM, int WN, int NSTAGE, Epi EPI = Epi::CONV>
 __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_conv_wg_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
     constexpr int TM = 64 * WM, TN = 64 * WN, NW = WM * WN, NT = NW * 64;
     using Gather = ConvGather<32, TM, TN, NW, false>;
@@ -1049,7 +1040,7 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_conv_wg_kernel(IGemmArg
         st_fill = (st_fill == NSTAGE - 1) ? 0 : st_fill + 1;
     }
     __syncthreads();
-    conv_epilogue_g<TM, TN, 4, 4, WN, NT, (WM == 2 && WN == 4 && NSTAGE == 3) ? EPI : 2>(a, acc, tm, tn, smem, wm, wn);
+    conv_epilogue_g<TM, TN, 4, 4, WN, NT, epi_mode(WM == 2 && WN == 4 && NSTAGE == 3, EPI)>(a, acc, tm, tn, smem, wm, wn);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1062,7 +1053,7 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void igemm_conv_wg_kernel(IGemmArg
 // logical chunk ^ ((row >> 1) & 7): every 16-lane service group of ds_read_b128 ({0-3,12-15,20-27}, ... = 8 rows of one
 // chunk + 8 rows of the next) lands on 16 distinct 16-byte bank slots.  Needs Ck % 64 == 0.
 // ------------------------------------------------------------------------------------------------
-template <int WM, int WN, int NSTAGE, int FM = 4, int FN = 4, int EPI = 0, bool SRC2 = false>
+template <int WM, int WN, int NSTAGE, int FM = 4, int FN = 4, Epi EPI = Epi::CONV, bool SRC2 = false>
 __global__ __launch_bounds__(WM * WN * 64) void igemm_conv_k64_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
     constexpr int TM = 16 * FM * WM, TN = 16 * FN * WN, NW = WM * WN, NT = NW * 64;     // per-wave sub-tile 16 FM x 16 FN
     using Gather = ConvGather<64, TM, TN, NW, SRC2>;
@@ -1113,7 +1104,7 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_conv_k64_kernel(IGemmArgs 
     }
     __syncthreads();
     if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
-    conv_epilogue_g<TM, TN, FM, FN, WN, NT, (WM == 4 && WN == 4 && NSTAGE == 2 && FM == 4) ? EPI : 2>(a, acc, tm, tn, smem, wm, wn);
+    conv_epilogue_g<TM, TN, FM, FN, WN, NT, epi_mode(WM == 4 && WN == 4 && NSTAGE == 2 && FM == 4, EPI)>(a, acc, tm, tn, smem, wm, wn);
     conv_stamp_stores(a);
 }
 
@@ -1122,7 +1113,7 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_conv_k64_kernel(IGemmArgs 
 // costs the issuing wave 60-185 cycles in which it cannot issue MFMAs, and the feed time added to the MFMA time instead of
 // hiding under it (ablations in scripts/ablate_conv.py, same finding and same cure as pairdist_dma_kernel in eval.hip).
 // The producers leave after the last k-step; the epilogue's barriers then count the consumers only.
-template <int WM, int WN, int NP, int NSTAGE, int FM = 4, int FN = 4, int EPI = 0, bool SRC2 = false>      // EPI: as igemm_conv_dma_kernel
+template <int WM, int WN, int NP, int NSTAGE, int FM = 4, int FN = 4, Epi EPI = Epi::CONV, bool SRC2 = false>
 __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_conv_k64s_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
     constexpr int TM = 16 * FM * WM, TN = 16 * FN * WN, NC = WM * WN, NT = NC * 64;       // consumer sub-tile 16 FM x 16 FN
     using Gather = ConvGather<64, TM, TN, NP, SRC2>;
@@ -1178,7 +1169,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_conv_k64s_kernel(IG
         st_cur = (st_cur == NSTAGE - 1) ? 0 : st_cur + 1;
     }
     conv_stamp(a, 2);
-    conv_epilogue_g<TM, TN, FM, FN, WN, NT, (WM == 2 && WN == 4 && NP == 8 && NSTAGE == 3) ? EPI : 2>(a, acc, tm, tn, smem, wm, wn);
+    conv_epilogue_g<TM, TN, FM, FN, WN, NT, epi_mode(WM == 2 && WN == 4 && NP == 8 && NSTAGE == 3, EPI)>(a, acc, tm, tn, smem, wm, wn);
     conv_stamp_stores(a);
 }
 
@@ -1196,7 +1187,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_conv_k64s_kernel(IG
 // mode 0: input pixel (h - 1 + kr, w - 1 + ks); mode 1 (data gradient, stride 1): (h + 1 - kr, w + 1 - ks): the same patch, taps mirrored.
 // ------------------------------------------------------------------------------------------------
 constexpr int HALO64_PX = 344;                           // >= (256 / W + 2) * (W + 2) for W = 16 (324), 32 (340); 43 DMA pieces of 8 pixels
-template <int NSTAGE, int EPI = 0>                    // EPI = 3: the fused output stage (IGemmArgs::out_scale ...), its own instantiation
+template <int NSTAGE, Epi EPI = Epi::CONV>
 __global__ __launch_bounds__(512, 4) void igemm_conv_halo64_kernel(IGemmArgs a, int tiles_n) {
     constexpr int TM = 64, TN = 256, NC = 4, NP = 4, NT = NC * 64, FM = 4, FN = 4;
     constexpr int A_ELEMS = TM * 64, RING = NSTAGE * A_ELEMS, NPIECE = HALO64_PX / 8, PPW = (NPIECE + NP - 1) / NP;   // 43 pieces, 11 per producer
@@ -1296,7 +1287,7 @@ __global__ __launch_bounds__(512, 4) void igemm_conv_halo64_kernel(IGemmArgs a, 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // my reads of this weight stage are complete before it can be refilled
         __builtin_amdgcn_s_barrier();
     }
-    conv_epilogue_g<TM, TN, FM, FN, 4, NT, (EPI == 3 || EPI == 5) ? EPI : 2>(a, acc, 0, tn, smem, 0, wn);
+    conv_epilogue_g<TM, TN, FM, FN, 4, NT, epi_mode(epi_fused(EPI), EPI)>(a, acc, 0, tn, smem, 0, wn);
 }
 
 }  // namespace dali
@@ -2384,23 +2375,22 @@ constexpr int REG128_LDS = GemmCfg<128, 128, 1, 1, 1>::LDS_BYTES, REG64_LDS = Ge
 constexpr int DMA128_LDS = REG128_LDS / 2 * 3, DMA64_LDS = REG64_LDS / 2 * 3;                                          // LDS-DMA: 3 stages
 constexpr int HALO64_LDS = (3 * 64 * 64 + HALO64_PX * 64) * 2;                                                         // 3 weight stages + the halo patch
 
-// Forward, data gradient and linear layers (IGemmArgs).  EPI 1: linear-layer extras; 3: the fused output stage; 4: the parity-class store with
-// scattered pixel rows; 5: the fused stage's scale / shift / bias / ReLU alone.  SRC2: a second operand tensor (IGemmArgs::X2).
+// Forward, data gradient and linear layers (IGemmArgs).  The output stage's mode: enum Epi.  SRC2: a second operand tensor (IGemmArgs::X2).
 static const GemmKernel
     // 128 x 128 / 4 waves, k-tile 32: register-staged (an operand transform, tensors beyond 2 GiB) and LDS-DMA
     CONV128_BN{kfn(&igemm_conv_kernel<128, 128, true>), 256, REG128_LDS, 128, 128, GRID_XCD},
     CONV128{kfn(&igemm_conv_kernel<128, 128, false>), 256, REG128_LDS, 128, 128, GRID_XCD},
     DMA128{kfn(&igemm_conv_dma_kernel<128, 128, 3>), 256, DMA128_LDS, 128, 128, GRID_XCD},
-    DMA128_LIN{kfn(&igemm_conv_dma_kernel<128, 128, 3, 1>), 256, DMA128_LDS, 128, 128, GRID_XCD},
-    DMA128_FUSED{kfn(&igemm_conv_dma_kernel<128, 128, 3, 3>), 256, DMA128_LDS, 128, 128, GRID_XCD},
-    DMA128_CLS{kfn(&igemm_conv_dma_kernel<128, 128, 3, 4>), 256, DMA128_LDS, 128, 128, GRID_CLASSES},
-    DMA128_SRC2{kfn(&igemm_conv_dma_kernel<128, 128, 3, 0, true>), 256, DMA128_LDS, 128, 128, GRID_XCD},
+    DMA128_LIN{kfn(&igemm_conv_dma_kernel<128, 128, 3, Epi::LIN>), 256, DMA128_LDS, 128, 128, GRID_XCD},
+    DMA128_FUSED{kfn(&igemm_conv_dma_kernel<128, 128, 3, Epi::FUSED>), 256, DMA128_LDS, 128, 128, GRID_XCD},
+    DMA128_CLS{kfn(&igemm_conv_dma_kernel<128, 128, 3, Epi::PARITY>), 256, DMA128_LDS, 128, 128, GRID_CLASSES},
+    DMA128_SRC2{kfn(&igemm_conv_dma_kernel<128, 128, 3, Epi::CONV, true>), 256, DMA128_LDS, 128, 128, GRID_XCD},
     // 64 x 256 for Cm <= 64
     CONV64_BN{kfn(&igemm_conv_kernel<64, 256, true>), 256, REG64_LDS, 64, 256, GRID_XCD},
     CONV64{kfn(&igemm_conv_kernel<64, 256, false>), 256, REG64_LDS, 64, 256, GRID_XCD},
     DMA64{kfn(&igemm_conv_dma_kernel<64, 256, 3>), 256, DMA64_LDS, 64, 256, GRID_XCD},
-    DMA64_LEAN{kfn(&igemm_conv_dma_kernel<64, 256, 3, 5>), 256, DMA64_LDS, 64, 256, GRID_XCD},
-    DMA64_SRC2{kfn(&igemm_conv_dma_kernel<64, 256, 3, 0, true>), 256, DMA64_LDS, 64, 256, GRID_XCD},
+    DMA64_LEAN{kfn(&igemm_conv_dma_kernel<64, 256, 3, Epi::FUSED_LEAN>), 256, DMA64_LDS, 64, 256, GRID_XCD},
+    DMA64_SRC2{kfn(&igemm_conv_dma_kernel<64, 256, 3, Epi::CONV, true>), 256, DMA64_LDS, 64, 256, GRID_XCD},
     // layer1's 3x3 (Cm = Cin = 64, K = 576): k-tile 64 = one full line per pixel and tap, 4 MFMA waves + 4 DMA waves, 2-stage ring,
     // two workgroups per CU: 94 -> 77 us forward, 90 -> 73 us data gradient (unspecialised k-tile 64: 84 / 79; 3-stage ring, one
     // workgroup per CU: 122 / 118).  (8 producer waves instead of 4: 74 -> 78 us; the L2 -> LDS feed, 9 taps per pixel, bounds it, not the
@@ -2408,30 +2398,30 @@ static const GemmKernel
     K64S64{kfn(&igemm_conv_k64s_kernel<1, 4, 4, 2>), 512, ring_lds(64, 256, 64, 2), 64, 256, GRID_XCD},
     // the same problem on halo64_ok's grids: the halo patch of a 256-pixel tile fetched once, taps read it at shifted pixels
     HALO64{kfn(&igemm_conv_halo64_kernel<3>), 512, HALO64_LDS, 64, 256, GRID_HALO},
-    HALO64_LEAN{kfn(&igemm_conv_halo64_kernel<3, 5>), 512, HALO64_LDS, 64, 256, GRID_HALO},
+    HALO64_LEAN{kfn(&igemm_conv_halo64_kernel<3, Epi::FUSED_LEAN>), 512, HALO64_LDS, 64, 256, GRID_HALO},
     // 128 x 256 / 8 waves, k-tile 32, 3-stage ring
     WG128{kfn(&igemm_conv_wg_kernel<2, 4, 3>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
-    WG128_LIN{kfn(&igemm_conv_wg_kernel<2, 4, 3, 1>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
-    WG128_FUSED{kfn(&igemm_conv_wg_kernel<2, 4, 3, 3>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
-    WG128_CLS{kfn(&igemm_conv_wg_kernel<2, 4, 3, 4>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_CLASSES},
+    WG128_LIN{kfn(&igemm_conv_wg_kernel<2, 4, 3, Epi::LIN>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
+    WG128_FUSED{kfn(&igemm_conv_wg_kernel<2, 4, 3, Epi::FUSED>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
+    WG128_CLS{kfn(&igemm_conv_wg_kernel<2, 4, 3, Epi::PARITY>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_CLASSES},
     // 256 x 256 / 16 waves, k-tile 32, 4-stage ring
     WG256{kfn(&igemm_conv_wg_kernel<4, 4, 4>), 1024, ring_lds(256, 256, 32, 4), 256, 256, GRID_XCD},
     // 128 x 256 k-tile 64, wave-specialised (8 MFMA + 8 DMA waves), 3-stage ring
     K64S{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
-    K64S_LIN{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 1>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
-    K64S_LEAN{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 5>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
-    K64S_SRC2{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, 0, true>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
+    K64S_LIN{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, Epi::LIN>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
+    K64S_LEAN{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, Epi::FUSED_LEAN>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
+    K64S_SRC2{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, Epi::CONV, true>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
     // 256 x 256 k-tile 64, 16 waves of 64 x 64, 2-stage ring.  (8 waves with 128 x 64 per wave, 25 % fewer LDS fragment bytes, 192 VGPRs: measured
     // 3-5 % slower than 16 waves of 64 x 64) and the wave-specialised form (8 consumers of 128 x 64 + 4 producers, 168 VGPRs, 2-stage ring): -2 % on
     // layer4's 3x3, +14 % on the stride-2 downsample dgrad -- a 256 x 256 tile has no room for producers beside 16 consumers (1024 threads per workgroup)
     K64{kfn(&igemm_conv_k64_kernel<4, 4, 2>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
-    K64_LIN{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 1>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
-    K64_FUSED{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 3>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
-    K64_CLS{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 4>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_CLASSES},
-    K64_SRC2{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 0, true>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
-    K64_FUSED_SRC2{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, 3, true>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
+    K64_LIN{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::LIN>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
+    K64_FUSED{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::FUSED>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
+    K64_CLS{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::PARITY>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_CLASSES},
+    K64_SRC2{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::CONV, true>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
+    K64_FUSED_SRC2{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::FUSED, true>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
     // 256 x 320 k-tile 64 (conv_prefers_320)
-    K64_320{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 5, 1>), 1024, ring_lds(256, 320, 64, 2), 256, 320, GRID_XCD};
+    K64_320{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 5, Epi::LIN>), 1024, ring_lds(256, 320, 64, 2), 256, 320, GRID_XCD};
 
 // the persistent streaming kernel (fused1x1.h): two result buffers for K <= 128, else one.  It takes launches with a residual, an output mask or
 // mask bits, or with a second operand tensor and none of the three: F1[K > 128][residual][out_mask][bits_out], the none slot the SRC2 instantiation
@@ -2577,6 +2567,9 @@ static GemmChoice conv_choose(const IGemmArgs& a, int n_cus) {
     // instantiations compile none of it (code that is never executed still cost their register allocation 0.4-0.8 ms per step)
     const bool fused = a.out_scale || a.out_shift || a.out_relu || a.bits_out || a.out_mask || a.res_scale;
     const bool lin = a.act != 0 || a.O2 != nullptr || a.dact_pre != nullptr || a.row_scale != nullptr;      // linear-layer epilogue extras: the LIN instantiations
+    // (dali_conv2d_dgrad, the only caller that sets res_mask, sets neither: the staged extras and the fused stage compile no residual mask)
+    if (a.res_mask && (fused || lin))
+        return GemmChoice(DALI_ERR_INVALID, "conv: a residual mask goes with neither a fused output stage nor the linear-layer extras");
     int cfg = conv_pick_cfg(a.Cm, a.P, K);
     if (dma_ok && !a.stats && !fused && !g.sub && g.Ck % 64 == 0 && (a.Cm & 7) == 0 && conv_prefers_320(a.Cm, a.P, K)) cfg = CONV_256x320;
     if (!dma_ok && !in_bn && a.stats && (cfg == CONV_128x256 || cfg == CONV_256x256))
@@ -2614,12 +2607,12 @@ static GemmChoice conv_choose(const IGemmArgs& a, int n_cus) {
         // 1x1 conv3 forwards and the masked conv1 data gradients, Cm >= 256 and K <= 512)
         // short-K 1x1 with a residual / mask stream: the persistent streaming kernel (fused1x1.h).  K <= 256: at K = 512 (layer4) its four ring
         // producers cannot issue the 32 DMA pieces of a k-step as fast as the consumers multiply it (141 against 125 us; the block is capped at 16 waves)
-        if (plain_rows(g) && !g.sub && !a.res_mask && a.Cm % F1_TM == 0 && (g.Ck & 63) == 0 && g.Ck <= F1_KMAX && dma_addressable((long long)a.P * a.Cm * 2) &&
+        if (plain_rows(g) && !g.sub && a.Cm % F1_TM == 0 && (g.Ck & 63) == 0 && g.Ck <= F1_KMAX && dma_addressable((long long)a.P * a.Cm * 2) &&
             (a.Res || a.out_mask || a.bits_out || a.X2)) {
             if (n_cus <= 0) return GemmChoice(DALI_ERR_HIP, "conv: device query failed");
             if (f1_fills(a.Cm, a.P, n_cus)) return use(F1[g.Ck > 128][a.Res != nullptr][a.out_mask != nullptr][a.bits_out != nullptr]);
         }
-        const bool lean = !a.Res && !a.out_mask && !a.bits_out && !a.res_mask && !a.res_scale && !a.X2;      // scale / shift / bias / ReLU only: the EPI = 5 instantiations
+        const bool lean = !a.Res && !a.out_mask && !a.bits_out && !a.res_scale && !a.X2;      // scale / shift / bias / ReLU only: the Epi::FUSED_LEAN instantiations
         if (lean && narrow_k64 && halo64_ok(a)) return use(HALO64_LEAN);
         if (lean && narrow) return use(DMA64_LEAN);
         if (lean && k64 && cfg == CONV_128x256 && !g.sub) return use(K64S_LEAN);
@@ -2632,7 +2625,7 @@ static GemmChoice conv_choose(const IGemmArgs& a, int n_cus) {
         if (k64 && cfg == CONV_256x256) return use(K64_FUSED);
         return use(cfg == CONV_128x256 || cfg == CONV_256x256 ? WG128_FUSED : DMA128_FUSED);
     }
-    if (g.sub && dma_ok && !narrow && !lin && (a.Cm & 7) == 0) {        // a parity class of a stride-2 data gradient (EPI = 4)
+    if (g.sub && dma_ok && !narrow && !lin && (a.Cm & 7) == 0) {        // a parity class of a stride-2 data gradient (Epi::PARITY)
         if (k64 && cfg == CONV_256x256) return use(K64_CLS);
         return use(cfg == CONV_128x256 || cfg == CONV_256x256 ? WG128_CLS : DMA128_CLS);
     }

@@ -372,7 +372,7 @@ __global__ __launch_bounds__((F1_NC + F1_NP + F1_NR) * 64) void fused1x1_persist
                                                    return has_om ? *reinterpret_cast<const uint8_t*>(mb + pix * 16 + chunk) : 0u; };
             auto put = [&](int itr, uint4 v, unsigned m) {
                 const int s = itr * (F1_NC * 64) + tid, pix = s >> 4, chunk = s & 15;
-                if (has_om) { v.x = gate_bf16x2(v.x, m); v.y = gate_bf16x2(v.y, m >> 2); v.z = gate_bf16x2(v.z, m >> 4); v.w = gate_bf16x2(v.w, m >> 6); }
+                if (has_om) gate_bf16x8(v, m);
                 const size_t e = ((size_t)(tn * F1_TN + pix) * Cm + tm * F1_TM + chunk * 8);
                 *reinterpret_cast<uint4*>(a.O + e) = v;
                 if (has_bits) a.bits_out[e >> 3] = (uint8_t)(f1_pos_bits(v.x) | (f1_pos_bits(v.y) << 2) | (f1_pos_bits(v.z) << 4) | (f1_pos_bits(v.w) << 6));
@@ -390,10 +390,7 @@ __global__ __launch_bounds__((F1_NC + F1_NP + F1_NR) * 64) void fused1x1_persist
             for (int itr = 0; itr < 4; ++itr) {
                 const int s = itr * (F1_NC * 64) + tid, pix = s >> 4, chunk = s & 15;
                 uint4 v = *reinterpret_cast<const uint4*>(rb + pix * 256 + ((chunk ^ (pix & 15)) << 4));
-                if (has_om) {
-                    const unsigned m = *reinterpret_cast<const uint8_t*>(mb + pix * 16 + chunk);
-                    v.x = gate_bf16x2(v.x, m); v.y = gate_bf16x2(v.y, m >> 2); v.z = gate_bf16x2(v.z, m >> 4); v.w = gate_bf16x2(v.w, m >> 6);
-                }
+                if (has_om) gate_bf16x8(v, *reinterpret_cast<const uint8_t*>(mb + pix * 16 + chunk));
                 if (tn * F1_TN + pix < P) {
                     const size_t e = ((size_t)(tn * F1_TN + pix) * Cm + tm * F1_TM + chunk * 8);
                     *reinterpret_cast<uint4*>(a.O + e) = v;

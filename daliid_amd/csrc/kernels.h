@@ -29,7 +29,8 @@ struct IGemmArgs {
     uint16_t* O;              // [P][Cm]
     const uint16_t* Res;      // optional residual [P][Cm], added in the epilogue
     const uint8_t* res_mask;  // optional 1-bit gate of Res (bit e & 7 of byte e >> 3, e = p*Cm + c): the ReLU mask of a block output,
-                              // so that dz = dy * (y > 0) is formed here instead of being written by the BatchNorm backward
+                              // so that dz = dy * (y > 0) is formed here instead of being written by the BatchNorm backward; refused
+                              // beside the fused output stage and beside the linear-layer extras (conv_choose)
     const float* in_scale;    // optional [Ck] affine (+ReLU) applied to X on load
     const float* in_shift;
     float* stats;             // optional [tiles_n][Cm][2] partial sum / sumsq of the fp32 results
@@ -40,7 +41,7 @@ struct IGemmArgs {
     int Cm, P, in_relu;
     GatherGeom g;
     unsigned long long* stamps;   // diagnostic (dali_debug_set_conv_stamps): [block][12] s_memrealtime stamps (see scripts/conv_block_timeline.py)
-    // ---- fused output stage (the EPI = 3 kernel instantiations; all optional) ----
+    // ---- fused output stage (the Epi::FUSED / Epi::FUSED_LEAN kernel instantiations; all optional) ----
     // value = acc * out_scale[c] + out_shift[c] (+ Res) -> ReLU if out_relu -> gated by out_mask -> O; bits_out gets (value > 0).
     // Forward: the BatchNorm of a 1x1 convolution whose batch statistics were derived from the Gram matrix of its input BEFORE the
     // GEMM ran (bnlin.hip), so that y = relu(bn(conv(x)) + identity) leaves the GEMM directly and the raw conv output is never stored.

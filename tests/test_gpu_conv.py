@@ -235,3 +235,39 @@ def test_conv1x1_cat_act_refuses_and_leaves_output(nn, parts, c1, c2, cout):
     torch.cuda.synchronize()
     assert rc == -1, (rc, _lib.last_error())
     assert torch.equal(y, before)
+
+
+# conv + BatchNorm + ReLU in one launch (dali_conv2d_bn_act) at pixel / channel counts that are no multiple of the tile: every tile is an edge
+# tile, so the fused output stage runs in the predicated general store of both fused epilogue modes (scale / shift / ReLU alone on the 64 x 256
+# kernel; the full stage's instantiation of the 128 x 128 kernel at 136 channels and 105 pixels).  The batch-256 plan shapes are all interior.
+@pytest.mark.parametrize("relu", [True, False])
+@pytest.mark.parametrize("case", [(3, 9, 5, 64, 64, 3, 3, 1, 1), (3, 7, 5, 128, 136, 3, 3, 1, 1), (2, 9, 8, 256, 64, 1, 1, 1, 0)])
+def test_conv2d_bn_act_edge_tiles_exact_integers(nn, case, relu):
+    """Small integers, power-of-two scales and integer shifts: acc * scale + shift is exact in fp32, so y equals the fp32 reference rounded once."""
+    n, h, w, cin, cout, r, s, stride, pad = case
+    gen = torch.Generator().manual_seed(sum(case) * 5 + cout)
+    x = _ints((n, cin, h, w), gen)
+    wt = _ints((cout, cin, r, s), gen, density=0.5)
+    scale = torch.tensor([0.5, 1.0, 2.0, 0.25])[torch.randint(0, 4, (cout,), generator=gen)]
+    shift = torch.randint(-3, 4, (cout,), generator=gen).float()
+    ref = nhwc(F.conv2d(x, wt, stride=stride, padding=pad)) * scale + shift
+    if relu:
+        ref = ref.clamp_min(0)
+    y = nn.conv2d_bn_act(nhwc(x).to(bf16).cuda(), wt.permute(0, 2, 3, 1).contiguous().to(bf16).cuda(), scale.cuda(), shift.cuda(), stride, pad, relu=relu)
+    assert torch.equal(y.cpu(), ref.to(bf16)), (y.cpu().float() - ref).abs().max()
+
+
+def test_conv_dgrad_masked_residual_on_256x320_tile_exact_integers(nn):
+    """1x1 data gradient into 512 channels at 32896 pixels: the 256 x 320 tile's column-block store (conv_epilogue_cols) with a masked residual,
+    which dali_conv2d_dgrad reaches and the linear layers (the tile's other users) do not."""
+    n, h, w, cin, cout = 257, 16, 8, 512, 512
+    gen = torch.Generator().manual_seed(320)
+    dy = _ints((n * h * w, cout), gen, density=0.5)
+    wt = _ints((cout, cin), gen, density=0.5)
+    res = _ints((n * h * w, cin), gen)
+    bits = torch.randint(0, 2, (n * h * w, cin), generator=gen)
+    packed = (bits.reshape(-1, 8) << torch.arange(8)).sum(1).to(torch.uint8).cuda()
+    ref = ((dy.cuda() @ wt.cuda()).cpu() + res * bits).to(bf16)
+    w_dg = wt.t().contiguous().reshape(cin, 1, 1, cout).to(bf16).cuda()
+    dx = nn.conv2d_dgrad(dy.reshape(n, h, w, cout).to(bf16).cuda(), w_dg, (h, w), 1, 0, residual=res.reshape(n, h, w, cin).to(bf16).cuda(), residual_mask=packed)
+    assert torch.equal(dx.cpu().reshape(-1, cin), ref)
