@@ -1,6 +1,6 @@
 // eval.hip -- evaluation path of validateModels.validate (validateModels.py:35-76):
-//   row L2 normalisation (:41-42), distmat = 1 - q @ g.T (:47) on MFMA, and the market1501 CMC/mAP
-//   arithmetic of torchreid.metrics.evaluate_rank (:68) without a full row sort.
+//   row L2 normalisation (:41-42) and distmat = 1 - q @ g.T (:47) on MFMA, plus the loss heads' small similarity GEMMs.
+//   The market1501 CMC/mAP ranking (:68) that follows them is rank.hip.
 #include "gemm_tile.h"
 #include "topk_key.h"
 #include <cstdlib>
@@ -515,426 +515,6 @@ __global__ __launch_bounds__(1024) void pairdist_dma_kernel(const uint16_t* __re
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// market1501 ranking without a row sort.  One 256-thread block per query.
-//   kept(g)  = !(g_pid == q_pid && g_cam == q_cam)                  (junk removal)
-//   match(g) = kept(g) && g_pid == q_pid
-// The gallery is indexed by identity ONCE per evaluation (rank_index_*: counting sort of the gallery positions by pid, on
-// the device), so a query finds its same-identity entries -- matches and junk -- as one slice of that index instead of
-// scanning all ng ids (10k x 100k: 4 GB of id reads gone; only the distance row is read, 4 bytes per pair).
-// Sort the matches by key (dist, index) in LDS (bitonic).  Every kept gallery entry is binned by the
-// number of matches with a smaller key (binary search); with c[b] the bin counts,
-//   position (1-based, among kept) of the j-th match = c[0] + ... + c[j]
-//   AP = mean_j (j+1) / position_j ,  first-hit rank = c[0] - 1.
-// LDS is sized in two tiers (the row scan is HBM-bound and needs many workgroups per CU in flight): RANK_PSMALL same-identity
-// entries per query in the first launch (16 KiB of LDS: 8+ workgroups per CU); queries with more are flagged and redone by a
-// second launch with room for RANK_PMAX; beyond that DALI_ERR_LIMIT through status[0].
-// ------------------------------------------------------------------------------------------------
-constexpr int RANK_PSMALL = 512, RANK_PMAX = 4096, RANK_BINS = 1024;
-constexpr int RANK_MAX_PID_RANGE = 1 << 20;      // identity codes must span at most this range (the mirrors pass dense codes): status 2 otherwise
-
-__device__ __forceinline__ bool key_less(float da, int ia, float db, int ib) {
-    return da < db || (da == db && ia < ib);
-}
-// (dist, index) as one unsigned 64-bit key with the same order as key_less: IEEE bits made monotonic (negative values
-// flipped, sign bit set on the others; -0.0 is folded onto +0.0 first so that equal distances compare by index)
-__device__ __forceinline__ unsigned long long rank_key(float d, int g) {
-    unsigned int b = __float_as_uint(d + 0.0f);
-    b ^= (b >> 31) ? 0xffffffffu : 0x80000000u;
-    return ((unsigned long long)b << 32) | (unsigned int)g;
-}
-
-// ---- gallery index by identity: info = {min pid, max pid}; counts/starts over [min, max]; order = gallery positions grouped by pid ----
-__global__ __launch_bounds__(256) void rank_index_minmax_kernel(const int32_t* __restrict__ g_pids, int ng, int32_t* __restrict__ info) {
-    int lo = 0x7fffffff, hi = (int)0x80000000;
-    for (int g = blockIdx.x * 256 + threadIdx.x; g < ng; g += gridDim.x * 256) { const int p = g_pids[g]; lo = min(lo, p); hi = max(hi, p); }
-    for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o, 64)); hi = max(hi, __shfl_xor(hi, o, 64)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(&info[0], lo); atomicMax(&info[1], hi); }
-}
-__global__ __launch_bounds__(256) void rank_index_count_kernel(const int32_t* __restrict__ g_pids, int ng, const int32_t* __restrict__ info,
-                                                                int32_t* __restrict__ counts, int32_t* __restrict__ status) {
-    const int lo = info[0];
-    const long long range = (long long)info[1] - lo + 1;
-    if (range > RANK_MAX_PID_RANGE) { if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(status, 2); return; }
-    for (int g = blockIdx.x * 256 + threadIdx.x; g < ng; g += gridDim.x * 256) atomicAdd(&counts[g_pids[g] - lo], 1);
-}
-// one block: starts[r] = exclusive prefix of counts (range + 1 entries), cursors zeroed
-__global__ __launch_bounds__(1024) void rank_index_scan_kernel(const int32_t* __restrict__ info, const int32_t* __restrict__ counts,
-                                                               int32_t* __restrict__ starts, int32_t* __restrict__ cursor) {
-    __shared__ int s_part[1024];
-    const long long range64 = (long long)info[1] - info[0] + 1;
-    if (range64 > RANK_MAX_PID_RANGE) return;
-    const int range = (int)range64, tid = threadIdx.x;
-    const int per = (range + 1023) / 1024, b = tid * per, e = min(b + per, range);
-    int sum = 0;
-    for (int r = b; r < e; ++r) sum += counts[r];
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int add = tid >= o ? s_part[tid - o] : 0;
-        __syncthreads();
-        s_part[tid] += add;
-        __syncthreads();
-    }
-    int run = s_part[tid] - sum;
-    for (int r = b; r < e; ++r) { starts[r] = run; cursor[r] = 0; run += counts[r]; }
-    if (tid == 1023) starts[range] = s_part[1023];
-}
-__global__ __launch_bounds__(256) void rank_index_scatter_kernel(const int32_t* __restrict__ g_pids, int ng, const int32_t* __restrict__ info,
-                                                                  const int32_t* __restrict__ starts, int32_t* __restrict__ cursor,
-                                                                  int32_t* __restrict__ order) {
-    const int lo = info[0];
-    if ((long long)info[1] - lo + 1 > RANK_MAX_PID_RANGE) return;
-    for (int g = blockIdx.x * 256 + threadIdx.x; g < ng; g += gridDim.x * 256) {
-        const int r = g_pids[g] - lo;
-        order[starts[r] + atomicAdd(&cursor[r], 1)] = g;          // order inside an identity is irrelevant: matches are sorted by key below
-    }
-}
-
-// PASS 0: every query, LDS for PCAP = RANK_PSMALL; larger identities set pending[q].  PASS 1: only the pending queries, PCAP = RANK_PMAX.
-template <int PCAP, int PASS>
-__global__ __launch_bounds__(256) void rank_query_kernel(const float* __restrict__ distmat, const int32_t* __restrict__ q_pids,
-                                                          const int32_t* __restrict__ q_cams, const int32_t* __restrict__ g_cams,
-                                                          const int32_t* __restrict__ info, const int32_t* __restrict__ starts,
-                                                          const int32_t* __restrict__ order, int nq, int ng,
-                                                          float* __restrict__ ap_out, int32_t* __restrict__ first_rank,
-                                                          int32_t* __restrict__ pending, int32_t* __restrict__ status) {
-    __shared__ unsigned long long s_key[PCAP];    // (orderable distance bits << 32) | gallery index: one 8-byte LDS read per compare
-    __shared__ unsigned s_cell[RANK_BINS];
-    __shared__ int s_cnt[PCAP + 1];
-    __shared__ int s_junk[PCAP];
-    __shared__ int s_n, s_nj;
-    __shared__ float s_red[4];
-    __shared__ int s_scan[256];
-    const int q = blockIdx.x, tid = threadIdx.x;
-    if (PASS == 1 && pending[q] == 0) return;
-    const float* drow = distmat + (size_t)q * ng;
-    const int qp = q_pids[q], qc = q_cams[q];
-    // 1. this query's identity slice of the gallery index: matches (other camera) and junk (same camera)
-    const int lo = info[0], hi = info[1];
-    if ((long long)hi - lo + 1 > RANK_MAX_PID_RANGE) { if (tid == 0) { ap_out[q] = 0.f; first_rank[q] = -1; } return; }     // status 2 set by the index build
-    int sb = 0, se = 0;
-    if (qp >= lo && qp <= hi) { sb = starts[qp - lo]; se = starts[qp - lo + 1]; }
-    const int nsame = se - sb;
-    if (nsame == 0) {
-        if (tid == 0) { ap_out[q] = 0.f; first_rank[q] = -1; if (PASS == 0) pending[q] = 0; }
-        return;
-    }
-    if (nsame > PCAP) {
-        if (tid == 0) {
-            ap_out[q] = 0.f; first_rank[q] = -1;
-            if (PASS == 0) pending[q] = 1; else atomicMax(status, 1);
-        }
-        return;
-    }
-    if (tid == 0) { s_n = 0; s_nj = 0; if (PASS == 0) pending[q] = 0; }
-    __syncthreads();
-    for (int t = tid; t < nsame; t += 256) {
-        const int g = order[sb + t];
-        if (g_cams[g] != qc) s_key[atomicAdd(&s_n, 1)] = rank_key(drow[g], g);
-        else s_junk[atomicAdd(&s_nj, 1)] = g;
-    }
-    __syncthreads();
-    const int np = s_n, nj = s_nj;
-    if (np == 0) {
-        if (tid == 0) { ap_out[q] = 0.f; first_rank[q] = -1; }
-        return;
-    }
-    const bool vec = (ng & 3) == 0 && (reinterpret_cast<uintptr_t>(drow) & 15) == 0;
-    int npad = 1;
-    while (npad < np) npad <<= 1;
-    for (int t = np + tid; t < npad; t += 256) s_key[t] = ~0ull;                  // above every real key
-    for (int t = tid; t <= np; t += 256) s_cnt[t] = 0;
-    __syncthreads();
-    // 2. bitonic sort of (dist, idx)
-    for (int k = 2; k <= npad; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < npad; t += 256) {
-                const int p = t ^ j;
-                if (p > t) {
-                    const bool up = (t & k) == 0;
-                    const unsigned long long ka = s_key[t], kb = s_key[p];
-                    if (up ? kb < ka : ka < kb) { s_key[t] = kb; s_key[p] = ka; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    // 3. bin EVERY gallery entry by the number of matches with a smaller key (only the distance row is read: 4 bytes per pair, coalesced
-    //    16 B per lane), then take the junk entries back out of their bins.
-    //    The lower bound over the sorted matches is NOT searched per entry (7 dependent LDS reads per entry at ~100 matches left the pass
-    //    LDS-bound on random distances: 1.7 ms for 10k x 100k against 0.8 ms of HBM time).  The distance axis between the first and the
-    //    last match is cut into RANK_BINS uniform cells; s_cell[c] = (matches in lower cells) | (matches in cell c) << 16.  An entry reads
-    //    its cell's word: that IS its lower bound unless the cell holds matches itself (about one cell in ten), where a short search
-    //    inside the cell's matches finishes it.  floor((d - lo) * scale) is monotone in d, so cells never reorder keys.
-    const unsigned long long last_key = s_key[np - 1];
-    auto key_dist = [](unsigned long long k) { unsigned b = (unsigned)(k >> 32); b = (b & 0x80000000u) ? (b ^ 0x80000000u) : ~b; return __uint_as_float(b); };
-    const float dlo = key_dist(s_key[0]), dhi = key_dist(last_key);
-    const float cscale = dhi > dlo ? (float)RANK_BINS / (dhi - dlo) : 0.f;
-    auto cell_of = [&](float dn) { const unsigned c = (unsigned)(int)((dn - dlo) * cscale); return (int)(c < (unsigned)RANK_BINS ? c : RANK_BINS - 1); };   // (always in bounds)
-    for (int t = tid; t < RANK_BINS; t += 256) s_cell[t] = 0;
-    __syncthreads();
-    for (int t = tid; t < np; t += 256) atomicAdd(&s_cell[cell_of(key_dist(s_key[t]))], 1u << 16);
-    __syncthreads();
-    {   // exclusive scan of the per-cell match counts into the low halves (RANK_BINS = 4 * 256: four cells per thread)
-        unsigned c4[4], run = 0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { c4[u] = s_cell[tid * 4 + u] >> 16; run += c4[u]; }
-        s_scan[tid] = (int)run;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            const int add = (tid >= o) ? s_scan[tid - o] : 0;
-            __syncthreads();
-            s_scan[tid] += add;
-            __syncthreads();
-        }
-        unsigned base = (unsigned)s_scan[tid] - run;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { s_cell[tid * 4 + u] = base | (c4[u] << 16); base += c4[u]; }
-        __syncthreads();
-    }
-    auto lower_bound_in = [&](unsigned long long k, float dn) {          // number of matches with a key below k, for dlo <= dn and k <= last_key
-        const unsigned cw = s_cell[cell_of(dn)];
-        int p = (int)(cw & 0xffffu), len = (int)(cw >> 16);
-        while (len > 0) {                                               // only cells that hold matches: a search among THEIR keys
-            const int half = len >> 1;
-            if (s_key[p + half] < k) { p += half + 1; len -= half + 1; } else len = half;
-        }
-        return p;
-    };
-    auto bin = [&](float d, int g, int delta) {
-        const float dn = d + 0.0f;
-        const unsigned long long k = rank_key(d, g);
-        if (k > last_key) return;                                       // beyond the last match: affects no position
-        atomicAdd(&s_cnt[dn < dlo ? 0 : lower_bound_in(k, dn)], delta);
-    };
-    auto bin4 = [&](const float4 v, int g, int delta) { bin(v.x, g, delta); bin(v.y, g + 1, delta); bin(v.z, g + 2, delta); bin(v.w, g + 3, delta); };
-    if (vec) {
-        int g = tid * 4;
-        for (; g + 3072 < ng; g += 4096) {                            // 4 independent 16-byte loads in flight
-            const float4 v0 = *reinterpret_cast<const float4*>(drow + g);
-            const float4 v1 = *reinterpret_cast<const float4*>(drow + g + 1024);
-            const float4 v2 = *reinterpret_cast<const float4*>(drow + g + 2048);
-            const float4 v3 = *reinterpret_cast<const float4*>(drow + g + 3072);
-            bin4(v0, g, 1); bin4(v1, g + 1024, 1); bin4(v2, g + 2048, 1); bin4(v3, g + 3072, 1);
-        }
-        for (; g < ng; g += 1024) bin4(*reinterpret_cast<const float4*>(drow + g), g, 1);
-    } else {
-        for (int g = tid; g < ng; g += 256) bin(drow[g], g, 1);
-    }
-    __syncthreads();
-    for (int t = tid; t < nj; t += 256) bin(drow[s_junk[t]], s_junk[t], -1);
-    __syncthreads();
-    // 4. inclusive scan of the bins + AP (sequential chunks of 256)
-    float ap_part = 0.f;
-    int carry = 0;
-    for (int base = 0; base < np; base += 256) {
-        const int t = base + tid;
-        const int v = (t < np) ? s_cnt[t] : 0;
-        s_scan[tid] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            const int add = (tid >= o) ? s_scan[tid - o] : 0;
-            __syncthreads();
-            s_scan[tid] += add;
-            __syncthreads();
-        }
-        const int pos = carry + s_scan[tid];
-        if (t < np) ap_part += (float)(t + 1) / (float)pos;
-        if (t == 0) first_rank[q] = pos - 1;
-        carry += s_scan[255];
-        __syncthreads();
-    }
-    ap_part = wave_sum(ap_part);
-    if ((tid & 63) == 0) s_red[tid >> 6] = ap_part;
-    __syncthreads();
-    if (tid == 0) ap_out[q] = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (float)np;
-}
-
-// Single-block deterministic reduction: CMC curve + mAP over valid queries.
-__global__ __launch_bounds__(256) void rank_reduce_kernel(const float* __restrict__ ap, const int32_t* __restrict__ first_rank,
-                                                           int nq, int max_rank, float* __restrict__ cmc, float* __restrict__ mAP,
-                                                           double* __restrict__ map64, int32_t* __restrict__ num_valid) {
-    __shared__ double s_sum[256];
-    __shared__ int s_valid[256];
-    __shared__ int s_hist[1024];
-    const int tid = threadIdx.x;
-    for (int t = tid; t < 1024; t += 256) s_hist[t] = 0;
-    __syncthreads();
-    double s = 0.0;
-    int nv = 0;
-    for (int q = tid; q < nq; q += 256) {
-        const int fr = first_rank[q];
-        if (fr >= 0) {
-            s += (double)ap[q];
-            ++nv;
-            if (fr < max_rank) atomicAdd(&s_hist[fr], 1);
-        }
-    }
-    s_sum[tid] = s; s_valid[tid] = nv;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) { s_sum[tid] += s_sum[tid + o]; s_valid[tid] += s_valid[tid + o]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const int n = s_valid[0];
-        num_valid[0] = n;
-        const double m = n > 0 ? s_sum[0] / (double)n : 0.0;
-        mAP[0] = (float)m;
-        if (map64) map64[0] = m;
-        int run = 0;
-        for (int k = 0; k < max_rank; ++k) {
-            run += s_hist[k];
-            cmc[k] = n > 0 ? (float)((double)run / (double)n) : 0.f;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Gallery-sharded ranking (the evaluation path over N GPUs): every rank holds the distances of ALL queries to ITS slice of
-// the gallery.  The position of a match in the full ranking is 1 + (kept gallery entries of every shard with a smaller key), keys being
-// (distance, GLOBAL gallery index), so the merge is a sum of per-shard counts:
-//   (1) rank_shard_matches_kernel: the keys of the query's matches inside this shard (identity slice of the shard's index, other camera);
-//   (2) [host: all-gather of the keys]
-//   (3) rank_shard_bins_kernel: all shards' match keys sorted in LDS (the same order on every rank: keys are unique); every kept entry of THIS
-//       shard is binned by the number of matches with a smaller key, exactly as rank_query_kernel bins the whole row;
-//   (4) [host: all-reduce SUM of the integer bins]
-//   (5) rank_shard_finish_kernel: positions = inclusive scan of the bins, AP and first-hit rank with rank_query_kernel's summation order
-//       (bit-identical to the single-GPU result), then rank_reduce_kernel.
-// Plain binary search over the sorted keys (no distance cells): this path is bounded by the collectives, not by the bins.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rank_shard_matches_kernel(const float* __restrict__ dist, const int32_t* __restrict__ q_pids,
-                                                                  const int32_t* __restrict__ q_cams, const int32_t* __restrict__ g_cams,
-                                                                  const int32_t* __restrict__ info, const int32_t* __restrict__ starts,
-                                                                  const int32_t* __restrict__ order, int ng, int g_offset, int cap,
-                                                                  unsigned long long* __restrict__ keys, int32_t* __restrict__ counts,
-                                                                  int32_t* __restrict__ status) {
-    __shared__ int s_n;
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int lo = info[0], hi = info[1];
-    unsigned long long* krow = keys + (size_t)q * cap;
-    for (int t = tid; t < cap; t += 256) krow[t] = ~0ull;
-    if ((long long)hi - lo + 1 > RANK_MAX_PID_RANGE) { if (tid == 0) counts[q] = 0; return; }        // status 2 set by the index build
-    const int qp = q_pids[q], qc = q_cams[q];
-    int sb = 0, se = 0;
-    if (qp >= lo && qp <= hi) { sb = starts[qp - lo]; se = starts[qp - lo + 1]; }
-    if (tid == 0) s_n = 0;
-    __syncthreads();
-    const float* drow = dist + (size_t)q * ng;
-    for (int t = sb + tid; t < se; t += 256) {
-        const int g = order[t];
-        if (g_cams[g] != qc) {
-            const int slot = atomicAdd(&s_n, 1);
-            if (slot < cap) krow[slot] = rank_key(drow[g], g + g_offset);
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        counts[q] = s_n < cap ? s_n : cap;
-        if (s_n > cap) atomicMax(status, 1);
-    }
-}
-
-__global__ __launch_bounds__(256) void rank_shard_bins_kernel(const float* __restrict__ dist, const int32_t* __restrict__ q_pids,
-                                                               const int32_t* __restrict__ q_cams, const int32_t* __restrict__ g_cams,
-                                                               const int32_t* __restrict__ info, const int32_t* __restrict__ starts,
-                                                               const int32_t* __restrict__ order, int nq, int ng, int g_offset,
-                                                               const unsigned long long* __restrict__ keys_all, const int32_t* __restrict__ counts_all,
-                                                               int world, int cap, int32_t* __restrict__ bins, int bins_cap,
-                                                               int32_t* __restrict__ status) {
-    __shared__ unsigned long long s_key[RANK_PMAX];
-    __shared__ int s_cnt[RANK_PMAX + 1];
-    const int q = blockIdx.x, tid = threadIdx.x;
-    int32_t* brow = bins + (size_t)q * (bins_cap + 1);
-    int np = 0;
-    for (int r = 0; r < world; ++r) np += counts_all[(size_t)r * nq + q];
-    if (np > bins_cap || np > RANK_PMAX) { if (tid == 0) atomicMax(status, 1); np = 0; }
-    for (int t = tid; t <= bins_cap; t += 256) brow[t] = 0;
-    if (np == 0) return;
-    // all shards' match keys of this query, in rank order (any order: they are sorted next)
-    int base = 0;
-    for (int r = 0; r < world; ++r) {
-        const int n = counts_all[(size_t)r * nq + q];
-        const unsigned long long* src = keys_all + ((size_t)r * nq + q) * cap;
-        for (int t = tid; t < n; t += 256) s_key[base + t] = src[t];
-        base += n;
-    }
-    int npad = 1;
-    while (npad < np) npad <<= 1;
-    for (int t = np + tid; t < npad; t += 256) s_key[t] = ~0ull;
-    for (int t = tid; t <= np; t += 256) s_cnt[t] = 0;
-    __syncthreads();
-    for (int k = 2; k <= npad; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < npad; t += 256) {
-                const int p = t ^ j;
-                if (p > t) {
-                    const bool up = (t & k) == 0;
-                    const unsigned long long ka = s_key[t], kb = s_key[p];
-                    if (up ? kb < ka : ka < kb) { s_key[t] = kb; s_key[p] = ka; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    const unsigned long long last_key = s_key[np - 1];
-    auto bin = [&](float d, int g, int delta) {
-        const unsigned long long k = rank_key(d, g + g_offset);
-        if (k > last_key) return;                                     // beyond the last match: affects no position
-        int p = 0, len = np;
-        while (len > 0) { const int half = len >> 1; if (s_key[p + half] < k) { p += half + 1; len -= half + 1; } else len = half; }
-        atomicAdd(&s_cnt[p], delta);
-    };
-    const float* drow = dist + (size_t)q * ng;
-    for (int g = tid; g < ng; g += 256) bin(drow[g], g, 1);
-    // junk of this shard (same identity, same camera) comes back out
-    const int lo = info[0], hi = info[1];
-    const int qp = q_pids[q], qc = q_cams[q];
-    if ((long long)hi - lo + 1 <= RANK_MAX_PID_RANGE && qp >= lo && qp <= hi) {
-        const int sb = starts[qp - lo], se = starts[qp - lo + 1];
-        __syncthreads();
-        for (int t = sb + tid; t < se; t += 256) { const int g = order[t]; if (g_cams[g] == qc) bin(drow[g], g, -1); }
-    }
-    __syncthreads();
-    for (int t = tid; t <= np; t += 256) brow[t] = s_cnt[t];
-}
-
-__global__ __launch_bounds__(256) void rank_shard_finish_kernel(const int32_t* __restrict__ bins, const int32_t* __restrict__ counts_all, int world,
-                                                                 int nq, int bins_cap, float* __restrict__ ap_out, int32_t* __restrict__ first_rank) {
-    __shared__ int s_scan[256];
-    __shared__ float s_red[4];
-    const int q = blockIdx.x, tid = threadIdx.x;
-    int np = 0;
-    for (int r = 0; r < world; ++r) np += counts_all[(size_t)r * nq + q];
-    if (np == 0 || np > bins_cap) { if (tid == 0) { ap_out[q] = 0.f; first_rank[q] = -1; } return; }
-    const int32_t* brow = bins + (size_t)q * (bins_cap + 1);
-    // inclusive scan of the bins + AP in sequential chunks of 256: the arithmetic and its order are rank_query_kernel's step 4
-    float ap_part = 0.f;
-    int carry = 0;
-    for (int base = 0; base < np; base += 256) {
-        const int t = base + tid;
-        const int v = (t < np) ? brow[t] : 0;
-        s_scan[tid] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            const int add = (tid >= o) ? s_scan[tid - o] : 0;
-            __syncthreads();
-            s_scan[tid] += add;
-            __syncthreads();
-        }
-        const int pos = carry + s_scan[tid];
-        if (t < np) ap_part += (float)(t + 1) / (float)pos;
-        if (t == 0) first_rank[q] = pos - 1;
-        carry += s_scan[255];
-        __syncthreads();
-    }
-    ap_part = wave_sum(ap_part);
-    if ((tid & 63) == 0) s_red[tid >> 6] = ap_part;
-    __syncthreads();
-    if (tid == 0) ap_out[q] = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (float)np;
-}
-
 }  // namespace dali
 
 using namespace dali;
@@ -1190,116 +770,4 @@ extern "C" int dali_pairdist_blend(dali_ctx* ctx, void* stream, const float* Q, 
     if (rc != DALI_OK) return rc;
     return launch_pairdist(ctx->num_cus, (hipStream_t)stream, g_img, sq, q_img, sq + ng, nq, ng, d, DALI_METRIC_COSINE, precision == DALI_PREC_BF16X3, inout,
                            PairBlend{q_mag_prev, g_mag_prev, q_mag, g_mag, 1});
-}
-
-// gallery positions counting-sorted by identity (info = {min, max} pid; starts over [min, max]; order = positions grouped by pid)
-static int build_gallery_index(hipStream_t st, const int32_t* g_pids, int ng, int32_t* info, int32_t* counts, int32_t* starts, int32_t* cursor,
-                               int32_t* order, int32_t* status) {
-    const int32_t init[2] = {0x7fffffff, (int32_t)0x80000000};
-    DALI_HIP(hipMemcpyAsync(info, init, sizeof(init), hipMemcpyHostToDevice, st));
-    const int gb = (ng + 255) / 256 < 1024 ? (ng + 255) / 256 : 1024;
-    hipLaunchKernelGGL(rank_index_minmax_kernel, dim3(gb), dim3(256), 0, st, g_pids, ng, info);
-    DALI_LAUNCH_CHECK();
-    DALI_HIP(hipMemsetAsync(counts, 0, ((size_t)RANK_MAX_PID_RANGE + 1) * 4, st));
-    hipLaunchKernelGGL(rank_index_count_kernel, dim3(gb), dim3(256), 0, st, g_pids, ng, info, counts, status);
-    DALI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rank_index_scan_kernel, dim3(1), dim3(1024), 0, st, info, counts, starts, cursor);
-    DALI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rank_index_scatter_kernel, dim3(gb), dim3(256), 0, st, g_pids, ng, info, starts, cursor, order);
-    DALI_LAUNCH_CHECK();
-    return DALI_OK;
-}
-// the index of a gallery (shard) in the context workspace: -> info / starts / order
-static int shard_index(dali_ctx* ctx, hipStream_t st, const int32_t* g_pids, int ng, int32_t* status, int32_t*& info, int32_t*& starts, int32_t*& order) {
-    const size_t b_info = 256, b_order = align_up((size_t)ng * 4, 256), b_tab = align_up(((size_t)RANK_MAX_PID_RANGE + 1) * 4, 256);
-    char* ws = static_cast<char*>(workspace(ctx, b_info + b_order + 3 * b_tab));
-    if (!ws) return DALI_ERR_NOMEM;
-    info = reinterpret_cast<int32_t*>(ws);
-    order = reinterpret_cast<int32_t*>(ws + b_info);
-    int32_t* counts = reinterpret_cast<int32_t*>(ws + b_info + b_order);
-    starts = counts + b_tab / 4;
-    return build_gallery_index(st, g_pids, ng, info, counts, starts, starts + b_tab / 4, order, status);
-}
-
-extern "C" int dali_rank_shard_matches(dali_ctx* ctx, void* stream, const float* dist_shard, const int32_t* q_pids, const int32_t* g_pids,
-                                       const int32_t* q_camids, const int32_t* g_camids, int nq, int ng, int g_offset, int cap,
-                                       int64_t* keys, int32_t* counts, int32_t* status) {
-    DALI_REQUIRE(ctx && dist_shard && q_pids && g_pids && q_camids && g_camids && keys && counts && status, "dali_rank_shard_matches: null argument");
-    DALI_REQUIRE(nq > 0 && ng > 0 && g_offset >= 0 && cap > 0 && cap <= RANK_PMAX, "dali_rank_shard_matches: bad shape nq=%d ng=%d offset=%d cap=%d", nq, ng, g_offset, cap);
-    hipStream_t st = (hipStream_t)stream;
-    DALI_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
-    int32_t *info, *starts, *order;
-    if (int rc = shard_index(ctx, st, g_pids, ng, status, info, starts, order)) return rc;
-    hipLaunchKernelGGL(rank_shard_matches_kernel, dim3(nq), dim3(256), 0, st, dist_shard, q_pids, q_camids, g_camids, info, starts, order, ng, g_offset, cap,
-                       reinterpret_cast<unsigned long long*>(keys), counts, status);
-    DALI_LAUNCH_CHECK();
-    return DALI_OK;
-}
-
-extern "C" int dali_rank_shard_bins(dali_ctx* ctx, void* stream, const float* dist_shard, const int32_t* q_pids, const int32_t* g_pids,
-                                    const int32_t* q_camids, const int32_t* g_camids, int nq, int ng, int g_offset, const int64_t* keys_all,
-                                    const int32_t* counts_all, int world, int cap, int32_t* bins, int bins_cap, int32_t* status) {
-    DALI_REQUIRE(ctx && dist_shard && q_pids && g_pids && q_camids && g_camids && keys_all && counts_all && bins && status, "dali_rank_shard_bins: null argument");
-    DALI_REQUIRE(nq > 0 && ng > 0 && g_offset >= 0 && world > 0 && cap > 0 && bins_cap > 0 && bins_cap <= RANK_PMAX,
-                 "dali_rank_shard_bins: bad shape nq=%d ng=%d world=%d cap=%d bins_cap=%d (<= %d)", nq, ng, world, cap, bins_cap, RANK_PMAX);
-    hipStream_t st = (hipStream_t)stream;
-    DALI_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
-    int32_t *info, *starts, *order;
-    if (int rc = shard_index(ctx, st, g_pids, ng, status, info, starts, order)) return rc;
-    hipLaunchKernelGGL(rank_shard_bins_kernel, dim3(nq), dim3(256), 0, st, dist_shard, q_pids, q_camids, g_camids, info, starts, order, nq, ng, g_offset,
-                       reinterpret_cast<const unsigned long long*>(keys_all), counts_all, world, cap, bins, bins_cap, status);
-    DALI_LAUNCH_CHECK();
-    return DALI_OK;
-}
-
-extern "C" int dali_rank_shard_finish(dali_ctx* ctx, void* stream, const int32_t* bins, const int32_t* counts_all, int world, int nq, int bins_cap,
-                                      int max_rank, float* cmc, float* mAP, double* map64, int32_t* num_valid, float* ap, int32_t* first_rank) {
-    DALI_REQUIRE(ctx && bins && counts_all && cmc && mAP && num_valid && ap && first_rank, "dali_rank_shard_finish: null argument");
-    DALI_REQUIRE(nq > 0 && world > 0 && bins_cap > 0 && max_rank > 0 && max_rank <= 1024, "dali_rank_shard_finish: bad shape");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(rank_shard_finish_kernel, dim3(nq), dim3(256), 0, st, bins, counts_all, world, nq, bins_cap, ap, first_rank);
-    DALI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rank_reduce_kernel, dim3(1), dim3(256), 0, st, ap, first_rank, nq, max_rank, cmc, mAP, map64, num_valid);
-    DALI_LAUNCH_CHECK();
-    return DALI_OK;
-}
-
-extern "C" int dali_rank_eval(dali_ctx* ctx, void* stream, const float* distmat, const int32_t* q_pids,
-                              const int32_t* g_pids, const int32_t* q_camids, const int32_t* g_camids, int nq, int ng,
-                              int max_rank, float* cmc, float* mAP, double* map64, int32_t* num_valid, float* ap,
-                              int32_t* first_rank, int32_t* status) {
-    DALI_REQUIRE(ctx && distmat && q_pids && g_pids && q_camids && g_camids && cmc && mAP && num_valid && status,
-                 "dali_rank_eval: null argument");
-    DALI_REQUIRE(nq > 0 && ng > 0, "dali_rank_eval: bad shape nq=%d ng=%d", nq, ng);
-    DALI_REQUIRE(max_rank > 0 && max_rank <= 1024, "dali_rank_eval: max_rank %d outside 1..1024", max_rank);
-    hipStream_t st = (hipStream_t)stream;
-    float* ap_buf = ap;
-    int32_t* fr_buf = first_rank;
-    // gallery index by identity (counting sort over [min pid, max pid]) in the context workspace, behind the ap / first_rank scratch
-    DALI_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
-    {
-        const size_t head = (!ap || !first_rank) ? align_up((size_t)nq * 4, 256) * 2 : 0;
-        const size_t b_info = 256, b_order = align_up((size_t)ng * 4, 256), b_pend = align_up((size_t)nq * 4, 256);
-        const size_t b_tab = align_up(((size_t)RANK_MAX_PID_RANGE + 1) * 4, 256);
-        char* ws = static_cast<char*>(workspace(ctx, head + b_info + b_order + b_pend + 3 * b_tab));
-        if (!ws) return DALI_ERR_NOMEM;
-        if (!ap) ap_buf = reinterpret_cast<float*>(ws);
-        if (!first_rank) fr_buf = reinterpret_cast<int32_t*>(ws + align_up((size_t)nq * 4, 256));
-        int32_t* info = reinterpret_cast<int32_t*>(ws + head);
-        int32_t* order = reinterpret_cast<int32_t*>(ws + head + b_info);
-        int32_t* pending = reinterpret_cast<int32_t*>(ws + head + b_info + b_order);
-        int32_t* counts = reinterpret_cast<int32_t*>(ws + head + b_info + b_order + b_pend);
-        int32_t* starts = counts + b_tab / 4;
-        int32_t* cursor = starts + b_tab / 4;
-        if (int rc = build_gallery_index(st, g_pids, ng, info, counts, starts, cursor, order, status)) return rc;
-        hipLaunchKernelGGL((rank_query_kernel<RANK_PSMALL, 0>), dim3(nq), dim3(256), 0, st, distmat, q_pids, q_camids, g_camids, info, starts, order,
-                           nq, ng, ap_buf, fr_buf, pending, status);
-        DALI_LAUNCH_CHECK();
-        hipLaunchKernelGGL((rank_query_kernel<RANK_PMAX, 1>), dim3(nq), dim3(256), 0, st, distmat, q_pids, q_camids, g_camids, info, starts, order,
-                           nq, ng, ap_buf, fr_buf, pending, status);
-        DALI_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(rank_reduce_kernel, dim3(1), dim3(256), 0, st, ap_buf, fr_buf, nq, max_rank, cmc, mAP, map64, num_valid);
-    DALI_LAUNCH_CHECK();
-    return DALI_OK;
 }

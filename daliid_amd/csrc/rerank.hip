@@ -15,7 +15,7 @@
 // Every float sum has a fixed order, so the result is bitwise identical run to run: the only atomics are integer counters of the
 // inverted index, whose slot order inside a column cannot reach a sum (a column's rows are distinct, so each accumulator t[j] receives
 // at most one term per column, and the columns are walked in ascending order with a barrier between them).
-#include "common.h"
+#include "block_prims.h"
 #include <climits>
 
 namespace {
@@ -27,6 +27,8 @@ constexpr int RR_KMAX = 64;        // K = k1 + 1 <= 64: one neighbour per lane
 constexpr int RR_LDS_ACC_MAX = 128 * 1024 / 4;   // galleries up to 32,768 keep the Jaccard accumulator in LDS (one 128 KiB block per CU)
 
 typedef unsigned long long u64;
+using dali::shfl_u64;
+using dali::shfl_up_u64;
 
 // full[j][i], every offset 64-bit (ng * ng exceeds 2^31 once ng > 46,340)
 __device__ __forceinline__ float rr_full(const float* __restrict__ q_g, const float* __restrict__ q_q, const float* __restrict__ g_g,
@@ -35,14 +37,6 @@ __device__ __forceinline__ float rr_full(const float* __restrict__ q_g, const fl
     return i < nq ? q_g[(size_t)i * ng + (j - nq)] : g_g[(size_t)(j - nq) * ng + (i - nq)];
 }
 
-__device__ __forceinline__ u64 rr_shfl(u64 v, int src) {
-    const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 rr_shfl_up1(u64 v) {
-    const unsigned lo = __shfl_up((unsigned)v, 1, 64), hi = __shfl_up((unsigned)(v >> 32), 1, 64);
-    return ((u64)hi << 32) | lo;
-}
 __device__ __forceinline__ int rr_wave_min(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
@@ -99,13 +93,13 @@ __global__ __launch_bounds__(RR_COL_THREADS) void rr_columns_kernel(const float*
             } else if (i0 + w * 4 + t < N) {                                     // wave-uniform
                 const float v = a / cm[t];                                       // IEEE division (no fast reciprocal)
                 const u64 kv = ((u64)__float_as_uint(v) << 32) | (unsigned)j;
-                const u64 th = rr_shfl(key[t], K - 1);
+                const u64 th = shfl_u64(key[t], K - 1);
                 u64 m = __ballot(j < N && kv < th);
                 while (m) {                                                       // insert into the sorted per-lane list
                     const int b = __ffsll((long long)m) - 1;
                     m &= m - 1;
-                    const u64 kc = rr_shfl(kv, b);
-                    const u64 prev = rr_shfl_up1(key[t]);
+                    const u64 kc = shfl_u64(kv, b);
+                    const u64 prev = shfl_up_u64(key[t], 1);
                     key[t] = key[t] < kc ? key[t] : ((lane == 0 || prev < kc) ? kc : prev);
                 }
             }
@@ -177,6 +171,8 @@ __global__ __launch_bounds__(64) void rr_vrow_kernel(const float* __restrict__ q
     while (p2 < ncand) p2 <<= 1;
     for (int k = ncand + lane; k < p2; k += 64) s_cand[k] = INT_MAX;
     __syncthreads();
+    // (a network of its own, not an instance of block_sort_keys: one wave, ints, one compare pair per lane and pass, where the shared form
+    //  walks every element with 256 threads and idles the upper partner -- another schedule for this kernel, not measured, so not taken)
     for (int size = 2; size <= p2; size <<= 1)
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
             for (int t = lane; t < (p2 >> 1); t += 64) {
@@ -262,21 +258,7 @@ __global__ __launch_bounds__(256) void rr_inv_count_kernel(const int32_t* __rest
 // one block: off[c] = exclusive prefix of colcnt over N columns (off[N] = total), cursors zeroed
 __global__ __launch_bounds__(1024) void rr_inv_scan_kernel(const int32_t* __restrict__ colcnt, int N, int32_t* __restrict__ off,
                                                            int32_t* __restrict__ cursor) {
-    __shared__ int s_part[1024];
-    const int tid = threadIdx.x, per = (N + 1023) / 1024, b = min(tid * per, N), e = min(b + per, N);
-    int sum = 0;
-    for (int c = b; c < e; ++c) sum += colcnt[c];
-    s_part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int add = tid >= o ? s_part[tid - o] : 0;
-        __syncthreads();
-        s_part[tid] += add;
-        __syncthreads();
-    }
-    int run = s_part[tid] - sum;
-    for (int c = b; c < e; ++c) { off[c] = run; cursor[c] = 0; run += colcnt[c]; }
-    if (tid == 1023) off[N] = s_part[1023];
+    dali::block_counts_to_offsets_1024(colcnt, N, off, cursor);
 }
 __global__ __launch_bounds__(256) void rr_inv_scatter_kernel(const int32_t* __restrict__ vidx, const float* __restrict__ vval,
                                                              const int32_t* __restrict__ vcnt, int cap, int nq, int ng,

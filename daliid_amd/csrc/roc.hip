@@ -21,7 +21,7 @@
 //
 // Every count is an integer, so the order in which atomics land cannot change a result: the output is bitwise identical run to run.
 // In LDS, a wave whose lanes all hit one bin adds once (the all-tied matrix would otherwise serialise on one address).
-#include "common.h"
+#include "block_prims.h"
 #include <algorithm>
 
 namespace {
@@ -70,6 +70,10 @@ Layout roc_layout(long long N) {
     return L;
 }
 
+// The key is dali::ordered_bits(s) for every finite and infinite s (the map agrees bit for bit there, -0 folded onto +0), and its inverse
+// below IS ordered_bits_inv.  NaN policy of this file: a non-finite score sets `bad` (status 1 of dali_roc_build) and is still counted
+// under its key, so a NaN's key reaches the point counts and the scratch.  The key is therefore taken from the raw bits, folding by
+// comparison: ordered_bits folds by `s + 0.0f`, an addition, and what an addition leaves of a NaN's payload is the hardware's choice.
 __device__ __forceinline__ unsigned roc_key(float d, bool& bad) {
     const float s = 1.0f - d / 2.0f;                        // numpy's fl32(1 - fl32(d / 2)); the library builds without contraction
     unsigned u = __float_as_uint(s);
@@ -77,9 +81,7 @@ __device__ __forceinline__ unsigned roc_key(float d, bool& bad) {
     if (u == 0x80000000u) u = 0u;                            // -0 and +0 are one score
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-__device__ __forceinline__ float roc_score(unsigned key) {
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
+__device__ __forceinline__ float roc_score(unsigned key) { return dali::ordered_bits_inv(key); }
 
 __device__ __forceinline__ int roc_lane() { return threadIdx.x & 63; }
 __device__ __forceinline__ unsigned roc_mbcnt(u64 m) {
@@ -107,15 +109,6 @@ __device__ __forceinline__ unsigned roc_lds_add(unsigned* h, unsigned bin, unsig
     return valid ? atomicAdd(&h[bin], inc) : 0u;
 }
 
-__device__ __forceinline__ u64 roc_shfl_u64(u64 v, int src) {
-    const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 roc_shfl_up_u64(u64 v, int d) {
-    const unsigned lo = __shfl_up((unsigned)v, d, 64), hi = __shfl_up((unsigned)(v >> 32), d, 64);
-    return ((u64)hi << 32) | lo;
-}
-
 // block-wide exclusive scan of NV u64 values (blockDim.x a multiple of 64, at most 1024); totals[] receive the block sums.
 // `sh` holds at least 16 * NV u64.  Ends with a barrier, so `sh` may be reused at once.
 template <int NV>
@@ -126,7 +119,7 @@ __device__ __forceinline__ void roc_block_scan(u64 (&v)[NV], u64 (&totals)[NV], 
     for (int k = 0; k < NV; ++k) {
         inc[k] = v[k];
         for (int d = 1; d < 64; d <<= 1) {
-            const u64 t = roc_shfl_up_u64(inc[k], d);
+            const u64 t = dali::shfl_up_u64(inc[k], d);
             if (lane >= d) inc[k] += t;
         }
     }

@@ -1,6 +1,7 @@
 // topk.hip -- exact top-k retrieval (include/daliid.h: dali_topk_rows, dali_topk_decode, dali_pairdist_topk): the k best entries of every
-//   row under the order of topk_key.h, as sorted lists of 64-bit keys that later calls merge into.  dali_pairdist_topk takes the rows
-//   from the distance kernel's accumulators (pairdist_epilogue_topk, eval.hip) and never holds more than a [nq, boot_cols] block of them.
+//   row under the order of topk_key.h, as sorted lists of 64-bit keys that later calls merge into; the lists are sorted in LDS by
+//   block_pad_sort (block_prims.h, shared with the ranking).  dali_pairdist_topk takes the rows from the distance kernel's accumulators
+//   (pairdist_epilogue_topk, eval.hip) and never holds more than a [nq, boot_cols] block of them.
 #include "kernels.h"
 #include "topk_key.h"
 
@@ -9,32 +10,6 @@ namespace dali {
 constexpr int TOPK_BUF = 2048;                  // keys a row's workgroup holds in LDS (16 KiB: 8+ workgroups per CU, the scan is HBM-bound)
 constexpr int TOPK_BATCH = 1024;                // elements scanned between two looks at the fill level (4 per thread)
 constexpr int TOPK_CAND_MAX = TOPK_BUF - TOPK_K_MAX;
-
-// ascending bitonic sort of s_key[0 .. npad), npad a power of two <= TOPK_BUF, by a 256-thread block.  Keys are unique except for the
-// sentinel, so the sorted sequence does not depend on the order the keys arrived in.
-__device__ __forceinline__ void block_sort_keys(unsigned long long* s_key, int npad, int tid) {
-    for (int k = 2; k <= npad; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < npad; t += 256) {
-                const int p = t ^ j;
-                if (p > t) {
-                    const bool up = (t & k) == 0;
-                    const unsigned long long ka = s_key[t], kb = s_key[p];
-                    if (up ? kb < ka : ka < kb) { s_key[t] = kb; s_key[p] = ka; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-// pads s_key[n ..) with sentinels up to the next power of two >= max(n, at_least) and sorts.  All threads pass the same n.
-__device__ __forceinline__ void block_pad_sort(unsigned long long* s_key, int n, int at_least, int tid) {
-    int npad = 1;
-    while (npad < n || npad < at_least) npad <<= 1;
-    for (int t = n + tid; t < npad; t += 256) s_key[t] = TOPK_SENTINEL;
-    __syncthreads();
-    block_sort_keys(s_key, npad, tid);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Row selection: one 256-thread workgroup per row, one read of the row (4 bytes per element, 16-byte loads where the row is aligned).

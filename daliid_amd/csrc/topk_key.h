@@ -1,12 +1,12 @@
 // topk_key.h -- the selection order of include/daliid.h (dali_topk_rows) as one unsigned 64-bit key, shared by the row selection
 // (topk.hip) and the selecting epilogue of the distance kernel (eval.hip):
 //   key = (ordered value bits << 32) | global column index;  smaller key = better entry.
-// Ordered value bits: IEEE bits made monotonic (negative values flipped, sign bit set on the others; -0.0 folded onto +0.0 first, so
-// that equal values compare by index), complemented for `largest`; a NaN of either sign is 0xffffffff in both directions, i.e. after
-// +inf (-inf for largest), where numpy and torch sort it.  No other value maps to 0xffffffff, and indices stay below 2^31, so the all-ones
+// Ordered value bits: ordered_bits (block_prims.h: monotone, -0.0 folded onto +0.0, so that equal values compare by index), complemented
+// for `largest`.  NaN policy of this key, stated here once: a NaN of either sign is 0xffffffff in both directions, i.e. after +inf (-inf
+// for largest), where numpy and torch sort it.  No other value maps to 0xffffffff, and indices stay below 2^31, so the all-ones
 // key is free: it marks an unfilled slot and sorts after every entry.
 #pragma once
-#include "common.h"
+#include "block_prims.h"
 
 namespace dali {
 
@@ -15,8 +15,7 @@ constexpr unsigned long long TOPK_SENTINEL = ~0ull;
 
 __device__ __forceinline__ unsigned int topk_ordered_bits(float v, int largest) {
     if (v != v) return 0xffffffffu;
-    unsigned int b = __float_as_uint(v + 0.0f);
-    b ^= (b >> 31) ? 0xffffffffu : 0x80000000u;
+    const unsigned int b = ordered_bits(v);
     return largest ? ~b : b;
 }
 __device__ __forceinline__ unsigned long long topk_key(float v, int index, int largest) {
@@ -30,8 +29,7 @@ __device__ __forceinline__ void topk_key_decode(unsigned long long key, int larg
         v = (key == TOPK_SENTINEL) ? __uint_as_float(largest ? 0xff800000u : 0x7f800000u) : __uint_as_float(0x7fc00000u);
         return;
     }
-    const unsigned int b = largest ? ~hi : hi;
-    v = __uint_as_float((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b);
+    v = ordered_bits_inv(largest ? ~hi : hi);
 }
 
 // Selecting epilogue of pairdist_dma_kernel: instead of storing its tile, a consumer lane compares every distance with its query's

@@ -212,7 +212,7 @@ def rank_eval(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50, return_p
     return res
 
 
-RANK_PMAX = 4096          # matches + junk of one query the ranking kernels hold in LDS (csrc/eval.hip)
+RANK_PMAX = 4096          # matches + junk of one query the ranking kernels hold in LDS (csrc/rank.hip)
 
 
 def shard_bounds(n, world):

@@ -287,3 +287,51 @@ def test_sharded_ranking_equals_whole_gallery_ranking(ops, world, nq, ng, n_ids,
     assert np.array_equal(o["ap"].cpu().numpy(), ap_ref) and np.array_equal(o["first_rank"].cpu().numpy(), fr_ref)
     assert np.array_equal(o["cmc"].cpu().numpy(), cmc_ref) and float(o["map64"].item()) == map_ref
     assert (fr_ref[:3] == -1).all() and (fr_ref[3:] >= 0).any()
+
+
+def _many_match_case():
+    """8 queries x 1536 gallery entries, 3 cameras; identity 0 holds 700 gallery entries spread over the gallery, four queries have identity
+    0 and the last one an identity the gallery lacks; distances rounded to 1/16, so ties cross every shard boundary."""
+    rng = np.random.default_rng(1536)
+    nq, ng = 8, 1536
+    g_pids = rng.integers(1, 10, ng)
+    g_pids[rng.permutation(ng)[:700]] = 0
+    q_pids = np.array([0, 3, 0, 7, 0, 1, 0, 99])
+    q_cams = rng.integers(0, 3, nq); g_cams = rng.integers(0, 3, ng)
+    d = np.round(rng.random((nq, ng), dtype=np.float32) * 16) / 16
+    return d.astype(np.float32), q_pids, g_pids, q_cams, g_cams
+
+
+def test_sharded_ranking_equals_whole_gallery_ranking_across_scan_chunks(ops):
+    """As the test above, at the size where the AP tail's 256-entry chunks carry into each other: about 470 matches per identity-0 query
+    (two chunks, so the carry is compared between the whole-gallery and the sharded path), 700 same-identity entries > RANK_PSMALL (the
+    whole-gallery side runs the RANK_PMAX pass), fewer than 512 of them per shard (world = 3, 512-row slices: no status raised).  Bit for
+    bit between the two paths, and both against the oracle at 1e-6."""
+    dist, qp_s, gp_s, qc_s, gc_s = _many_match_case()
+    nq, ng, world = dist.shape[0], dist.shape[1], 3
+    matches = [int(((gp_s == 0) & (gc_s != qc_s[q])).sum()) for q in np.flatnonzero(qp_s == 0)]
+    assert len(matches) == nq // 2 and min(matches) > 256 and max(matches) <= 512 and int((gp_s == 0).sum()) == 700
+    D = torch.from_numpy(dist).cuda()
+    cmc_ref, map_ref, ap_ref, fr_ref = ops.rank_eval(D, qp_s, gp_s, qc_s, gc_s, max_rank=50, return_per_query=True)
+    bounds = ops.shard_bounds(ng, world)
+    assert bounds == [0, 512, 1024, 1536]
+    t = lambda a: torch.from_numpy(a).cuda()
+    shards = []
+    for r in range(world):
+        lo, hi = bounds[r], bounds[r + 1]
+        qp, gp = ops.factorize_ids(qp_s, gp_s[lo:hi]); qc, gc = ops.factorize_ids(qc_s, gc_s[lo:hi])
+        shards.append((D[:, lo:hi].contiguous(), t(qp), t(gp), t(qc), t(gc), lo))
+    cap = max(int(np.unique(gp_s[bounds[r]:bounds[r + 1]], return_counts=True)[1].max()) for r in range(world))
+    bins_cap = min(world * cap, ops.RANK_PMAX)
+    assert cap < 512 and bins_cap < ops.RANK_PMAX
+    ks, cs, st1 = zip(*[ops.rank_shard_matches(*sh, cap) for sh in shards])
+    keys_all, counts_all = torch.stack(ks), torch.stack(cs)
+    bins, st2 = zip(*[ops.rank_shard_bins(*sh, keys_all, counts_all, bins_cap) for sh in shards])
+    assert all(int(s.item()) == 0 for s in st1 + st2)
+    o = ops.rank_shard_finish(sum(bins), counts_all, 50)
+    assert np.array_equal(o["ap"].cpu().numpy(), ap_ref) and np.array_equal(o["first_rank"].cpu().numpy(), fr_ref)
+    assert np.array_equal(o["cmc"].cpu().numpy(), cmc_ref) and float(o["map64"].item()) == map_ref
+    assert fr_ref[-1] == -1 and (fr_ref[:-1] >= 0).all()
+    ref_cmc, ref_map = E.eval_market1501(dist, qp_s, gp_s, qc_s, gc_s, max_rank=50)
+    np.testing.assert_allclose(cmc_ref, ref_cmc, atol=1e-6)
+    assert abs(map_ref - ref_map) < 1e-6
