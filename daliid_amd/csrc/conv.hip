@@ -282,15 +282,8 @@ __device__ __forceinline__ float gelu_grad_f(float x) { float c, p; gelu_parts(x
 __device__ __forceinline__ void unpack4(uint2 q, float (&f)[4]) {
     f[0] = bf16_bits_to_f32(q.x & 0xffffu); f[1] = bf16_bits_to_f32(q.x >> 16); f[2] = bf16_bits_to_f32(q.y & 0xffffu); f[3] = bf16_bits_to_f32(q.y >> 16);
 }
-__device__ __forceinline__ void unpack8(const uint4& q, float (&f)[8]) {
-    f[0] = bf16_bits_to_f32(q.x & 0xffffu); f[1] = bf16_bits_to_f32(q.x >> 16); f[2] = bf16_bits_to_f32(q.y & 0xffffu); f[3] = bf16_bits_to_f32(q.y >> 16);
-    f[4] = bf16_bits_to_f32(q.z & 0xffffu); f[5] = bf16_bits_to_f32(q.z >> 16); f[6] = bf16_bits_to_f32(q.w & 0xffffu); f[7] = bf16_bits_to_f32(q.w >> 16);
-}
-// the one rounding to bf16 at the end of every path
+// the one rounding to bf16 at the end of every path (pack8: common.h)
 __device__ __forceinline__ uint2 pack4(const float (&v)[4]) { return make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])); }
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-    return make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
-}
 // this lane's 4 channels of every 16-row block of a per-channel vector (bias, scale, shift); `vec` points at the lane's first channel
 template <int FM>
 __device__ __forceinline__ void load_rows4(float4 (&d)[FM], const float* vec) {

@@ -134,9 +134,7 @@ inline size_t reduce_scratch_bytes(int C, int NV) { return (size_t)REDUCE_SMAX *
 int launch_bn_finalize(hipStream_t st, const float* partial, int tiles, int C, double count, const float* gamma, const float* beta,
                        float* rm, float* rv, float momentum, float eps, float* scale, float* shift, float* mean, float* invstd,
                        double* scratch);
-int launch_bn_eval_coeffs(hipStream_t st, const float* gamma, const float* beta, const float* rm, const float* rv, float eps, int C,
-                          float* scale, float* shift);
-// many bn_eval_coeffs in one launch (kernel arguments hold the job table: at most BnEvalJobs::MAX jobs per launch)
+// eval-mode scale / shift of many BatchNorms in one launch (kernel arguments hold the job table: at most BnEvalJobs::MAX jobs per launch)
 struct BnEvalJob { const float *gamma, *beta, *rm, *rv; float *scale, *shift; int C; };
 struct BnEvalJobs { static constexpr int MAX = 56; BnEvalJob job[MAX]; };
 int launch_bn_eval_coeffs_batched(hipStream_t st, const BnEvalJob* jobs, int n, float eps);
@@ -162,6 +160,8 @@ int launch_stem_conv_bn_pool(hipStream_t st, const uint16_t* ximg, const uint16_
 int launch_stem_unpack_wgrad(hipStream_t st, const float* padded, int Cout, float* dw);
 int launch_maxpool_bn_fwd(hipStream_t st, const uint16_t* raw, const float* scale, const float* shift, int N, int H, int W, int C,
                           uint16_t* out, uint8_t* arg);
+// blocks (= rows of `partial`, [blocks][C][2] floats) of launch_maxpool_bn_bwd's reduce pass
+int maxpool_bn_bwd_blocks(int N, int H, int W, int C, int* quads_per_block);
 int launch_maxpool_bn_bwd(hipStream_t st, const uint16_t* dp, const uint8_t* arg, const uint16_t* raw, const float* mean, const float* invstd,
                           const float* scale, int N, int H, int W, int C, float* partial, float* coef, float* dgamma, float* dbeta,
                           uint16_t* draw, double* scratch);
@@ -188,7 +188,6 @@ int launch_layernorm_bwd(hipStream_t st, const uint16_t* g, const uint16_t* x, c
                          const float* g32 = nullptr);
 size_t colsum_partial_floats(int rows, int C);
 int launch_colsum(hipStream_t st, const uint16_t* y, int rows, int C, float* out, float* partial, double* scratch);
-int launch_colsum_partials(hipStream_t st, const uint16_t* y, int rows, int C, float* partial, int* n_rows);
 // out = (res or 0) + scale[row / rows_per_sample] * branch   (DropPath per sample; C % 8 == 0)
 int launch_rowscale_add(hipStream_t st, const uint16_t* branch, const float* scale, int samples, int rows_per_sample, int C, const uint16_t* res,
                         uint16_t* out);

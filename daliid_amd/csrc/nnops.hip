@@ -7,20 +7,6 @@
 
 namespace dali {
 
-__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
-    f[0] = bf16_bits_to_f32(v.x & 0xffffu); f[1] = bf16_bits_to_f32(v.x >> 16);
-    f[2] = bf16_bits_to_f32(v.y & 0xffffu); f[3] = bf16_bits_to_f32(v.y >> 16);
-    f[4] = bf16_bits_to_f32(v.z & 0xffffu); f[5] = bf16_bits_to_f32(v.z >> 16);
-    f[6] = bf16_bits_to_f32(v.w & 0xffffu); f[7] = bf16_bits_to_f32(v.w >> 16);
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-    return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
-}
-__device__ __forceinline__ void load8f(const float* __restrict__ p, float (&f)[8]) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-
 // ------------------------------------------------------------------------------------------------
 // BatchNorm finalise: partial (sum, sumsq) [tiles][C][2] -> mean, invstd, scale = gamma*invstd,
 // shift = beta - mean*scale; running stats updated as torch does (momentum, unbiased variance).
@@ -51,18 +37,8 @@ struct FinBnFwd {
     }
 };
 
-// eval mode: scale/shift from the running statistics
-__global__ void bn_eval_coeffs_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                                      const float* __restrict__ rm, const float* __restrict__ rv, float eps, int C,
-                                      float* __restrict__ scale, float* __restrict__ shift) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const float sc = gamma[c] / sqrtf(rv[c] + eps);
-    scale[c] = sc;
-    shift[c] = beta[c] - rm[c] * sc;
-}
-
-// the same for many BatchNorms in one launch (the inference forward folds all of them into conv epilogues: 53 coefficient launches -> 2)
+// eval mode: scale / shift from the running statistics, for many BatchNorms in one launch (the inference forward folds all of them
+// into conv epilogues: 53 coefficient launches -> 2)
 __global__ void bn_eval_coeffs_batched_kernel(BnEvalJobs jobs, float eps) {
     const BnEvalJob j = jobs.job[blockIdx.y];
     for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < j.C; c += gridDim.x * blockDim.x) {
@@ -151,6 +127,33 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const uint16_t* __restrict_
 // A second BN sharing the same dz (the downsample branch of a bottleneck) is handled in the same passes.
 // Work split: a thread owns one 16-byte channel chunk and strides over pixels; partials per block.
 // ------------------------------------------------------------------------------------------------
+// which mask source a launch uses, in order of precedence; none of them: dz = g
+struct DzMask { bool bits, y, recompute; };
+__device__ __forceinline__ DzMask dz_mask(const uint8_t* ybits, const uint16_t* ymask, int relu) {
+    return {ybits != nullptr, !ybits && ymask, !ybits && !ymask && relu};
+}
+// the bits arm: bit t of m = (y[c+t] > 0), as bn_act_kernel wrote it
+__device__ __forceinline__ void dz_gate_bits(float (&gv)[8], const unsigned m) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t) gv[t] = ((m >> t) & 1u) ? gv[t] : 0.f;
+}
+// g -> dz for one 16-byte chunk: m = the chunk's byte of ybits, yq = its 8 bf16 of ymask, sc / sh = scale / shift of its 8 channels
+// (each read only by its own arm)
+__device__ __forceinline__ void dz_gate(float (&gv)[8], const float (&rv)[8], const DzMask mk, const unsigned m, const uint4& yq,
+                                        const float* sc, const float* sh) {
+    if (mk.bits) {
+        dz_gate_bits(gv, m);
+    } else if (mk.y) {
+        float yv[8];
+        unpack8(yq, yv);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) gv[t] = yv[t] > 0.f ? gv[t] : 0.f;
+    } else if (mk.recompute) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) gv[t] = (rv[t] * sc[t] + sh[t]) > 0.f ? gv[t] : 0.f;
+    }
+}
+
 template <bool DUAL>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const uint16_t* __restrict__ g, const uint16_t* __restrict__ ymask,
                                                              const uint8_t* __restrict__ ybits, BnBwdSide a, BnBwdSide b, int relu, int P, int C,
@@ -163,10 +166,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const uint16_t* __re
     const int c = col * 8;
     const int p0 = blockIdx.x * rows_per_block;
     const int p1 = min(P, p0 + rows_per_block);
-    float s1[8], s2a[8], s2b[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) { s1[t] = 0.f; s2a[t] = 0.f; s2b[t] = 0.f; }
     if (rsub < rif) {
+        float s[NV][8] = {};
         float ma[8], ia[8], sa[8], ha[8], mb[8], ib[8];
         load8f(a.mean + c, ma); load8f(a.invstd + c, ia);
         if (!ymask && !ybits && relu) { load8f(a.scale + c, sa); load8f(a.shift + c, ha); }
@@ -176,9 +177,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const uint16_t* __re
             float gv[8], rv[8];
             unpack8(gq, gv);
             unpack8(rq, rv);
+            // (dz_gate written out: as a call the compiler laid the three arms out with 27 more scalar branches per kernel and the pass
+            //  measured 0.35 us slower per launch, 19.4 -> 19.75 us; same arms, same precedence)
             if (ybits) {
-#pragma unroll
-                for (int t = 0; t < 8; ++t) gv[t] = ((m >> t) & 1u) ? gv[t] : 0.f;
+                dz_gate_bits(gv, m);
             } else if (ymask) {
                 float yv[8];
                 unpack8(yq, yv);
@@ -189,12 +191,12 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const uint16_t* __re
                 for (int t = 0; t < 8; ++t) gv[t] = (rv[t] * sa[t] + ha[t]) > 0.f ? gv[t] : 0.f;
             }
 #pragma unroll
-            for (int t = 0; t < 8; ++t) { s1[t] += gv[t]; s2a[t] += gv[t] * ((rv[t] - ma[t]) * ia[t]); }
-            if (DUAL) {
+            for (int t = 0; t < 8; ++t) { s[0][t] += gv[t]; s[1][t] += gv[t] * ((rv[t] - ma[t]) * ia[t]); }
+            if constexpr (DUAL) {
                 float r2[8];
                 unpack8(r2q, r2);
 #pragma unroll
-                for (int t = 0; t < 8; ++t) s2b[t] += gv[t] * ((r2[t] - mb[t]) * ib[t]);
+                for (int t = 0; t < 8; ++t) s[2][t] += gv[t] * ((r2[t] - mb[t]) * ib[t]);
             }
         };
         // four rows' loads are issued before the first is used: with 16 waves per CU and two 16-byte loads per thread in flight
@@ -222,19 +224,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const uint16_t* __re
                     (!ybits && ymask) ? *reinterpret_cast<const uint4*>(ymask + o) : make_uint4(0, 0, 0, 0),
                     DUAL ? *reinterpret_cast<const uint4*>(b.raw + o) : make_uint4(0, 0, 0, 0));
         }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            float* d = red + ((size_t)rsub * C + c + t) * NV;
-            d[0] = s1[t]; d[1] = s2a[t];
-            if (DUAL) d[2] = s2b[t];
-        }
+        block_partial_store<NV>(red, rsub, C, c, s);
     }
-    __syncthreads();
-    for (int e = threadIdx.x; e < C * NV; e += 256) {
-        float s = 0.f;
-        for (int r = 0; r < rif; ++r) s += red[(size_t)r * C * NV + e];
-        partial[(size_t)blockIdx.x * C * NV + e] = s;
-    }
+    block_partial_finish<NV>(red, rif, C, partial);
 }
 
 // partial [blocks][C][NV] -> dgamma = S2, dbeta = S1 and the folded apply coefficients, structure-of-arrays coef [3][C]:
@@ -275,13 +267,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const uint16_t* __res
     // coefficients once per thread when the grid stride is a multiple of C (see bn_act_kernel)
     const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x;
     const bool fixed_c = ((size_t)gridDim.x * 2048) % (size_t)C == 0;
-    const bool need_relu_coef = !ybits && !ymask && relu;
+    const DzMask mk = dz_mask(ybits, ymask, relu);
     int c = (int)((first * 8) % (size_t)C);
     float A[8], K[8], Q[8], A2[8], K2[8], Q2[8], sa[8], ha[8];
     auto load_coef = [&]() {
         load8f(coef_a + c, A); load8f(coef_a + C + c, K); load8f(coef_a + 2 * C + c, Q);
         if (DUAL) { load8f(coef_b + c, A2); load8f(coef_b + C + c, K2); load8f(coef_b + 2 * C + c, Q2); }
-        if (need_relu_coef) { load8f(a.scale + c, sa); load8f(a.shift + c, ha); }
+        if (mk.recompute) { load8f(a.scale + c, sa); load8f(a.shift + c, ha); }
     };
     load_coef();
     for (size_t i = first; i < chunks; i += (size_t)gridDim.x * 256) {
@@ -289,19 +281,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const uint16_t* __res
         float gv[8], rv[8];
         unpack8(*reinterpret_cast<const uint4*>(g + i * 8), gv);
         unpack8(*reinterpret_cast<const uint4*>(a.raw + i * 8), rv);
-        if (ybits) {
-            const unsigned m = ybits[i];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) gv[t] = ((m >> t) & 1u) ? gv[t] : 0.f;
-        } else if (ymask) {
-            float yv[8];
-            unpack8(*reinterpret_cast<const uint4*>(ymask + i * 8), yv);
-#pragma unroll
-            for (int t = 0; t < 8; ++t) gv[t] = yv[t] > 0.f ? gv[t] : 0.f;
-        } else if (relu) {
-#pragma unroll
-            for (int t = 0; t < 8; ++t) gv[t] = (rv[t] * sa[t] + ha[t]) > 0.f ? gv[t] : 0.f;
-        }
+        dz_gate(gv, rv, mk, mk.bits ? ybits[i] : 0u, mk.y ? *reinterpret_cast<const uint4*>(ymask + i * 8) : make_uint4(0, 0, 0, 0), sa, ha);
         float o[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) o[t] = A[t] * gv[t] + K[t] - Q[t] * rv[t];
@@ -403,182 +383,18 @@ __global__ __launch_bounds__(256) void maxpool_bn_fwd_kernel(const uint16_t* __r
     }
 }
 
-// dz[n,h,w,c] = sum over the (<=4) windows containing (h,w) of dp[window] * [arg[window] == tap of (h,w)]
-__device__ __forceinline__ void maxpool_gather_dz(const uint16_t* __restrict__ dp, const uint8_t* __restrict__ arg, int n, int h, int w,
-                                                  int cc, int C, int Ho, int Wo, float (&dz)[8]) {
-    // 3x3 / stride 2 / pad 1: row h lies in window h>>1 (at offset 1 for even h, 2 for odd h) and, for odd h, in window (h>>1)+1 at
-    // offset 0; the same for columns.  The (up to) four windows are read unconditionally from clamped addresses and gated by a
-    // predicate, so the four load pairs are in flight together (the data-dependent 1..2 x 1..2 loops serialised them).
-    const int ho0 = h >> 1, wo0 = w >> 1;
-    const int rh[2] = {1 + (h & 1), 0}, rw[2] = {1 + (w & 1), 0};           // offsets inside window 0 / window 1
-    const bool vh[2] = {ho0 < Ho, (h & 1) && ho0 + 1 < Ho}, vw[2] = {wo0 < Wo, (w & 1) && wo0 + 1 < Wo};
-    uint4 gq[4];
-    uint2 aq[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int a = k >> 1, b = k & 1;
-        const int ho = min(ho0 + a, Ho - 1), wo = min(wo0 + b, Wo - 1);
-        const size_t o = (((size_t)n * Ho + ho) * Wo + wo) * C + cc;
-        aq[k] = *reinterpret_cast<const uint2*>(arg + o);
-        gq[k] = *reinterpret_cast<const uint4*>(dp + o);
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) dz[t] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                                            // same order as the loops it replaces: (ho, wo) ascending
-        const int a = k >> 1, b = k & 1;
-        const int tap = (vh[a] && vw[b]) ? rh[a] * 3 + rw[b] : -1;
-        float g[8];
-        unpack8(gq[k], g);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int av = (t < 4 ? (aq[k].x >> (8 * t)) : (aq[k].y >> (8 * (t - 4)))) & 0xff;
-            if (av == tap) dz[t] += g[t];
-        }
-    }
-}
-
-// pass 1: partial sums of dz and dz*xhat over the stem output;  pass 2: d_raw = scale*(dz - S1/N - xhat*S2/N)
-__global__ __launch_bounds__(256) void maxpool_bn_bwd_reduce_kernel(const uint16_t* __restrict__ dp, const uint8_t* __restrict__ arg,
-                                                                     const uint16_t* __restrict__ raw, const float* __restrict__ mean,
-                                                                     const float* __restrict__ invstd, int N, int H, int W, int C,
-                                                                     int Ho, int Wo, int rows_per_block, float* __restrict__ partial) {
-    extern __shared__ float red[];                  // [rif][C][2]
-    const int cpr = C >> 3, rif = 256 / cpr;
-    const int col = threadIdx.x % cpr, rsub = threadIdx.x / cpr;
-    const int cc = col * 8;
-    const int P = N * H * W;
-    const int p0 = blockIdx.x * rows_per_block, p1 = min(P, p0 + rows_per_block);
-    float s1[8], s2[8], m[8], iv[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) { s1[t] = 0.f; s2[t] = 0.f; }
-    if (rsub < rif) {
-        load8f(mean + cc, m); load8f(invstd + cc, iv);
-        for (int p = p0 + rsub; p < p1; p += rif) {
-            const int w = p % W, h = (p / W) % H, n = p / (W * H);
-            float dz[8], rv[8];
-            maxpool_gather_dz(dp, arg, n, h, w, cc, C, Ho, Wo, dz);
-            unpack8(*reinterpret_cast<const uint4*>(raw + (size_t)p * C + cc), rv);
-#pragma unroll
-            for (int t = 0; t < 8; ++t) { s1[t] += dz[t]; s2[t] += dz[t] * ((rv[t] - m[t]) * iv[t]); }
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) { red[((size_t)rsub * C + cc + t) * 2] = s1[t]; red[((size_t)rsub * C + cc + t) * 2 + 1] = s2[t]; }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < C * 2; e += 256) {
-        float s = 0.f;
-        for (int r = 0; r < rif; ++r) s += red[(size_t)r * C * 2 + e];
-        partial[(size_t)blockIdx.x * C * 2 + e] = s;
-    }
-}
-__global__ __launch_bounds__(256) void maxpool_bn_bwd_apply_kernel(const uint16_t* __restrict__ dp, const uint8_t* __restrict__ arg,
-                                                                    const uint16_t* __restrict__ raw, const float* __restrict__ mean,
-                                                                    const float* __restrict__ invstd, const float* __restrict__ coef,
-                                                                    int N, int H, int W, int C, int Ho, int Wo, uint16_t* __restrict__ draw) {
-    const int cpr = C >> 3;
-    const unsigned total = (unsigned)N * H * W * cpr;              // < 2^32 (checked by the launcher): 32-bit index arithmetic
-    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-        const int cc = (int)(i % (unsigned)cpr) * 8;
-        const unsigned p = i / (unsigned)cpr;
-        const unsigned pw = p / (unsigned)W;
-        const int w = (int)(p - pw * W), n = (int)(pw / (unsigned)H), h = (int)(pw - (unsigned)n * H);
-        float dz[8], rv[8], A[8], K[8], Q[8], o[8];
-        maxpool_gather_dz(dp, arg, n, h, w, cc, C, Ho, Wo, dz);
-        unpack8(*reinterpret_cast<const uint4*>(raw + (size_t)p * C + cc), rv);
-        load8f(coef + cc, A); load8f(coef + C + cc, K); load8f(coef + 2 * C + cc, Q);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) o[t] = A[t] * dz[t] + K[t] - Q[t] * rv[t];
-        *reinterpret_cast<uint4*>(draw + (size_t)p * C + cc) = pack8(o);
-    }
-}
-
-// Reduce pass on 2 x 2 pixel quads (H, W even), same window sharing as the apply pass below; a block owns a range of quads.
-__global__ __launch_bounds__(256) void maxpool_bn_bwd_reduce_quad_kernel(const uint16_t* __restrict__ dp, const uint8_t* __restrict__ arg,
-                                                                          const uint16_t* __restrict__ raw, const float* __restrict__ mean,
-                                                                          const float* __restrict__ invstd, int N, int H, int W, int C,
-                                                                          int Ho, int Wo, int quads_per_block, float* __restrict__ partial) {
-    extern __shared__ float red[];                  // [rif][C][2]
-    const int cpr = C >> 3, rif = 256 / cpr;
-    const int col = threadIdx.x % cpr, rsub = threadIdx.x / cpr;
-    const int cc = col * 8;
-    const int Pq = N * Ho * Wo;
-    const int q0 = blockIdx.x * quads_per_block, q1 = min(Pq, q0 + quads_per_block);
-    float s1[8], s2[8], m[8], iv[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) { s1[t] = 0.f; s2[t] = 0.f; }
-    if (rsub < rif) {
-        load8f(mean + cc, m); load8f(invstd + cc, iv);
-        for (int q = q0 + rsub; q < q1; q += rif) {
-            const int j = q % Wo, k = (q / Wo) % Ho, n = q / (Wo * Ho);
-            float g[4][8];
-            int av[4][8];
-            const bool vk = k + 1 < Ho, vj = j + 1 < Wo;
-            uint4 rq[4];                                    // the quad's four raw chunks, requested with the windows' (not behind their arithmetic)
-#pragma unroll
-            for (int wdx = 0; wdx < 4; ++wdx)
-                rq[wdx] = *reinterpret_cast<const uint4*>(raw + (((size_t)n * H + 2 * k + (wdx >> 1)) * W + 2 * j + (wdx & 1)) * C + cc);
-#pragma unroll
-            for (int wdx = 0; wdx < 4; ++wdx) {
-                const int ho = min(k + (wdx >> 1), Ho - 1), wo = min(j + (wdx & 1), Wo - 1);
-                const size_t o = (((size_t)n * Ho + ho) * Wo + wo) * C + cc;
-                const uint2 a2 = *reinterpret_cast<const uint2*>(arg + o);
-                unpack8(*reinterpret_cast<const uint4*>(dp + o), g[wdx]);
-#pragma unroll
-                for (int t = 0; t < 8; ++t) av[wdx][t] = (int)(((t < 4 ? (a2.x >> (8 * t)) : (a2.y >> (8 * (t - 4)))) & 0xff));
-            }
-#pragma unroll
-            for (int pa = 0; pa < 2; ++pa)
-#pragma unroll
-                for (int pb = 0; pb < 2; ++pb) {
-                    float dz[8];
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) dz[t] = 0.f;
-#pragma unroll
-                    for (int wdx = 0; wdx < 4; ++wdx) {
-                        const int da = wdx >> 1, db = wdx & 1;
-                        if ((da && !pa) || (db && !pb)) continue;
-                        const bool ok = (!da || vk) && (!db || vj);
-                        const int tap = ok ? (da ? 0 : 1 + pa) * 3 + (db ? 0 : 1 + pb) : -1;
-#pragma unroll
-                        for (int t = 0; t < 8; ++t)
-                            if (av[wdx][t] == tap) dz[t] += g[wdx][t];
-                    }
-                    float rv[8];
-                    unpack8(rq[pa * 2 + pb], rv);
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) { s1[t] += dz[t]; s2[t] += dz[t] * ((rv[t] - m[t]) * iv[t]); }
-                }
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) { red[((size_t)rsub * C + cc + t) * 2] = s1[t]; red[((size_t)rsub * C + cc + t) * 2 + 1] = s2[t]; }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < C * 2; e += 256) {
-        float sum = 0.f;
-        for (int r = 0; r < rif; ++r) sum += red[(size_t)r * C * 2 + e];
-        partial[(size_t)blockIdx.x * C * 2 + e] = sum;
-    }
-}
-// Apply pass on 2 x 2 pixel quads (H, W even): the four pixels of a quad draw on the same four pooling windows, so a thread loads each
-// (dp, arg) window once instead of once per pixel (the gather above re-reads every window four times: 400 MB of L2 traffic for a
-// 67 MB tensor).  Per pixel the windows are added in the same (ho, wo) order as maxpool_gather_dz: bit-identical results.
-__global__ __launch_bounds__(256) void maxpool_bn_bwd_apply_quad_kernel(const uint16_t* __restrict__ dp, const uint8_t* __restrict__ arg,
-                                                                         const uint16_t* __restrict__ raw, const float* __restrict__ coef,
-                                                                         int N, int H, int W, int C, int Ho, int Wo, uint16_t* __restrict__ draw) {
-    const int cpr = C >> 3;
-    const unsigned total = (unsigned)N * Ho * Wo * cpr;
-    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-        const unsigned q = i / (unsigned)cpr;
-        const int cc = (int)(i - q * cpr) * 8;
-        const unsigned qrow = q / (unsigned)Wo;
-        const int j = (int)(q - qrow * Wo), n = (int)(qrow / (unsigned)Ho), k = (int)(qrow - (unsigned)n * Ho);
-        float A[8], K[8], Q[8];
-        load8f(coef + cc, A); load8f(coef + C + cc, K); load8f(coef + 2 * C + cc, Q);
-        // windows (k, j), (k, j+1), (k+1, j), (k+1, j+1): clamped addresses, validity as predicates
-        float g[4][8];
-        int av[4][8];
-        const bool vk = k + 1 < Ho, vj = j + 1 < Wo;
+// Backward of the pool and the stem BN on 2 x 2 pixel quads.  Ho = ceil(H/2), Wo = ceil(W/2) for this pool, so the thread of
+// pooling-window origin (k, j) owning pixels (2k+pa, 2j+pb) covers every pixel once, odd sides included.  3x3 / stride 2 / pad 1: row
+// 2k+pa lies in window k (at offset 1+pa) and, for pa = 1, in window k+1 at offset 0; the same for columns.  So the quad's four pixels
+// draw on the same four windows (k, j), (k, j+1), (k+1, j), (k+1, j+1) and a thread loads each (dp, arg) window once instead of once
+// per pixel (a per-pixel gather re-read every window four times: 400 MB of L2 traffic for a 67 MB tensor).
+struct PoolQuad {
+    float g[4][8];      // dp of the four windows
+    int av[4][8];       // their arg-max taps
+    bool vk, vj;        // windows k+1 / j+1 exist
+    // the windows are read unconditionally from clamped addresses and gated by a predicate, so the four load pairs are in flight together
+    __device__ __forceinline__ PoolQuad(const uint16_t* __restrict__ dp, const uint8_t* __restrict__ arg, int n, int k, int j, int cc, int C,
+                                        int Ho, int Wo) : vk(k + 1 < Ho), vj(j + 1 < Wo) {
 #pragma unroll
         for (int wdx = 0; wdx < 4; ++wdx) {
             const int ho = min(k + (wdx >> 1), Ho - 1), wo = min(j + (wdx & 1), Wo - 1);
@@ -588,30 +404,104 @@ __global__ __launch_bounds__(256) void maxpool_bn_bwd_apply_quad_kernel(const ui
 #pragma unroll
             for (int t = 0; t < 8; ++t) av[wdx][t] = (int)(((t < 4 ? (a2.x >> (8 * t)) : (a2.y >> (8 * (t - 4)))) & 0xff));
         }
-        // (window, tap) lists per pixel (a, b) of the quad, in (ho, wo) order; tap = row offset * 3 + column offset inside the window
+    }
+    // dz of pixel (pa, pb) of the quad: the windows whose arg-max is this pixel's tap (row offset * 3 + column offset inside the window),
+    // added in (ho, wo) order
+    __device__ __forceinline__ void dz(int pa, int pb, float (&d)[8]) const {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) d[t] = 0.f;
+#pragma unroll
+        for (int wdx = 0; wdx < 4; ++wdx) {
+            const int da = wdx >> 1, db = wdx & 1;
+            if ((da && !pa) || (db && !pb)) continue;                 // an even row / column lies in one window only
+            const bool ok = (!da || vk) && (!db || vj);
+            const int tap = ok ? (da ? 0 : 1 + pa) * 3 + (db ? 0 : 1 + pb) : -1;
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                if (av[wdx][t] == tap) d[t] += g[wdx][t];
+        }
+    }
+};
+// Pixel (pa, pb) of quad (n, k, j): its index in the [N][H][W] tensor.  EVEN (H, W even): every pixel of every quad exists.  Otherwise a
+// pixel past the last row / column gets ok = false and the index of its clamped neighbour, so that its raw chunk is requested with the
+// others and discarded by the predicate (no branch around the load).
+template <bool EVEN>
+__device__ __forceinline__ size_t pool_quad_pixel(int n, int k, int j, int pa, int pb, int H, int W, bool& ok) {
+    if constexpr (EVEN) {
+        ok = true;
+        return ((size_t)n * H + 2 * k + pa) * W + 2 * j + pb;
+    }
+    const int h = 2 * k + pa, w = 2 * j + pb;
+    ok = h < H && w < W;
+    return ((size_t)n * H + min(h, H - 1)) * W + min(w, W - 1);
+}
+
+// pass 1: partial sums of dz and dz*xhat over the stem output; a block owns a range of quads
+template <bool EVEN>
+__global__ __launch_bounds__(256) void maxpool_bn_bwd_reduce_kernel(const uint16_t* __restrict__ dp, const uint8_t* __restrict__ arg,
+                                                                     const uint16_t* __restrict__ raw, const float* __restrict__ mean,
+                                                                     const float* __restrict__ invstd, int N, int H, int W, int C,
+                                                                     int Ho, int Wo, int quads_per_block, float* __restrict__ partial) {
+    extern __shared__ float red[];                  // [rif][C][2]
+    const int cpr = C >> 3, rif = 256 / cpr;
+    const int col = threadIdx.x % cpr, rsub = threadIdx.x / cpr;
+    const int cc = col * 8;
+    const int Pq = N * Ho * Wo;
+    const int q0 = blockIdx.x * quads_per_block, q1 = min(Pq, q0 + quads_per_block);
+    if (rsub < rif) {
+        float s[2][8] = {}, m[8], iv[8];
+        load8f(mean + cc, m); load8f(invstd + cc, iv);
+        for (int q = q0 + rsub; q < q1; q += rif) {
+            const int j = q % Wo, k = (q / Wo) % Ho, n = q / (Wo * Ho);
+            uint4 rq[4];                                    // the quad's four raw chunks, requested with the windows' (not behind their arithmetic)
+            bool ok[4];
+#pragma unroll
+            for (int px = 0; px < 4; ++px)
+                rq[px] = *reinterpret_cast<const uint4*>(raw + pool_quad_pixel<EVEN>(n, k, j, px >> 1, px & 1, H, W, ok[px]) * C + cc);
+            const PoolQuad quad(dp, arg, n, k, j, cc, C, Ho, Wo);
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                float dz[8], rv[8];
+                quad.dz(px >> 1, px & 1, dz);
+                unpack8(rq[px], rv);
+#pragma unroll
+                for (int t = 0; t < 8; ++t) {
+                    const float d = ok[px] ? dz[t] : 0.f;
+                    s[0][t] += d; s[1][t] += d * ((rv[t] - m[t]) * iv[t]);
+                }
+            }
+        }
+        block_partial_store<2>(red, rsub, C, cc, s);
+    }
+    block_partial_finish<2>(red, rif, C, partial);
+}
+// pass 2: d_raw = scale*(dz - S1/N - xhat*S2/N) = A*dz + K - Q*raw (FinBnBwd)
+template <bool EVEN>
+__global__ __launch_bounds__(256) void maxpool_bn_bwd_apply_kernel(const uint16_t* __restrict__ dp, const uint8_t* __restrict__ arg,
+                                                                    const uint16_t* __restrict__ raw, const float* __restrict__ coef,
+                                                                    int N, int H, int W, int C, int Ho, int Wo, uint16_t* __restrict__ draw) {
+    const int cpr = C >> 3;
+    const unsigned total = (unsigned)N * Ho * Wo * cpr;            // < 2^32 (checked by the launcher): 32-bit index arithmetic
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        const unsigned q = i / (unsigned)cpr;
+        const int cc = (int)(i - q * cpr) * 8;
+        const unsigned qrow = q / (unsigned)Wo;
+        const int j = (int)(q - qrow * Wo), n = (int)(qrow / (unsigned)Ho), k = (int)(qrow - (unsigned)n * Ho);
+        float A[8], K[8], Q[8];
+        load8f(coef + cc, A); load8f(coef + C + cc, K); load8f(coef + 2 * C + cc, Q);
+        const PoolQuad quad(dp, arg, n, k, j, cc, C, Ho, Wo);
 #pragma unroll
         for (int pa = 0; pa < 2; ++pa)
 #pragma unroll
             for (int pb = 0; pb < 2; ++pb) {
-                float dz[8];
-#pragma unroll
-                for (int t = 0; t < 8; ++t) dz[t] = 0.f;
-#pragma unroll
-                for (int wdx = 0; wdx < 4; ++wdx) {
-                    const int da = wdx >> 1, db = wdx & 1;
-                    if ((da && !pa) || (db && !pb)) continue;                 // an even row / column lies in one window only
-                    const bool ok = (!da || vk) && (!db || vj);
-                    const int tap = ok ? (da ? 0 : 1 + pa) * 3 + (db ? 0 : 1 + pb) : -1;
-#pragma unroll
-                    for (int t = 0; t < 8; ++t)
-                        if (av[wdx][t] == tap) dz[t] += g[wdx][t];
-                }
-                const size_t p = ((size_t)n * H + 2 * k + pa) * W + 2 * j + pb;
-                float rv[8], o8[8];
+                float dz[8], rv[8], o8[8];
+                quad.dz(pa, pb, dz);
+                bool ok;
+                const size_t p = pool_quad_pixel<EVEN>(n, k, j, pa, pb, H, W, ok);
                 unpack8(*reinterpret_cast<const uint4*>(raw + p * C + cc), rv);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) o8[t] = A[t] * dz[t] + K[t] - Q[t] * rv[t];
-                *reinterpret_cast<uint4*>(draw + p * C + cc) = pack8(o8);
+                if (ok) *reinterpret_cast<uint4*>(draw + p * C + cc) = pack8(o8);
             }
     }
 }
@@ -678,11 +568,8 @@ __global__ __launch_bounds__(256) void head_pool_bwd_kernel(const float* __restr
             const float avg = hw_pow2 ? g[t] * inv_hw : g[t] / (float)HW;
             o[t] = (mode == DALI_FEATURE_GMP ? 0.f : avg) + ((mode != DALI_FEATURE_GAP && a[t] == p) ? g[t] : 0.f);
         }
-        if (ybits) {                                  // dz = dy * (y > 0): the block's BatchNorm backward consumes the masked gradient
-            const unsigned m = ybits[((size_t)pix * C + cc) >> 3];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) o[t] = ((m >> t) & 1u) ? o[t] : 0.f;
-        }
+        // dz = dy * (y > 0): the block's BatchNorm backward consumes the masked gradient
+        if (ybits) dz_gate_bits(o, ybits[((size_t)pix * C + cc) >> 3]);
         *reinterpret_cast<uint4*>(dx + (size_t)pix * C + cc) = pack8(o);
     }
 }
@@ -786,30 +673,11 @@ __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restr
         }
     }
 }
-// one block transposes a 32(co) x 32(ci) tile of one tap
-__global__ __launch_bounds__(256) void weight_transpose_kernel(const uint16_t* __restrict__ w, int Co, int T, int Ci,
-                                                                uint16_t* __restrict__ wt) {
-    __shared__ uint16_t tile[32][33];
-    const int tiles_ci = (Ci + 31) / 32, tiles_co = (Co + 31) / 32;
-    const int b = blockIdx.x;
-    const int tci = b % tiles_ci, tco = (b / tiles_ci) % tiles_co, tap = b / (tiles_ci * tiles_co);
-    const int x = threadIdx.x & 31, y0 = threadIdx.x >> 5;
-    for (int y = y0; y < 32; y += 8) {
-        const int co = tco * 32 + y, ci = tci * 32 + x;
-        tile[y][x] = (co < Co && ci < Ci) ? w[((size_t)co * T + tap) * Ci + ci] : (uint16_t)0;
-    }
-    __syncthreads();
-    for (int y = y0; y < 32; y += 8) {
-        const int ci = tci * 32 + y, co = tco * 32 + x;
-        if (ci < Ci && co < Co) wt[((size_t)ci * T + tap) * Co + co] = tile[x][y];
-    }
-}
-
 // all dgrad weight images of a net in one launch: the job table travels as a kernel argument
 constexpr int TRANSPOSE_BATCH = 56;
 struct TransposeBatch { TransposeJob job[TRANSPOSE_BATCH]; int n; };
 // 64 x 64 tiles moved with 16-byte global accesses (Co, Ci multiples of 64: every conv / linear weight of the nets); the
-// 2-byte-per-lane 32 x 32 form below ran the 47 MB of weights at 0.9 TB/s
+// 2-byte-per-lane form below ran the 47 MB of weights at 0.9 TB/s
 __global__ __launch_bounds__(256) void weight_transpose64_batched_kernel(TransposeBatch batch) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[64][72];
     int ji = 0;
@@ -838,6 +706,7 @@ __global__ __launch_bounds__(256) void weight_transpose64_batched_kernel(Transpo
         *reinterpret_cast<uint4*>(jb.wt + ((size_t)(tci * 64 + row) * T + tap) * Co + tco * 64 + ch * 8) = v;
     }
 }
+// any Co, Ci, any alignment: one block per 32(co) x 32(ci) tile of one tap, 2 bytes per lane through a padded LDS tile
 __global__ __launch_bounds__(256) void weight_transpose_batched_kernel(TransposeBatch batch) {
     __shared__ uint16_t tile[32][33];
     int ji = 0;
@@ -871,12 +740,6 @@ int launch_bn_finalize(hipStream_t st, const float* partial, int tiles, int C, d
                        float* rm, float* rv, float momentum, float eps, float* scale, float* shift, float* mean, float* invstd,
                        double* scratch) {
     return launch_reduce_finish<2>(st, partial, tiles, C, scratch, FinBnFwd{count, gamma, beta, rm, rv, momentum, eps, scale, shift, mean, invstd});
-}
-int launch_bn_eval_coeffs(hipStream_t st, const float* gamma, const float* beta, const float* rm, const float* rv, float eps, int C,
-                          float* scale, float* shift) {
-    hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3((C + 255) / 256), dim3(256), 0, st, gamma, beta, rm, rv, eps, C, scale, shift);
-    DALI_LAUNCH_CHECK();
-    return DALI_OK;
 }
 int launch_bn_eval_coeffs_batched(hipStream_t st, const BnEvalJob* jobs, int n, float eps) {
     for (int first = 0; first < n; first += BnEvalJobs::MAX) {
@@ -974,33 +837,27 @@ int launch_maxpool_bn_fwd(hipStream_t st, const uint16_t* raw, const float* scal
     DALI_LAUNCH_CHECK();
     return DALI_OK;
 }
+// blocks of the stem pool backward's reduce pass and quads per block: its rows are the N * Ho * Wo pixel quads
+int maxpool_bn_bwd_blocks(int N, int H, int W, int C, int* quads_per_block) {
+    return bn_bwd_blocks(N * ((H + 2 - 3) / 2 + 1) * ((W + 2 - 3) / 2 + 1), C, quads_per_block);
+}
 int launch_maxpool_bn_bwd(hipStream_t st, const uint16_t* dp, const uint8_t* arg, const uint16_t* raw, const float* mean, const float* invstd,
                           const float* scale, int N, int H, int W, int C, float* partial, float* coef, float* dgamma, float* dbeta,
                           uint16_t* draw, double* scratch) {
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const int P = N * H * W;
     if ((long long)P * (C / 8) >= (1ll << 32)) { set_error("maxpool_bn_bwd: more than 2^32 16-byte chunks"); return DALI_ERR_LIMIT; }
-    int rpb;
-    const bool quads = (H & 1) == 0 && (W & 1) == 0;
-    // (the partial buffer is sized for bn_bwd_blocks(P, C): the quad form needs at most as many rows)
-    const int blocks = quads ? bn_bwd_blocks(N * Ho * Wo, C, &rpb) : bn_bwd_blocks(P, C, &rpb);
-    const int rif = 256 / (C / 8);
-    if (quads) hipLaunchKernelGGL(maxpool_bn_bwd_reduce_quad_kernel, dim3(blocks), dim3(256), (size_t)rif * C * 2 * sizeof(float), st, dp, arg, raw, mean,
-                                  invstd, N, H, W, C, Ho, Wo, rpb, partial);
-    else hipLaunchKernelGGL(maxpool_bn_bwd_reduce_kernel, dim3(blocks), dim3(256), (size_t)rif * C * 2 * sizeof(float), st, dp, arg, raw, mean, invstd,
-                            N, H, W, C, Ho, Wo, rpb, partial);
+    int qpb;
+    const int blocks = maxpool_bn_bwd_blocks(N, H, W, C, &qpb);
+    const bool even = (H & 1) == 0 && (W & 1) == 0;
+    const size_t lds = (size_t)(256 / (C / 8)) * C * 2 * sizeof(float);
+    auto reduce = even ? maxpool_bn_bwd_reduce_kernel<true> : maxpool_bn_bwd_reduce_kernel<false>;
+    hipLaunchKernelGGL(reduce, dim3(blocks), dim3(256), lds, st, dp, arg, raw, mean, invstd, N, H, W, C, Ho, Wo, qpb, partial);
     DALI_LAUNCH_CHECK();
-    int rc;
-    {
-        FinBnBwd<2> fin{(double)P, C, {{scale, mean, invstd, coef, dgamma, dbeta}}};
-        if ((rc = launch_reduce_finish<2>(st, partial, blocks, C, scratch, fin))) return rc;
-    }
-    if ((H & 1) == 0 && (W & 1) == 0)
-        hipLaunchKernelGGL(maxpool_bn_bwd_apply_quad_kernel, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(256), 0, st, dp, arg, raw, coef, N, H, W, C,
-                           Ho, Wo, draw);
-    else
-        hipLaunchKernelGGL(maxpool_bn_bwd_apply_kernel, dim3(grid_for((size_t)P * (C / 8))), dim3(256), 0, st, dp, arg, raw, mean, invstd, coef, N, H,
-                           W, C, Ho, Wo, draw);
+    FinBnBwd<2> fin{(double)P, C, {{scale, mean, invstd, coef, dgamma, dbeta}}};
+    if (int rc = launch_reduce_finish<2>(st, partial, blocks, C, scratch, fin)) return rc;
+    auto apply = even ? maxpool_bn_bwd_apply_kernel<true> : maxpool_bn_bwd_apply_kernel<false>;
+    hipLaunchKernelGGL(apply, dim3(grid_for((size_t)N * Ho * Wo * (C / 8))), dim3(256), 0, st, dp, arg, raw, coef, N, H, W, C, Ho, Wo, draw);
     DALI_LAUNCH_CHECK();
     return DALI_OK;
 }
@@ -1053,10 +910,8 @@ int launch_weight_transpose_batched(hipStream_t st, const TransposeJob* jobs, in
     return DALI_OK;
 }
 int launch_weight_transpose(hipStream_t st, const uint16_t* w, int Co, int T, int Ci, uint16_t* wt) {
-    const int blocks = ((Ci + 31) / 32) * ((Co + 31) / 32) * T;
-    hipLaunchKernelGGL(weight_transpose_kernel, dim3(blocks), dim3(256), 0, st, w, Co, T, Ci, wt);
-    DALI_LAUNCH_CHECK();
-    return DALI_OK;
+    const TransposeJob job{w, wt, Co, T, Ci, 0};
+    return launch_weight_transpose_batched(st, &job, 1);
 }
 
 }  // namespace dali
@@ -1123,7 +978,8 @@ extern "C" int dali_maxpool_bn_bwd(dali_ctx* ctx, void* stream, const uint16_t* 
                                    float* dgamma, float* dbeta, uint16_t* draw) {
     DALI_REQUIRE(ctx && dpool && arg && raw && mean && invstd && scale && dgamma && dbeta && draw, "dali_maxpool_bn_bwd: null argument");
     DALI_REQUIRE(C % 8 == 0 && C <= 2048, "dali_maxpool_bn_bwd: C must be a multiple of 8, <= 2048");
-    const size_t pf = bn_bwd_partial_floats(n * h * w, C, false);
+    int qpb;
+    const size_t pf = (size_t)maxpool_bn_bwd_blocks(n, h, w, C, &qpb) * C * 2;
     const size_t need = align_up(pf * 4, 256) + align_up((size_t)C * 12, 256) + reduce_scratch_bytes(C, 2);
     char* ws = static_cast<char*>(workspace(ctx, need));
     if (!ws) return DALI_ERR_NOMEM;

@@ -109,6 +109,26 @@ inline int rf_levels(int rows) {
     return S;
 }
 
+// The block-level step in front of it, for kernels whose thread (rsub, chunk column) strides over rows with NV sums for each of the 8
+// channels c .. c+7 of its chunk: the rif threads of a column leave their sums in red[rif][C][NV] (LDS), then partial[block][C][NV]
+// gets them added in row order (s = 0; s += red[r], r = 0 .. rif-1).
+template <int NV>
+__device__ __forceinline__ void block_partial_store(float* red, int rsub, int C, int c, const float (&s)[NV][8]) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) red[((size_t)rsub * C + c + t) * NV + v] = s[v][t];
+}
+template <int NV>
+__device__ __forceinline__ void block_partial_finish(const float* red, int rif, int C, float* __restrict__ partial) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < C * NV; e += 256) {
+        float s = 0.f;
+        for (int r = 0; r < rif; ++r) s += red[(size_t)r * C * NV + e];
+        partial[(size_t)blockIdx.x * C * NV + e] = s;
+    }
+}
+
 template <int NV, class Fin>
 inline int launch_reduce_finish(hipStream_t st, const float* partial, int rows, int C, double* scratch, const Fin& fin) {
     constexpr int CG = (256 / NV) * NV;

@@ -240,7 +240,8 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
     reserve(net, a, net->pool_arg, N * net->pool_h * net->pool_w * wb);
     reserve_bn(net, a, net->stem_bn);
     size_t max_act = raw0_bytes, max_stat = (size_t)igemm_conv_stat_tiles(wb, (int)N * net->stem_h * net->stem_w, 224) * wb * 2 * 4;
-    size_t max_bwd_partial = bn_bwd_partial_floats((int)N * net->stem_h * net->stem_w, wb, false) * 4;
+    int stem_qpb;
+    size_t max_bwd_partial = (size_t)maxpool_bn_bwd_blocks((int)N, net->stem_h, net->stem_w, wb, &stem_qpb) * wb * 2 * 4;
     size_t max_slab = 0, max_cs = 256;
     {
         int sp, pps; size_t wsb;

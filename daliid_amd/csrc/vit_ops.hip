@@ -8,16 +8,6 @@
 
 namespace dali {
 
-__device__ __forceinline__ void unpack8v(const uint4& v, float (&f)[8]) {
-    f[0] = bf16_bits_to_f32(v.x & 0xffffu); f[1] = bf16_bits_to_f32(v.x >> 16);
-    f[2] = bf16_bits_to_f32(v.y & 0xffffu); f[3] = bf16_bits_to_f32(v.y >> 16);
-    f[4] = bf16_bits_to_f32(v.z & 0xffffu); f[5] = bf16_bits_to_f32(v.z >> 16);
-    f[6] = bf16_bits_to_f32(v.w & 0xffffu); f[7] = bf16_bits_to_f32(v.w >> 16);
-}
-__device__ __forceinline__ uint4 pack8v(const float (&f)[8]) {
-    return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
-}
-
 // ------------------------------------------------------------------------------------------------
 // PatchEmbed_overlap (vit_pytorch.py:251-288): the ps x ps / stride conv as a GEMM over extracted patches.
 // img fp32 [B,3,H,W] -> patches bf16 [B*ny*nx][3*ps*ps], K order (c, r, s) = the conv weight's flattening.
@@ -35,7 +25,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
         float v[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) v[t] = src[t];
-        *reinterpret_cast<uint4*>(out + patch * K + k) = pack8v(v);
+        *reinterpret_cast<uint4*>(out + patch * K + k) = pack8(v);
     }
 }
 
@@ -53,11 +43,11 @@ __global__ __launch_bounds__(256) void assemble_tokens_kernel(const uint16_t* __
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] = cls[c + q];
         } else {
-            unpack8v(*reinterpret_cast<const uint4*>(pe + ((size_t)b * (T - 1) + t - 1) * C + c), v);
+            unpack8(*reinterpret_cast<const uint4*>(pe + ((size_t)b * (T - 1) + t - 1) * C + c), v);
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] += pos[(size_t)t * C + c + q];
-        *reinterpret_cast<uint4*>(x + row * C + c) = pack8v(v);
+        *reinterpret_cast<uint4*>(x + row * C + c) = pack8(v);
     }
 }
 // dpos[t,:] = sum_b dx[b,t,:] (fp32; dcls = dpos[0]);  dpe[b*np+i,:] = dx[b,1+i,:]
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(256) void assemble_tokens_bwd_kernel(const uint16_t
     for (int b = 0; b < B; ++b) {
         const uint4 raw = *reinterpret_cast<const uint4*>(dx + ((size_t)b * T + t) * C + c);
         float v[8];
-        unpack8v(raw, v);
+        unpack8(raw, v);
 #pragma unroll
         for (int q = 0; q < 8; ++q) acc[q] += v[q];
         if (t > 0 && dpe) *reinterpret_cast<uint4*>(dpe + ((size_t)b * (T - 1) + t - 1) * C + c) = raw;
@@ -102,7 +92,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const uint16_t* __re
     for (int k = 0; k < LN_MAXCH; ++k) {
         const int c = (lane + k * 64) * 8;
         if (c < C) {
-            unpack8v(*reinterpret_cast<const uint4*>(x + (size_t)row * C + c), v[k]);
+            unpack8(*reinterpret_cast<const uint4*>(x + (size_t)row * C + c), v[k]);
 #pragma unroll
             for (int t = 0; t < 8; ++t) s += v[k][t];
         }
@@ -126,7 +116,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const uint16_t* __re
             float o[8];
 #pragma unroll
             for (int t = 0; t < 8; ++t) o[t] = (v[k][t] - mu) * rs * gamma[c + t] + beta[c + t];
-            if (y) *reinterpret_cast<uint4*>(y + (size_t)row * C + c) = pack8v(o);
+            if (y) *reinterpret_cast<uint4*>(y + (size_t)row * C + c) = pack8(o);
             if (y32) {
 #pragma unroll
                 for (int t = 0; t < 8; ++t) y32[(size_t)row * C + c + t] = o[t];
@@ -197,9 +187,9 @@ __global__ __launch_bounds__(256, MINW) void layernorm_bwd_kernel(const uint16_t
 #pragma unroll
                     for (int t = 0; t < 8; ++t) gv[k][t] = g32[(size_t)row * C + c + t];
                 } else {
-                    unpack8v(r.g[k], gv[k]);
+                    unpack8(r.g[k], gv[k]);
                 }
-                unpack8v(r.x[k], xv);
+                unpack8(r.x[k], xv);
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
                     xh[k][t] = (xv[t] - mu) * rs;
@@ -223,11 +213,11 @@ __global__ __launch_bounds__(256, MINW) void layernorm_bwd_kernel(const uint16_t
                 for (int t = 0; t < 8; ++t) o[t] = rs * (gv[k][t] - s1 - xh[k][t] * s2);
                 if (add) {
                     float a[8];
-                    unpack8v(ca[k], a);
+                    unpack8(ca[k], a);
 #pragma unroll
                     for (int t = 0; t < 8; ++t) o[t] += a[t];
                 }
-                *reinterpret_cast<uint4*>(dx + (size_t)row * C + c) = pack8v(o);
+                *reinterpret_cast<uint4*>(dx + (size_t)row * C + c) = pack8(o);
             }
         }
     };
@@ -261,24 +251,18 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const uint16_t* __r
     const int r0 = blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
     // C may exceed 2048 (3072-wide MLP): a thread then owns several chunk columns
     for (int cc = col; cc < cpr; cc += 256) {
-        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float acc[1][8] = {};
         if (rsub < rif) {
             for (int row = r0 + rsub; row < r1; row += rif) {
                 float v[8];
-                unpack8v(*reinterpret_cast<const uint4*>(y + (size_t)row * C + cc * 8), v);
+                unpack8(*reinterpret_cast<const uint4*>(y + (size_t)row * C + cc * 8), v);
 #pragma unroll
-                for (int t = 0; t < 8; ++t) acc[t] += v[t];
+                for (int t = 0; t < 8; ++t) acc[0][t] += v[t];
             }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) red[(size_t)rsub * C + cc * 8 + t] = acc[t];
+            block_partial_store<1>(red, rsub, C, cc * 8, acc);
         }
     }
-    __syncthreads();
-    for (int e = threadIdx.x; e < C; e += 256) {
-        float s = 0.f;
-        for (int r = 0; r < rif; ++r) s += red[(size_t)r * C + e];
-        partial[(size_t)blockIdx.x * C + e] = s;
-    }
+    block_partial_finish<1>(red, rif, C, partial);
 }
 // ------------------------------------------------------------------------------------------------
 // Multi-head self-attention, one block per (batch, head); head_dim 64; T <= 16 * NTILE tokens, NTILE in {13, 14, 16}
@@ -321,8 +305,8 @@ __global__ __launch_bounds__(256) void rowscale_add_kernel(const uint16_t* __res
         const size_t row = i / cpr;
         const float sc = scale[row / rows_per_sample];
         float v[8], r[8];
-        unpack8v(*reinterpret_cast<const uint4*>(branch + i * 8), v);
-        if (res) unpack8v(*reinterpret_cast<const uint4*>(res + i * 8), r);
+        unpack8(*reinterpret_cast<const uint4*>(branch + i * 8), v);
+        if (res) unpack8(*reinterpret_cast<const uint4*>(res + i * 8), r);
 #pragma unroll
         for (int t = 0; t < 8; ++t) v[t] = (res ? r[t] : 0.f) + sc * v[t];
         *reinterpret_cast<uint4*>(out + i * 8) = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
@@ -355,7 +339,7 @@ __global__ __launch_bounds__(256) void assemble_tokens_sie_kernel(const uint16_t
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] = cls[c + q];
         } else {
-            unpack8v(*reinterpret_cast<const uint4*>(pe + ((size_t)b * (T - 1) + t - 1) * C + c), v);
+            unpack8(*reinterpret_cast<const uint4*>(pe + ((size_t)b * (T - 1) + t - 1) * C + c), v);
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] += pos[(size_t)t * C + c + q];
@@ -364,7 +348,7 @@ __global__ __launch_bounds__(256) void assemble_tokens_sie_kernel(const uint16_t
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] += coef * sie[(size_t)si * C + c + q];
         }
-        *reinterpret_cast<uint4*>(x + row * C + c) = pack8v(v);
+        *reinterpret_cast<uint4*>(x + row * C + c) = pack8(v);
     }
 }
 // dsie[i][c] = coef * sum over the samples b with idx[b] == i and their tokens t of dx[b,t,c], fp32.  One workgroup per (embedding row,
@@ -381,7 +365,7 @@ __global__ __launch_bounds__(256) void sie_grad_kernel(const uint16_t* __restric
             if (idx[b] != i) continue;
             for (int t = slice; t < T; t += 32) {
                 float v[8];
-                unpack8v(*reinterpret_cast<const uint4*>(dx + ((size_t)b * T + t) * C + c), v);
+                unpack8(*reinterpret_cast<const uint4*>(dx + ((size_t)b * T + t) * C + c), v);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) acc[q] += v[q];
             }
@@ -440,7 +424,7 @@ __global__ __launch_bounds__(256) void jpm_head_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void tokens_f32_kernel(const uint16_t* __restrict__ x, size_t chunks, float* __restrict__ y) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (size_t)gridDim.x * 256) {
         float v[8];
-        unpack8v(*reinterpret_cast<const uint4*>(x + i * 8), v);
+        unpack8(*reinterpret_cast<const uint4*>(x + i * 8), v);
         *reinterpret_cast<float4*>(y + i * 8) = make_float4(v[0], v[1], v[2], v[3]);
         *reinterpret_cast<float4*>(y + i * 8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
     }
@@ -540,16 +524,6 @@ int launch_layernorm_bwd(hipStream_t st, const uint16_t* g, const uint16_t* x, c
     return launch_reduce_finish<2>(st, partial, blocks, C, scratch, FinStore{{dgamma, dbeta, nullptr, nullptr}, 2});
 }
 size_t colsum_partial_floats(int rows, int C) { int rpb; const int rif = 256 / ((C / 8) < 256 ? (C / 8) : 256); return (size_t)rows_blocks(rows, rif, &rpb) * C; }
-// first level only: partial[*n_rows][C] per-block column sums; the caller finishes the sum (bnlin.hip's row kernel)
-int launch_colsum_partials(hipStream_t st, const uint16_t* y, int rows, int C, float* partial, int* n_rows) {
-    const int cpr = C / 8, rif = 256 / (cpr < 256 ? cpr : 256);
-    int rpb;
-    const int blocks = rows_blocks(rows, rif, &rpb);
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(blocks), dim3(256), (size_t)rif * C * sizeof(float), st, y, rows, C, rpb, partial);
-    DALI_LAUNCH_CHECK();
-    *n_rows = blocks;
-    return DALI_OK;
-}
 int launch_colsum(hipStream_t st, const uint16_t* y, int rows, int C, float* out, float* partial, double* scratch) {
     const int cpr = C / 8, rif = 256 / (cpr < 256 ? cpr : 256);
     int rpb;
@@ -709,10 +683,10 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_dq_kernel(const uint
         {
             const bf16x8_t oa0 = frag_g(oo, C, qt * 16, 0, T, lane), oa1 = frag_g(oo, C, qt * 16, 32, T, lane);
             float a8[8], b8[8];
-            unpack8v(__builtin_bit_cast(uint4, ga0), a8); unpack8v(__builtin_bit_cast(uint4, oa0), b8);
+            unpack8(__builtin_bit_cast(uint4, ga0), a8); unpack8(__builtin_bit_cast(uint4, oa0), b8);
 #pragma unroll
             for (int t = 0; t < 8; ++t) di += a8[t] * b8[t];
-            unpack8v(__builtin_bit_cast(uint4, ga1), a8); unpack8v(__builtin_bit_cast(uint4, oa1), b8);
+            unpack8(__builtin_bit_cast(uint4, ga1), a8); unpack8(__builtin_bit_cast(uint4, oa1), b8);
 #pragma unroll
             for (int t = 0; t < 8; ++t) di += a8[t] * b8[t];
             di += __shfl_xor(di, 16, 64); di += __shfl_xor(di, 32, 64);
@@ -775,8 +749,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_dkv_kernel(const uin
         float acc = 0.f;
         if (i < T) {
             float ov[8], gv[8];
-            unpack8v(*reinterpret_cast<const uint4*>(o + ((size_t)b * T + i) * C + h * ATT_HD + ch * 8), ov);
-            unpack8v(*reinterpret_cast<const uint4*>(go + (size_t)i * C + ch * 8), gv);
+            unpack8(*reinterpret_cast<const uint4*>(o + ((size_t)b * T + i) * C + h * ATT_HD + ch * 8), ov);
+            unpack8(*reinterpret_cast<const uint4*>(go + (size_t)i * C + ch * 8), gv);
 #pragma unroll
             for (int d = 0; d < 8; ++d) acc += ov[d] * gv[d];
         }

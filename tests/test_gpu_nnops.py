@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from test_gpu_nnops_plan_sizes import _dev, _draw_bound_check, _gen, _ints, _pow2
+
 pytestmark = pytest.mark.gpu
 bf16 = torch.bfloat16
 
@@ -113,7 +115,10 @@ def test_bn_bwd_inner_and_block_output(nn, shape):
         assert torch.equal(t1, t2)
 
 
-@pytest.mark.parametrize("shape", [(2, 8, 6, 64), (3, 16, 8, 32), (1, 6, 10, 64)])
+# odd sides: the backward's thread of pooling-window origin (k, j) owns pixels (2k+pa, 2j+pb), some of them past the last row / column;
+# (2, 3, 1, 8): every quad's second column, with 256 rows in flight per block; (1, 1, 1, 8): one pixel, clamped loads in an 8-element tensor
+@pytest.mark.parametrize("shape", [(2, 8, 6, 64), (3, 16, 8, 32), (1, 6, 10, 64),
+                                   (2, 7, 5, 64), (1, 5, 8, 32), (1, 6, 9, 16), (2, 3, 1, 8), (1, 1, 1, 8)])
 def test_maxpool_bn_fwd_bwd(nn, shape):
     g = torch.Generator().manual_seed(sum(shape) + 2)
     n, h, w, C = shape
@@ -131,6 +136,42 @@ def test_maxpool_bn_fwd_bwd(nn, shape):
     close_bf16(draw, r.grad, ulps=1.5, atol=2e-3 * float(r.grad.abs().max()))
     np.testing.assert_allclose(dg.cpu().numpy(), gm.grad.numpy(), rtol=2e-3, atol=2e-3 * float(gm.grad.abs().max()))
     np.testing.assert_allclose(db.cpu().numpy(), bt.grad.numpy(), rtol=2e-3, atol=2e-3 * float(bt.grad.abs().max()))
+
+
+def test_maxpool_bn_bwd_odd_matches_padded_even(nn):
+    """Odd sides on exact inputs (small integers, power-of-two scale and invstd, as in test_gpu_nnops_plan_sizes): every sum is exact in
+    any order, so dgamma / dbeta must equal the host's integer sums over the H x W pixels -- what an even-sided tensor padded with
+    pixels that no window selects would give -- bit for bit, and draw meets the rounding bound of the folded formula."""
+    N, H, W, C = 2, 7, 5, 16
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    g = _gen("maxpool_odd", N, H, W, C)
+    raw = _ints(-2, 2, (N, H, W, C), g)
+    mean = _ints(-1, 1, (C,), g).float()
+    invstd = _pow2(C, g, -2, 0, signed=False)
+    scale = _pow2(C, g, -1, 1) * invstd
+    shift = _ints(-2, 2, (C,), g).float()
+    dp = _ints(-2, 2, (N, Ho, Wo, C), g)
+    rg = _dev(raw)
+    _, arg = nn.maxpool_bn_fwd(rg, scale.cuda(), shift.cuda())
+    draw, dg, db = nn.maxpool_bn_bwd(_dev(dp), arg, rg, mean.cuda(), invstd.cuda(), scale.cuda())
+    # host: arg-max of z = raw*scale + shift (exact) by torch's own pool, dz scattered through it
+    z = nchw(raw.float() * scale + shift)
+    _, idx = F.max_pool2d(z, 3, 2, 1, return_indices=True)                       # flat h * W + w per (n, c, ho, wo)
+    # ties are everywhere in these inputs: the kernel's tap must be unfold + argmax's (first maximum in row-major window order) and
+    # name the pixel that torch's pool chose, or a tie-rule mismatch would show below as a wrong sum
+    tap = F.unfold(F.pad(z, (1, 1, 1, 1), value=float("-inf")), 3, stride=2).view(N, C, 9, Ho * Wo).argmax(2).view(N, C, Ho, Wo)
+    assert torch.equal(arg.cpu(), tap.permute(0, 2, 3, 1).to(torch.uint8)), "arg is not the first maximum of its window"
+    origin = (2 * torch.arange(Ho).view(Ho, 1) - 1) * W + 2 * torch.arange(Wo) - 1
+    assert torch.equal(idx, origin + (tap // 3) * W + tap % 3), "torch's pool and unfold + argmax disagree on a tie"
+    dz = torch.zeros(N, C, H * W, dtype=torch.int64).scatter_add_(2, idx.flatten(2), nchw(dp).flatten(2).to(torch.int64))
+    dz = dz.view(N, C, H, W).permute(0, 2, 3, 1).reshape(-1, C)
+    raw2 = raw.view(-1, C)
+    S1 = dz.sum(0)
+    T = (dz * (raw2.to(torch.int64) - mean.to(torch.int64))).sum(0)
+    S1, S2 = S1.double(), T.double() * invstd.double()
+    assert torch.equal(db.cpu().double(), S1), "dbeta is not the exact sum"
+    assert torch.equal(dg.cpu().double(), S2), "dgamma is not the exact sum"
+    _draw_bound_check(draw.view(-1, C).cpu(), dz, raw2, mean, invstd, scale, S1, S2, N * H * W, "maxpool odd draw")
 
 
 @pytest.mark.parametrize("shape", [(4, 16, 8, 2048), (3, 5, 3, 64)])
