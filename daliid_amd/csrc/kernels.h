@@ -147,6 +147,9 @@ size_t bn_bwd_partial_floats(int P, int C, bool dual);
 int launch_bn_bwd(hipStream_t st, const uint16_t* g, const uint16_t* ymask, const uint8_t* ybits, const BnBwdSide& a, const BnBwdSide* b, int relu, int P, int C,
                   float* partial, float* coef_a, float* coef_b, float* dgamma_a, float* dbeta_a, float* dgamma_b, float* dbeta_b,
                   uint16_t* draw_a, uint16_t* draw_b, uint16_t* dz_out, double* scratch);
+// gather geometry of the stem's GEMMs on the packed [N][H+6][W+8][4] image (R = 7 tap rows of Ck = 32, stride 2): the net plan's forward and
+// weight gradient, and dali_debug_stem_wgrad
+GatherGeom stem_geom(int H, int W);
 int launch_stem_pack_image(hipStream_t st, const float* img, int N, int H, int W, uint16_t* out);
 int launch_stem_pack_weight(hipStream_t st, const float* w, int Cout, uint16_t* out);
 // stem.hip: the inference stem (conv1 -> bn1 by running statistics -> 3x3 / 2 max-pool) in one launch, packed image -> pooled [N][H/4][W/4][64]

@@ -813,6 +813,16 @@ size_t bn_bwd_partial_floats(int P, int C, bool dual) {
     int rpb;
     return (size_t)bn_bwd_blocks(P, C, &rpb) * C * (dual ? 3 : 2);
 }
+// the stem reads the packed [N][H+6][W+8][4] image: one tap row (8 taps x 4 ch) per k-tile
+GatherGeom stem_geom(int H, int W) {
+    GatherGeom g{};
+    g.Hout = (H - 1) / 2 + 1; g.Wout = (W - 1) / 2 + 1;      // 7x7 / stride 2 / pad 3
+    g.Hin = H + 6; g.Win = W + 8;
+    g.Ck = 32; g.R = 7; g.S = 1; g.stride = 2; g.pad = 0; g.mode = 0;
+    g.pix_pitch = 4; g.row_pitch = (W + 8) * 4; g.img_pitch = (long long)(H + 6) * (W + 8) * 4;
+    g.lw = g.lhw = -1;
+    return g;
+}
 int launch_stem_pack_image(hipStream_t st, const float* img, int N, int H, int W, uint16_t* out) {
     const int Hp = H + 6, Wp = W + 8;
     hipLaunchKernelGGL(stem_pack_image_kernel, dim3(grid_for((size_t)N * Hp * Wp)), dim3(256), 0, st, img, N, H, W, Hp, Wp, out);
@@ -999,6 +1009,39 @@ extern "C" int dali_head_pool_bwd(dali_ctx* ctx, void* stream, const float* df, 
     DALI_REQUIRE(mode >= DALI_FEATURE_BOTH && mode <= DALI_FEATURE_GMP, "dali_head_pool_bwd: bad feature mode %d", mode);
     DALI_REQUIRE(C % 8 == 0 && hw > 0, "dali_head_pool_bwd: bad shape");
     return launch_head_pool_bwd((hipStream_t)stream, df, arg, n, hw, C, mode, dx);
+}
+// Diagnostic (include/daliid_debug.h): the same launcher with the ReLU mask bits of the tensor the gradient belongs to, as the net plan calls it
+extern "C" int dali_debug_head_pool_bwd_masked(dali_ctx* ctx, void* stream, const float* df, const int16_t* arg, int n, int hw, int C, int mode,
+                                               const uint8_t* ybits, uint16_t* dx) {
+    DALI_REQUIRE(ctx && df && arg && ybits && dx, "dali_debug_head_pool_bwd_masked: null argument");
+    DALI_REQUIRE(mode >= DALI_FEATURE_BOTH && mode <= DALI_FEATURE_GMP, "dali_debug_head_pool_bwd_masked: bad feature mode %d", mode);
+    DALI_REQUIRE(C % 8 == 0 && hw > 0 && n > 0, "dali_debug_head_pool_bwd_masked: bad shape");
+    return launch_head_pool_bwd((hipStream_t)stream, df, arg, n, hw, C, mode, dx, ybits);
+}
+// Diagnostic (include/daliid_debug.h): the stem weight gradient as the net plan's stem_backward runs it -- pack the image, the split plan of
+// (Cout, 224, P, taps 7), the weight-gradient GEMM on stem_geom, unpack [Cout][7][8][4] -> [Cout][7][7][3] -- on workspace buffers.
+// images fp32 [N][3][H][W], d_raw0 bf16 [N][H/2][W/2][Cout], dw fp32 [Cout][7][7][3]; shape rules of dali_resnet_create.
+extern "C" int dali_debug_stem_wgrad(dali_ctx* ctx, void* stream, const float* images, const uint16_t* d_raw0, int N, int H, int W, int Cout, float* dw) {
+    DALI_REQUIRE(ctx && images && d_raw0 && dw, "dali_debug_stem_wgrad: null argument");
+    DALI_REQUIRE(N > 0 && H >= 32 && W >= 32 && H % 32 == 0 && W % 16 == 0 && (Cout == 32 || Cout == 64),
+                 "dali_debug_stem_wgrad: bad shape %dx%dx%d, Cout %d (height %% 32, width %% 16, Cout 32 or 64)", N, H, W, Cout);
+    DALI_REQUIRE((long long)N * (H / 2) * (W / 2) < (1ll << 31), "dali_debug_stem_wgrad: more than 2^31 pixels");
+    hipStream_t st = (hipStream_t)stream;
+    WGradArgs a{};
+    a.Cm = Cout; a.P = N * (H / 2) * (W / 2); a.Ntot = 224;
+    a.g = stem_geom(H, W);
+    size_t wsb;
+    wgrad_plan(a.Cm, a.Ntot, a.P, 512, &a.splits, &a.pix_per_split, &wsb, 7);
+    const size_t b_img = align_up((size_t)N * (H + 6) * (W + 8) * 4 * 2, 256), b_slab = align_up(wsb, 256), b_pad = align_up((size_t)Cout * 224 * 4, 256);
+    char* ws = static_cast<char*>(workspace(ctx, b_img + b_slab + b_pad));
+    if (!ws) return DALI_ERR_NOMEM;
+    uint16_t* ximg = reinterpret_cast<uint16_t*>(ws);
+    float* dw_pad = reinterpret_cast<float*>(ws + b_img + b_slab);
+    a.dY = d_raw0; a.X = ximg; a.partial = reinterpret_cast<float*>(ws + b_img);
+    int rc;
+    if ((rc = launch_stem_pack_image(st, images, N, H, W, ximg))) return rc;
+    if ((rc = launch_igemm_wgrad(st, a, dw_pad, 0))) return rc;
+    return launch_stem_unpack_wgrad(st, dw_pad, Cout, dw);
 }
 extern "C" int dali_bn1d_fwd(dali_ctx* ctx, void* stream, const float* x, int n, int C, const float* gamma, const float* beta,
                              float* running_mean, float* running_var, int training, float momentum, float eps, float* y, float* mean,

@@ -92,6 +92,7 @@ struct dali_resnet {
     // backward state
     uint16_t* cur_dy = nullptr;
     int64_t cur_dy_bytes = 0;
+    uint16_t* dbg_d_raw0 = nullptr;          // where the last stem backward left d(raw0) (scratch: valid until the next backward runs)
     bool fwd_training = false;
     int feature_mode = DALI_FEATURE_BOTH;
 };
@@ -159,16 +160,6 @@ Conv square_conv(const Conv& c3) {
     Conv q = c3;
     q.cin = c3.cin; q.cout = c3.cin; q.w_off = 0; q.w_bf16 = nullptr; q.wt_bf16 = nullptr;
     return q;
-}
-// the stem reads the packed [N][H+6][W+8][4] image: one tap row (8 taps x 4 ch) per k-tile
-GatherGeom stem_geom(const dali_resnet* net) {
-    GatherGeom g{};
-    g.Hout = net->stem_h; g.Wout = net->stem_w;
-    g.Hin = net->H + 6; g.Win = net->W + 8;
-    g.Ck = 32; g.R = 7; g.S = 1; g.stride = 2; g.pad = 0; g.mode = 0;
-    g.pix_pitch = 4; g.row_pitch = (net->W + 8) * 4; g.img_pitch = (long long)(net->H + 6) * (net->W + 8) * 4;
-    g.lw = g.lhw = -1;
-    return g;
 }
 
 }  // namespace
@@ -485,7 +476,7 @@ extern "C" int dali_resnet_forward(dali_resnet* net, void* stream, const float* 
         a.W = net->w_stem; a.X = net->ximg; a.O = net->raw0; a.Res = nullptr; a.in_scale = nullptr; a.in_shift = nullptr; a.in_relu = 0;
         a.stats = tr ? net->stat_partial : nullptr;
         a.Cm = net->stem.cout; a.P = net->N * net->stem_h * net->stem_w;
-        a.g = stem_geom(net);
+        a.g = stem_geom(net->H, net->W);
         if ((rc = launch_igemm_conv(st, a))) return rc;
         if (tr && (rc = bn_train(net, st, net->stem_bn, igemm_conv_stat_tiles(a.Cm, a.P, 224), (double)a.P))) return rc;
     }
@@ -672,7 +663,8 @@ static int stem_backward(dali_resnet* net, hipStream_t st) {
     WGradArgs a{};
     a.dY = d_raw0; a.X = net->ximg; a.partial = net->wgrad_slab; a.in_scale = nullptr; a.in_shift = nullptr; a.in_relu = 0;
     a.Cm = net->stem.cout; a.P = net->N * net->stem_h * net->stem_w; a.Ntot = 224;
-    a.g = stem_geom(net);
+    a.g = stem_geom(net->H, net->W);
+    net->dbg_d_raw0 = d_raw0;
     size_t wsb;
     wgrad_plan(a.Cm, a.Ntot, a.P, 512, &a.splits, &a.pix_per_split, &wsb, 7);
     if ((rc = launch_igemm_wgrad(st, a, net->stem_dw_pad, 0))) return rc;
@@ -730,7 +722,10 @@ extern "C" int dali_debug_resnet_backward_block(dali_resnet* net, void* stream, 
 }
 
 // Debug/inspection: device pointer + byte size of a named intermediate (valid after a forward).
-// Names: raw0, pool0, feat, grad_cur (gradient wrt the input of the last block processed by backward), block<i>.{raw1,raw2,rawd,y}, block<i>.bn{1,2,3,d}.{scale,shift,mean,invstd}, bn1.{...}
+// Names: raw0, pool0, feat, grad_cur (gradient wrt the input of the last block processed by backward), block<i>.{raw1,raw2,rawd,y,d_raw1}, block<i>.bn{1,2,3,d}.{scale,shift,mean,invstd}, bn1.{...};
+// ximg (packed image bf16 [N][H+6][W+8][4]), w_stem (bf16 [Cout][7][8][4]), d_raw0 (after a stem backward); the weight images block<i>.conv{1,2,3,d}.w
+// (bf16 [cout][r][s][cin]) and .wt (bf16 [cin][r*s][cout]), and, where the inference forward folds conv3 + downsample into one GEMM,
+// block<i>.wcat (bf16 [cout][2 (w + cin)]: W3 hi | W3 lo | Wd hi | Wd lo) and block<i>.shcat (fp32 [cout])
 extern "C" int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void** ptr, int64_t* bytes) {
     DALI_REQUIRE(net && name && ptr && bytes && net->arena, "dali_resnet_debug_tensor: bad argument / net not bound");
     const std::string n(name);
@@ -745,6 +740,9 @@ extern "C" int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void
     if (n == "pool0") { *ptr = net->pool0; *bytes = (int64_t)(N * net->pool_h * net->pool_w * net->stem.cout * 2); return DALI_OK; }
     if (n == "grad_cur" && net->cur_dy) { *ptr = net->cur_dy; *bytes = net->cur_dy_bytes; return DALI_OK; }
     if (n == "feat") { *ptr = net->feat; *bytes = (int64_t)(N * net->feat_dim * 4); return DALI_OK; }
+    if (n == "ximg") { *ptr = net->ximg; *bytes = (int64_t)(N * (net->H + 6) * (net->W + 8) * 4 * 2); return DALI_OK; }
+    if (n == "w_stem") { *ptr = net->w_stem; *bytes = (int64_t)net->stem.cout * 224 * 2; return DALI_OK; }
+    if (n == "d_raw0" && net->dbg_d_raw0) { *ptr = net->dbg_d_raw0; *bytes = (int64_t)(N * net->stem_h * net->stem_w * net->stem.cout * 2); return DALI_OK; }
     if (n.rfind("bn1.", 0) == 0 && bn_field(net->stem_bn, n.substr(4))) return DALI_OK;
     if (n.rfind("block", 0) == 0) {
         const size_t dot = n.find('.');
@@ -759,6 +757,14 @@ extern "C" int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void
                 if (f == "rawd" && b.has_ds) { *ptr = b.rawd; *bytes = (int64_t)(pout * b.cout * 2); return DALI_OK; }
                 if (f == "y") { *ptr = b.y; *bytes = (int64_t)(pout * b.cout * 2); return DALI_OK; }
                 if (f == "d_raw1" && b.dbg_d_raw1) { *ptr = b.dbg_d_raw1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }
+                if (f == "wcat" && b.cat_eval) { *ptr = b.wcat; *bytes = (int64_t)b.cout * 2 * (b.width + b.cin) * 2; return DALI_OK; }
+                if (f == "shcat" && b.cat_eval) { *ptr = b.shcat; *bytes = (int64_t)b.cout * 4; return DALI_OK; }
+                if (f.rfind("conv", 0) == 0 && f.size() > 6 && f[5] == '.') {
+                    Conv* c = f[4] == '1' ? &b.c1 : f[4] == '2' ? &b.c2 : f[4] == '3' ? &b.c3 : (f[4] == 'd' && b.has_ds) ? &b.cd : nullptr;
+                    const std::string img = f.substr(6);
+                    uint16_t* p = !c ? nullptr : img == "w" ? c->w_bf16 : img == "wt" ? c->wt_bf16 : nullptr;
+                    if (p) { *ptr = p; *bytes = (int64_t)c->cout * c->r * c->s * c->cin * 2; return DALI_OK; }
+                }
                 if (f.rfind("bn", 0) == 0 && f.size() > 4) {
                     Bn* bn = f[2] == '1' ? &b.b1 : f[2] == '2' ? &b.b2 : f[2] == '3' ? &b.b3 : (f[2] == 'd' && b.has_ds) ? &b.bd : nullptr;
                     if (bn && bn_field(*bn, f.substr(4))) return DALI_OK;

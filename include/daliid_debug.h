@@ -1,5 +1,8 @@
 /* daliid_debug.h -- diagnostic entry points of libdaliid_hip.so.  NOT part of the drop-in surface (include/daliid.h):
- * nothing under daliid_amd/ binds them; scripts/ (timing, in-kernel stamps) and tests do, through ctypes.
+ * nothing under daliid_amd/ binds them; scripts/ (timing, in-kernel stamps) and tests do, through ctypes: the split plan and the split-K
+ * reduce alone, the net plan's backward block by block, and the pieces of the plan that have no single-op entry point in daliid.h (the stem
+ * weight gradient on the packed image, the head-pool backward with its ReLU gate).  Named intermediates of a plan (packed image and weight
+ * images included) are read through dali_resnet_debug_tensor (daliid.h).
  * Declared here so that the shared library exports nothing that no header names (tests/test_abi.py compares the
  * two headers with `nm -D` of the library).
  */
@@ -29,6 +32,17 @@ int dali_debug_splitk_reduce(void* stream, const float* partial, float* out, lon
  * in the same order as dali_resnet_backward (tests/test_gpu_resnet_blocks.py, the batch-256 composition check) */
 struct dali_resnet;
 int dali_debug_resnet_backward_block(struct dali_resnet* net, void* stream, const float* d_emb, int block);
+
+/* pieces that only the net plan reaches, on their own (tests/test_gpu_plan_only.py) */
+struct dali_ctx;
+/* the stem weight gradient as the plan's backward runs it: pack the image, the split plan of (Cout, 224, P, taps 7), the weight-gradient GEMM on
+ * the packed image with the plan's own gather geometry, unpack.  images fp32 [N][3][H][W], d_raw0 bf16 [N][H/2][W/2][Cout] -> dw fp32 [Cout][7][7][3];
+ * H % 32 == 0, W % 16 == 0, Cout 32 or 64 (dali_resnet_create's rules); buffers from the context workspace */
+int dali_debug_stem_wgrad(struct dali_ctx* ctx, void* stream, const float* images, const unsigned short* d_raw0, int N, int H, int W, int Cout, float* dw);
+/* dali_head_pool_bwd with the ReLU mask bits of the tensor the gradient belongs to (bit e & 7 of byte e >> 3, e = pixel * C + c): the store
+ * forms dz = dy * (y > 0), as in the plan's backward */
+int dali_debug_head_pool_bwd_masked(struct dali_ctx* ctx, void* stream, const float* df, const short* arg, int n, int hw, int C, int mode,
+                                    const unsigned char* ybits, unsigned short* dx);
 
 #ifdef __cplusplus
 }
