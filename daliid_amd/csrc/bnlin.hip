@@ -473,25 +473,19 @@ extern "C" int dali_bnlin_fwd(dali_ctx* ctx, void* stream, const uint16_t* a, co
     DALI_REQUIRE(P > 0 && C % 32 == 0 && w % 32 == 0, "dali_bnlin_fwd: C %% 32, w %% 32 (C=%d w=%d)", C, w);
     hipStream_t st = (hipStream_t)stream;
     WGradArgs wa{};
-    wa.dY = a; wa.X = a; wa.Cm = w; wa.P = P; wa.Ntot = w; wa.g = bl_geom(P, w);
-    size_t wsb;
-    wgrad_plan(w, w, P, 512, &wa.splits, &wa.pix_per_split, &wsb, 1, 0);
-    const bool fused_cs = wgrad_colsum_supported(w, w, 1, P);
-    const int cs_rows = wgrad_colsum_rows(w, w, 1, P, wa.splits);             // one row per split, or per (split, n tile) from the 128 x 256 kernels
-    const size_t b_cs = align_up(std::max(colsum_partial_floats(P, w), (size_t)cs_rows * w) * 4, 256), b_sc = align_up(reduce_scratch_bytes(w, 1), 256);
+    wa.dY = a; wa.X = a; wa.Cm = w; wa.P = P; wa.g = bl_geom(P, w);
+    const WGradNeed need = wgrad_need(w, P, wa.g, true);
+    const size_t b_slab = align_up(need.slab_bytes, 256), b_cs = align_up(need.colsum_floats * 4, 256), b_sc = align_up(reduce_scratch_bytes(w, 1), 256);
     const size_t b_wt = align_up((size_t)C * w * 2, 256), b_dot = align_up((size_t)(w / 32) * C * 12, 256);      // quadratic-form partials (fp32) + mean partials (fp64)
-    char* ws = static_cast<char*>(workspace(ctx, align_up(wsb, 256) + b_cs + b_sc + b_wt + b_dot));
+    char* ws = static_cast<char*>(workspace(ctx, b_slab + b_cs + b_sc + b_wt + b_dot));
     if (!ws) return DALI_ERR_NOMEM;
-    wa.partial = reinterpret_cast<float*>(ws);
-    char* p = ws + align_up(wsb, 256);
-    float* cs_partial = reinterpret_cast<float*>(p); p += b_cs;
-    double* scratch = reinterpret_cast<double*>(p); p += b_sc;
+    char* p = ws + b_slab;
+    const WGradBufs bufs{reinterpret_cast<float*>(ws), reinterpret_cast<float*>(p), reinterpret_cast<double*>(p + b_cs)};
+    p += b_cs + b_sc;
     uint16_t* wt = reinterpret_cast<uint16_t*>(p); p += b_wt;
     float* dot = reinterpret_cast<float*>(p);
     int rc;
-    if (fused_cs) wa.colsum = cs_partial;
-    if ((rc = launch_igemm_wgrad(st, wa, gram, 0, fused_cs ? m2 : nullptr, cs_rows))) return rc;
-    if (!fused_cs && (rc = launch_colsum(st, a, P, w, m2, cs_partial, scratch))) return rc;
+    if ((rc = launch_wgrad(st, wa, bufs, gram, 0, m2))) return rc;             // gram = a^T a, m2 = colsum(a)
     if ((rc = launch_weight_transpose(st, W, C, 1, w, wt))) return rc;
     return launch_bnlin_stats(st, W, wt, gram, m2, C, w, (double)P, gamma, beta, running_mean, running_var, momentum, eps, ut, dot, scale, shift, mean, invstd);
 }
@@ -503,26 +497,20 @@ extern "C" int dali_bnlin_bwd(dali_ctx* ctx, void* stream, const uint16_t* dz, c
     DALI_REQUIRE(P > 0 && C % 32 == 0 && w % 32 == 0, "dali_bnlin_bwd: C %% 32, w %% 32 (C=%d w=%d)", C, w);
     hipStream_t st = (hipStream_t)stream;
     WGradArgs wa{};
-    wa.dY = dz; wa.X = a; wa.Cm = C; wa.P = P; wa.Ntot = w; wa.g = bl_geom(P, w);
-    size_t wsb;
-    wgrad_plan(C, w, P, 512, &wa.splits, &wa.pix_per_split, &wsb, 1, 0);
-    const bool fused_cs = wgrad_colsum_supported(C, w, 1, P);
-    const int cs_rows = wgrad_colsum_rows(C, w, 1, P, wa.splits);
-    const size_t b_cs = align_up(std::max(colsum_partial_floats(P, C), (size_t)cs_rows * C) * 4, 256), b_sc = align_up(reduce_scratch_bytes(C, 1), 256);
+    wa.dY = dz; wa.X = a; wa.Cm = C; wa.P = P; wa.g = bl_geom(P, w);
+    const WGradNeed need = wgrad_need(C, P, wa.g, true);
+    const size_t b_slab = align_up(need.slab_bytes, 256), b_cs = align_up(need.colsum_floats * 4, 256), b_sc = align_up(reduce_scratch_bytes(C, 1), 256);
     const size_t b_v = align_up((size_t)C * 4, 256), b_wt = align_up((size_t)C * w * 2, 256);
-    char* ws = static_cast<char*>(workspace(ctx, align_up(wsb, 256) + b_cs + b_sc + 3 * b_v + b_wt));
+    char* ws = static_cast<char*>(workspace(ctx, b_slab + b_cs + b_sc + 3 * b_v + b_wt));
     if (!ws) return DALI_ERR_NOMEM;
-    wa.partial = reinterpret_cast<float*>(ws);
-    char* p = ws + align_up(wsb, 256);
-    float* cs_partial = reinterpret_cast<float*>(p); p += b_cs;
-    double* scratch = reinterpret_cast<double*>(p); p += b_sc;
+    char* p = ws + b_slab;
+    const WGradBufs bufs{reinterpret_cast<float*>(ws), reinterpret_cast<float*>(p), reinterpret_cast<double*>(p + b_cs)};
+    p += b_cs + b_sc;
     float* sdz = reinterpret_cast<float*>(p); p += b_v;
     float* qk = reinterpret_cast<float*>(p); p += 2 * b_v;
     uint16_t* wt = reinterpret_cast<uint16_t*>(p);
     int rc;
-    if (fused_cs) wa.colsum = cs_partial;
     if ((rc = launch_weight_transpose(st, W, C, 1, w, wt))) return rc;
-    if ((rc = launch_igemm_wgrad(st, wa, dW, 0, fused_cs ? sdz : nullptr, cs_rows))) return rc;                       // G0 -> dW
-    if (!fused_cs && (rc = launch_colsum(st, dz, P, C, sdz, cs_partial, scratch))) return rc;
+    if ((rc = launch_wgrad(st, wa, bufs, dW, 0, sdz))) return rc;              // G0 = dz^T a -> dW, sdz = colsum(dz)
     return launch_bnlin_bwd(st, W, wt, ut, m2, sdz, C, w, (double)P, scale, mean, invstd, dW, dgamma, dbeta, wd1, wd2, bvec, qk);
 }

@@ -2713,7 +2713,7 @@ int launch_igemm_conv(hipStream_t st, const IGemmArgs& a) {
 // (The limit was 40 tiles until the pipelined kernel carried the column sums: with them it wins at the ViT's 54 / 72 tiles too -- 48 weight
 //  gradients 5.46 -> 4.67 ms -- and at layer4's downsample, 64 tiles: 162 -> 125 us.)
 static bool wgrad_spec(int Cm, int Ntot) { return ((Cm + 127) / 128) * ((Ntot + 255) / 256) <= 100; }
-int wgrad_pick_cfg(int Cm, int Ntot, int taps, int P, int halo_w) {
+static int wgrad_pick_cfg(int Cm, int Ntot, int taps, int P, int halo_w) {
     // 3 = 3x3 halo kernel (128 co x 64 ci x 9 taps per block)
     if (taps == 9 && (halo_w == 8 || halo_w == 16 || halo_w == 32) && Cm % 64 == 0 && (Ntot / 9) % 64 == 0 && P % 32 == 0) return 3;
     if (taps == 7 && Ntot == 224 && P >= 16384) return 2;         // the stem (7 tap rows of 32): one 256-wide n tile, dY read once (187 -> ~155 us)
@@ -2734,8 +2734,9 @@ static bool wgrad_colsum_ok(int cfg, bool in_bn, bool dma_ok) { return cfg != 3 
 // (split, n tile) from the 128 x 256 kernels (every n tile takes a share)
 static int colsum_rows_of(const GemmKernel& k, int Ntot, int splits) { return k.tn == 128 ? splits : splits * ((Ntot + k.tn - 1) / k.tn); }
 
-// Chooses the split count so that the grid has ~target blocks; returns slab bytes through *ws_bytes.
-void wgrad_plan(int Cm, int Ntot, int P, int target_blocks, int* splits, int* pix_per_split, size_t* ws_bytes, int taps, int halo_w) {
+// Chooses the split count so that the grid has ~target blocks; the slabs are [splits][Cm][Ntot] floats.
+// taps = R*S of the convolution (1 for 1x1 convolutions and linear layers): selects the tile shape; halo_w: wgrad_halo_w's answer
+static void wgrad_plan(int Cm, int Ntot, int P, int target_blocks, int* splits, int* pix_per_split, int taps, int halo_w) {
     const GemmKernel& k = wgrad_kernel(wgrad_pick_cfg(Cm, Ntot, taps, P, halo_w), Cm, Ntot, false, true, false, true);
     if (k.plan_wgs) target_blocks = k.plan_wgs;
     const int tiles = ((Cm + k.tm - 1) / k.tm) * ((Ntot + k.tn - 1) / k.tn);
@@ -2758,51 +2759,59 @@ void wgrad_plan(int Cm, int Ntot, int P, int target_blocks, int* splits, int* pi
     int pps = ((P + sp - 1) / sp + 31) & ~31;
     sp = (P + pps - 1) / pps;
     *splits = sp; *pix_per_split = pps;
-    *ws_bytes = (size_t)sp * Cm * Ntot * sizeof(float);
 }
 
-// The kernel, tiles and grid of one weight-gradient GEMM, or the refusal; no HIP calls
-static GemmChoice wgrad_choose(const WGradArgs& a) {
-    const GatherGeom& g = a.g;
-    const bool dma_ok = gather_dma_ok(g, a.P, (long long)a.P * a.Cm * 2);
-    const bool halo = g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.mode == 0 && g.lw >= 0 && g.lhw >= 7 && g.Hin == g.Hout && g.Win == g.Wout &&
-                      g.pix_pitch == g.Ck && g.row_pitch == g.Win * g.Ck;
-    const int cfg = wgrad_pick_cfg(a.Cm, a.Ntot, g.R * g.S, a.P, halo ? g.Wout : 0);
-    if (a.colsum && !wgrad_colsum_ok(cfg, a.in_scale != nullptr, dma_ok))
-        return GemmChoice(DALI_ERR_INVALID, "wgrad: column sums ride on the 128 x 128 and 128 x 256 LDS-DMA kernels only (wgrad_colsum_supported)");
-    return gemm_place(wgrad_kernel(cfg, a.Cm, a.Ntot, a.in_scale != nullptr, dma_ok, a.colsum != nullptr, plain_rows(g)), a.Cm, a.Ntot, a.splits, g.Ck);
+// Output width where the 3x3 halo kernel takes this gather (3x3 / stride 1 / pad 1 over dense images on a power-of-two pixel grid of at least 128
+// pixels), else 0.  The one answer to "does this 3x3 take the halo kernel?": it decides the split and the kernel.  An operand transform
+// (in_bn) runs on the register-staged kernel and takes no halo split.
+static int wgrad_halo_w(const GatherGeom& g, bool in_bn) {
+    const bool halo = !in_bn && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.mode == 0 && ilog2_exact(g.Wout) >= 0 &&
+                      ilog2_exact(g.Hout * g.Wout) >= 7 && g.Hin == g.Hout && g.Win == g.Wout && g.pix_pitch == g.Ck && g.row_pitch == g.Win * g.Ck;
+    return halo ? g.Wout : 0;
 }
 
-int launch_igemm_wgrad(hipStream_t st, const WGradArgs& a, float* out, int accumulate, float* colsum_out, int colsum_rows) {
-    WGradArgs args = a;
-    args.stamps = g_conv_stamps;
-    args.g.lw = ilog2_exact(a.g.Wout);
-    args.g.lhw = ilog2_exact(a.g.Hout * a.g.Wout);
-    const GemmChoice c = wgrad_choose(args);
+// One weight-gradient GEMM out [Cm][R*S*Ck] = dY^T gather(X) over P pixels: the split-K plan, the kernel with its tiles and grid, and whether the
+// column sums of dY ride on it.  wgrad_need sizes from this and launch_wgrad launches from it.  No HIP calls.
+struct WGradChoice { int Ntot, splits, pix_per_split, colsum_rows; GemmChoice c; };
+static WGradChoice wgrad_choose(int Cm, int P, const GatherGeom& g, bool in_bn, bool want_colsum) {
+    WGradChoice w{};
+    const int taps = g.R * g.S, halo_w = wgrad_halo_w(g, in_bn);
+    w.Ntot = taps * g.Ck;
+    wgrad_plan(Cm, w.Ntot, P, 512, &w.splits, &w.pix_per_split, taps, halo_w);
+    const int cfg = wgrad_pick_cfg(Cm, w.Ntot, taps, P, halo_w);
+    const bool dma_ok = gather_dma_ok(g, P, (long long)P * Cm * 2);
+    const bool colsum = want_colsum && wgrad_colsum_ok(cfg, in_bn, dma_ok);
+    w.c = gemm_place(wgrad_kernel(cfg, Cm, w.Ntot, in_bn, dma_ok, colsum, plain_rows(g)), Cm, w.Ntot, w.splits, g.Ck);
+    w.colsum_rows = colsum ? colsum_rows_of(*w.c.k, w.Ntot, w.splits) : 0;
+    return w;
+}
+
+WGradNeed wgrad_need(int Cm, int P, const GatherGeom& g, bool colsum, bool operand_transform) {
+    const WGradChoice w = wgrad_choose(Cm, P, g, operand_transform, colsum);
+    return WGradNeed{(size_t)w.splits * Cm * w.Ntot * sizeof(float), colsum ? std::max((size_t)w.colsum_rows * Cm, colsum_partial_floats(P, Cm)) : 0};
+}
+
+int launch_wgrad(hipStream_t st, WGradArgs a, const WGradBufs& ws, float* out, int accumulate, float* colsum_out) {
+    const WGradChoice w = wgrad_choose(a.Cm, a.P, a.g, a.in_scale != nullptr, colsum_out != nullptr);
+    a.Ntot = w.Ntot; a.splits = w.splits; a.pix_per_split = w.pix_per_split;
+    a.partial = ws.slab;
+    a.colsum = w.colsum_rows ? ws.cs_partial : nullptr;
+    a.stamps = g_conv_stamps;
+    a.g.lw = ilog2_exact(a.g.Wout);
+    a.g.lhw = ilog2_exact(a.g.Hout * a.g.Wout);
     {
     char what[160] = "";
     if (g_prof)
         snprintf(what, sizeof what, "wgrad,Cm=%d,K=%d,P=%d,taps=%d,stride=%d,sub=0,fused=%d,stats=0,res=0,mask=0,lin=%d", a.Cm, a.Ntot, a.P, a.g.R * a.g.S, a.g.stride,
                  a.in_scale ? 1 : 0, a.colsum ? 1 : 0);
     ProfScope prof_scope(st, 1, 2.0 * a.Cm * (double)a.Ntot * a.P, what);
-    if (!c.k) return c.refuse();
-    if (a.colsum && colsum_out && colsum_rows != colsum_rows_of(*c.k, a.Ntot, a.splits)) {      // the caller sized them with wgrad_colsum_rows
-        set_error("wgrad: %d column-sum rows passed, the chosen kernel leaves %d", colsum_rows, colsum_rows_of(*c.k, a.Ntot, a.splits));
-        return DALI_ERR_UNSUPPORTED;
+    if (int rc = gemm_launch(st, w.c, a)) return rc;
     }
-    if (int rc = gemm_launch(st, c, args)) return rc;
-    }
-    if (!out) return DALI_OK;                       // the caller reduces the slabs itself
-    // the column sums that rode on the GEMM (a.colsum, colsum_rows partial rows of Cm) are reduced in the same launch
-    return launch_splitk_reduce2(st, a.partial, out, (size_t)a.Cm * a.Ntot, a.splits, accumulate, (a.colsum && colsum_out) ? a.colsum : nullptr, colsum_out,
-                                 (size_t)a.Cm, colsum_rows);
-}
-
-int wgrad_colsum_rows(int Cm, int Ntot, int taps, int P, int splits) {
-    return colsum_rows_of(wgrad_kernel(wgrad_pick_cfg(Cm, Ntot, taps, P, 0), Cm, Ntot, false, true, true, true), Ntot, splits);
-}
-bool wgrad_colsum_supported(int Cm, int Ntot, int taps, int P) {
-    return wgrad_colsum_ok(wgrad_pick_cfg(Cm, Ntot, taps, P, 0), false, dma_addressable((long long)P * Cm * 2) && dma_addressable((long long)P * Ntot * 2));
+    // the column sums that rode on the GEMM (colsum_rows partial rows of Cm) are reduced in the slab reduce's launch
+    if (int rc = launch_splitk_reduce2(st, a.partial, out, (size_t)a.Cm * a.Ntot, a.splits, accumulate, a.colsum, colsum_out, (size_t)a.Cm, w.colsum_rows)) return rc;
+    if (!colsum_out || a.colsum) return DALI_OK;
+    // the chosen kernel carries no column sums (an operand beyond the buffer descriptors' 2 GiB reach): a pass of their own over dY
+    return launch_colsum(st, a.dY, a.P, a.Cm, colsum_out, ws.cs_partial, ws.scratch);
 }
 
 int launch_splitk_reduce(hipStream_t st, const float* partial, float* out, size_t elems, int splits, int accumulate) {
@@ -2847,8 +2856,8 @@ int launch_splitk_reduce2(hipStream_t st, const float* partial, float* out, size
 extern "C" int dali_debug_set_conv_stamps(void* dev_ptr) { g_conv_stamps = static_cast<unsigned long long*>(dev_ptr); return DALI_OK; }
 // Diagnostics for scripts/bench_reduce.py (include/daliid_debug.h): the split count wgrad_plan picks, and the reduce alone.
 extern "C" int dali_debug_wgrad_splits(int Cm, int Ntot, int P, int taps, int halo_w) {
-    int sp = 0, pps = 0; size_t wsb = 0;
-    wgrad_plan(Cm, Ntot, P, 512, &sp, &pps, &wsb, taps, halo_w);
+    int sp = 0, pps = 0;
+    wgrad_plan(Cm, Ntot, P, 512, &sp, &pps, taps, halo_w);
     return sp;
 }
 extern "C" int dali_debug_splitk_reduce(void* stream, const float* partial, float* out, long long elems, int splits, int accumulate) {
@@ -2930,10 +2939,6 @@ extern "C" int dali_conv2d_bn_act(dali_ctx* ctx, void* stream, const uint16_t* x
     return launch_igemm_conv((hipStream_t)stream, a);
 }
 
-// output width if the geometry is what the 3x3 halo kernels take (3x3, stride 1, pad 1, power-of-two pixel grid), else 0
-static int halo_width(int r, int s, int stride, int pad, int ho, int wo) {
-    return (r == 3 && s == 3 && stride == 1 && pad == 1 && ilog2_exact(wo) >= 0 && ilog2_exact(ho * wo) >= 0 && ho * wo >= 128) ? wo : 0;
-}
 extern "C" int dali_conv2d_stat_tiles(int cout, int cin, int r, int s, int stride, int pad, int n, int ho, int wo, int fused_operand) {
     (void)stride; (void)pad;
     return igemm_conv_stat_tiles(cout, n * ho * wo, r * s * cin, fused_operand != 0);
@@ -2964,14 +2969,11 @@ extern "C" int dali_conv2d_wgrad(dali_ctx* ctx, void* stream, const uint16_t* x,
     const int ho = (h + 2 * pad - r) / stride + 1, wo = (wd + 2 * pad - s) / stride + 1;
     WGradArgs a{};
     a.dY = dy; a.X = x; a.in_scale = in_scale; a.in_shift = in_shift; a.in_relu = in_relu;
-    a.Cm = cout; a.P = n * ho * wo; a.Ntot = r * s * cin;
+    a.Cm = cout; a.P = n * ho * wo;
     fill_geom(a.g, n, h, wd, cin, ho, wo, r, s, stride, pad, 0);
-    size_t ws_bytes;
-    wgrad_plan(a.Cm, a.Ntot, a.P, 512, &a.splits, &a.pix_per_split, &ws_bytes, r * s,
-               in_scale == nullptr ? halo_width(r, s, stride, pad, ho, wo) : 0);
-    a.partial = static_cast<float*>(workspace(ctx, ws_bytes));
-    if (!a.partial) return DALI_ERR_NOMEM;
-    return launch_igemm_wgrad((hipStream_t)stream, a, dw, accumulate);
+    float* slab = static_cast<float*>(workspace(ctx, wgrad_need(a.Cm, a.P, a.g, false, in_scale != nullptr).slab_bytes));
+    if (!slab) return DALI_ERR_NOMEM;
+    return launch_wgrad((hipStream_t)stream, a, WGradBufs{slab, nullptr, nullptr}, dw, accumulate);
 }
 
 // ---- Linear layers (ViT: qkv / proj / fc1 / fc2 / patch embedding) on the same engine: a Linear is a 1x1 conv over tokens ----
@@ -3029,29 +3031,17 @@ int launch_linear_fwd(hipStream_t st, const uint16_t* x, const uint16_t* w, cons
     linear_geom(a.g, K);
     return launch_igemm_conv(st, a);
 }
-// dbias (nullable) = column sums of dy: they ride on the weight-gradient GEMM (per-split partial sums in cs_partial [splits][N], reduced
-// like the slabs) where the kernel supports it; *bias_done says whether they did (otherwise the caller runs the column-sum pass)
-int launch_linear_wgrad(hipStream_t st, const uint16_t* x, const uint16_t* dy, float* dw, int rows, int K, int N, float* slab, float* dbias,
-                        float* cs_partial, bool* bias_done) {
+// dw [N][K] = dy^T x; dbias (nullable) = column sums of dy.  ws: what linear_wgrad_need asks for
+int launch_linear_wgrad(hipStream_t st, const uint16_t* x, const uint16_t* dy, float* dw, int rows, int K, int N, const WGradBufs& ws, float* dbias) {
     WGradArgs a{};
-    a.dY = dy; a.X = x; a.partial = slab; a.Cm = N; a.P = rows; a.Ntot = K;
+    a.dY = dy; a.X = x; a.Cm = N; a.P = rows;
     linear_geom(a.g, K);
-    size_t wsb;
-    wgrad_plan(a.Cm, a.Ntot, a.P, 512, &a.splits, &a.pix_per_split, &wsb);
-    const bool ride = dbias && cs_partial && wgrad_colsum_supported(N, K, 1, rows);
-    if (bias_done) *bias_done = ride;
-    if (ride) a.colsum = cs_partial;
-    return launch_igemm_wgrad(st, a, dw, 0, ride ? dbias : nullptr, ride ? wgrad_colsum_rows(N, K, 1, rows, a.splits) : 0);
+    return launch_wgrad(st, a, ws, dw, 0, dbias);
 }
-size_t linear_wgrad_colsum_floats(int rows, int K, int N) {
-    int sp, pps; size_t wsb;
-    wgrad_plan(N, K, rows, 512, &sp, &pps, &wsb);
-    return (size_t)wgrad_colsum_rows(N, K, 1, rows, sp) * N;
-}
-size_t linear_wgrad_slab_bytes(int rows, int K, int N) {
-    int sp, pps; size_t wsb;
-    wgrad_plan(N, K, rows, 512, &sp, &pps, &wsb);
-    return wsb;
+WGradNeed linear_wgrad_need(int rows, int K, int N, bool bias) {
+    GatherGeom g{};
+    linear_geom(g, K);
+    return wgrad_need(N, rows, g, bias);
 }
 }  // namespace dali
 
@@ -3084,12 +3074,10 @@ extern "C" int dali_linear_wgrad(dali_ctx* ctx, void* stream, const uint16_t* x,
                                  int K, int N) {
     DALI_REQUIRE(ctx && x && dy && dw, "dali_linear_wgrad: null argument");
     DALI_REQUIRE(K % 8 == 0 && N % 8 == 0 && rows > 0, "dali_linear_wgrad: K and N must be multiples of 8");
-    const size_t slab = align_up(linear_wgrad_slab_bytes(rows, K, N), 256);
-    const size_t part = align_up(std::max(colsum_partial_floats(rows, N), linear_wgrad_colsum_floats(rows, K, N)) * 4, 256);
+    const WGradNeed need = linear_wgrad_need(rows, K, N, dbias != nullptr);
+    const size_t slab = align_up(need.slab_bytes, 256), part = align_up(need.colsum_floats * 4, 256);
     char* ws = static_cast<char*>(workspace(ctx, slab + part + reduce_scratch_bytes(N, 1)));
     if (!ws) return DALI_ERR_NOMEM;
-    bool bias_done = false;
-    int rc = launch_linear_wgrad((hipStream_t)stream, x, dy, dw, rows, K, N, reinterpret_cast<float*>(ws), dbias, reinterpret_cast<float*>(ws + slab), &bias_done);
-    if (rc || !dbias || bias_done) return rc;
-    return launch_colsum((hipStream_t)stream, dy, rows, N, dbias, reinterpret_cast<float*>(ws + slab), reinterpret_cast<double*>(ws + slab + part));
+    const WGradBufs bufs{reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + slab), reinterpret_cast<double*>(ws + slab + part)};
+    return launch_linear_wgrad((hipStream_t)stream, x, dy, dw, rows, K, N, bufs, dbias);
 }

@@ -66,17 +66,18 @@ struct IGemmArgs {
     int x_rep;
 };
 
+// The caller of launch_wgrad sets dY, X, in_scale / in_shift / in_relu, Cm, P and g; the launcher fills the rest
 struct WGradArgs {
     const uint16_t* dY;       // [P][Cm]
     const uint16_t* X;        // gathered tensor
     float* partial;           // [splits][Cm][Ntot]
     const float* in_scale; const float* in_shift;
-    int Cm, P, Ntot, in_relu;
+    int Cm, P, Ntot, in_relu;     // Ntot = g.R * g.S * g.Ck
     int splits, pix_per_split;    // pix_per_split multiple of 32
     GatherGeom g;
     unsigned long long* stamps;   // diagnostic, as in IGemmArgs
-    float* colsum;                // optional [splits][Cm]: per-split column sums over the pixels of dY, by one extra MFMA per fragment against a
-                                  // ones operand in the n-tile-0 workgroups (128 x 128 kernel only: wgrad_colsum_supported); bnlin.hip's s / m2
+    float* colsum;                // optional [rows][Cm]: per-split column sums over the pixels of dY, by one extra MFMA per fragment against a
+                                  // ones operand (the LDS-DMA 128 x 128 and 128 x 256 kernels); bnlin.hip's s / m2, the linear layers' bias gradient
 };
 
 
@@ -93,25 +94,25 @@ int gemm_profile_begin(hipStream_t st, int cls, double flops, const char* what);
 void gemm_profile_end(hipStream_t st, int slot);
 int igemm_conv_stat_tiles(int Cm, int P, int K, bool operand_transform = false);
 bool conv_cat_act_supported(int Cm, int c1, int c2, int P, int parts = 1);      // [X | X2] GEMM with the scale / shift / ReLU output stage at this size?
-// taps = R*S of the convolution (1 for 1x1 convolutions and linear layers): selects the tile shape
-// halo_w = output width of a 3x3 / stride 1 / pad 1 convolution whose H*W is a power of two (0 otherwise): enables the halo kernel
-void wgrad_plan(int Cm, int Ntot, int P, int target_blocks, int* splits, int* pix_per_split, size_t* ws_bytes, int taps = 1, int halo_w = 0);
-// out == nullptr: leave the split-K slabs in a.partial ([splits][Cm][Ntot]) for the caller to reduce
-// colsum_out (nullable): where the column sums that rode on the GEMM (a.colsum, colsum_rows partial rows) are reduced to, in the slab reduce's launch
-int launch_igemm_wgrad(hipStream_t st, const WGradArgs& a, float* out, int accumulate, float* colsum_out = nullptr, int colsum_rows = 0);
+// The weight-gradient GEMM out [Cm][R*S*Ck] (+)= dY^T gather(X) over P pixels, split-K with a fixed-order slab reduce.
+struct WGradNeed { size_t slab_bytes, colsum_floats; };
+// What launch_wgrad needs for this problem.  colsum_floats covers the rows that ride on the GEMM and the partials of the fallback column-sum
+// pass; 0 when no column sums are asked for.  operand_transform: WGradArgs::in_scale will be set
+WGradNeed wgrad_need(int Cm, int P, const GatherGeom& g, bool colsum, bool operand_transform = false);
+struct WGradBufs { float* slab; float* cs_partial; double* scratch; };      // scratch: reduce_scratch_bytes(Cm, 1); the last two for colsum_out only
+// colsum_out (nullable) = column sums of dY [Cm]: on the GEMM, reduced in the slab reduce's launch, where the chosen kernel carries them; by
+// launch_colsum right after it otherwise
+int launch_wgrad(hipStream_t st, WGradArgs a, const WGradBufs& ws, float* out, int accumulate, float* colsum_out = nullptr);
 int launch_splitk_reduce2(hipStream_t st, const float* partial, float* out, size_t elems, int splits, int accumulate,
                           const float* partial2, float* out2, size_t elems2, int splits2);
-bool wgrad_colsum_supported(int Cm, int Ntot, int taps, int P);
 // out[e] (+)= sum_k partial[k][e], fixed order
 int launch_splitk_reduce(hipStream_t st, const float* partial, float* out, size_t elems, int splits, int accumulate);
 
 int launch_linear_fwd(hipStream_t st, const uint16_t* x, const uint16_t* w, const float* bias, int act, const uint16_t* residual, uint16_t* y,
                       uint16_t* pre, const uint16_t* dact_pre, int rows, int K, int N, const float* row_scale = nullptr);
-int launch_linear_wgrad(hipStream_t st, const uint16_t* x, const uint16_t* dy, float* dw, int rows, int K, int N, float* slab,
-                        float* dbias = nullptr, float* cs_partial = nullptr, bool* bias_done = nullptr);
-size_t linear_wgrad_colsum_floats(int rows, int K, int N);
-int wgrad_colsum_rows(int Cm, int Ntot, int taps, int P, int splits);
-size_t linear_wgrad_slab_bytes(int rows, int K, int N);
+// dw [N][K] = dy^T x, dbias (nullable) = column sums of dy; ws as linear_wgrad_need(rows, K, N, dbias != nullptr) asks
+int launch_linear_wgrad(hipStream_t st, const uint16_t* x, const uint16_t* dy, float* dw, int rows, int K, int N, const WGradBufs& ws, float* dbias = nullptr);
+WGradNeed linear_wgrad_need(int rows, int K, int N, bool bias);
 
 // bnlin.hip: BatchNorm behind a 1x1 convolution from the moments of the convolution's INPUT (no raw conv output is stored)
 //   forward : scale / shift / mean / invstd of raw = a W^T from gram = a^T a [w][w] and m2 = colsum(a) [w]; W [C][w] and Wt = W^T [w][C] bf16;

@@ -1028,19 +1028,18 @@ extern "C" int dali_debug_stem_wgrad(dali_ctx* ctx, void* stream, const float* i
     DALI_REQUIRE((long long)N * (H / 2) * (W / 2) < (1ll << 31), "dali_debug_stem_wgrad: more than 2^31 pixels");
     hipStream_t st = (hipStream_t)stream;
     WGradArgs a{};
-    a.Cm = Cout; a.P = N * (H / 2) * (W / 2); a.Ntot = 224;
+    a.Cm = Cout; a.P = N * (H / 2) * (W / 2);
     a.g = stem_geom(H, W);
-    size_t wsb;
-    wgrad_plan(a.Cm, a.Ntot, a.P, 512, &a.splits, &a.pix_per_split, &wsb, 7);
-    const size_t b_img = align_up((size_t)N * (H + 6) * (W + 8) * 4 * 2, 256), b_slab = align_up(wsb, 256), b_pad = align_up((size_t)Cout * 224 * 4, 256);
+    const size_t b_img = align_up((size_t)N * (H + 6) * (W + 8) * 4 * 2, 256), b_slab = align_up(wgrad_need(a.Cm, a.P, a.g, false).slab_bytes, 256);
+    const size_t b_pad = align_up((size_t)Cout * 224 * 4, 256);
     char* ws = static_cast<char*>(workspace(ctx, b_img + b_slab + b_pad));
     if (!ws) return DALI_ERR_NOMEM;
     uint16_t* ximg = reinterpret_cast<uint16_t*>(ws);
     float* dw_pad = reinterpret_cast<float*>(ws + b_img + b_slab);
-    a.dY = d_raw0; a.X = ximg; a.partial = reinterpret_cast<float*>(ws + b_img);
+    a.dY = d_raw0; a.X = ximg;
     int rc;
     if ((rc = launch_stem_pack_image(st, images, N, H, W, ximg))) return rc;
-    if ((rc = launch_igemm_wgrad(st, a, dw_pad, 0))) return rc;
+    if ((rc = launch_wgrad(st, a, WGradBufs{reinterpret_cast<float*>(ws + b_img), nullptr, nullptr}, dw_pad, 0))) return rc;
     return launch_stem_unpack_wgrad(st, dw_pad, Cout, dw);
 }
 extern "C" int dali_bn1d_fwd(dali_ctx* ctx, void* stream, const float* x, int n, int C, const float* gamma, const float* beta,

@@ -14,6 +14,7 @@
 // A local_feature / JPM plan never runs a backward, so it reserves none of the backward's buffers (dgrad weight images, weight-gradient slab,
 // reduction partials, DropPath rows, gradient buffers) and its refresh_weights only casts.
 #include "kernels.h"
+#include "plan_table.h"
 #include <cstdio>
 #include <new>
 #include <string>
@@ -22,7 +23,6 @@
 using namespace dali;
 
 namespace {
-struct TInfo { std::string name; int64_t offset, numel; int shape[4]; int ndim; };
 struct Lin { int K, N; int64_t w_off, b_off; uint16_t *w, *wt; };
 struct Ln { int64_t g_off, b_off; float *mean, *rstd; };
 struct VBlock {
@@ -31,20 +31,15 @@ struct VBlock {
     float* lse;
 };
 struct Neck { int64_t g, b, rm, rv; };
-struct VArena { size_t used = 0; size_t take(size_t b) { size_t o = used; used = align_up(used + b, 256); return o; } };
 }  // namespace
 
-struct dali_vit {
+struct dali_vit : PlanTable {
     dali_ctx* ctx;
     dali_vit_cfg cfg;
     int B, T, np, C, H, rows;
-    std::vector<TInfo> params, buffers;
-    int64_t param_elems = 0, buffer_elems = 0;
     int64_t cls_off, pos_off, fcw_off, fcb_off;
     Lin patch; Ln fin; std::vector<VBlock> blocks;
     int64_t neck_g, neck_b, neck_rm, neck_rv;
-    size_t arena_bytes = 0;
-    std::vector<std::pair<void**, size_t>> fixups;
     uint16_t *wbf16 = nullptr, *patches = nullptr, *pe = nullptr, *x0 = nullptr, *cls_rows = nullptr, *dcls_rows = nullptr, *dgf16 = nullptr;
     float *gf = nullptr, *dgf = nullptr, *neck_mean = nullptr, *neck_invstd = nullptr, *slab = nullptr, *partial = nullptr;
     float *fin_mean = nullptr, *fin_rstd = nullptr, *dp_rows = nullptr;        // dp_rows [2*depth][rows]: DropPath factors per output row
@@ -71,24 +66,15 @@ struct dali_vit {
 };
 
 namespace {
-int64_t addt(std::vector<TInfo>& v, int64_t& total, const std::string& name, std::initializer_list<int> shape) {
-    TInfo t; t.name = name; t.ndim = (int)shape.size(); t.numel = 1;
-    int i = 0;
-    for (int s : shape) { t.shape[i++] = s; t.numel *= s; }
-    for (; i < 4; ++i) t.shape[i] = 1;
-    t.offset = total; total += (t.numel + 63) / 64 * 64;
-    v.push_back(t);
-    return t.offset;
-}
 void add_lin(dali_vit* n, Lin& l, const std::string& name, int K, int N) {
     l.K = K; l.N = N;
-    l.w_off = addt(n->params, n->param_elems, name + ".weight", {N, K});
-    l.b_off = addt(n->params, n->param_elems, name + ".bias", {N});
+    l.w_off = n->add_param(name + ".weight", {N, K});
+    l.b_off = n->add_param(name + ".bias", {N});
     l.w = l.wt = nullptr;
 }
 void add_ln(dali_vit* n, Ln& l, const std::string& name, int C) {
-    l.g_off = addt(n->params, n->param_elems, name + ".weight", {C});
-    l.b_off = addt(n->params, n->param_elems, name + ".bias", {C});
+    l.g_off = n->add_param(name + ".weight", {C});
+    l.b_off = n->add_param(name + ".bias", {C});
 }
 void add_block(dali_vit* n, VBlock& b, const std::string& pre) {
     const int C = n->C;
@@ -99,7 +85,6 @@ void add_block(dali_vit* n, VBlock& b, const std::string& pre) {
     add_lin(n, b.fc1, pre + ".mlp.fc1", C, n->cfg.mlp_hidden);
     add_lin(n, b.fc2, pre + ".mlp.fc2", n->cfg.mlp_hidden, C);
 }
-template <class T> void rsv(dali_vit* n, VArena& a, T*& p, size_t bytes) { n->fixups.emplace_back(reinterpret_cast<void**>(&p), a.take(bytes)); }
 }  // namespace
 
 extern "C" int dali_vit_create(dali_ctx* ctx, const dali_vit_cfg* cfg, dali_vit** out) {
@@ -121,18 +106,18 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
     n->B = cfg->batch; n->np = ny * nx; n->T = n->np + 1; n->C = cfg->dim; n->H = cfg->heads; n->rows = n->B * n->T;
     if (n->T > 256) { set_error("dali_vit_create: %d tokens exceed the attention kernel's limit of 256", n->T); delete n; return DALI_ERR_LIMIT; }
     const int C = n->C, Kp = 3 * cfg->patch * cfg->patch;
-    n->cls_off = addt(n->params, n->param_elems, "base.cls_token", {1, 1, C});
-    n->pos_off = addt(n->params, n->param_elems, "base.pos_embed", {1, n->T, C});
+    n->cls_off = n->add_param("base.cls_token", {1, 1, C});
+    n->pos_off = n->add_param("base.pos_embed", {1, n->T, C});
     if (ext->n_sie < 0) { set_error("dali_vit_create: n_sie = %d", ext->n_sie); delete n; return DALI_ERR_INVALID; }
-    if (ext->n_sie > 0) n->sie_off = addt(n->params, n->param_elems, "base.sie_embed", {ext->n_sie, 1, C});      // vit_pytorch.py:316-331
+    if (ext->n_sie > 0) n->sie_off = n->add_param("base.sie_embed", {ext->n_sie, 1, C});      // vit_pytorch.py:316-331
     n->patch.K = Kp; n->patch.N = C;
-    n->patch.w_off = addt(n->params, n->param_elems, "base.patch_embed.proj.weight", {C, 3, cfg->patch, cfg->patch});
-    n->patch.b_off = addt(n->params, n->param_elems, "base.patch_embed.proj.bias", {C});
+    n->patch.w_off = n->add_param("base.patch_embed.proj.weight", {C, 3, cfg->patch, cfg->patch});
+    n->patch.b_off = n->add_param("base.patch_embed.proj.bias", {C});
     n->blocks.resize(cfg->depth);
     for (int i = 0; i < cfg->depth; ++i) add_block(n, n->blocks[i], "base.blocks." + std::to_string(i));
     add_ln(n, n->fin, "base.norm", C);
-    n->fcw_off = addt(n->params, n->param_elems, "base.fc.weight", {cfg->num_classes, C});
-    n->fcb_off = addt(n->params, n->param_elems, "base.fc.bias", {cfg->num_classes});
+    n->fcw_off = n->add_param("base.fc.weight", {cfg->num_classes, C});
+    n->fcb_off = n->add_param("base.fc.bias", {cfg->num_classes});
     if (n->ext.jpm) {
         // make_models.py:249-258, 279-288: b1 / b2 = (block, norm) copies, then the five unused classifiers, in the state dict's order
         if (n->ext.id_classes < 1) { set_error("dali_vit_create: JPM needs id_classes >= 1 (the classifiers' rows)"); delete n; return DALI_ERR_INVALID; }
@@ -150,15 +135,15 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
         n->Tl = 1 + n->L; n->rows2 = n->ext.divide * n->B * n->Tl;
         add_block(n, n->b1, "b1.0"); add_ln(n, n->fin1, "b1.1", C);
         add_block(n, n->b2, "b2.0"); add_ln(n, n->fin2, "b2.1", C);
-        for (int i = 0; i < 5; ++i) addt(n->params, n->param_elems, i ? "classifier_" + std::to_string(i) + ".weight" : std::string("classifier.weight"), {n->ext.id_classes, C});
+        for (int i = 0; i < 5; ++i) n->add_param(i ? "classifier_" + std::to_string(i) + ".weight" : std::string("classifier.weight"), {n->ext.id_classes, C});
     }
     for (int i = 0; i < (n->ext.jpm ? 5 : 1); ++i) {
         const std::string nm = i ? "bottleneck_" + std::to_string(i) : std::string("bottleneck");
         Neck& k = n->necks[i];
-        k.g = addt(n->params, n->param_elems, nm + ".weight", {C});
-        k.b = addt(n->params, n->param_elems, nm + ".bias", {C});
-        k.rm = addt(n->buffers, n->buffer_elems, nm + ".running_mean", {C});
-        k.rv = addt(n->buffers, n->buffer_elems, nm + ".running_var", {C});
+        k.g = n->add_param(nm + ".weight", {C});
+        k.b = n->add_param(nm + ".bias", {C});
+        k.rm = n->add_buffer(nm + ".running_mean", {C});
+        k.rv = n->add_buffer(nm + ".running_var", {C});
     }
     n->neck_g = n->necks[0].g; n->neck_b = n->necks[0].b; n->neck_rm = n->necks[0].rm; n->neck_rv = n->necks[0].rv;
     // backward stages = gradient buckets of the data-parallel reducer: up to 4 groups of consecutive blocks, last blocks first
@@ -166,53 +151,53 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
     n->stage_first_block.resize(n->n_stages + 1);
     for (int s = 0; s <= n->n_stages; ++s) n->stage_first_block[s] = cfg->depth - (int)((int64_t)cfg->depth * s / n->n_stages);
 
-    VArena a;
     const size_t rows = n->rows, Hd = cfg->mlp_hidden;
-    rsv(n, a, n->wbf16, (size_t)n->param_elems * 2);
-    rsv(n, a, n->patches, (size_t)n->B * n->np * Kp * 2);
-    rsv(n, a, n->pe, (size_t)n->B * n->np * C * 2);
-    rsv(n, a, n->x0, rows * C * 2);
+    n->reserve(n->wbf16, (size_t)n->param_elems * 2);
+    n->reserve(n->patches, (size_t)n->B * n->np * Kp * 2);
+    n->reserve(n->pe, (size_t)n->B * n->np * C * 2);
+    n->reserve(n->x0, rows * C * 2);
     const bool eval_only = n->ext.local_feature != 0;
-    if (!eval_only) rsv(n, a, n->patch.wt, (size_t)Kp * C * 2);          // unused (images need no gradient) but keeps Lin uniform
-    size_t slab = linear_wgrad_slab_bytes(n->B * n->np, Kp, C);
-    size_t part = std::max(layernorm_bwd_partial_floats((int)rows, C), colsum_partial_floats((int)rows, (int)std::max<size_t>(Hd, 3 * C))) * 4;
+    if (!eval_only) n->reserve(n->patch.wt, (size_t)Kp * C * 2);          // unused (images need no gradient) but keeps Lin uniform
+    // the weight-gradient workspace is sized for every linear layer the backward runs (patch embedding, then each block's four)
+    WGradNeed need = linear_wgrad_need(n->B * n->np, Kp, C, true);
+    size_t part = std::max(layernorm_bwd_partial_floats((int)rows, C), colsum_partial_floats((int)rows, (int)std::max<size_t>(Hd, 3 * C)));
     for (auto& b : n->blocks) {
-        rsv(n, a, b.h1, rows * C * 2); rsv(n, a, b.qkv_o, rows * 3 * C * 2); rsv(n, a, b.att, rows * C * 2);
-        rsv(n, a, b.x_mid, rows * C * 2); rsv(n, a, b.h2, rows * C * 2); rsv(n, a, b.pre1, rows * Hd * 2);
-        rsv(n, a, b.act1, rows * Hd * 2); rsv(n, a, b.x_out, rows * C * 2);
-        rsv(n, a, b.lse, (size_t)n->B * n->H * n->T * 4);
-        rsv(n, a, b.n1.mean, rows * 4); rsv(n, a, b.n1.rstd, rows * 4); rsv(n, a, b.n2.mean, rows * 4); rsv(n, a, b.n2.rstd, rows * 4);
+        n->reserve(b.h1, rows * C * 2); n->reserve(b.qkv_o, rows * 3 * C * 2); n->reserve(b.att, rows * C * 2);
+        n->reserve(b.x_mid, rows * C * 2); n->reserve(b.h2, rows * C * 2); n->reserve(b.pre1, rows * Hd * 2);
+        n->reserve(b.act1, rows * Hd * 2); n->reserve(b.x_out, rows * C * 2);
+        n->reserve(b.lse, (size_t)n->B * n->H * n->T * 4);
+        n->reserve(b.n1.mean, rows * 4); n->reserve(b.n1.rstd, rows * 4); n->reserve(b.n2.mean, rows * 4); n->reserve(b.n2.rstd, rows * 4);
         Lin* ls[4] = {&b.qkv, &b.proj, &b.fc1, &b.fc2};
         for (Lin* l : ls) {
-            if (!eval_only) rsv(n, a, l->wt, (size_t)l->K * l->N * 2);
-            slab = std::max(slab, linear_wgrad_slab_bytes((int)rows, l->K, l->N));
+            if (!eval_only) n->reserve(l->wt, (size_t)l->K * l->N * 2);
+            const WGradNeed ln = linear_wgrad_need((int)rows, l->K, l->N, true);
+            need = WGradNeed{std::max(need.slab_bytes, ln.slab_bytes), std::max(need.colsum_floats, ln.colsum_floats)};
         }
     }
-    rsv(n, a, n->cls_rows, (size_t)n->B * C * 2); rsv(n, a, n->dcls_rows, (size_t)n->B * C * 2); rsv(n, a, n->dgf16, (size_t)n->B * C * 2);
-    rsv(n, a, n->gf, (size_t)n->B * C * 4); rsv(n, a, n->dgf, (size_t)n->B * C * 4);
-    rsv(n, a, n->neck_mean, C * 4); rsv(n, a, n->neck_invstd, C * 4);
-    rsv(n, a, n->fin_mean, n->B * 4); rsv(n, a, n->fin_rstd, n->B * 4);
+    n->reserve(n->cls_rows, (size_t)n->B * C * 2); n->reserve(n->dcls_rows, (size_t)n->B * C * 2); n->reserve(n->dgf16, (size_t)n->B * C * 2);
+    n->reserve(n->gf, (size_t)n->B * C * 4); n->reserve(n->dgf, (size_t)n->B * C * 4);
+    n->reserve(n->neck_mean, C * 4); n->reserve(n->neck_invstd, C * 4);
+    n->reserve(n->fin_mean, n->B * 4); n->reserve(n->fin_rstd, n->B * 4);
     if (!eval_only) {
-        rsv(n, a, n->slab, slab); rsv(n, a, n->partial, part);
-        rsv(n, a, n->dp_rows, (size_t)2 * cfg->depth * rows * 4);
+        n->reserve(n->slab, need.slab_bytes); n->reserve(n->partial, std::max(part, need.colsum_floats) * 4);
+        n->reserve(n->dp_rows, (size_t)2 * cfg->depth * rows * 4);
     }
-    rsv(n, a, n->scratch, reduce_scratch_bytes((int)std::max<size_t>(Hd, 3 * C), 2));
-    for (int i = 0; i < 4 && !eval_only; ++i) rsv(n, a, n->gbuf[i], rows * std::max<size_t>(Hd, 3 * C) * 2);
+    n->reserve(n->scratch, reduce_scratch_bytes((int)std::max<size_t>(Hd, 3 * C), 2));
+    for (int i = 0; i < 4 && !eval_only; ++i) n->reserve(n->gbuf[i], rows * std::max<size_t>(Hd, 3 * C) * 2);
     if (n->ext.jpm) {
         // b1 runs on the B*T rows in the buffers of the idle blocks[depth-1] (bind); b2 gets its own for the divide * B sequences of 1 + L tokens
         VBlock& b = n->b2;
         const size_t r2 = n->rows2, seqs = (size_t)n->ext.divide * n->B;
-        rsv(n, a, n->jseq, r2 * C * 2);
-        rsv(n, a, b.h1, r2 * C * 2); rsv(n, a, b.qkv_o, r2 * 3 * C * 2); rsv(n, a, b.att, r2 * C * 2);
-        rsv(n, a, b.x_mid, r2 * C * 2); rsv(n, a, b.h2, r2 * C * 2); rsv(n, a, b.pre1, r2 * Hd * 2);
-        rsv(n, a, b.act1, r2 * Hd * 2); rsv(n, a, b.x_out, r2 * C * 2);
-        rsv(n, a, b.lse, seqs * n->H * n->Tl * 4);
-        rsv(n, a, b.n1.mean, r2 * 4); rsv(n, a, b.n1.rstd, r2 * 4); rsv(n, a, b.n2.mean, r2 * 4); rsv(n, a, b.n2.rstd, r2 * 4);
-        rsv(n, a, n->cls2, seqs * C * 2); rsv(n, a, n->gf2, seqs * C * 4);
-        rsv(n, a, n->fin2_mean, seqs * 4); rsv(n, a, n->fin2_rstd, seqs * 4);
-        rsv(n, a, n->map_dev, n->map_host.size() * 4);
+        n->reserve(n->jseq, r2 * C * 2);
+        n->reserve(b.h1, r2 * C * 2); n->reserve(b.qkv_o, r2 * 3 * C * 2); n->reserve(b.att, r2 * C * 2);
+        n->reserve(b.x_mid, r2 * C * 2); n->reserve(b.h2, r2 * C * 2); n->reserve(b.pre1, r2 * Hd * 2);
+        n->reserve(b.act1, r2 * Hd * 2); n->reserve(b.x_out, r2 * C * 2);
+        n->reserve(b.lse, seqs * n->H * n->Tl * 4);
+        n->reserve(b.n1.mean, r2 * 4); n->reserve(b.n1.rstd, r2 * 4); n->reserve(b.n2.mean, r2 * 4); n->reserve(b.n2.rstd, r2 * 4);
+        n->reserve(n->cls2, seqs * C * 2); n->reserve(n->gf2, seqs * C * 4);
+        n->reserve(n->fin2_mean, seqs * 4); n->reserve(n->fin2_rstd, seqs * 4);
+        n->reserve(n->map_dev, n->map_host.size() * 4);
     }
-    n->arena_bytes = a.used;
     *out = n;
     return DALI_OK;
 }
@@ -222,29 +207,18 @@ extern "C" int dali_vit_destroy(dali_vit* n) { delete n; return DALI_OK; }
 extern "C" int dali_vit_sizes(const dali_vit* n, int64_t* param_elems, int64_t* buffer_elems, int64_t* arena_bytes, int* feat_dim,
                               int* n_params, int* n_buffers) {
     DALI_REQUIRE(n, "dali_vit_sizes: null net");
-    if (param_elems) *param_elems = n->param_elems;
-    if (buffer_elems) *buffer_elems = n->buffer_elems;
-    if (arena_bytes) *arena_bytes = (int64_t)n->arena_bytes;
-    if (feat_dim) *feat_dim = n->ext.jpm ? 5 * n->C : n->C;
-    if (n_params) *n_params = (int)n->params.size();
-    if (n_buffers) *n_buffers = (int)n->buffers.size();
-    return DALI_OK;
+    return n->sizes(n->ext.jpm ? 5 * n->C : n->C, param_elems, buffer_elems, arena_bytes, feat_dim, n_params, n_buffers);
 }
 extern "C" int dali_vit_tensor_info(const dali_vit* n, int kind, int index, char* name, int name_cap, int64_t* offset, int64_t* numel,
                                     int* shape4, int* ndim) {
-    DALI_REQUIRE(n && name && offset && numel && shape4 && ndim, "dali_vit_tensor_info: null argument");
-    const auto& v = kind == 0 ? n->params : n->buffers;
-    DALI_REQUIRE(index >= 0 && index < (int)v.size(), "dali_vit_tensor_info: index %d out of range", index);
-    snprintf(name, name_cap, "%s", v[index].name.c_str());
-    *offset = v[index].offset; *numel = v[index].numel; *ndim = v[index].ndim;
-    for (int i = 0; i < 4; ++i) shape4[i] = v[index].shape[i];
-    return DALI_OK;
+    DALI_REQUIRE(n, "dali_vit_tensor_info: null argument");
+    return n->tensor_info("dali_vit_tensor_info", kind, index, name, name_cap, offset, numel, shape4, ndim);
 }
 extern "C" int dali_vit_bind(dali_vit* n, float* params, float* grads, float* buffers, void* arena, size_t arena_bytes) {
     DALI_REQUIRE(n && params && buffers && arena, "dali_vit_bind: null argument");
     DALI_REQUIRE(arena_bytes >= n->arena_bytes, "dali_vit_bind: arena too small (%zu < %zu)", arena_bytes, n->arena_bytes);
     n->P = params; n->G = grads; n->Bf = buffers; n->arena = static_cast<char*>(arena);
-    for (auto& f : n->fixups) *f.first = n->arena + f.second;
+    n->bind_arena(n->arena);
     n->patch.w = n->wbf16 + n->patch.w_off;
     for (auto& b : n->blocks) { b.qkv.w = n->wbf16 + b.qkv.w_off; b.proj.w = n->wbf16 + b.proj.w_off; b.fc1.w = n->wbf16 + b.fc1.w_off; b.fc2.w = n->wbf16 + b.fc2.w_off; }
     if (n->ext.jpm) {
@@ -361,9 +335,7 @@ extern "C" int dali_vit_forward_ex(dali_vit* n, void* stream, const float* image
 namespace {
 int lin_bwd(dali_vit* n, hipStream_t st, const Lin& l, const uint16_t* x, const uint16_t* dy, const uint16_t* gelu_pre, uint16_t* dx, int rows) {
     int rc;
-    bool bias_done = false;                                       // the bias gradient rides on the weight-gradient GEMM where the kernel supports it
-    if ((rc = launch_linear_wgrad(st, x, dy, n->G + l.w_off, rows, l.K, l.N, n->slab, n->G + l.b_off, n->partial, &bias_done))) return rc;
-    if (!bias_done && (rc = launch_colsum(st, dy, rows, l.N, n->G + l.b_off, n->partial, n->scratch))) return rc;
+    if ((rc = launch_linear_wgrad(st, x, dy, n->G + l.w_off, rows, l.K, l.N, WGradBufs{n->slab, n->partial, n->scratch}, n->G + l.b_off))) return rc;
     if (dx) return launch_linear_fwd(st, dy, l.wt, nullptr, 0, nullptr, dx, nullptr, gelu_pre, rows, l.N, l.K);
     return DALI_OK;
 }

@@ -7,7 +7,7 @@ Why beside tests/test_gpu_conv.py: tile shapes, XCD super-tile maps, grids, spli
 count, and at batch 256 they are not the ones the small cases take (4096-tile launches in layer1, 16-way splits of 524288 pixels, the
 256 x 256 / 256 x 320 tiles).  A deterministic indexing error in one of them passes every property test of the full-size step (finite,
 Adam-sized, bit-reproducible) and drowns in the train-mode tolerances of the end-to-end tests; here it is a failed torch.equal.
-The C-ABI entry points take the same launchers and plans as the net (launch_igemm_conv / launch_igemm_wgrad + wgrad_plan)."""
+The C-ABI entry points take the same launchers and plans as the net (launch_igemm_conv / launch_wgrad)."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -55,6 +55,19 @@ def test_state_dict_keys_match_torchvision_names(enc):
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("layers,width,shape,sizes", [
+    ((1, 1, 1, 1), 32, (8, 64, 32), (2013440, 11904, 19311616, 1024, 53, 36)),
+    ((1, 2, 1, 2), 64, (4, 128, 64), (12762688, 31104, 103237632, 2048, 71, 48)),
+    ((3, 4, 6, 3), 64, (256, 256, 128), (23512128, 57216, 7656899072, 2048, 161, 108))])
+def test_plan_sizes_are_pinned(enc, layers, width, shape, sizes):
+    """Parameter elements, buffer elements, arena bytes, feature width and table lengths of three plans (two small nets and ResNet-50 at the
+    benchmark's batch), as the library gave them on an MI355X before the weight-gradient workspace was sized through wgrad_need and the tensor
+    table moved to plan_table.h.  Plans are created only, nothing is bound or run.  (arena_bytes depends on the CU count through
+    conv_cat_act_supported.)"""
+    p = enc._Plan(torch.device("cuda", 0), *shape, layers, width)
+    assert (p.param_elems, p.buffer_elems, p.arena_bytes, p.feat_dim, p.n_params, p.n_buffers) == sizes
+
+
 def test_stem_and_maxpool_layer_local(enc):
     ref, net = _pair(enc, (1, 1, 1, 1), 32, 3)
     x = torch.randn(4, 3, 64, 32, generator=torch.Generator().manual_seed(9))
