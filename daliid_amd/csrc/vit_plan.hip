@@ -359,58 +359,154 @@ extern "C" int dali_vit_stage_param_range(const dali_vit* n, int stage, int64_t*
     return DALI_OK;
 }
 
+namespace {
+// The three pieces of the backward; dali_vit_backward_stages and dali_debug_vit_backward_block both run exactly these, in this order.
+// The gradient wrt the tokens entering a piece lives in gbuf[0] throughout.
+
+// neck (bias frozen, make_models.py:181: no dbeta) + final LayerNorm (cls rows) -> gbuf[0] = dcls_rows at token 0 of every sample, 0 elsewhere
+int bwd_head(dali_vit* n, hipStream_t st, const float* d_feat) {
+    const int C = n->C;
+    uint16_t* dx = n->gbuf[0];
+    int rc;
+    if ((rc = launch_bn1d_bwd(st, n->gf, d_feat, n->B, C, n->P + n->neck_g, n->neck_mean, n->neck_invstd, n->dgf, n->G + n->neck_g, nullptr))) return rc;
+    if ((rc = launch_layernorm_bwd(st, nullptr, n->cls_rows, n->P + n->fin.g_off, n->fin_mean, n->fin_rstd, nullptr, n->B, C, n->dcls_rows,
+                                   n->G + n->fin.g_off, n->G + n->fin.b_off, n->partial, n->scratch, n->dgf))) return rc;
+    DALI_HIP(hipMemsetAsync(dx, 0, (size_t)n->rows * C * 2, st));
+    DALI_HIP(hipMemcpy2DAsync(dx, (size_t)n->T * C * 2, n->dcls_rows, (size_t)C * 2, (size_t)C * 2, n->B, hipMemcpyDeviceToDevice, st));
+    return DALI_OK;
+}
+
+// block i: gbuf[0] = d x_out  ->  gbuf[0] = d x_in, and the block's 12 parameter gradients
+int bwd_block(dali_vit* n, hipStream_t st, int i) {
+    const int C = n->C, rows = n->rows;
+    const float* dp = n->dp_used;
+    int rc;
+    VBlock& b = n->blocks[i];
+    uint16_t* dx = n->gbuf[0]; uint16_t* t1 = n->gbuf[1]; uint16_t* t2 = n->gbuf[2]; uint16_t* t3 = n->gbuf[3];
+    const float* s_att = dp ? dp + (size_t)(2 * i) * n->B : nullptr;
+    const float* s_mlp = dp ? dp + (size_t)(2 * i + 1) * n->B : nullptr;
+    // x_out = x_mid + s_mlp * fc2(gelu(fc1(LN2(x_mid))))
+    const uint16_t* d_branch = dx;
+    if (dp) { if ((rc = launch_rowscale_add(st, dx, s_mlp, n->B, n->T, C, nullptr, t2))) return rc; d_branch = t2; }
+    if ((rc = lin_bwd(n, st, b.fc2, b.act1, d_branch, b.pre1, t1, rows))) return rc;           // t1 = d_pre1 (GELU' fused)
+    if ((rc = lin_bwd(n, st, b.fc1, b.h2, t1, nullptr, t2, rows))) return rc;                  // t2 = d_h2
+    if ((rc = launch_layernorm_bwd(st, t2, b.x_mid, n->P + b.n2.g_off, b.n2.mean, b.n2.rstd, dx, rows, C, t3, n->G + b.n2.g_off,
+                                   n->G + b.n2.b_off, n->partial, n->scratch))) return rc;     // t3 = dx_mid
+    // x_mid = x_in + s_att * proj(attn(qkv(LN1(x_in))))
+    d_branch = t3;
+    if (dp) { if ((rc = launch_rowscale_add(st, t3, s_att, n->B, n->T, C, nullptr, t2))) return rc; d_branch = t2; }
+    if ((rc = lin_bwd(n, st, b.proj, b.att, d_branch, nullptr, t1, rows))) return rc;          // t1 = d_att
+    if ((rc = launch_attention_bwd(st, b.qkv_o, b.att, t1, b.lse, n->B, n->T, n->H, 0.125f, t2))) return rc;   // t2 = d_qkv
+    if ((rc = lin_bwd(n, st, b.qkv, b.h1, t2, nullptr, t1, rows))) return rc;                  // t1 = d_h1
+    return launch_layernorm_bwd(st, t1, b.x_in, n->P + b.n1.g_off, b.n1.mean, b.n1.rstd, t3, rows, C, dx, n->G + b.n1.g_off,
+                                n->G + b.n1.b_off, n->partial, n->scratch);                    // dx = dx_in
+}
+
+// tokens: d pos_embed, d cls_token, d patch embedding (gbuf[1] = the patch rows of gbuf[0]), d sie_embed
+int bwd_tokens(dali_vit* n, hipStream_t st) {
+    const int C = n->C;
+    uint16_t* dx = n->gbuf[0];
+    int rc;
+    if ((rc = launch_assemble_tokens_bwd(st, dx, n->B, n->T, C, n->G + n->pos_off, n->G + n->cls_off, n->gbuf[1]))) return rc;
+    if ((rc = lin_bwd(n, st, n->patch, n->patches, n->gbuf[1], nullptr, nullptr, n->B * n->np))) return rc;
+    // d sie_embed from the same dx (every token of sample b carries coef * sie[idx[b]], vit_pytorch.py:382-387)
+    if (n->ext.n_sie > 0) {
+        DALI_REQUIRE(n->sie_used != nullptr, "dali_vit_backward: no SIE indices from the last training forward");
+        if ((rc = launch_sie_grad(st, dx, n->sie_used, n->B, n->T, C, n->ext.n_sie, n->ext.sie_coef, n->G + n->sie_off))) return rc;
+    }
+    return DALI_OK;
+}
+}  // namespace
+
 extern "C" int dali_vit_backward_stages(dali_vit* n, void* stream, const float* d_feat, int stage_begin, int stage_end) {
     DALI_REQUIRE(n && n->P && n->G, "dali_vit_backward: null argument or net not bound");
     DALI_REQUIRE(!n->ext.local_feature, "dali_vit_backward: a local_feature / JPM net is eval only (its train-mode forward feeds an ID loss that is out of scope)");
     DALI_REQUIRE(n->fwd_training, "dali_vit_backward: the last forward was not in training mode");
     DALI_REQUIRE(stage_begin >= 0 && stage_end < n->n_stages && stage_begin <= stage_end, "dali_vit_backward: bad stage range %d..%d", stage_begin, stage_end);
     hipStream_t st = (hipStream_t)stream;
-    const int C = n->C, rows = n->rows;
-    const float* dp = n->dp_used;
     int rc;
-    uint16_t* dx = n->gbuf[0];
     for (int stage = stage_begin; stage <= stage_end; ++stage) {
         if (stage == 0) {
             DALI_REQUIRE(d_feat != nullptr, "dali_vit_backward: d_feat is null");
-            // neck (bias frozen, make_models.py:181: no dbeta) + final LayerNorm (cls rows)
-            if ((rc = launch_bn1d_bwd(st, n->gf, d_feat, n->B, C, n->P + n->neck_g, n->neck_mean, n->neck_invstd, n->dgf, n->G + n->neck_g, nullptr))) return rc;
-            if ((rc = launch_layernorm_bwd(st, nullptr, n->cls_rows, n->P + n->fin.g_off, n->fin_mean, n->fin_rstd, nullptr, n->B, C, n->dcls_rows,
-                                           n->G + n->fin.g_off, n->G + n->fin.b_off, n->partial, n->scratch, n->dgf))) return rc;
-            DALI_HIP(hipMemsetAsync(dx, 0, (size_t)rows * C * 2, st));
-            DALI_HIP(hipMemcpy2DAsync(dx, (size_t)n->T * C * 2, n->dcls_rows, (size_t)C * 2, (size_t)C * 2, n->B, hipMemcpyDeviceToDevice, st));
+            if ((rc = bwd_head(n, st, d_feat))) return rc;
         }
-        for (int i = n->stage_first_block[stage] - 1; i >= n->stage_first_block[stage + 1]; --i) {
-            VBlock& b = n->blocks[i];
-            uint16_t* t1 = n->gbuf[1]; uint16_t* t2 = n->gbuf[2]; uint16_t* t3 = n->gbuf[3];
-            const float* s_att = dp ? dp + (size_t)(2 * i) * n->B : nullptr;
-            const float* s_mlp = dp ? dp + (size_t)(2 * i + 1) * n->B : nullptr;
-            // x_out = x_mid + s_mlp * fc2(gelu(fc1(LN2(x_mid))))
-            const uint16_t* d_branch = dx;
-            if (dp) { if ((rc = launch_rowscale_add(st, dx, s_mlp, n->B, n->T, C, nullptr, t2))) return rc; d_branch = t2; }
-            if ((rc = lin_bwd(n, st, b.fc2, b.act1, d_branch, b.pre1, t1, rows))) return rc;           // t1 = d_pre1 (GELU' fused)
-            if ((rc = lin_bwd(n, st, b.fc1, b.h2, t1, nullptr, t2, rows))) return rc;                  // t2 = d_h2
-            if ((rc = launch_layernorm_bwd(st, t2, b.x_mid, n->P + b.n2.g_off, b.n2.mean, b.n2.rstd, dx, rows, C, t3, n->G + b.n2.g_off,
-                                           n->G + b.n2.b_off, n->partial, n->scratch))) return rc;     // t3 = dx_mid
-            // x_mid = x_in + s_att * proj(attn(qkv(LN1(x_in))))
-            d_branch = t3;
-            if (dp) { if ((rc = launch_rowscale_add(st, t3, s_att, n->B, n->T, C, nullptr, t2))) return rc; d_branch = t2; }
-            if ((rc = lin_bwd(n, st, b.proj, b.att, d_branch, nullptr, t1, rows))) return rc;          // t1 = d_att
-            if ((rc = launch_attention_bwd(st, b.qkv_o, b.att, t1, b.lse, n->B, n->T, n->H, 0.125f, t2))) return rc;   // t2 = d_qkv
-            if ((rc = lin_bwd(n, st, b.qkv, b.h1, t2, nullptr, t1, rows))) return rc;                  // t1 = d_h1
-            if ((rc = launch_layernorm_bwd(st, t1, b.x_in, n->P + b.n1.g_off, b.n1.mean, b.n1.rstd, t3, rows, C, dx, n->G + b.n1.g_off,
-                                           n->G + b.n1.b_off, n->partial, n->scratch))) return rc;     // dx = dx_in
+        for (int i = n->stage_first_block[stage] - 1; i >= n->stage_first_block[stage + 1]; --i)
+            if ((rc = bwd_block(n, st, i))) return rc;
+        if (stage == n->n_stages - 1 && (rc = bwd_tokens(n, st))) return rc;
+    }
+    return DALI_OK;
+}
+
+// ---- diagnostics (include/daliid_debug.h) ----
+extern "C" int dali_debug_vit_backward_block(dali_vit* n, void* stream, const float* d_feat, int block) {
+    DALI_REQUIRE(n && n->P && n->G, "dali_debug_vit_backward_block: null argument or net not bound");
+    DALI_REQUIRE(!n->ext.local_feature, "dali_debug_vit_backward_block: a local_feature / JPM net is eval only");
+    DALI_REQUIRE(n->fwd_training, "dali_debug_vit_backward_block: the last forward was not in training mode");
+    const int depth = (int)n->blocks.size();
+    DALI_REQUIRE(block >= -1 && block <= depth, "dali_debug_vit_backward_block: block %d not in -1 .. %d", block, depth);
+    hipStream_t st = (hipStream_t)stream;
+    if (block == depth) {
+        DALI_REQUIRE(d_feat != nullptr, "dali_debug_vit_backward_block: d_feat is null");
+        return bwd_head(n, st, d_feat);
+    }
+    return block >= 0 ? bwd_block(n, st, block) : bwd_tokens(n, st);
+}
+
+extern "C" int dali_debug_vit_tensor(const dali_vit* n, const char* name, void** ptr, int64_t* bytes) {
+    DALI_REQUIRE(n && name && ptr && bytes, "dali_debug_vit_tensor: null argument");
+    DALI_REQUIRE(n->arena, "dali_debug_vit_tensor: net not bound");
+    const size_t rows = n->rows, C = n->C, Hd = n->cfg.mlp_hidden, B = n->B;
+    const void* p = nullptr; size_t sz = 0;
+    auto is = [&](const char* s) { return std::string(name) == s; };
+    if (is("patches")) { p = n->patches; sz = B * n->np * (size_t)n->patch.K * 2; }
+    else if (is("pe")) { p = n->pe; sz = B * n->np * C * 2; }
+    else if (is("x0")) { p = n->x0; sz = rows * C * 2; }
+    else if (is("cls_rows")) { p = n->cls_rows; sz = B * C * 2; }
+    else if (is("dcls_rows")) { p = n->dcls_rows; sz = B * C * 2; }
+    else if (is("gf")) { p = n->gf; sz = B * C * 4; }
+    else if (is("dgf")) { p = n->dgf; sz = B * C * 4; }
+    else if (is("fin.mean")) { p = n->fin_mean; sz = B * 4; }
+    else if (is("fin.rstd")) { p = n->fin_rstd; sz = B * 4; }
+    else if (is("neck.mean")) { p = n->neck_mean; sz = C * 4; }
+    else if (is("neck.invstd")) { p = n->neck_invstd; sz = C * 4; }
+    else if (is("dp_rows")) { p = n->dp_rows; sz = 2 * n->blocks.size() * rows * 4; }
+    else if (is("wbf16")) { p = n->wbf16; sz = (size_t)n->param_elems * 2; }
+    else if (is("grad_cur")) { p = n->gbuf[0]; sz = rows * C * 2; }
+    else if (is("dpe")) { p = n->gbuf[1]; sz = B * n->np * C * 2; }                  // what the token tail hands to the patch weight gradient
+    else {
+        int bi = -1, used = 0;
+        if (sscanf(name, "block%d.%n", &bi, &used) < 1 || used == 0 || bi < 0 || bi >= (int)n->blocks.size()) {
+            set_error("dali_debug_vit_tensor: unknown tensor '%s'", name); return DALI_ERR_INVALID;
         }
-        if (stage == n->n_stages - 1) {
-            // tokens: d pos_embed, d cls_token, d patch embedding
-            if ((rc = launch_assemble_tokens_bwd(st, dx, n->B, n->T, C, n->G + n->pos_off, n->G + n->cls_off, n->gbuf[1]))) return rc;
-            if ((rc = lin_bwd(n, st, n->patch, n->patches, n->gbuf[1], nullptr, nullptr, n->B * n->np))) return rc;
-            // d sie_embed from the same dx (every token of sample b carries coef * sie[idx[b]], vit_pytorch.py:382-387)
-            if (n->ext.n_sie > 0) {
-                DALI_REQUIRE(n->sie_used != nullptr, "dali_vit_backward: no SIE indices from the last training forward");
-                if ((rc = launch_sie_grad(st, dx, n->sie_used, n->B, n->T, C, n->ext.n_sie, n->ext.sie_coef, n->G + n->sie_off))) return rc;
-            }
+        const VBlock& b = n->blocks[bi];
+        const std::string f = name + used;
+        const Lin* l = nullptr;
+        if (f == "h1") { p = b.h1; sz = rows * C * 2; }
+        else if (f == "qkv") { p = b.qkv_o; sz = rows * 3 * C * 2; }
+        else if (f == "att") { p = b.att; sz = rows * C * 2; }
+        else if (f == "x_mid") { p = b.x_mid; sz = rows * C * 2; }
+        else if (f == "h2") { p = b.h2; sz = rows * C * 2; }
+        else if (f == "pre1") { p = b.pre1; sz = rows * Hd * 2; }
+        else if (f == "act1") { p = b.act1; sz = rows * Hd * 2; }
+        else if (f == "x_out") { p = b.x_out; sz = rows * C * 2; }
+        else if (f == "lse") { p = b.lse; sz = B * n->H * (size_t)n->T * 4; }
+        else if (f == "n1.mean") { p = b.n1.mean; sz = rows * 4; }
+        else if (f == "n1.rstd") { p = b.n1.rstd; sz = rows * 4; }
+        else if (f == "n2.mean") { p = b.n2.mean; sz = rows * 4; }
+        else if (f == "n2.rstd") { p = b.n2.rstd; sz = rows * 4; }
+        else if (f.rfind("qkv.", 0) == 0) l = &b.qkv;
+        else if (f.rfind("proj.", 0) == 0) l = &b.proj;
+        else if (f.rfind("fc1.", 0) == 0) l = &b.fc1;
+        else if (f.rfind("fc2.", 0) == 0) l = &b.fc2;
+        if (l) {
+            const std::string leaf = f.substr(f.find('.') + 1);
+            sz = (size_t)l->K * l->N * 2;
+            if (leaf == "w") p = l->w; else if (leaf == "wt") p = l->wt;
         }
     }
+    // a name the plan did not reserve (dgrad images, DropPath rows, gradient buffers of an eval-only plan) was never bound: still null
+    if (!p) { set_error("dali_debug_vit_tensor: unknown tensor '%s', or one this plan does not hold", name); return DALI_ERR_INVALID; }
+    *ptr = const_cast<void*>(p); *bytes = (int64_t)sz;
     return DALI_OK;
 }
 

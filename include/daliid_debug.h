@@ -9,6 +9,8 @@
 #ifndef DALIID_DEBUG_H
 #define DALIID_DEBUG_H
 
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -32,6 +34,19 @@ int dali_debug_splitk_reduce(void* stream, const float* partial, float* out, lon
  * in the same order as dali_resnet_backward (tests/test_gpu_resnet_blocks.py, the batch-256 composition check) */
 struct dali_resnet;
 int dali_debug_resnet_backward_block(struct dali_resnet* net, void* stream, const float* d_emb, int block);
+
+/* the ViT plan's backward ONE piece at a time: block = depth runs the head only (neck, final LayerNorm on the cls rows, memset + scatter of
+ * their gradient into the token gradient), depth-1 .. 0 runs that one transformer block, -1 the token tail (assemble_tokens_bwd, the patch
+ * embedding's weight gradient, sie_grad).  The same launches in the same order as dali_vit_backward_stages: both call the same three helpers
+ * (tests/test_gpu_vit_plan.py).  d_feat is read by the head call only */
+struct dali_vit;
+int dali_debug_vit_backward_block(struct dali_vit* net, void* stream, const float* d_feat, int block);
+/* device pointer and byte size of a named arena tensor of a bound ViT plan, valid after a forward: patches, pe, x0, cls_rows, gf, dgf, dcls_rows,
+ * fin.mean, fin.rstd, neck.mean, neck.invstd, dp_rows, wbf16, grad_cur (the token gradient between two pieces of the backward), dpe (the patch
+ * rows of it, as the token tail hands them to the patch weight gradient), block<i>.{h1,qkv,att,x_mid,h2,pre1,act1,x_out,lse,n1.mean,n1.rstd,
+ * n2.mean,n2.rstd} and block<i>.{qkv,proj,fc1,fc2}.{w,wt}.  DALI_ERR_INVALID for an unknown name and for one the plan did not reserve (wt,
+ * dp_rows, grad_cur, dpe of an eval-only plan) */
+int dali_debug_vit_tensor(const struct dali_vit* net, const char* name, void** ptr, int64_t* bytes);
 
 /* pieces that only the net plan reaches, on their own (tests/test_gpu_plan_only.py) */
 struct dali_ctx;

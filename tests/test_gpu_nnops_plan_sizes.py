@@ -18,6 +18,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from vit_checks import check_bn1d_bwd, check_layernorm_fwd
+
 pytestmark = pytest.mark.gpu
 bf16 = torch.bfloat16
 U = 2.0 ** -24                      # fp32 unit roundoff
@@ -567,17 +569,7 @@ def test_bn1d_train_plan_sizes(nn, shape):
     # backward, from the kernel's own mean / invstd
     dy = torch.randn(N, C, generator=g)
     dx, dg, db = nn.bn1d_bwd(x.cuda(), dy.cuda(), gamma.cuda(), mean, invstd)
-    dyd = dy.double()
-    xh = (xd - mk) * ik
-    s1, s2 = dyd.sum(0), (dyd * xh).sum(0)
-    a2 = (dyd * xh).abs().sum(0)                                  # the kernel's xhat is fp32((fp32(x - mean)) * invstd): 2u each
-    _assert_within(db.cpu().double(), s1, torch.from_numpy(_ulp(s1.numpy())) + 2.0 ** -45 * dyd.abs().sum(0), "bn1d dbeta")
-    _assert_within(dg.cpu().double(), s2, torch.from_numpy(_ulp(s2.numpy())) + 2 * U * a2, "bn1d dgamma")
-    # dx = sc*(dy - a - xh*b): <= 8u |sc|(|dy| + |a| + |xh b|), plus the kernel's b = s2/N off by <= 2u * sum|dy xh| / N
-    sc = gamma.double() * ik
-    ref = sc * (dyd - s1 / N - xh * (s2 / N))
-    bound = sc.abs() * (8 * U * (dyd.abs() + (s1 / N).abs() + (xh * (s2 / N)).abs()) + xh.abs() * 2 * U * a2 / N)
-    _assert_within(dx.cpu().double(), ref, bound, "bn1d dx")
+    check_bn1d_bwd(dx.cpu(), dg.cpu(), db.cpu(), x, dy, gamma, mk, ik)                 # shared with tests/test_gpu_vit_plan.py
 
 
 @pytest.mark.parametrize("shape", [(500, 2048), (37, 2040)], ids=["500x2048", "37x2040_ragged"])
@@ -629,13 +621,4 @@ def test_layernorm_fwd_vit_plan_size(nn):
     gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
     eps = float(np.float32(1e-6))
     y, mean, rstd = ops_vit.layernorm_fwd(x.cuda(), gamma.cuda(), beta.cuda(), eps=eps)
-    xd = x.double()
-    m64 = xd.mean(1)
-    r64 = 1.0 / torch.sqrt(((xd - m64.unsqueeze(1)) ** 2).mean(1) + eps)
-    dmu = 24 * U * xd.abs().mean(1) + torch.from_numpy(_ulp(m64.numpy()))
-    _assert_within(mean.cpu().double(), m64, dmu, "LayerNorm mean")
-    _assert_within(rstd.cpu().double(), r64, 32 * U * r64, "LayerNorm rstd")
-    xh = (xd - m64.unsqueeze(1)) * r64.unsqueeze(1)
-    ref = xh * gamma.double() + beta.double()
-    E = gamma.double().abs() * (36 * U * xh.abs() + r64.unsqueeze(1) * dmu.unsqueeze(1)) + 4 * U * (beta.double().abs() + ref.abs())
-    _assert_within(y.cpu().double(), ref, HB * ref.abs() + (1 + HB) * E, "LayerNorm y")
+    check_layernorm_fwd(y.cpu(), mean.cpu(), rstd.cpu(), x, gamma, beta, eps)          # the bound above, shared with tests/test_gpu_vit_plan.py
