@@ -50,6 +50,10 @@ _SIGNATURES = {
     "dali_topk_decode": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "dali_pairdist_topk_scratch_bytes": [c_int] * 7,
     "dali_pairdist_topk": [c_void_p] * 6 + [c_int] * 9 + [c_void_p] + [c_int] * 3 + [c_void_p],
+    "dali_mr_kill_transpose": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p],
+    "dali_mr_fit_rows": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "dali_mr_wscore": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "dali_mr_fuse": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "dali_conv2d_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_int, c_void_p],
     "dali_conv2d_bn_act": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_int],
     "dali_stem_fused_supported": [c_int, c_int, c_int],

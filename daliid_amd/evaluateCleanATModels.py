@@ -53,9 +53,12 @@ def fuse_distmats(q_clean, g_clean, q_dist, g_dist, mags_clean=None, mags_dist=N
     return ops_eval.pairdist_blend(distmat, q_dist.contiguous(), g_dist.contiguous(), mags_clean, mags_dist, precision=precision, normalize=True)
 
 
-def validate(queries_images, gallery_images, model_clean, model_distortion, img_height, img_width, gpu_indexes, verbose=True):
+def validate(queries_images, gallery_images, model_clean, model_distortion, img_height, img_width, gpu_indexes, verbose=True,
+             meta_recognition=False):
     """:78-245 in the reference's order: concatenated features, each model alone, simple ensemble, then the
-    magnitude-weighted ensembles for GAP (the paper's number), GMP and GAP+GMP.  -> dict name -> (cmc, mAP)."""
+    magnitude-weighted ensembles for GAP (the paper's number), GMP and GAP+GMP.  -> dict name -> (cmc, mAP).
+    ``meta_recognition`` adds "ensemble_mr": the two models' similarities 1 - d blended by Weibull w-score
+    (Meta_Recognition.mrfuse, evaluate.py:277, 610-627; ops_eval.mr_fuse), ranked as the distance 1 - fused."""
     model_clean.eval(); model_distortion.eval()
     ex = lambda subset, model: extractFeatures(subset, img_height, img_width, model, 500, gpu_index=gpu_indexes[0], keep_on_device=True,
                                                verbose=False)
@@ -73,4 +76,7 @@ def validate(queries_images, gallery_images, model_clean, model_distortion, img_
         gm_c, _ = getWeightsByMagnitude(gallery_images, pooling, img_height, img_width, model_clean, gpu_indexes)
         gm_d, _ = getWeightsByMagnitude(gallery_images, pooling, img_height, img_width, model_distortion, gpu_indexes)
         out["ensemble_" + pooling] = metrics(fuse_distmats(q_c, g_c, q_d, g_d, (qm_c, gm_c), (qm_d, gm_d)))
+    if meta_recognition:
+        sims = [1 - ops_eval.pairdist(q, g, precision=precision, normalize=True) for q, g in ((q_c, g_c), (q_d, g_d))]
+        out["ensemble_mr"] = metrics(1 - ops_eval.mr_fuse(sims))
     return out

@@ -530,3 +530,120 @@ def verification_metrics(distmat, q_pids, g_pids, fars=(1e-1, 1e-2, 1e-3, 1e-4, 
     del scratch
     auc, eer, eer_thr, tar = verification_summary(*curves[0], *curves[1], fars)
     return dict(n_pos=n_pos, n_neg=n_neg, auc=auc, eer=eer, eer_threshold=eer_thr, tar_at_far=tar)
+
+
+# ---- Weibull meta-recognition score fusion (include/daliid.h, dali_mr_*; the reference's libmr / Meta_Recognition, evaluate.py:394-627) ----
+MR_N_MAX = 16384          # longest row the fit kernel keeps in LDS (include/daliid.h, dali_mr_fit_rows)
+
+
+def _mr_matrix(t, name):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError("%s must be a 2-D tensor" % name)
+    if not t.is_cuda or t.dtype != torch.float32:
+        raise _lib.DaliError("%s must be a CUDA float32 tensor" % name)
+    if not t.is_contiguous():
+        raise _lib.DaliError("%s must be contiguous" % name)
+    return t
+
+
+def _mr_kill_transpose(scores, topk, use_columns, killscale):
+    """-> (KT fp32 [ng, nq], status int32 [2] on the device); nothing synchronises."""
+    s = _mr_matrix(scores, "scores")
+    nq, ng = s.shape
+    kt = torch.empty(ng, nq, device=s.device, dtype=torch.float32)
+    status = torch.zeros(2, device=s.device, dtype=torch.int32)
+    _lib.check(_lib.lib().dali_mr_kill_transpose(_lib.ctx(s.device), _lib.stream_ptr(), _lib.ptr(s), nq, ng, int(topk), int(bool(use_columns)),
+                                                  float(killscale), _lib.ptr(kt), _lib.ptr(status)), "dali_mr_kill_transpose")
+    return kt, status
+
+
+def _mr_fit_rows(x, tail, iters=False):
+    """-> (fits fp64 [nrows, 2], small fp32 [nrows], status int32 [2] = {non-finite input, unfit rows}[, iters int32 [nrows]]) on the
+    device; nothing synchronises."""
+    x = _mr_matrix(x, "x")
+    nrows, n = x.shape
+    dev = x.device
+    fits = torch.empty(nrows, 2, device=dev, dtype=torch.float64)
+    small = torch.empty(nrows, device=dev, dtype=torch.float32)
+    status = torch.zeros(2, device=dev, dtype=torch.int32)
+    it = torch.zeros(nrows, device=dev, dtype=torch.int32) if iters else None
+    _lib.check(_lib.lib().dali_mr_fit_rows(_lib.ctx(dev), _lib.stream_ptr(), _lib.ptr(x), nrows, n, int(tail), _lib.ptr(fits), _lib.ptr(small),
+                                           _lib.ptr(it), _lib.ptr(status)), "dali_mr_fit_rows")
+    return (fits, small, status, it) if iters else (fits, small, status)
+
+
+def _mr_check_finite(status, who):
+    if int(status[0]) != 0:
+        raise ValueError("%s: input contains NaN or infinity" % who)
+
+
+def mr_kill_transpose(scores, topk, use_columns=False, killscale=1.0):
+    """Meta_Recognition.metarec's kill (evaluate.py:597-618; include/daliid.h, dali_mr_kill_transpose): the ``topk`` largest entries of
+    every row (``use_columns``: of every column) of the CUDA fp32 similarity matrix [nq, ng] become ``s - killscale * s``, in the order
+    of ``topk_rows(largest=True)``; the result is returned TRANSPOSED, fp32 [ng, nq].  ``scores`` is left unchanged."""
+    kt, status = _mr_kill_transpose(scores, topk, use_columns, killscale)
+    _mr_check_finite(status, "mr_kill_transpose")
+    return kt
+
+
+def mr_fit_rows(x, tail, return_iters=False):
+    """libmr.FitHigh (evaluate.py:444-447 -> :487-505 -> :541-590; include/daliid.h, dali_mr_fit_rows): a Weibull fitted by maximum
+    likelihood to the ``tail`` largest values of every row of the CUDA fp32 matrix x [nrows, n].  -> (fits fp64 [nrows, 2] = (shape, scale),
+    small fp32 [nrows] = the tail-th largest value, n_unfit[, iters int32 [nrows]]).  Unfit rows hold (NaN, NaN)."""
+    out = _mr_fit_rows(x, tail, iters=return_iters)
+    _mr_check_finite(out[2], "mr_fit_rows")
+    return (out[0], out[1], int(out[2][1])) + ((out[3],) if return_iters else ())
+
+
+def mr_wscore(scores, fits, small):
+    """libmr.wscore (evaluate.py:449-485; include/daliid.h, dali_mr_wscore): fp64 [nq, ng] Weibull CDF of every score under its
+    column's fit; exactly 0 at or below the column's ``small - 1`` and for an unfit column."""
+    s = _mr_matrix(scores, "scores")
+    nq, ng = s.shape
+    if tuple(fits.shape) != (ng, 2) or small.numel() != ng:
+        raise ValueError("mr_wscore: fits %s / small %s do not fit %d columns" % (tuple(fits.shape), tuple(small.shape), ng))
+    out = torch.empty(nq, ng, device=s.device, dtype=torch.float64)
+    _lib.check(_lib.lib().dali_mr_wscore(_lib.ctx(s.device), _lib.stream_ptr(), _lib.ptr(s), nq, ng, _lib.ptr(fits, torch.float64, "fits"),
+                                         _lib.ptr(small.reshape(-1), torch.float32, "small"), _lib.ptr(out)), "dali_mr_wscore")
+    return out
+
+
+def mr_fuse_fitted(score_list, fits_list, small_list, out_dtype=torch.float32):
+    """dali_mr_fuse on fitted columns: sum_a w_a s_a / sum_a w_a over 1 .. 3 models, the w-scores never stored; the plain mean where
+    every w is 0.  fp64, or rounded once to fp32."""
+    m = len(score_list)
+    if not 1 <= m <= 3 or len(fits_list) != m or len(small_list) != m:
+        raise ValueError("mr_fuse: 1 .. 3 models with one fit table each, got %d" % m)
+    if out_dtype not in (torch.float32, torch.float64):
+        raise ValueError("mr_fuse: out_dtype must be torch.float32 or torch.float64")
+    ss = [_mr_matrix(s, "scores[%d]" % a) for a, s in enumerate(score_list)]
+    nq, ng = ss[0].shape
+    dev = ss[0].device
+    smalls = [sm.reshape(-1) for sm in small_list]
+    for s, f, sm in zip(ss, fits_list, smalls):
+        if tuple(s.shape) != (nq, ng) or s.device != dev or tuple(f.shape) != (ng, 2) or sm.numel() != ng:
+            raise ValueError("mr_fuse: the score matrices and fit tables do not have one shape")
+    arr = lambda ts, dt, name: (_lib.c_void_p * m)(*[_lib.ptr(t, dt, name).value for t in ts])
+    out = torch.empty(nq, ng, device=dev, dtype=out_dtype)
+    _lib.check(_lib.lib().dali_mr_fuse(_lib.ctx(dev), _lib.stream_ptr(), arr(ss, torch.float32, "scores"), arr(fits_list, torch.float64, "fits"),
+                                       arr(smalls, torch.float32, "small"), m, nq, ng, int(out_dtype == torch.float64), _lib.ptr(out)),
+               "dali_mr_fuse")
+    return out
+
+
+def mr_fuse(score_list, topk=20, use_columns=False, killscale=1.0, out_dtype=torch.float32):
+    """Meta_Recognition.mrfuse (evaluate.py:620-637) generalised to 1 .. 3 CUDA fp32 similarity matrices [nq, ng]: per model kill ->
+    fit every gallery column with tail nq - topk - 1 -> w-score weighted blend (include/daliid.h, dali_mr_*).  One read of the status
+    words at the end; a non-finite score raises ValueError."""
+    if not 1 <= len(score_list) <= 3:
+        raise ValueError("mr_fuse: 1 .. 3 models, got %d" % len(score_list))
+    fits, smalls, stats = [], [], []
+    for s in score_list:
+        kt, st0 = _mr_kill_transpose(s, topk, use_columns, killscale)
+        f, sm, st1 = _mr_fit_rows(kt, kt.shape[1] - int(topk) - 1)
+        del kt
+        fits.append(f); smalls.append(sm); stats += [st0, st1]
+    out = mr_fuse_fitted(score_list, fits, smalls, out_dtype)
+    if stats and int(torch.stack(stats)[:, 0].max()) != 0:
+        raise ValueError("mr_fuse: input contains NaN or infinity")
+    return out

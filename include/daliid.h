@@ -210,6 +210,53 @@ int dali_pairdist_topk(dali_ctx* ctx, void* stream, const void* q_image, const f
                        int nq, int ng, int d, int metric, int precision, int k, int largest, int g_offset, int accumulate,
                        int64_t* keys, int boot_cols, int chunk_cols, int cand_cap, int32_t* stats);
 
+/* Weibull meta-recognition score fusion: libmr.FitHigh / libmr.wscore and Meta_Recognition.metarec / mrfuse (evaluate.py:394-627), the
+ * `1.0 - meta_rec.mrfuse(1 - d_backbone, 1 - d_head01, 1 - d_head02)` line evaluate.py:277 leaves commented out.  Every gallery column of a
+ * similarity matrix gets a Weibull fitted by maximum likelihood to the tail of its scores, a score becomes its w-score (the Weibull CDF),
+ * and up to three models' matrices are blended by w-score weight.  Inputs are fp32 device matrices of FINITE scores, larger = more
+ * similar, row-major S [nq][ng].  A non-finite score sets status[0] = 1 in the two calls that take a status (results are then
+ * unspecified; nothing faults).  fl32(.) is one rounding to fp32; everything else below is fp64.
+ *   dali_mr_kill_transpose  (metarec :597-618) use_columns == 0: in every row of S the topk largest entries -- THE ORDER of dali_topk_rows
+ *                    with `largest`: descending value, exact ties by ascending index -- become fl32(s - fl32((float)killscale * s)), +0 at
+ *                    killscale = 1.  use_columns != 0: the same for every column over its nq rows (dali_topk_rows on the rows of the
+ *                    transposed copy).  Either way the result is written transposed, KT [ng][nq]: a gallery column is a contiguous row.
+ *                    S is left unchanged.  status [1] int32.
+ *   dali_mr_fit_rows (FitHigh -> _weibullFitting -> _fit :444-447, :487-505, :541-590, translateAmount = 1) for every row of x [nrows][n]
+ *                    and a tail size T (metarec: x = KT, n = nq, T = nq - topk - 1):
+ *                      tail: the n - T + 1 smallest keys of the row (dali_topk_rows, largest = 0); the last of them is the boundary key,
+ *                            small_r its element's value (the T-th largest value), and the tail is every element whose (value, index)
+ *                            key is >= the boundary key: exactly T elements, ties included;
+ *                      terms: x_t = fl32(fl32(v_t + 1) - small_r), L_t = log((double)x_t), l_t = (double)fl32(L_t)  (the reference takes
+ *                            the logarithm in fp32 and the power in fp64);
+ *                      Newton: k = 1; at most 100 times: e_t = exp(k L_t), fg = sum e_t, ff = sum e_t l_t, ff' = sum (e_t l_t) l_t,
+ *                            f = ff/fg - (sum l_t)/T - 1/k, f' = ff'/fg - (ff/fg)^2 + 1/k^2, k_new = k - f/f'; if |k_new - k| < 1e-6:
+ *                            shape = k_new, scale = ((sum exp(k_new L_t))/T)^(1/k_new), stop; else k = k_new.
+ *                    Every row stops on its own (the reference's global loop keeps stepping finished rows, which by quadratic convergence
+ *                    moves k by less than 1e-11).  A row that does not stop within 100 steps, or meets a non-finite f, f' or k_new, is
+ *                    UNFIT: (shape, scale) = (NaN, NaN), counted in status[1].  The reference leaves such rows with (0, 0) or NaN and
+ *                    their w-score is then an accident of pow (0.5 for a constant column); here an unfit column has w-score 0, i.e. no
+ *                    weight in the fusion.  Outputs: fits [nrows][2] fp64 (shape, scale), small [nrows] fp32, iters [nrows] int32
+ *                    (nullable: Newton steps taken), status [2] int32 = {non-finite input, unfit rows}.
+ *   dali_mr_wscore   (wscore :449-485) out [nq][ng] fp64: d = max(fl32(fl32(S[i][j] + 1) - small_j), 0),
+ *                    w = 1 - exp(-pow((double)d / scale_j, shape_j)); d == 0 gives exactly 0 and so does an unfit column.
+ *   dali_mr_fuse     (mrfuse :620-637) m = 1 .. 3 models; scores_host / fits_host / small_host are HOST arrays of m device pointers
+ *                    (S_a [nq][ng], fits_a [ng][2], small_a [ng]).  out[i][j] = (sum_a w_a (double)s_a) / (sum_a w_a), summed in model
+ *                    order, the w-scores computed in the same kernel and never stored; written as fp64 (out_fp64 != 0) or rounded once
+ *                    to fp32.  Where sum_a w_a == 0 exactly the output is the plain mean (sum_a (double)s_a) / m: the reference gives
+ *                    0/0 = NaN there, which would poison a ranking.
+ * Preconditions (DALI_ERR_INVALID otherwise): topk >= 1, nq >= topk + 2, ng >= topk when use_columns == 0; 1 <= T <= n.  Limits
+ * (DALI_ERR_LIMIT): topk <= 128; n - T + 1 <= 128 (the dali_topk_rows cap; metarec: topk <= 126); n <= 16384 (a row's L_t stay in LDS
+ * across the Newton steps: 128 KiB of the CU's 160).  Workspace, from the context: the selections' keys only, max(nq or ng rows) * topk
+ * * 8 bytes for the kill and nrows * (n - T + 1) * 8 for the fit; KT is the caller's.  Enqueued on `stream`, nothing synchronises; all
+ * sums run in a fixed order and the only atomic is the integer count of unfit rows: bitwise identical results run to run. */
+int dali_mr_kill_transpose(dali_ctx* ctx, void* stream, const float* S, int nq, int ng, int topk, int use_columns, double killscale,
+                           float* KT, int32_t* status);
+int dali_mr_fit_rows(dali_ctx* ctx, void* stream, const float* x, int nrows, int n, int tail, double* fits, float* small_out,
+                     int32_t* iters, int32_t* status);
+int dali_mr_wscore(dali_ctx* ctx, void* stream, const float* S, int nq, int ng, const double* fits, const float* small_in, double* out);
+int dali_mr_fuse(dali_ctx* ctx, void* stream, const float* const* scores_host, const double* const* fits_host,
+                 const float* const* small_host, int m, int nq, int ng, int out_fp64, void* out);
+
 /* ---- training path: Encoders.ResNet50ReID trunk (Encoders.py:330-339) ----------------------------- *
  * Single-op entry points (the parity tests call these; the net plan below chains the same kernels).
  * Layouts: activations NHWC bf16; forward weights [cout][r][s][cin] bf16; dgrad weights
