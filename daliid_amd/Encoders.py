@@ -22,7 +22,7 @@ import ctypes
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, ops_nn
 
 
 class _Cfg(ctypes.Structure):
@@ -85,6 +85,16 @@ class _NetFn(torch.autograd.Function):
 
 
 _FEATURE_MODES = {"both": 0, "gap": 1, "gmp": 2}        # dali_feature in include/daliid.h
+
+
+def default_parts(map_rows):
+    """Row ranges (upper, middle, lower) of a ``map_rows``-row layer4 map: ``((0, R//2), (R//4, R//4 + R//2), (R//2, R))``.  At the
+    reference's 16-row map (256-row images) these are exactly its slices ``:8``, ``4:12`` and ``8:`` (mainKIT.py:252-254).  The reference
+    hard-codes those three slices whatever the image height; the proportional split for other heights is this project's choice."""
+    R = int(map_rows)
+    if R < 2:
+        raise _lib.DaliError("default_parts: a map of %d row(s) has no upper / middle / lower parts (at least 2 rows)" % R)
+    return (0, R // 2), (R // 4, R // 4 + R // 2), (R // 2, R)
 
 
 class ResNet50ReID(nn.Module):
@@ -241,6 +251,37 @@ class ResNet50ReID(nn.Module):
             self._bwd_plan = plan
         return emb
 
+    def _eval_only(self, what):
+        if self.training:
+            raise _lib.DaliError("%s is an inference output (running statistics); call .eval() first" % what)
+
+    def head_map(self, height, width, batch=1):
+        """(rows, columns) of the layer4 map for images of height x width: what the row ranges of ``forward_heads`` count."""
+        h, w = ctypes.c_int(), ctypes.c_int()
+        _lib.check(_lib.lib().dali_resnet_head_map(self._plan(batch, height, width).h, ctypes.byref(h), ctypes.byref(w)), "dali_resnet_head_map")
+        return h.value, w.value
+
+    def forward_heads(self, x, heads, heatmap=False):
+        """Several heads from ONE trunk pass (dali_resnet_forward_heads), eval mode only, no autograd graph.
+        ``heads``: sequence of ``(mode_name, rows)``, mode_name "both" | "gap" | "gmp", rows ``None`` (the whole map) or ``(row_begin, row_end)``
+        of the layer4 map (``head_map`` / ``default_parts``).  -> ``[n_heads, B, feat_dim]`` fp32, every head through ``last_bn``; with
+        ``heatmap=True`` also the channel-sum activation map ``[B, Hm, Wm]``.  A whole-map head equals ``forward`` under
+        ``feature = mode_name`` bit for bit.  ``self.feature`` is neither read nor changed."""
+        self._eval_only("forward_heads")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise _lib.DaliError("expected images [B,3,H,W], got %s" % (tuple(x.shape),))
+        specs, nh = ops_nn.head_specs(heads)
+        with torch.no_grad():
+            x = x.to(device=self._device, dtype=torch.float32).contiguous()
+            plan = self._plan(x.shape[0], x.shape[2], x.shape[3])
+            self._activate(plan)
+            emb = torch.empty(nh, x.shape[0], plan.feat_dim, device=self._device, dtype=torch.float32)
+            heat = torch.empty((x.shape[0],) + self.head_map(x.shape[2], x.shape[3], x.shape[0]), device=self._device,
+                               dtype=torch.float32) if heatmap else None
+            _lib.check(_lib.lib().dali_resnet_forward_heads(plan.h, _lib.stream_ptr(), _lib.ptr(x), specs, nh, _lib.ptr(emb), _lib.ptr(heat)),
+                       "dali_resnet_forward_heads")
+        return (emb, heat) if heatmap else emb
+
     n_bwd_stages = 4          # 0: neck + head + layer4, 1: layer3, 2: layer2, 3: layer1 + stem (dali_resnet_backward)
 
     def _run_backward(self, d_emb):
@@ -275,7 +316,17 @@ class ResNet50ReID(nn.Module):
         return self._arena[off:off + nbytes.value].view(dtype).view(*shape).clone()
 
     # ---- nn.Module protocol -----------------------------------------------------------------------------
-    def forward(self, x):
+    def forward(self, x, multipart=False, attention_map=False):
+        """``multipart``: (upper, middle, lower, whole), each max-pooled over its rows (``default_parts``) and passed through ``last_bn``, whatever
+        ``self.feature`` says (mainKIT.py:251-292).  ``attention_map``: the channel-sum map [Hm, Wm] of image 0 (mainKIT.py:294-298).  Both are
+        eval-only; with both set, the parts are returned, as in the reference."""
+        if multipart:
+            self._eval_only("forward(multipart=True)")
+            parts = default_parts(self.head_map(x.shape[2], x.shape[3], x.shape[0])[0])
+            return tuple(self.forward_heads(x, [("gmp", rows) for rows in parts] + [("gmp", None)]))
+        if attention_map:
+            self._eval_only("forward(attention_map=True)")
+            return self.forward_heads(x, [("gmp", None)], heatmap=True)[1][0]
         if self.training and torch.is_grad_enabled():
             return _NetFn.apply(x, self._anchor, self)
         return self._run_forward(x, training=self.training)

@@ -74,6 +74,8 @@ _SIGNATURES = {
     "dali_maxpool_bn_bwd": [c_void_p] * 8 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p],
     "dali_head_pool_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "dali_head_pool_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "dali_head_pool_multi": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p],
+    "dali_channel_sum": [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p],
     "dali_bn1d_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
                       c_void_p, c_void_p, c_void_p],
     "dali_bn1d_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 6,
@@ -122,6 +124,8 @@ _SIGNATURES = {
     "dali_resnet_bind": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t],
     "dali_resnet_refresh_weights": [c_void_p, c_void_p],
     "dali_resnet_forward": [c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "dali_resnet_head_map": [c_void_p, c_void_p, c_void_p],
+    "dali_resnet_forward_heads": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "dali_resnet_backward": [c_void_p, c_void_p, c_void_p, c_int, c_int],
     "dali_resnet_debug_tensor": [c_void_p, ctypes.c_char_p, c_void_p, c_void_p],
     "dali_vit_create": [c_void_p, c_void_p, ctypes.POINTER(c_void_p)],

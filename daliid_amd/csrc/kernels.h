@@ -172,6 +172,11 @@ int launch_maxpool_bn_bwd(hipStream_t st, const uint16_t* dp, const uint8_t* arg
 int launch_head_pool_fwd(hipStream_t st, const uint16_t* x, int N, int HW, int C, int mode, float* f, int16_t* arg);
 // ybits (nullable): ReLU mask of the tensor the gradient belongs to; the masked gradient dz = dy * (y > 0) is what is written
 int launch_head_pool_bwd(hipStream_t st, const float* df, const int16_t* arg, int N, int HW, int C, int mode, uint16_t* dx, const uint8_t* ybits = nullptr);
+// n_heads heads from one read of x [N][H][W][C]: f [n_heads][N][C]; validates the specs (DALI_ERR_INVALID before any launch), as
+// check_head_specs does alone
+int check_head_specs(const dali_head_spec* heads, int n_heads, int H, int W);
+int launch_head_pool_multi(hipStream_t st, const uint16_t* x, int N, int H, int W, int C, const dali_head_spec* heads, int n_heads, float* f);
+int launch_channel_sum(hipStream_t st, const uint16_t* x, int64_t rows, int C, float* out);
 int launch_bn1d_fwd(hipStream_t st, const float* x, int N, int C, const float* gamma, const float* beta, float* rm, float* rv, int training,
                     float momentum, float eps, float* y, float* mean, float* invstd);
 int launch_bn1d_bwd(hipStream_t st, const float* x, const float* dy, int N, int C, const float* gamma, const float* mean, const float* invstd,

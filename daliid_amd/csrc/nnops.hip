@@ -574,6 +574,92 @@ __global__ __launch_bounds__(256) void head_pool_bwd_kernel(const float* __restr
     }
 }
 
+// Several heads from ONE read of the map (inference outputs: no argmax).  Head i pools the pixels of its range -- whole rows of the map --
+// by its mode into f[i][n][c].  The launcher hands over the DISTINCT ranges (the three poolings of the whole map are one range, the body
+// parts one each): range r keeps its own sum and maximum per channel, never built from another range's partial sums, with pixels going to
+// lanes and lanes being combined exactly as in head_pool_fwd_kernel.  A head over every row therefore goes through the very additions of
+// head_pool_fwd_kernel and agrees with it bit for bit (only a maximum of zero may differ in its sign: no index is kept to break the tie of
+// -0 and +0).  A lane that sees no pixel of a range keeps sum 0 and maximum -inf, which change nothing in the combination.
+struct HeadRanges {
+    int n_heads, mode[DALI_MAX_HEADS], range[DALI_MAX_HEADS];          // per head: dali_feature, index of its range
+    int pix_begin[DALI_MAX_HEADS], pix_end[DALI_MAX_HEADS];           // per range
+};
+template <int NR>
+__global__ __launch_bounds__(256) void head_pool_multi_kernel(const uint16_t* __restrict__ x, int N, int HW, int C, HeadRanges hr,
+                                                               float* __restrict__ f) {
+    const int cpr = C >> 3;
+    const int item = (blockIdx.x * 256 + threadIdx.x) >> 3, sub = threadIdx.x & 7;
+    const bool live = item < N * cpr;
+    const int cc = live ? (item % cpr) * 8 : 0, n = live ? item / cpr : 0;
+    float sum[NR][8], best[NR][8];
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) { sum[r][t] = 0.f; best[r][t] = -__builtin_inff(); }
+    if (live)
+        for (int p = sub; p < HW; p += 8) {
+            float v[8];
+            unpack8(*reinterpret_cast<const uint4*>(x + ((size_t)n * HW + p) * C + cc), v);
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+                if (p >= hr.pix_begin[r] && p < hr.pix_end[r]) {
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) { sum[r][t] += v[t]; if (v[t] > best[r][t]) best[r][t] = v[t]; }
+                }
+        }
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1)
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                sum[r][t] += __shfl_xor(sum[r][t], o, 64);
+                const float ob = __shfl_xor(best[r][t], o, 64);
+                if (ob > best[r][t]) best[r][t] = ob;
+            }
+    if (live && sub == 0)
+        for (int h = 0; h < hr.n_heads; ++h) {
+            const int mode = hr.mode[h];
+            float* dst = f + ((size_t)h * N + n) * C + cc;
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+                if (hr.range[h] == r) {
+                    const float count = (float)(hr.pix_end[r] - hr.pix_begin[r]);
+                    float o8[8];
+#pragma unroll
+                    for (int t = 0; t < 8; ++t)
+                        o8[t] = (mode == DALI_FEATURE_GMP ? 0.f : sum[r][t] / count) + (mode == DALI_FEATURE_GAP ? 0.f : best[r][t]);
+                    *reinterpret_cast<float4*>(dst) = make_float4(o8[0], o8[1], o8[2], o8[3]);
+                    *reinterpret_cast<float4*>(dst + 4) = make_float4(o8[4], o8[5], o8[6], o8[7]);
+                }
+        }
+}
+
+// out[r] = sum_c x[r][c] (torch.sum(x, dim=1) of an NHWC map): one wave per pixel.  Lane l owns the 16-byte chunks l, l + 64, ... of the
+// pixel's C channels and loads four of them before it adds the first (C = 2048: the whole row in flight); it adds chunk by chunk, channel
+// by channel, and the 64 lane sums meet in the xor shuffles: a fixed order, no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void channel_sum_kernel(const uint16_t* __restrict__ x, long long rows, int C, float* __restrict__ out) {
+    const int cpr = C >> 3, lane = threadIdx.x & 63;
+    for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (long long)gridDim.x * 4) {
+        const uint4* row = reinterpret_cast<const uint4*>(x + (size_t)r * C);
+        float s = 0.f;
+        for (int c0 = lane; c0 < cpr; c0 += 256) {
+            uint4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = c0 + 64 * k < cpr ? row[c0 + 64 * k] : make_uint4(0u, 0u, 0u, 0u);      // (+0 adds nothing)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float f8[8];
+                unpack8(v[k], f8);
+#pragma unroll
+                for (int t = 0; t < 8; ++t) s += f8[t];
+            }
+        }
+        s = wave_sum(s);
+        if (lane == 0) out[r] = s;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // BatchNorm1d neck on fp32 [N,C].
 // ------------------------------------------------------------------------------------------------
@@ -882,6 +968,52 @@ int launch_head_pool_bwd(hipStream_t st, const float* df, const int16_t* arg, in
     DALI_LAUNCH_CHECK();
     return DALI_OK;
 }
+// The specs of a multi-head pooling over a map of H rows and W columns -> the kernel's argument: the distinct ranges and, per head, its range
+// and mode.  DALI_ERR_INVALID for what include/daliid.h lists (counts, ranges, modes)
+static int head_ranges(const dali_head_spec* heads, int n_heads, int H, int W, HeadRanges* out, int* n_ranges) {
+    DALI_REQUIRE(n_heads >= 1 && n_heads <= DALI_MAX_HEADS, "head_pool_multi: %d heads (1 .. %d)", n_heads, DALI_MAX_HEADS);
+    DALI_REQUIRE(H >= 1 && W >= 1 && (long long)H * W < 32768, "head_pool_multi: bad map %d x %d (fewer than 32768 pixels)", H, W);
+    HeadRanges hr{};
+    hr.n_heads = n_heads;
+    *n_ranges = 0;
+    for (int i = 0; i < n_heads; ++i) {
+        const dali_head_spec& s = heads[i];
+        DALI_REQUIRE(s.mode >= DALI_FEATURE_BOTH && s.mode <= DALI_FEATURE_GMP, "head_pool_multi: head %d: bad feature mode %d", i, s.mode);
+        const bool whole = s.row_begin == 0 && s.row_end == 0;
+        DALI_REQUIRE(whole || (s.row_begin >= 0 && s.row_begin < s.row_end && s.row_end <= H), "head_pool_multi: head %d: rows [%d, %d) of a %d-row map", i,
+                     s.row_begin, s.row_end, H);
+        const int pb = s.row_begin * W, pe = (whole ? H : s.row_end) * W;
+        int r = 0;
+        while (r < *n_ranges && (hr.pix_begin[r] != pb || hr.pix_end[r] != pe)) ++r;
+        if (r == *n_ranges) { hr.pix_begin[r] = pb; hr.pix_end[r] = pe; ++*n_ranges; }
+        hr.mode[i] = s.mode; hr.range[i] = r;
+    }
+    *out = hr;
+    return DALI_OK;
+}
+int check_head_specs(const dali_head_spec* heads, int n_heads, int H, int W) {
+    HeadRanges hr;
+    int n_ranges;
+    return head_ranges(heads, n_heads, H, W, &hr, &n_ranges);
+}
+int launch_head_pool_multi(hipStream_t st, const uint16_t* x, int N, int H, int W, int C, const dali_head_spec* heads, int n_heads, float* f) {
+    HeadRanges hr;
+    int n_ranges;
+    if (int rc = head_ranges(heads, n_heads, H, W, &hr, &n_ranges)) return rc;
+    DALI_REQUIRE(N >= 1 && C >= 8 && C % 8 == 0, "head_pool_multi: bad shape %dx%dx%dx%d (C %% 8)", N, H, W, C);
+    if ((long long)N * C >= (1ll << 31)) { set_error("head_pool_multi: more than 2^31 outputs per head"); return DALI_ERR_LIMIT; }
+    using Kernel = void (*)(const uint16_t*, int, int, int, HeadRanges, float*);
+    static const Kernel kernels[DALI_MAX_HEADS] = {head_pool_multi_kernel<1>, head_pool_multi_kernel<2>, head_pool_multi_kernel<3>, head_pool_multi_kernel<4>,
+                                                   head_pool_multi_kernel<5>, head_pool_multi_kernel<6>, head_pool_multi_kernel<7>, head_pool_multi_kernel<8>};
+    hipLaunchKernelGGL(kernels[n_ranges - 1], dim3((N * (C / 8) * 8 + 255) / 256), dim3(256), 0, st, x, N, H * W, C, hr, f);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+int launch_channel_sum(hipStream_t st, const uint16_t* x, int64_t rows, int C, float* out) {
+    hipLaunchKernelGGL(channel_sum_kernel, dim3(grid_for((size_t)rows * 64)), dim3(256), 0, st, x, (long long)rows, C, out);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
 int launch_bn1d_fwd(hipStream_t st, const float* x, int N, int C, const float* gamma, const float* beta, float* rm, float* rv, int training,
                     float momentum, float eps, float* y, float* mean, float* invstd) {
     hipLaunchKernelGGL(bn1d_fwd_kernel, dim3((C + 31) / 32), dim3(256), 0, st, x, N, C, gamma, beta, rm, rv, training, momentum, eps, y, mean, invstd);
@@ -1009,6 +1141,16 @@ extern "C" int dali_head_pool_bwd(dali_ctx* ctx, void* stream, const float* df, 
     DALI_REQUIRE(mode >= DALI_FEATURE_BOTH && mode <= DALI_FEATURE_GMP, "dali_head_pool_bwd: bad feature mode %d", mode);
     DALI_REQUIRE(C % 8 == 0 && hw > 0, "dali_head_pool_bwd: bad shape");
     return launch_head_pool_bwd((hipStream_t)stream, df, arg, n, hw, C, mode, dx);
+}
+extern "C" int dali_head_pool_multi(dali_ctx* ctx, void* stream, const uint16_t* x, int n, int h, int w, int C, const dali_head_spec* heads, int n_heads,
+                                    float* f) {
+    DALI_REQUIRE(ctx && x && heads && f, "dali_head_pool_multi: null argument");
+    return launch_head_pool_multi((hipStream_t)stream, x, n, h, w, C, heads, n_heads, f);
+}
+extern "C" int dali_channel_sum(dali_ctx* ctx, void* stream, const uint16_t* x, int64_t rows, int C, float* out) {
+    DALI_REQUIRE(ctx && x && out, "dali_channel_sum: null argument");
+    DALI_REQUIRE(rows >= 1 && C >= 8 && C % 8 == 0, "dali_channel_sum: bad shape %lld x %d (C %% 8)", (long long)rows, C);
+    return launch_channel_sum((hipStream_t)stream, x, rows, C, out);
 }
 // Diagnostic (include/daliid_debug.h): the same launcher with the ReLU mask bits of the tensor the gradient belongs to, as the net plan calls it
 extern "C" int dali_debug_head_pool_bwd_masked(dali_ctx* ctx, void* stream, const float* df, const int16_t* arg, int n, int hw, int C, int mode,

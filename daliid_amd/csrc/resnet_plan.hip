@@ -79,6 +79,7 @@ struct dali_resnet : PlanTable {
     double* red_scratch = nullptr;
     int16_t* head_arg = nullptr;
     uint16_t* gbuf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t gbuf_bytes = 0;                   // of each; they are reserved back to back: gbuf[0] heads one region of 6 * gbuf_bytes
     uint16_t* wbf16_flat = nullptr;          // bf16 cast of the whole flat parameter buffer
     // bound storages
     float *P = nullptr, *G = nullptr, *B = nullptr;
@@ -271,7 +272,8 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
     net->reserve(net->cs_partial, max_cs);
     net->reserve(net->stem_dw_pad, (size_t)wb * 224 * 4);
     net->reserve(net->red_scratch, reduce_scratch_bytes(net->feat_dim, 3));
-    for (int i = 0; i < 6; ++i) net->reserve(net->gbuf[i], max_act);
+    net->gbuf_bytes = align_up(max_act, 256);
+    for (int i = 0; i < 6; ++i) net->reserve(net->gbuf[i], net->gbuf_bytes);
     *out = net;
     return DALI_OK;
 }
@@ -502,10 +504,10 @@ extern "C" int dali_resnet_set_feature(dali_resnet* net, int mode) {
     return DALI_OK;
 }
 
-extern "C" int dali_resnet_forward(dali_resnet* net, void* stream, const float* images, int training, float* emb) {
-    DALI_REQUIRE(net && net->P && images && emb, "dali_resnet_forward: null argument or net not bound");
-    hipStream_t st = (hipStream_t)stream;
-    const bool tr = training != 0;
+namespace {
+
+// The trunk of a forward: (inference) every BatchNorm's coefficients, the stem and the blocks.  -> the layer4 map, bf16 [N][head_hw][feat_dim]
+int trunk_forward(dali_resnet* net, hipStream_t st, const float* images, bool tr, const uint16_t** map) {
     net->fwd_training = tr;
     int rc;
     if (!tr) {                                               // inference: every BatchNorm's scale / shift from the running statistics, one launch
@@ -521,10 +523,51 @@ extern "C" int dali_resnet_forward(dali_resnet* net, void* stream, const float* 
         if ((rc = block_forward(net, st, b, x, tr))) return rc;
         x = b.y;
     }
+    *map = x;
+    return DALI_OK;
+}
+
+}  // namespace
+
+extern "C" int dali_resnet_forward(dali_resnet* net, void* stream, const float* images, int training, float* emb) {
+    DALI_REQUIRE(net && net->P && images && emb, "dali_resnet_forward: null argument or net not bound");
+    hipStream_t st = (hipStream_t)stream;
+    const bool tr = training != 0;
+    const uint16_t* x;
+    int rc;
+    if ((rc = trunk_forward(net, st, images, tr, &x))) return rc;
     // ---- head: avg-pool + max-pool, BatchNorm1d ----
     if ((rc = launch_head_pool_fwd(st, x, net->N, net->head_hw, net->feat_dim, net->feature_mode, net->feat, net->head_arg))) return rc;
     const BnParams p = bn_params(net, net->neck);
     return launch_bn1d_fwd(st, net->feat, net->N, net->feat_dim, p.gamma, p.beta, p.rm, p.rv, tr ? 1 : 0, 0.1f, 1e-5f, emb, net->neck_mean, net->neck_invstd);
+}
+
+extern "C" int dali_resnet_head_map(dali_resnet* net, int* h, int* w) {
+    DALI_REQUIRE(net && h && w, "dali_resnet_head_map: null argument");
+    *h = net->blocks.back().hout; *w = net->blocks.back().wout;
+    return DALI_OK;
+}
+
+// Inference with several heads from one trunk pass: the pooled values of every head in one launch ([n_heads][N][feat_dim]), the neck by the
+// running statistics over the n_heads * N rows at once (an affine map per element: each row gets what dali_resnet_forward gives it), and the
+// channel sums of the map when asked for.  Neither the neck's saved statistics nor feature_mode are touched.  The pooled values take no
+// arena of their own: they lie in the backward's gradient buffers (gbuf[0..5], one region), which no forward uses.
+extern "C" int dali_resnet_forward_heads(dali_resnet* net, void* stream, const float* images, const dali_head_spec* heads, int n_heads, float* emb,
+                                         float* heat) {
+    DALI_REQUIRE(net && net->P && images && heads && emb, "dali_resnet_forward_heads: null argument or net not bound");
+    hipStream_t st = (hipStream_t)stream;
+    const Block& last = net->blocks.back();
+    const uint16_t* x;
+    int rc;
+    if ((rc = check_head_specs(heads, n_heads, last.hout, last.wout))) return rc;       // before anything runs
+    float* pooled = reinterpret_cast<float*>(net->gbuf[0]);
+    DALI_REQUIRE((size_t)n_heads * net->N * net->feat_dim * 4 <= 6 * net->gbuf_bytes, "dali_resnet_forward_heads: %d heads do not fit the plan's scratch", n_heads);
+    if ((rc = trunk_forward(net, st, images, false, &x))) return rc;
+    if ((rc = launch_head_pool_multi(st, x, net->N, last.hout, last.wout, net->feat_dim, heads, n_heads, pooled))) return rc;
+    const BnParams p = bn_params(net, net->neck);
+    if ((rc = launch_bn1d_fwd(st, pooled, n_heads * net->N, net->feat_dim, p.gamma, p.beta, p.rm, p.rv, 0, 0.1f, 1e-5f, emb, nullptr, nullptr)))
+        return rc;
+    return heat ? launch_channel_sum(st, x, (int64_t)net->N * net->head_hw, net->feat_dim, heat) : DALI_OK;
 }
 
 // Every block receives and hands on the MASKED gradient dz = dL/dy * (y > 0) (the gradient in front of the block's final ReLU): the

@@ -24,6 +24,22 @@ def getWeightsByMagnitude(subset, pooling, img_height, img_width, model, gpu_ind
     return norms[:, None], unit
 
 
+POOLINGS = ("both", "gap", "gmp")
+
+
+def _magnitudes(fvs):
+    """-> (norms [N,1], unit rows) of un-normalised features, as getWeightsByMagnitude takes them."""
+    unit, norms = ops_eval.l2norm_rows(fvs.contiguous(), 0.0, return_norms=True)
+    return norms[:, None], unit
+
+
+def getWeightsByMagnitudeAll(subset, img_height, img_width, model, gpu_indexes):
+    """getWeightsByMagnitude for the three poolings from ONE pass over ``subset`` (extractFeatures(features=...)): -> dict pooling ->
+    (norms [N,1], unit rows), each what getWeightsByMagnitude(subset, pooling, ...) returns.  ``model.module.feature`` is not touched."""
+    fvs = extractFeatures(subset, img_height, img_width, model, 500, gpu_index=gpu_indexes[0], keep_on_device=True, verbose=False, features=POOLINGS)
+    return {pooling: _magnitudes(fvs[pooling]) for pooling in POOLINGS}
+
+
 def calculateMetrics(queries_images, gallery_images, distmat, pooling=None, version=None, verbose=True):
     """:259-276: market1501 CMC / mAP of a distance matrix, ranks 1/5/10/20 printed.  With ``pooling`` truthy, :276-292 as well: the
     exact ROC over every query-gallery pair (ops_eval.roc_curve, bitwise sklearn's roc_curve) saved as FPR_<version>.npy,
@@ -57,13 +73,16 @@ def validate(queries_images, gallery_images, model_clean, model_distortion, img_
              meta_recognition=False):
     """:78-245 in the reference's order: concatenated features, each model alone, simple ensemble, then the
     magnitude-weighted ensembles for GAP (the paper's number), GMP and GAP+GMP.  -> dict name -> (cmc, mAP).
+    Every (model, subset) is extracted ONCE: the three poolings of a batch leave one trunk pass (extractFeatures(features=...)), where the
+    reference forwards each of them four times (:96-100 and once per getWeightsByMagnitude call, :128-153).
     ``meta_recognition`` adds "ensemble_mr": the two models' similarities 1 - d blended by Weibull w-score
     (Meta_Recognition.mrfuse, evaluate.py:277, 610-627; ops_eval.mr_fuse), ranked as the distance 1 - fused."""
     model_clean.eval(); model_distortion.eval()
     ex = lambda subset, model: extractFeatures(subset, img_height, img_width, model, 500, gpu_index=gpu_indexes[0], keep_on_device=True,
-                                               verbose=False)
-    q_c, q_d = ex(queries_images, model_clean), ex(queries_images, model_distortion)
-    g_c, g_d = ex(gallery_images, model_clean), ex(gallery_images, model_distortion)
+                                               verbose=False, features=POOLINGS)
+    fq_c, fq_d = ex(queries_images, model_clean), ex(queries_images, model_distortion)
+    fg_c, fg_d = ex(gallery_images, model_clean), ex(gallery_images, model_distortion)
+    q_c, q_d, g_c, g_d = (f["both"] for f in (fq_c, fq_d, fg_c, fg_d))
     out = {}
     metrics = lambda dm: calculateMetrics(queries_images, gallery_images, dm, verbose=verbose)
     out["concatenation"] = metrics(ops_eval.pairdist(torch.cat((q_c, q_d), 1), torch.cat((g_c, g_d), 1), precision=precision, normalize=True))
@@ -71,10 +90,7 @@ def validate(queries_images, gallery_images, model_clean, model_distortion, img_
     out["distortion"] = metrics(ops_eval.pairdist(q_d, g_d, precision=precision, normalize=True))
     out["simple_ensemble"] = metrics(fuse_distmats(q_c, g_c, q_d, g_d))
     for pooling in ("gap", "gmp", "both"):
-        qm_c, _ = getWeightsByMagnitude(queries_images, pooling, img_height, img_width, model_clean, gpu_indexes)
-        qm_d, _ = getWeightsByMagnitude(queries_images, pooling, img_height, img_width, model_distortion, gpu_indexes)
-        gm_c, _ = getWeightsByMagnitude(gallery_images, pooling, img_height, img_width, model_clean, gpu_indexes)
-        gm_d, _ = getWeightsByMagnitude(gallery_images, pooling, img_height, img_width, model_distortion, gpu_indexes)
+        (qm_c, _), (qm_d, _), (gm_c, _), (gm_d, _) = (_magnitudes(f[pooling]) for f in (fq_c, fq_d, fg_c, fg_d))
         out["ensemble_" + pooling] = metrics(fuse_distmats(q_c, g_c, q_d, g_d, (qm_c, gm_c), (qm_d, gm_d)))
     if meta_recognition:
         sims = [1 - ops_eval.pairdist(q, g, precision=precision, normalize=True) for q, g in ((q_c, g_c), (q_d, g_d))]

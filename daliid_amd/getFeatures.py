@@ -55,12 +55,24 @@ def get_image_loader():
 
 
 def extractFeatures(subset, img_height, img_width, model, batch_size, gpu_index=0, dataset=None, turbulance_dir_path=None,
-                    turb_strength=None, keep_on_device=False, verbose=True, cam_labels=None, view_labels=None):
+                    turb_strength=None, keep_on_device=False, verbose=True, cam_labels=None, view_labels=None, features=None):
     """-> fp32 [N, D] features in dataset order; on the CPU like the reference (getFeatures.py:62) unless
     ``keep_on_device`` (the in-tree callers keep them on the GPU and skip the D2H/H2D round trip).
     ``cam_labels`` / ``view_labels``: integer arrays aligned with ``subset`` for a model with SIE embeddings (make_models.py:184-185); each
-    batch's slice is handed to the model as ``cam_label`` / ``view_label``."""
+    batch's slice is handed to the model as ``cam_label`` / ``view_label``.
+    ``features``: a tuple of pooling names ("both" / "gap" / "gmp") -> a dict name -> [N, D], every pooling from ONE pass over the subset
+    (``forward_heads``: one trunk run per batch, images loaded once) instead of one pass per ``model.module.feature`` setting."""
     model.eval()
+    forward = model
+    if features is not None:
+        features = tuple(features)
+        net = getattr(model, "module", model)
+        if not hasattr(net, "forward_heads"):
+            raise TypeError("extractFeatures(features=...): %s has no forward_heads (several poolings from one pass exist for ResNet50ReID only)"
+                            % type(net).__name__)
+        if not features:
+            raise ValueError("extractFeatures(features=...): no pooling named")
+        forward = lambda x, **side: net.forward_heads(x, [(name, None) for name in features], **side)
     dev = torch.device("cuda", gpu_index)
     paths = [row[0] for row in subset]
     start = time.time()
@@ -85,17 +97,42 @@ def extractFeatures(subset, img_height, img_width, model, batch_size, gpu_index=
                 if i + 1 < len(starts):
                     b = starts[i + 1]
                     ahead.append(_loader.submit(_loader.plan(paths[b:b + batch_size], img_height, img_width, turb)))
-                chunks.append(model(_loader.finish(ahead.pop(0), dev), **labels(starts[i])))
+                chunks.append(forward(_loader.finish(ahead.pop(0), dev), **labels(starts[i])))
         else:
             for b in starts:
                 batch = _loader(paths[b:b + batch_size], img_height, img_width, turb)
-                chunks.append(model(batch.to(dev, non_blocking=True), **labels(b)))
-    fvs = torch.cat(chunks, 0) if chunks else torch.empty(0, 0, device=dev)
+                chunks.append(forward(batch.to(dev, non_blocking=True), **labels(b)))
+    if features is not None:                             # chunks: [n_features, batch, D] each
+        fvs = torch.cat(chunks, 1) if chunks else torch.empty(len(features), 0, 0, device=dev)
+    else:
+        fvs = torch.cat(chunks, 0) if chunks else torch.empty(0, 0, device=dev)
     if not keep_on_device:
         fvs = fvs.cpu()
     if verbose:
         print("Features extracted in %.2f seconds" % (time.time() - start))
-    return fvs
+    return fvs if features is None else {name: fvs[i] for i, name in enumerate(features)}
+
+
+def extractFeaturesMultiPart(subset, img_height, img_width, model, batch_size, gpu_index=0, eval_mode=True, sobel=False, grayscale=False, BGR=False):
+    """getFeatures.extractFeaturesMultiPart (getFeatures.py:110-156): -> (upper, middle, lower, whole) body-part embeddings, fp32 [N, D] each,
+    on the CPU, from ``model(x=batch, multipart=True)`` -- one trunk pass per batch.  The parts are inference outputs here: ``eval_mode=False``
+    is not implemented, nor are the ``sobel`` (the reference's own ``sampleSobel`` does not exist), ``grayscale`` and ``BGR`` inputs."""
+    if not eval_mode:
+        raise NotImplementedError("extractFeaturesMultiPart: the body-part heads are inference outputs (eval_mode=False is out of scope)")
+    if sobel or grayscale or BGR:
+        raise NotImplementedError("extractFeaturesMultiPart: sobel / grayscale / BGR inputs are out of scope of this build")
+    model.eval()
+    dev = torch.device("cuda", gpu_index)
+    paths = [row[0] for row in subset]
+    start = time.time()
+    chunks = []
+    with torch.no_grad():
+        for b in range(0, len(paths), batch_size):
+            batch = _loader(paths[b:b + batch_size], img_height, img_width, None)
+            chunks.append(torch.stack(model(x=batch.to(dev, non_blocking=True), multipart=True)))
+    parts = torch.cat(chunks, 1).cpu() if chunks else torch.empty(4, 0, 0)
+    print("Features extracted in %.2f seconds" % (time.time() - start))
+    return parts[0], parts[1], parts[2], parts[3]
 
 
 def get_subset_one_encoder(selected_sample, train_set, topK, encoder, batch_size=500, gpu_index=0):

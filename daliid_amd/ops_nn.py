@@ -1,6 +1,8 @@
 """Python entry points of the trunk kernels (single ops; thin wrappers over the C ABI).
 
 Tensors are torch CUDA tensors; activations NHWC bf16 ([N,H,W,C] contiguous), see include/daliid.h."""
+import ctypes
+
 import torch
 
 from . import _lib
@@ -243,6 +245,42 @@ def head_pool_bwd(df, arg, hw_shape, feature="both"):
     _lib.check(_lib.lib().dali_head_pool_bwd(_lib.ctx(df.device), _lib.stream_ptr(), _lib.ptr(df, torch.float32), _lib.ptr(arg), n, h * w, C,
                                               FEATURE_MODES[feature], _lib.ptr(dx)), "dali_head_pool_bwd")
     return dx
+
+
+class HeadSpec(ctypes.Structure):
+    """dali_head_spec (include/daliid.h): pooling mode and the rows [row_begin, row_end) of the map; 0, 0 = every row."""
+    _fields_ = [("mode", ctypes.c_int32), ("row_begin", ctypes.c_int32), ("row_end", ctypes.c_int32)]
+
+
+def head_specs(heads):
+    """heads: sequence of (mode_name, rows) with rows = None (every row) or (row_begin, row_end) -> a host array of dali_head_spec.
+    Only the names are resolved here; counts, ranges and modes are checked by the library."""
+    heads = list(heads)
+    arr = (HeadSpec * max(len(heads), 1))()
+    for i, (mode, rows) in enumerate(heads):
+        if mode not in FEATURE_MODES:
+            raise _lib.DaliError("head %d: pooling must be 'both', 'gap' or 'gmp' (got %r)" % (i, mode))
+        b, e = (0, 0) if rows is None else rows
+        arr[i] = HeadSpec(FEATURE_MODES[mode], int(b), int(e))
+    return arr, len(heads)
+
+
+def head_pool_multi(x, heads):
+    """x [N,H,W,C] bf16, heads as for ``head_specs`` -> fp32 [n_heads, N, C]: every head from one read of the map (dali_head_pool_multi)."""
+    n, h, w, C = x.shape
+    arr, nh = head_specs(heads)
+    f = torch.empty(nh, n, C, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dali_head_pool_multi(_lib.ctx(x.device), _lib.stream_ptr(), _lib.ptr(x, bf16), n, h, w, C, arr, nh, _lib.ptr(f)),
+               "dali_head_pool_multi")
+    return f
+
+
+def channel_sum(x):
+    """x [..., C] bf16 -> fp32 [...]: the sum over the channels of every pixel (``torch.sum(x, dim=1)`` of the NCHW view; dali_channel_sum)."""
+    C = x.shape[-1]
+    out = torch.empty(x.shape[:-1], device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dali_channel_sum(_lib.ctx(x.device), _lib.stream_ptr(), _lib.ptr(x, bf16), out.numel(), C, _lib.ptr(out)), "dali_channel_sum")
+    return out
 
 
 def bn1d_fwd(x, gamma, beta, running_mean=None, running_var=None, training=True, momentum=0.1, eps=1e-5):

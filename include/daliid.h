@@ -371,6 +371,19 @@ int dali_maxpool_bn_bwd(dali_ctx* ctx, void* stream, const uint16_t* dpool, cons
 int dali_head_pool_fwd(dali_ctx* ctx, void* stream, const uint16_t* x, int n, int hw, int C, int mode, float* f, int16_t* arg);
 int dali_head_pool_bwd(dali_ctx* ctx, void* stream, const float* df, const int16_t* arg, int n, int hw, int C, int mode,
                        uint16_t* dx);
+/* Several heads from ONE read of the map (inference outputs: no argmax is kept).  x bf16 [n][h][w][C]; head i pools rows
+ * [row_begin, row_end) of the map -- 0,0 = every row -- by mode (dali_feature: mean + max, mean or max) into f[i] of f fp32 [n_heads][n][C].
+ * The body parts of mainKIT.ResNet50ReID.forward(multipart=True) (mainKIT.py:251-292) are max heads over rows :8, 4:12 and 8: of the 16-row
+ * map.  A head over every row is bitwise what dali_head_pool_fwd writes for the same mode.  heads is a HOST array.
+ * DALI_ERR_INVALID: n_heads outside 1..DALI_MAX_HEADS, row_end > h, row_begin >= row_end (unless both 0), a bad mode, C % 8 != 0,
+ * h * w >= 32768. */
+typedef struct { int32_t mode; int32_t row_begin; int32_t row_end; } dali_head_spec;
+#define DALI_MAX_HEADS 8
+int dali_head_pool_multi(dali_ctx* ctx, void* stream, const uint16_t* x, int n, int h, int w, int C, const dali_head_spec* heads, int n_heads,
+                         float* f);
+/* out[r] = sum_c x[r][c], fp32: `torch.sum(x, dim=1)` over an NHWC map, one value per pixel (the activation map of mainKIT.py:294-298).
+ * x bf16 [rows][C], C % 8 == 0.  No atomics: bitwise identical run to run. */
+int dali_channel_sum(dali_ctx* ctx, void* stream, const uint16_t* x, int64_t rows, int C, float* out);
 /* BatchNorm1d neck (Encoders.py:350) on fp32 [n,C]. */
 int dali_bn1d_fwd(dali_ctx* ctx, void* stream, const float* x, int n, int C, const float* gamma, const float* beta,
                   float* running_mean, float* running_var, int training, float momentum, float eps, float* y, float* mean,
@@ -571,6 +584,16 @@ int dali_resnet_set_feature(dali_resnet* net, int mode);
  * (model.train()); else running statistics (model.eval()).  Stands under `model_online(batch_imgs)`
  * (train_encodersKIT.py:197) and `model(batch_gpu)` (getFeatures.py:61). */
 int dali_resnet_forward(dali_resnet* net, void* stream, const float* images, int training, float* emb);
+/* Height and width of the layer4 map of this plan (the rows a dali_head_spec counts). */
+int dali_resnet_head_map(dali_resnet* net, int* h, int* w);
+/* Inference with several heads from ONE trunk pass (model.eval(): running statistics, nothing is updated): emb fp32
+ * [n_heads][batch][feat_dim], head i = last_bn(pool_i(layer4 map)) (dali_head_pool_multi); a head over every row is bitwise what
+ * dali_resnet_forward(training = 0) gives under dali_resnet_set_feature(mode_i).  heat (nullable) fp32 [batch][h * w]: the channel sum of
+ * the map (dali_channel_sum).  The plan's own feature mode is neither read nor changed.  Stands under
+ * `model(x, multipart=True)` / `model(x, attention_map=True)` (mainKIT.py:239-298) and the three poolings of
+ * evaluateCleanATModels.getWeightsByMagnitude (:249-256). */
+int dali_resnet_forward_heads(dali_resnet* net, void* stream, const float* images, const dali_head_spec* heads, int n_heads, float* emb,
+                              float* heat);
 /* Backward of the last training forward, stages stage_begin..stage_end (0: neck+head+layer4, 1: layer3,
  * 2: layer2, 3: layer1+stem); fills the flat gradient buffer (overwrites, no accumulation).
  * Stands under `batch_loss.backward()` (train_encodersKIT.py:215). */
