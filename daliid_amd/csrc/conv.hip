@@ -14,6 +14,7 @@
 // (c) the dgrad epilogue can add a residual gradient.
 #include "gemm_tile.h"
 #include "kernels.h"
+#include "../../include/daliid_debug.h"
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
@@ -101,9 +102,9 @@ __device__ __forceinline__ int parity_block(IGemmArgs& a) {
 
 // Diagnostic timeline (dali_debug_set_conv_stamps; IGemmArgs / WGradArgs::stamps, 12 slots per workgroup, s_memrealtime ticks; read by
 // scripts/conv_block_timeline.py).  Slots: 0 start, 1 first tile landed, 2 main loop done, 3 stores acknowledged, 4 stores issued,
-// 5 statistics done, 6 / 8 half staged, 7 / 9 half's stores issued, 10 HW_ID (igemm_conv_k64_kernel).
-// (igemm_conv_dma_kernel and igemm_conv_k64_kernel write their slots 0 - 2 out instead of calling conv_stamp: with the call their linear-layer
-// instantiations, which sit at the 128-register limit, spilled 3 and 2 more registers in the epilogue.)
+// 5 statistics done, 6 / 8 half staged, 7 / 9 half's stores issued, 10 HW_ID (the k-tile-64 instantiations of igemm_conv_ring_kernel).
+// (igemm_conv_ring_kernel writes its slots 0 - 2 out instead of calling conv_stamp: with the call its linear-layer instantiations at k-tile
+// 32 and 64, which sit at the 128-register limit, spilled 3 and 2 more registers in the epilogue.)
 template <class Args>
 __device__ __forceinline__ void conv_stamp(const Args& a, int slot) {
     if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + slot] = __builtin_amdgcn_s_memrealtime();
@@ -234,9 +235,9 @@ __device__ __forceinline__ float row16_reduce8(const float (&v)[8], int lane) {
 // Generic over the block shape: TM x TN tile, WNW waves along n, NT threads; this wave sits at (wm, wn) and owns an
 // (FM*16) x (FN*16) sub-tile.
 //
-// What an instantiation's output stage compiles in (conv_epilogue_g; the kernels' EPI parameter, the GemmKernel table).  Each mode is its own
-// instantiation so that the hot convolution kernels compile none of the others' code: code that is never executed still cost their register
-// allocation 0.4-0.8 ms per ResNet step.
+// What an instantiation's output stage compiles in (conv_epilogue_g; the kernels' MODE / EPI parameter, which the GemmKernel table names for
+// every entry).  Each mode is its own instantiation so that the hot convolution kernels compile none of the others' code: code that is never
+// executed still cost their register allocation 0.4-0.8 ms per ResNet step.
 enum class Epi : int {
     CONV = 0,        // convolution only: the lean staged store (+ residual, + residual mask); no linear-layer extras compiled in at all
     LIN = 1,         // linear-layer extras (GELU, pre-activation copy O2, GELU' factor, DropPath row factor) in a staged block and in the general path
@@ -246,8 +247,6 @@ enum class Epi : int {
     FUSED_LEAN = 5,  // the fused stage WITHOUT residual, masks and mask bits (scale / shift / bias / ReLU only): the inference forward's conv + BatchNorm
                      // + ReLU launches on the 3x3 and narrow kernels, whose register budgets the full stage's residual prefetch overflowed
 };
-// the mode of one kernel instantiation: the shape that has a variant per mode (`own`) gets its own, every other one the extras in the general path only
-constexpr Epi epi_mode(bool own, Epi asked) { return own ? asked : Epi::GENERAL; }
 constexpr bool epi_fused(Epi m) { return m == Epi::FUSED || m == Epi::FUSED_LEAN; }
 
 // keep the bf16 halves of `w` whose mask bits (bit 0: low half, bit 1: high half) are set
@@ -400,7 +399,7 @@ struct EpiStage {
     }
     // that chunk of tensor `src`; the staged chunk -> `dst`.  (The loops over `it` stay in the store paths, inside their loop over the halves: a
     // member holding the loop is unrolled before it is inlined, its chunk addresses are then hoisted out of the half loop and stay live across
-    // both halves: 105 -> 122 VGPRs for igemm_conv_dma_kernel<128, 128, 3>.)
+    // both halves: 105 -> 122 VGPRs for the 128 x 128 tile of igemm_conv_ring_kernel, DMA128.)
     __device__ __forceinline__ uint4 in(const uint16_t* src, int h, int it) const {
         return *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(src) + offset(h, it));
     }
@@ -927,149 +926,63 @@ __device__ __forceinline__ void mma_ktile(const uint16_t* sa, const uint16_t* sb
     }
 }
 
-template <int TM, int TN, int NSTAGE, Epi EPI = Epi::CONV, bool SRC2 = false>
-__global__ __launch_bounds__(256, (TM >= 128 ? (EPI == Epi::FUSED ? 3 : 4) : 2)) void igemm_conv_dma_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
-    // 128 x 128: <= 128 VGPRs (4 waves per SIMD); the 64 x 256 shape carries twice the per-lane gather state and would spill
-    using Cfg = GemmCfg<TM, TN, 1, 1, 1>;
-    using Gather = ConvGather<32, TM, TN, 4, SRC2>;
-    constexpr int FM = Cfg::FM, FN = Cfg::FN, NDMA = Gather::NDMA;
-    extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
-    int tm, tn;
-    if (!xcd_tile_map(parity_block(a), tiles_m, tiles_n, tm, tn)) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 0] = __builtin_amdgcn_s_memrealtime();   // (written out: see conv_stamp)
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const GatherGeom g = a.g;                          // (after parity_block, which rewrites a.g)
-    const int ktiles = (g.nr * g.ns * g.Ck) >> 5;      // taps actually visited (all of them unless g.sub)
-    Gather gather(a, g, tm, tn, wave, lane);
-    auto issue = [&](int stage) { uint16_t* sa = smem + stage * Cfg::STAGE_ELEMS; gather.issue(sa, sa + Cfg::A_ELEMS); };
-
-    f32x4_t acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int a_row0 = wm * (TM / 2), b_row0 = wn * (TN / 2);
-
-    // 3-stage ring: the DMA of tile t+2 is issued before tile t is multiplied; the wait at the end of iteration t retires
-    // tile t+1 only (counted vmcnt leaves tile t+2's NDMA DMAs in flight ACROSS the barrier, so a raw s_barrier is
-    // used: __syncthreads() would drain them).  A stage is read one iteration after the wait+barrier that retired it, and
-    // re-filled two barriers after its last read.
-    constexpr int AHEAD = NSTAGE - 1;                   // tiles in flight beyond the one being multiplied
-    issue(0);
-    if (AHEAD == 2 && ktiles > 1) issue(1);
-    if (AHEAD == 2 && ktiles > 1) dma_wait<NDMA>(); else dma_wait<0>();
-    __builtin_amdgcn_s_barrier();
-    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
-    int st_cur = 0, st_nxt2 = AHEAD;
-    for (int kt = 0; kt < ktiles; ++kt) {
-        if (kt + AHEAD < ktiles) issue(st_nxt2);
-        const uint16_t* sa = smem + st_cur * Cfg::STAGE_ELEMS;
-        mma_ktile<32>(sa, sa + Cfg::A_ELEMS, a_row0, b_row0, lane, acc);
-        if (AHEAD == 2 && kt + 2 < ktiles) dma_wait<NDMA>(); else dma_wait<0>();
-        __builtin_amdgcn_s_barrier();
-        st_cur = (st_cur == NSTAGE - 1) ? 0 : st_cur + 1;
-        st_nxt2 = (st_nxt2 == NSTAGE - 1) ? 0 : st_nxt2 + 1;
-    }
-    __syncthreads();
-    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
-
-    conv_epilogue<Cfg, epi_mode((TM == 128 && TN == 128 && NSTAGE == 3) || epi_fused(EPI), EPI)>(a, acc, tm, tn, smem);
-    conv_stamp_stores(a);
-}
-
-// Wave-grid variant for the large layers: WM x WN waves, each owning a 64 x 64 sub-tile (same per-wave code and register
-// budget as the 128 x 128 kernel), block tile (64*WM) x (64*WN).  256 x 256 with 16 waves halves the L2->LDS bytes per
-// FLOP (measured limiter of the 128 x 128 kernel: ~47 GB/s per CU of operand traffic at 0.8 PFLOP/s) and leaves room
-// for a 4-deep LDS ring (3 k-tiles in flight) at one block per CU.
-// (launch bounds: 4 waves per SIMD.  The 8-wave shapes are meant to run two workgroups per CU; their linear-layer instantiation compiled
-// to 130 VGPRs = 3 waves per SIMD = ONE workgroup of 8 waves per CU, and fc1 forward / fc2 data gradient ran at 440 TFLOP/s for it.)
-template <int WM, int WN, int NSTAGE, Epi EPI = Epi::CONV>
-__global__ __launch_bounds__(WM * WN * 64, 4) void igemm_conv_wg_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
-    constexpr int TM = 64 * WM, TN = 64 * WN, NW = WM * WN, NT = NW * 64;
-    using Gather = ConvGather<32, TM, TN, NW, false>;
-    constexpr int NDMA = Gather::NDMA;
-    constexpr int A_ELEMS = TM * 32, B_ELEMS = TN * 32, STAGE_ELEMS = A_ELEMS + B_ELEMS;
-    constexpr int AHEAD = NSTAGE - 1;
-    extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
-    int tm, tn;
-    if (!xcd_tile_map(parity_block(a), tiles_m, tiles_n, tm, tn)) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const GatherGeom g = a.g;                          // (after parity_block, which rewrites a.g)
-    const int ktiles = (g.nr * g.ns * g.Ck) >> 5;      // taps actually visited (all of them unless g.sub)
-    Gather gather(a, g, tm, tn, wave, lane);
-    auto issue = [&](int stage) { uint16_t* sa = smem + stage * STAGE_ELEMS; gather.issue(sa, sa + A_ELEMS); };
-    f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int a_row0 = wm * 64, b_row0 = wn * 64;
-    // prologue: AHEAD tiles in flight, wait for the first
-    int issued = 0;
-    for (; issued < AHEAD && issued < ktiles; ++issued) issue(issued);
-    if (issued == 1) dma_wait<0>();
-    else if (issued == 2) dma_wait<NDMA>();
-    else dma_wait<2 * NDMA>();
-    __builtin_amdgcn_s_barrier();
-    int st_cur = 0, st_fill = AHEAD % NSTAGE;
-    for (int kt = 0; kt < ktiles; ++kt) {
-        const bool more = kt + AHEAD < ktiles;
-        if (more) issue(st_fill);
-        const uint16_t* sa = smem + st_cur * STAGE_ELEMS;
-        mma_ktile<32>(sa, sa + A_ELEMS, a_row0, b_row0, lane, acc);
-        // retire tile kt+1: everything but the youngest min(AHEAD-1, remaining) tiles must have landed
-        const int left = ktiles - 1 - kt;                    // tiles after this one
-        int inflight_after = left < AHEAD ? left : AHEAD;      // tiles issued and not yet multiplied (excl. current)
-        // allowed still-in-flight tiles = inflight_after - 1 (tile kt+1 must be complete)
-        if (inflight_after <= 1) dma_wait<0>();
-        else if (inflight_after == 2) dma_wait<NDMA>();
-        else dma_wait<2 * NDMA>();
-        __builtin_amdgcn_s_barrier();
-        st_cur = (st_cur == NSTAGE - 1) ? 0 : st_cur + 1;
-        st_fill = (st_fill == NSTAGE - 1) ? 0 : st_fill + 1;
-    }
-    __syncthreads();
-    conv_epilogue_g<TM, TN, 4, 4, WN, NT, epi_mode(WM == 2 && WN == 4 && NSTAGE == 3, EPI)>(a, acc, tm, tn, smem, wm, wn);
-}
-
 // ------------------------------------------------------------------------------------------------
-// k-tile of 64 (128-byte operand rows).  Measured with scripts/micro/dma_segments.hip: the L2 -> LDS path of a CU retires
-// about one cache line per 3 clocks whatever part of the line is used, so a [rows][32 bf16] k-tile (64 B = half a line per
-// row) feeds 70-79 GB/s per CU and a [rows][64 bf16] k-tile (a full 128-B line per row) 98-132 GB/s; the ablated 256 x 256
-// kernel (scripts/ablate_conv.py) spent 0.66 us per 32-deep k-step in the feed alone against 0.43 us of MFMA work.
-// Same wave grid, per-wave 64 x 64 sub-tile and epilogue as igemm_conv_wg_kernel; a DMA piece is 8 rows x 128 B, a stage is
-// (TM + TN) x 128 B, one barrier per 64 deep k-step (2 x 16 MFMAs per wave).  Swizzle: physical 16-byte chunk =
-// logical chunk ^ ((row >> 1) & 7): every 16-lane service group of ds_read_b128 ({0-3,12-15,20-27}, ... = 8 rows of one
-// chunk + 8 rows of the next) lands on 16 distinct 16-byte bank slots.  Needs Ck % 64 == 0.
+// The unspecialised LDS-DMA kernel: WM x WN waves, each owning a (16 FM) x (16 FN) sub-tile, all of them issuing their share of the DMA
+// pieces of an NSTAGE-deep ring of k-tiles.  Every instantiation launched is an entry of the GemmKernel table (ring_kernel).
+//
+// Tile shapes.  128 x 128 / 4 waves for short K (prologue-bound).  256 x 256 with 16 waves halves the L2->LDS bytes per FLOP (measured
+// limiter of the 128 x 128 tile: ~47 GB/s per CU of operand traffic at 0.8 PFLOP/s) and leaves room for a 4-deep ring (3 k-tiles in
+// flight) at one workgroup per CU.
+//
+// k-tile depth.  Measured with scripts/micro/dma_segments.hip: the L2 -> LDS path of a CU retires about one cache line per 3 clocks
+// whatever part of the line is used, so a [rows][32 bf16] k-tile (64 B = half a line per row) feeds 70-79 GB/s per CU and a
+// [rows][64 bf16] k-tile (a full 128-B line per row) 98-132 GB/s; the ablated 256 x 256 k-tile-32 kernel (scripts/ablate_conv.py) spent
+// 0.66 us per 32-deep k-step in the feed alone against 0.43 us of MFMA work.  KT = 64: a DMA piece is 8 rows x 128 B, one barrier per
+// 64 deep k-step (2 x FM FN MFMAs per wave).  Swizzle: physical 16-byte chunk = logical chunk ^ ((row >> 1) & 7): every 16-lane service
+// group of ds_read_b128 ({0-3,12-15,20-27}, ... = 8 rows of one chunk + 8 rows of the next) lands on 16 distinct 16-byte bank slots.
+// Needs Ck % 64 == 0.
+//
+// Registers (MINW, the waves per SIMD the launch bounds ask for).  The 64 x 64 sub-tile fits 128 VGPRs = 4 waves per SIMD; the 4-wave
+// 64 x 256 tile (2 x 8 fragments) carries twice the per-lane gather state and would spill at that bound.  The 8-wave shapes are meant to run
+// two workgroups per CU: without the bound their linear-layer instantiation compiled to 130 VGPRs = 3 waves per SIMD = ONE workgroup of
+// 8 waves per CU, and fc1 forward / fc2 data gradient ran at 440 TFLOP/s for it.
+//
+// STAMPS: the instantiation writes the diagnostic timeline (conv_stamp).  Several instantiations sit at 125-128 VGPRs, so the ones
+// that never carried the stamps still compile none.
 // ------------------------------------------------------------------------------------------------
-template <int WM, int WN, int NSTAGE, int FM = 4, int FN = 4, Epi EPI = Epi::CONV, bool SRC2 = false>
-__global__ __launch_bounds__(WM * WN * 64) void igemm_conv_k64_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
-    constexpr int TM = 16 * FM * WM, TN = 16 * FN * WN, NW = WM * WN, NT = NW * 64;     // per-wave sub-tile 16 FM x 16 FN
-    using Gather = ConvGather<64, TM, TN, NW, SRC2>;
+// what the shape arguments determine: read by the kernel and by its table entry (ring_kernel) alike
+template <int KT, int WM, int WN, int FM, int FN, int NSTAGE>
+struct RingShape {
+    static constexpr int TM = 16 * FM * WM, TN = 16 * FN * WN, NW = WM * WN, NT = NW * 64;
+    static constexpr int A_ELEMS = TM * KT, STAGE_ELEMS = (TM + TN) * KT;     // a stage: the weight image [TM][KT] bf16, then the pixel image [TN][KT]
+    static constexpr int LDS_BYTES = NSTAGE * STAGE_ELEMS * 2;
+};
+template <int KT, int WM, int WN, int FM, int FN, int NSTAGE, int MINW, bool STAMPS, Epi MODE, bool SRC2 = false>
+__global__ __launch_bounds__(WM * WN * 64, MINW) void igemm_conv_ring_kernel(IGemmArgs a, int tiles_m, int tiles_n) {
+    using Shape = RingShape<KT, WM, WN, FM, FN, NSTAGE>;
+    constexpr int TM = Shape::TM, TN = Shape::TN, NW = Shape::NW, NT = Shape::NT, A_ELEMS = Shape::A_ELEMS, STAGE_ELEMS = Shape::STAGE_ELEMS;
+    using Gather = ConvGather<KT, TM, TN, NW, SRC2>;
     constexpr int NDMA = Gather::NDMA;
-    constexpr int A_ELEMS = TM * 64, B_ELEMS = TN * 64, STAGE_ELEMS = A_ELEMS + B_ELEMS;
-    constexpr int AHEAD = NSTAGE - 1;
+    constexpr int AHEAD = NSTAGE - 1;                  // tiles in flight beyond the one being multiplied
+    static_assert(NSTAGE >= 2 && NSTAGE <= 4, "ring depth (the waits below count up to 2 tiles in flight across a barrier)");
     static_assert(!Gather::B_RAGGED || NSTAGE == 2, "a ragged piece count needs the wait-for-all of the 2-stage ring (dma_wait<NDMA> counts pieces per wave)");
-    static_assert(NSTAGE == 2 || NSTAGE == 3, "ring depth");
     extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
     int tm, tn;
     if (!xcd_tile_map(parity_block(a), tiles_m, tiles_n, tm, tn)) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 0] = __builtin_amdgcn_s_memrealtime();   // (written out: see conv_stamp)
-    if (a.stamps && tid == 0) {
-        unsigned hw, xcc;                              // where this workgroup sits (slot 10: HW_ID | XCC_ID << 32)
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        a.stamps[(size_t)blockIdx.x * 12 + 10] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
+    if constexpr (STAMPS) {
+        if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 0] = __builtin_amdgcn_s_memrealtime();   // (slots 0 - 2 written out: see conv_stamp)
+        if (KT == 64 && a.stamps && tid == 0) {
+            unsigned hw, xcc;                          // where this workgroup sits (slot 10: HW_ID | XCC_ID << 32)
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+            a.stamps[(size_t)blockIdx.x * 12 + 10] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
+        }
     }
     const GatherGeom g = a.g;                          // (after parity_block, which rewrites a.g)
-    const int ktiles = (g.nr * g.ns * g.Ck) >> 6;      // taps actually visited (all of them unless g.sub)
+    const int ktiles = (g.nr * g.ns * g.Ck) >> (KT == 64 ? 6 : 5);      // taps actually visited (all of them unless g.sub)
     Gather gather(a, g, tm, tn, wave, lane);
     auto issue = [&](int stage) { uint16_t* sa = smem + stage * STAGE_ELEMS; gather.issue(sa, sa + A_ELEMS); };
     f32x4_t acc[FM][FN];
@@ -1078,27 +991,39 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_conv_k64_kernel(IGemmArgs 
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const int a_row0 = wm * (16 * FM), b_row0 = wn * (16 * FN);
+
+    // The ring: the DMA of tile t + AHEAD is issued before tile t is multiplied; the wait at the end of iteration t retires tile t + 1 only.
+    // The counted vmcnt leaves the younger tiles' NDMA DMAs each in flight ACROSS the barrier, so a raw s_barrier is used: __syncthreads()
+    // would drain them.  A stage is read one iteration after the wait + barrier that retired it, and re-filled after the barrier that
+    // follows its last read.
+    // `inflight`: tiles issued and not yet multiplied; the oldest must have landed, the other (at most 2) may stay in flight
+    auto retire_oldest = [&](int inflight) {
+        if (AHEAD >= 3 && inflight >= 3) dma_wait<2 * NDMA>();
+        else if (AHEAD >= 2 && inflight == 2) dma_wait<NDMA>();
+        else dma_wait<0>();
+    };
     int issued = 0;
     for (; issued < AHEAD && issued < ktiles; ++issued) issue(issued);
-    if (issued == 2) dma_wait<NDMA>(); else dma_wait<0>();
+    retire_oldest(issued);
     __builtin_amdgcn_s_barrier();
-    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
+    if constexpr (STAMPS)
+        if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 1] = __builtin_amdgcn_s_memrealtime();
     int st_cur = 0, st_fill = AHEAD % NSTAGE;
     for (int kt = 0; kt < ktiles; ++kt) {
         if (kt + AHEAD < ktiles) issue(st_fill);
         const uint16_t* sa = smem + st_cur * STAGE_ELEMS;
-        mma_ktile<64>(sa, sa + A_ELEMS, a_row0, b_row0, lane, acc);
-        // retire tile kt+1: only the youngest tile (if any beyond kt+1) may still be in flight
-        const int left = ktiles - 1 - kt;
-        if (AHEAD == 2 && left >= 2) dma_wait<NDMA>(); else dma_wait<0>();
+        mma_ktile<KT>(sa, sa + A_ELEMS, a_row0, b_row0, lane, acc);
+        const int left = ktiles - 1 - kt;              // tiles after this one
+        retire_oldest(left < AHEAD ? left : AHEAD);
         __builtin_amdgcn_s_barrier();
         st_cur = (st_cur == NSTAGE - 1) ? 0 : st_cur + 1;
         st_fill = (st_fill == NSTAGE - 1) ? 0 : st_fill + 1;
     }
     __syncthreads();
-    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
-    conv_epilogue_g<TM, TN, FM, FN, WN, NT, epi_mode(WM == 4 && WN == 4 && NSTAGE == 2 && FM == 4, EPI)>(a, acc, tm, tn, smem, wm, wn);
-    conv_stamp_stores(a);
+    if constexpr (STAMPS)
+        if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 12 + 2] = __builtin_amdgcn_s_memrealtime();
+    conv_epilogue_g<TM, TN, FM, FN, WN, NT, MODE>(a, acc, tm, tn, smem, wm, wn);
+    if constexpr (STAMPS) conv_stamp_stores(a);
 }
 
 // Wave-specialised k-tile-64 kernel: WM x WN consumer waves (64 x 64 sub-tiles: fragment reads + MFMAs + epilogue) and NP
@@ -1162,7 +1087,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_conv_k64s_kernel(IG
         st_cur = (st_cur == NSTAGE - 1) ? 0 : st_cur + 1;
     }
     conv_stamp(a, 2);
-    conv_epilogue_g<TM, TN, FM, FN, WN, NT, epi_mode(WM == 2 && WN == 4 && NP == 8 && NSTAGE == 3, EPI)>(a, acc, tm, tn, smem, wm, wn);
+    conv_epilogue_g<TM, TN, FM, FN, WN, NT, EPI>(a, acc, tm, tn, smem, wm, wn);
     conv_stamp_stores(a);
 }
 
@@ -1180,7 +1105,7 @@ __global__ __launch_bounds__((WM * WN + NP) * 64) void igemm_conv_k64s_kernel(IG
 // mode 0: input pixel (h - 1 + kr, w - 1 + ks); mode 1 (data gradient, stride 1): (h + 1 - kr, w + 1 - ks): the same patch, taps mirrored.
 // ------------------------------------------------------------------------------------------------
 constexpr int HALO64_PX = 344;                           // >= (256 / W + 2) * (W + 2) for W = 16 (324), 32 (340); 43 DMA pieces of 8 pixels
-template <int NSTAGE, Epi EPI = Epi::CONV>
+template <int NSTAGE, Epi EPI>
 __global__ __launch_bounds__(512, 4) void igemm_conv_halo64_kernel(IGemmArgs a, int tiles_n) {
     constexpr int TM = 64, TN = 256, NC = 4, NP = 4, NT = NC * 64, FM = 4, FN = 4;
     constexpr int A_ELEMS = TM * 64, RING = NSTAGE * A_ELEMS, NPIECE = HALO64_PX / 8, PPW = (NPIECE + NP - 1) / NP;   // 43 pieces, 11 per producer
@@ -1280,7 +1205,7 @@ __global__ __launch_bounds__(512, 4) void igemm_conv_halo64_kernel(IGemmArgs a, 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // my reads of this weight stage are complete before it can be refilled
         __builtin_amdgcn_s_barrier();
     }
-    conv_epilogue_g<TM, TN, FM, FN, 4, NT, epi_mode(epi_fused(EPI), EPI)>(a, acc, 0, tn, smem, 0, wn);
+    conv_epilogue_g<TM, TN, FM, FN, 4, NT, EPI>(a, acc, 0, tn, smem, 0, wn);
 }
 
 }  // namespace dali
@@ -1664,7 +1589,7 @@ __global__ __launch_bounds__(256) void igemm_wgrad_dma_kernel(WGradArgs a, int t
     typedef short ones_vec_t __attribute__((ext_vector_type(8)));
     const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, ones_vec_t{0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80});
 
-    if (ksteps > 0) {                                   // same 3-stage ring / counted-vmcnt schedule as igemm_conv_dma_kernel
+    if (ksteps > 0) {                                   // same 3-stage ring / counted-vmcnt schedule as igemm_conv_ring_kernel
         issue(0, 0);
         if (ksteps > 1) issue(1, 1);
         if (ksteps > 1) dma_wait<4>(); else dma_wait<0>();
@@ -2352,6 +2277,7 @@ enum GemmGrid {
     GRID_SPLITS8,       // the same rounded up to whole XCD groups of 8
 };
 struct GemmKernel {
+    const char* name;           // the entry's name in this table (dali_debug_conv_kernel_name, the DALI_GEMM_PROFILE_DUMP lines)
     const void* fn;
     int block;                  // threads per workgroup
     int lds;                    // dynamic LDS bytes; above 64 KiB also the MaxDynamicSharedMemorySize it opts in to (gemm_launch).  The persistent
@@ -2365,62 +2291,80 @@ struct GemmKernel {
 template <class F> static const void* kfn(F* f) { return reinterpret_cast<const void*>(f); }
 constexpr int ring_lds(int tm, int tn, int k_tile, int stages) { return (tm + tn) * k_tile * 2 * stages; }      // a ring of bf16 A and B k-tiles
 constexpr int REG128_LDS = GemmCfg<128, 128, 1, 1, 1>::LDS_BYTES, REG64_LDS = GemmCfg<64, 256, 1, 1, 1>::LDS_BYTES;    // register-staged: 2 stages
-constexpr int DMA128_LDS = REG128_LDS / 2 * 3, DMA64_LDS = REG64_LDS / 2 * 3;                                          // LDS-DMA: 3 stages
 constexpr int HALO64_LDS = (3 * 64 * 64 + HALO64_PX * 64) * 2;                                                         // 3 weight stages + the halo patch
 
-// Forward, data gradient and linear layers (IGemmArgs).  The output stage's mode: enum Epi.  SRC2: a second operand tensor (IGemmArgs::X2).
+// An entry for an instantiation of igemm_conv_ring_kernel: block, LDS bytes and tile come from the constants the kernel itself uses (RingShape),
+// the grid from the mode (a parity class's addressing goes with the grid of classes).  Arguments as the kernel's:
+// <k-tile, WM, WN, FM, FN, stages, waves per SIMD, stamps, mode, SRC2>
+template <int KT, int WM, int WN, int FM, int FN, int NSTAGE, int MINW, bool STAMPS, Epi MODE, bool SRC2 = false>
+static GemmKernel ring_kernel(const char* name) {
+    using Shape = RingShape<KT, WM, WN, FM, FN, NSTAGE>;
+    return {name, kfn(&igemm_conv_ring_kernel<KT, WM, WN, FM, FN, NSTAGE, MINW, STAMPS, MODE, SRC2>), Shape::NT, Shape::LDS_BYTES, Shape::TM, Shape::TN,
+            MODE == Epi::PARITY ? GRID_CLASSES : GRID_XCD};
+}
+// the same for igemm_conv_k64s_kernel: the ring of a k-tile-64 WM x WN grid of 64 x 64 consumers, NP producer waves beside them
+template <int WM, int WN, int NP, int NSTAGE, Epi MODE, bool SRC2 = false>
+static GemmKernel k64s_kernel(const char* name) {
+    using Shape = RingShape<64, WM, WN, 4, 4, NSTAGE>;
+    return {name, kfn(&igemm_conv_k64s_kernel<WM, WN, NP, NSTAGE, 4, 4, MODE, SRC2>), Shape::NT + NP * 64, Shape::LDS_BYTES, Shape::TM, Shape::TN, GRID_XCD};
+}
+
+// Forward, data gradient and linear layers (IGemmArgs).  The output stage's mode is the one named here (enum Epi).  SRC2: a second operand
+// tensor (IGemmArgs::X2).
 static const GemmKernel
-    // 128 x 128 / 4 waves, k-tile 32: register-staged (an operand transform, tensors beyond 2 GiB) and LDS-DMA
-    CONV128_BN{kfn(&igemm_conv_kernel<128, 128, true>), 256, REG128_LDS, 128, 128, GRID_XCD},
-    CONV128{kfn(&igemm_conv_kernel<128, 128, false>), 256, REG128_LDS, 128, 128, GRID_XCD},
-    DMA128{kfn(&igemm_conv_dma_kernel<128, 128, 3>), 256, DMA128_LDS, 128, 128, GRID_XCD},
-    DMA128_LIN{kfn(&igemm_conv_dma_kernel<128, 128, 3, Epi::LIN>), 256, DMA128_LDS, 128, 128, GRID_XCD},
-    DMA128_FUSED{kfn(&igemm_conv_dma_kernel<128, 128, 3, Epi::FUSED>), 256, DMA128_LDS, 128, 128, GRID_XCD},
-    DMA128_CLS{kfn(&igemm_conv_dma_kernel<128, 128, 3, Epi::PARITY>), 256, DMA128_LDS, 128, 128, GRID_CLASSES},
-    DMA128_SRC2{kfn(&igemm_conv_dma_kernel<128, 128, 3, Epi::CONV, true>), 256, DMA128_LDS, 128, 128, GRID_XCD},
-    // 64 x 256 for Cm <= 64
-    CONV64_BN{kfn(&igemm_conv_kernel<64, 256, true>), 256, REG64_LDS, 64, 256, GRID_XCD},
-    CONV64{kfn(&igemm_conv_kernel<64, 256, false>), 256, REG64_LDS, 64, 256, GRID_XCD},
-    DMA64{kfn(&igemm_conv_dma_kernel<64, 256, 3>), 256, DMA64_LDS, 64, 256, GRID_XCD},
-    DMA64_LEAN{kfn(&igemm_conv_dma_kernel<64, 256, 3, Epi::FUSED_LEAN>), 256, DMA64_LDS, 64, 256, GRID_XCD},
-    DMA64_SRC2{kfn(&igemm_conv_dma_kernel<64, 256, 3, Epi::CONV, true>), 256, DMA64_LDS, 64, 256, GRID_XCD},
+    // 128 x 128 / 4 waves, k-tile 32: register-staged (an operand transform, tensors beyond 2 GiB) and the 3-stage LDS-DMA ring
+    CONV128_BN{"CONV128_BN", kfn(&igemm_conv_kernel<128, 128, true>), 256, REG128_LDS, 128, 128, GRID_XCD},
+    CONV128{"CONV128", kfn(&igemm_conv_kernel<128, 128, false>), 256, REG128_LDS, 128, 128, GRID_XCD},
+    DMA128 = ring_kernel<32, 2, 2, 4, 4, 3, 4, true, Epi::CONV>("DMA128"),
+    DMA128_LIN = ring_kernel<32, 2, 2, 4, 4, 3, 4, true, Epi::LIN>("DMA128_LIN"),
+    DMA128_FUSED = ring_kernel<32, 2, 2, 4, 4, 3, 3, true, Epi::FUSED>("DMA128_FUSED"),       // (3 waves per SIMD: 152 VGPRs)
+    DMA128_CLS = ring_kernel<32, 2, 2, 4, 4, 3, 4, true, Epi::PARITY>("DMA128_CLS"),
+    DMA128_SRC2 = ring_kernel<32, 2, 2, 4, 4, 3, 4, true, Epi::CONV, true>("DMA128_SRC2"),
+    // 64 x 256 for Cm <= 64 (4 waves of 32 x 128)
+    CONV64_BN{"CONV64_BN", kfn(&igemm_conv_kernel<64, 256, true>), 256, REG64_LDS, 64, 256, GRID_XCD},
+    CONV64{"CONV64", kfn(&igemm_conv_kernel<64, 256, false>), 256, REG64_LDS, 64, 256, GRID_XCD},
+    DMA64 = ring_kernel<32, 2, 2, 2, 8, 3, 2, true, Epi::GENERAL>("DMA64"),
+    DMA64_LEAN = ring_kernel<32, 2, 2, 2, 8, 3, 2, true, Epi::FUSED_LEAN>("DMA64_LEAN"),
+    DMA64_SRC2 = ring_kernel<32, 2, 2, 2, 8, 3, 2, true, Epi::GENERAL, true>("DMA64_SRC2"),
     // layer1's 3x3 (Cm = Cin = 64, K = 576): k-tile 64 = one full line per pixel and tap, 4 MFMA waves + 4 DMA waves, 2-stage ring,
     // two workgroups per CU: 94 -> 77 us forward, 90 -> 73 us data gradient (unspecialised k-tile 64: 84 / 79; 3-stage ring, one
     // workgroup per CU: 122 / 118).  (8 producer waves instead of 4: 74 -> 78 us; the L2 -> LDS feed, 9 taps per pixel, bounds it, not the
     // issue of the DMA pieces)
-    K64S64{kfn(&igemm_conv_k64s_kernel<1, 4, 4, 2>), 512, ring_lds(64, 256, 64, 2), 64, 256, GRID_XCD},
+    K64S64 = k64s_kernel<1, 4, 4, 2, Epi::GENERAL>("K64S64"),
     // the same problem on halo64_ok's grids: the halo patch of a 256-pixel tile fetched once, taps read it at shifted pixels
-    HALO64{kfn(&igemm_conv_halo64_kernel<3>), 512, HALO64_LDS, 64, 256, GRID_HALO},
-    HALO64_LEAN{kfn(&igemm_conv_halo64_kernel<3, Epi::FUSED_LEAN>), 512, HALO64_LDS, 64, 256, GRID_HALO},
-    // 128 x 256 / 8 waves, k-tile 32, 3-stage ring
-    WG128{kfn(&igemm_conv_wg_kernel<2, 4, 3>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
-    WG128_LIN{kfn(&igemm_conv_wg_kernel<2, 4, 3, Epi::LIN>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
-    WG128_FUSED{kfn(&igemm_conv_wg_kernel<2, 4, 3, Epi::FUSED>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_XCD},
-    WG128_CLS{kfn(&igemm_conv_wg_kernel<2, 4, 3, Epi::PARITY>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_CLASSES},
-    // 256 x 256 / 16 waves, k-tile 32, 4-stage ring
-    WG256{kfn(&igemm_conv_wg_kernel<4, 4, 4>), 1024, ring_lds(256, 256, 32, 4), 256, 256, GRID_XCD},
+    HALO64{"HALO64", kfn(&igemm_conv_halo64_kernel<3, Epi::GENERAL>), 512, HALO64_LDS, 64, 256, GRID_HALO},
+    HALO64_LEAN{"HALO64_LEAN", kfn(&igemm_conv_halo64_kernel<3, Epi::FUSED_LEAN>), 512, HALO64_LDS, 64, 256, GRID_HALO},
+    // 128 x 256 / 8 waves, k-tile 32, 3-stage ring, no stamps
+    WG128 = ring_kernel<32, 2, 4, 4, 4, 3, 4, false, Epi::CONV>("WG128"),
+    WG128_LIN = ring_kernel<32, 2, 4, 4, 4, 3, 4, false, Epi::LIN>("WG128_LIN"),
+    WG128_FUSED = ring_kernel<32, 2, 4, 4, 4, 3, 4, false, Epi::FUSED>("WG128_FUSED"),
+    WG128_CLS = ring_kernel<32, 2, 4, 4, 4, 3, 4, false, Epi::PARITY>("WG128_CLS"),
+    // 256 x 256 / 16 waves, k-tile 32, 4-stage ring, no stamps
+    WG256 = ring_kernel<32, 4, 4, 4, 4, 4, 4, false, Epi::GENERAL>("WG256"),
     // 128 x 256 k-tile 64, wave-specialised (8 MFMA + 8 DMA waves), 3-stage ring
-    K64S{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
-    K64S_LIN{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, Epi::LIN>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
-    K64S_LEAN{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, Epi::FUSED_LEAN>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
-    K64S_SRC2{kfn(&igemm_conv_k64s_kernel<2, 4, 8, 3, 4, 4, Epi::CONV, true>), 1024, ring_lds(128, 256, 64, 3), 128, 256, GRID_XCD},
+    K64S = k64s_kernel<2, 4, 8, 3, Epi::CONV>("K64S"),
+    K64S_LIN = k64s_kernel<2, 4, 8, 3, Epi::LIN>("K64S_LIN"),
+    K64S_LEAN = k64s_kernel<2, 4, 8, 3, Epi::FUSED_LEAN>("K64S_LEAN"),
+    K64S_SRC2 = k64s_kernel<2, 4, 8, 3, Epi::CONV, true>("K64S_SRC2"),
     // 256 x 256 k-tile 64, 16 waves of 64 x 64, 2-stage ring.  (8 waves with 128 x 64 per wave, 25 % fewer LDS fragment bytes, 192 VGPRs: measured
     // 3-5 % slower than 16 waves of 64 x 64) and the wave-specialised form (8 consumers of 128 x 64 + 4 producers, 168 VGPRs, 2-stage ring): -2 % on
     // layer4's 3x3, +14 % on the stride-2 downsample dgrad -- a 256 x 256 tile has no room for producers beside 16 consumers (1024 threads per workgroup)
-    K64{kfn(&igemm_conv_k64_kernel<4, 4, 2>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
-    K64_LIN{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::LIN>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
-    K64_FUSED{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::FUSED>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
-    K64_CLS{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::PARITY>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_CLASSES},
-    K64_SRC2{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::CONV, true>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
-    K64_FUSED_SRC2{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 4, Epi::FUSED, true>), 1024, ring_lds(256, 256, 64, 2), 256, 256, GRID_XCD},
-    // 256 x 320 k-tile 64 (conv_prefers_320)
-    K64_320{kfn(&igemm_conv_k64_kernel<4, 4, 2, 4, 5, Epi::LIN>), 1024, ring_lds(256, 320, 64, 2), 256, 320, GRID_XCD};
+    K64 = ring_kernel<64, 4, 4, 4, 4, 2, 4, true, Epi::CONV>("K64"),
+    K64_LIN = ring_kernel<64, 4, 4, 4, 4, 2, 4, true, Epi::LIN>("K64_LIN"),
+    K64_FUSED = ring_kernel<64, 4, 4, 4, 4, 2, 4, true, Epi::FUSED>("K64_FUSED"),
+    K64_CLS = ring_kernel<64, 4, 4, 4, 4, 2, 4, true, Epi::PARITY>("K64_CLS"),
+    K64_SRC2 = ring_kernel<64, 4, 4, 4, 4, 2, 4, true, Epi::CONV, true>("K64_SRC2"),
+    K64_FUSED_SRC2 = ring_kernel<64, 4, 4, 4, 4, 2, 4, true, Epi::FUSED, true>("K64_FUSED_SRC2"),
+    // 256 x 320 k-tile 64 (conv_prefers_320): 16 waves of 64 x 80
+    K64_320 = ring_kernel<64, 4, 4, 4, 5, 2, 4, true, Epi::LIN>("K64_320");
 
 // the persistent streaming kernel (fused1x1.h): two result buffers for K <= 128, else one.  It takes launches with a residual, an output mask or
 // mask bits, or with a second operand tensor and none of the three: F1[K > 128][residual][out_mask][bits_out], the none slot the SRC2 instantiation
 template <int RB, bool RES, bool OM, bool BITS, bool SRC2 = false>
 static GemmKernel f1_kernel() {
-    return {kfn(&fused1x1_persist_kernel<3, RB, RES, OM, BITS, SRC2>), (F1_NC + F1_NP + F1_NR) * 64, f1_lds_bytes(3, RB, RB == 2 ? 128 : F1_KMAX),
+    static char name[32];
+    snprintf(name, sizeof name, "F1_RB%d%s%s%s%s", RB, RES ? "_RES" : "", OM ? "_MASK" : "", BITS ? "_BITS" : "", SRC2 ? "_SRC2" : "");
+    return {name, kfn(&fused1x1_persist_kernel<3, RB, RES, OM, BITS, SRC2>), (F1_NC + F1_NP + F1_NR) * 64, f1_lds_bytes(3, RB, RB == 2 ? 128 : F1_KMAX),
             F1_TM, F1_TN, GRID_CUS, 0, RB};
 }
 static const GemmKernel F1[2][2][2][2] = {
@@ -2431,28 +2375,28 @@ static const GemmKernel F1[2][2][2][2] = {
 
 // Weight gradient (WGradArgs): split-K slabs of Cm x Ntot tiles.
 static const GemmKernel
-    WG_BN{kfn(&igemm_wgrad_kernel<true>), 256, 0, 128, 128, GRID_SPLITS},          // register-staged: an operand transform (in_scale)
-    WG_PLAIN{kfn(&igemm_wgrad_kernel<false>), 256, 0, 128, 128, GRID_SPLITS},      // register-staged: tensors beyond 2 GiB
+    WG_BN{"WG_BN", kfn(&igemm_wgrad_kernel<true>), 256, 0, 128, 128, GRID_SPLITS},          // register-staged: an operand transform (in_scale)
+    WG_PLAIN{"WG_PLAIN", kfn(&igemm_wgrad_kernel<false>), 256, 0, 128, 128, GRID_SPLITS},      // register-staged: tensors beyond 2 GiB
     // the 3x3 halo kernel (128 co x 64 ci x 9 taps per block), one 8-wave block per CU.  3 stages x 24 KiB (4 and 5 measured the same, before and
     // after the inline-asm reads: the k-step is bound by its 26 transposing reads + 36 MFMAs per wave, two waves per SIMD).  (measured and removed,
     // round 3: the same kernel software-pipelined -- layer4 conv2 161 us against 152 -- and as two wave groups half a k-step apart, 195 us.  PMC on
     // this kernel at the layer4 shape: matrix pipe busy 45 % of the SIMD cycles, LDS active 23 % (28 % of that bank conflicts), waves parked at
     // s_waitcnt / barriers 26 % of their cycles: neither the issue order nor the LDS bounds it.)
-    WG_3X3{kfn(&igemm_wgrad3x3_kernel<3>), 512, 3 * W3_STAGE * 2, 128, 9 * 64, GRID_SPLITS8, 256};
+    WG_3X3{"WG_3X3", kfn(&igemm_wgrad3x3_kernel<3>), 512, 3 * W3_STAGE * 2, 128, 9 * 64, GRID_SPLITS8, 256};
 static const GemmKernel WG_DMA[2] = {         // [colsum]: 128 x 128 / 4 waves, LDS-DMA
-    {kfn(&igemm_wgrad_dma_kernel<false>), 256, 0, 128, 128, GRID_SPLITS8},
-    {kfn(&igemm_wgrad_dma_kernel<true>), 256, 0, 128, 128, GRID_SPLITS8}};
+    {"WG_DMA", kfn(&igemm_wgrad_dma_kernel<false>), 256, 0, 128, 128, GRID_SPLITS8},
+    {"WG_DMA_COLSUM", kfn(&igemm_wgrad_dma_kernel<true>), 256, 0, 128, 128, GRID_SPLITS8}};
 static const GemmKernel WG_WG[2] = {          // [colsum]: 128 x 256 / 8 waves, 3 stages x 3 images x 8 KiB, two workgroups per CU
-    {kfn(&igemm_wgrad_wg_kernel<2, 4, 3>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_SPLITS8, 512},
-    {kfn(&igemm_wgrad_wg_kernel<2, 4, 3, true>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_SPLITS8, 512}};
+    {"WG_WG", kfn(&igemm_wgrad_wg_kernel<2, 4, 3>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_SPLITS8, 512},
+    {"WG_WG_COLSUM", kfn(&igemm_wgrad_wg_kernel<2, 4, 3, true>), 512, ring_lds(128, 256, 32, 3), 128, 256, GRID_SPLITS8, 512}};
 // [flat][colsum]: the pipelined wave-specialised 128 x 256 kernel, 6 stages x 3 images x 8 KiB, one workgroup per CU.  (measured, interleaved:
 // plain [P][C] operands 92 us with 4 consumers of 128 x 64 + 4 producers against 94 with 8 + 8 and 105 before; strided / gathered operands 83 us
 // with 4 producers of 6 pieces, 75 with 8 of 3)
 static const GemmKernel WG_P[2][2] = {
-    {{kfn(&igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6>), 1024, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256},
-     {kfn(&igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6, true>), 1024, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256}},
-    {{kfn(&igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6>), 512, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256},
-     {kfn(&igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6, true>), 512, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256}}};
+    {{"WG_P", kfn(&igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6>), 1024, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256},
+     {"WG_P_COLSUM", kfn(&igemm_wgrad_p_kernel<2, 4, 4, 4, 8, 6, true>), 1024, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256}},
+    {{"WG_P_FLAT", kfn(&igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6>), 512, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256},
+     {"WG_P_FLAT_COLSUM", kfn(&igemm_wgrad_p_kernel<1, 4, 8, 4, 4, 6, true>), 512, ring_lds(128, 256, 32, 6), 128, 256, GRID_SPLITS8, 256}}};
 
 // A chosen launch: the kernel, its tile counts and grid; with k == nullptr a refusal (rc, and the message format `why` of one int argument)
 struct GemmChoice {
@@ -2642,9 +2586,9 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
     const int K = a.g.nr * a.g.ns * a.g.Ck;
     char what[160] = "";
     if (g_prof)
-        snprintf(what, sizeof what, "%s,Cm=%d,K=%d,P=%d,taps=%d,stride=%d,sub=%d,fused=%d,stats=%d,res=%d,mask=%d,lin=%d", a.g.mode ? "dgrad" : "fwd", a.Cm, K, a.P,
-                 a.g.R * a.g.S, a.g.stride, a.g.sub, a.out_scale ? 1 : 0, a.stats ? 1 : 0, a.Res ? 1 : 0, (a.res_mask || a.out_mask) ? 1 : 0,
-                 (a.bias || a.row_scale || a.act) ? 1 : 0);
+        snprintf(what, sizeof what, "%s,Cm=%d,K=%d,P=%d,taps=%d,stride=%d,sub=%d,fused=%d,stats=%d,res=%d,mask=%d,lin=%d,kernel=%s", a.g.mode ? "dgrad" : "fwd",
+                 a.Cm, K, a.P, a.g.R * a.g.S, a.g.stride, a.g.sub, a.out_scale ? 1 : 0, a.stats ? 1 : 0, a.Res ? 1 : 0, (a.res_mask || a.out_mask) ? 1 : 0,
+                 (a.bias || a.row_scale || a.act) ? 1 : 0, c.k ? c.k->name : "refused");
     ProfScope prof_scope(st, 0, a.g.sub == 2 ? 2.0 * a.Cm * (double)a.P * a.g.R * a.g.S * a.g.Ck : 2.0 * a.Cm * (double)a.P * K, what);
     if (!c.k) return c.refuse();
     const int stat_tiles = a.stats ? igemm_conv_stat_tiles(a.Cm, a.P, K, a.in_scale != nullptr) : c.tiles_n;      // the slab the caller sized
@@ -2660,10 +2604,11 @@ static int launch_igemm_conv_one(hipStream_t st, const IGemmArgs& a) {
 // kr = (ph+pad) mod 2 + 2i, ks likewise, so each of the four classes is a dense stride-1-like problem on a quarter of
 // the pixels with 1, 2, 2 and 4 of a 3x3 kernel's 9 taps (the un-split form multiplies 3/4 zero operands).  A class
 // without taps (1x1 kernels: three of four) contributes nothing; it is skipped when the residual is accumulated in
-// place (Res == O), otherwise the un-split path is used.
-int launch_igemm_conv(hipStream_t st, const IGemmArgs& a) {
+// place (Res == O), otherwise the un-split path is used.  `one` receives every launch the problem becomes, in order, and ends the walk with a
+// non-zero status.
+template <class One>
+static int conv_for_each_launch(const IGemmArgs& a, One&& one) {
     IGemmArgs args = a;
-    args.stamps = g_conv_stamps;
     GatherGeom& g = args.g;
     g.sub = 0; g.oph = g.opw = 0; g.Hfull = g.Hout; g.Wfull = g.Wout;
     g.r0 = 0; g.rstep = 1; g.nr = g.R; g.s0 = 0; g.sstep = 1; g.ns = g.S;
@@ -2684,7 +2629,7 @@ int launch_igemm_conv(hipStream_t st, const IGemmArgs& a) {
             s.g.Hout = g.Hout / 2; s.g.Wout = g.Wout / 2; s.P = a.P / 4;
             s.g.r0 = s.g.s0 = 0; s.g.rstep = s.g.sstep = 2;
             s.g.nr = nr[0] > nr[1] ? nr[0] : nr[1]; s.g.ns = ns[0] > ns[1] ? ns[0] : ns[1];      // the longest class picks the kernel
-            return launch_igemm_conv_one(st, s);
+            return one(s);
         }
         if (all_have || (a.Res != nullptr && a.Res == a.O)) {
             for (int ph = 0; ph < 2; ++ph)
@@ -2695,13 +2640,18 @@ int launch_igemm_conv(hipStream_t st, const IGemmArgs& a) {
                     s.g.Hout = g.Hout / 2; s.g.Wout = g.Wout / 2; s.P = a.P / 4;
                     s.g.r0 = (ph + g.pad) & 1; s.g.rstep = 2; s.g.nr = nr[ph];
                     s.g.s0 = (pw + g.pad) & 1; s.g.sstep = 2; s.g.ns = ns[pw];
-                    const int rc = launch_igemm_conv_one(st, s);
+                    const int rc = one(s);
                     if (rc) return rc;
                 }
             return DALI_OK;
         }
     }
-    return launch_igemm_conv_one(st, args);
+    return one(args);
+}
+int launch_igemm_conv(hipStream_t st, const IGemmArgs& a) {
+    IGemmArgs args = a;
+    args.stamps = g_conv_stamps;
+    return conv_for_each_launch(args, [&](const IGemmArgs& s) { return launch_igemm_conv_one(st, s); });
 }
 
 // Tile shape of the weight-gradient GEMM (measured per layer, scripts/bench_convs.py): 0 = 128 x 128 / 4 waves,
@@ -2905,6 +2855,41 @@ static int fill_geom(GatherGeom& g, int n_img, int Hin, int Win, int Ck, int Hou
     g.lw = g.lhw = -1;
     (void)n_img;
     return 0;
+}
+
+// Diagnostic (include/daliid_debug.h): the table entries a forward / data-gradient / linear problem is launched on, without launching: the
+// operands are stand-in addresses that nothing dereferences (the chooser only asks which of them are present).
+extern "C" int dali_debug_conv_kernel_name(int Cm, int P, int h, int wd, int ck, int r, int s, int stride, int pad, int mode, int flags, int ck1, int x_rep,
+                                           int n_cus, char* out, int cap) {
+    DALI_REQUIRE(out && cap > 0 && Cm > 0 && P > 0 && ck > 0 && (mode == 0 || mode == 1) && (stride == 1 || stride == 2), "dali_debug_conv_kernel_name: bad argument");
+    static char here[4];
+    const auto stand_in = [&](int bit, int i) { return (flags & bit) ? here + i : nullptr; };
+    IGemmArgs a{};
+    a.W = reinterpret_cast<const uint16_t*>(here); a.X = a.W; a.O = reinterpret_cast<uint16_t*>(here + 1);
+    a.Cm = Cm; a.P = P;
+    if (mode == 0) fill_geom(a.g, 0, h, wd, ck, (h + 2 * pad - r) / stride + 1, (wd + 2 * pad - s) / stride + 1, r, s, stride, pad, 0);
+    else fill_geom(a.g, 0, (h + 2 * pad - r) / stride + 1, (wd + 2 * pad - s) / stride + 1, ck, h, wd, r, s, stride, pad, 1);
+    a.stats = reinterpret_cast<float*>(stand_in(DALI_DEBUG_CONV_STATS, 2));
+    a.Res = reinterpret_cast<const uint16_t*>(stand_in(DALI_DEBUG_CONV_RES, 2));
+    a.res_mask = reinterpret_cast<const uint8_t*>(stand_in(DALI_DEBUG_CONV_RES_MASK, 2));
+    a.out_mask = reinterpret_cast<const uint8_t*>(stand_in(DALI_DEBUG_CONV_OUT_MASK, 2));
+    a.bits_out = reinterpret_cast<uint8_t*>(stand_in(DALI_DEBUG_CONV_BITS, 2));
+    a.out_scale = a.out_shift = reinterpret_cast<const float*>(stand_in(DALI_DEBUG_CONV_FUSED, 2));
+    a.out_relu = (flags & DALI_DEBUG_CONV_FUSED) ? 1 : 0;
+    a.act = (flags & DALI_DEBUG_CONV_LIN) ? 1 : 0;
+    if (ck1 > 0) { a.X2 = a.X; a.Ck1 = ck1; a.x_rep = x_rep; }
+    std::string names;
+    const int rc = conv_for_each_launch(a, [&](const IGemmArgs& one) {
+        const GemmChoice c = conv_choose(one, n_cus);
+        if (!c.k) return c.refuse();
+        names += names.empty() ? "" : "+";
+        names += c.k->name;
+        return (int)DALI_OK;
+    });
+    if (rc) return rc;
+    DALI_REQUIRE((int)names.size() < cap, "dali_debug_conv_kernel_name: the name takes %d bytes", (int)names.size() + 1);
+    snprintf(out, (size_t)cap, "%s", names.c_str());
+    return DALI_OK;
 }
 
 // ---- single-op C ABI (used by the parity tests; the net plan calls the launchers directly) ----------------

@@ -132,7 +132,7 @@ __global__ __launch_bounds__((F1_NC + F1_NP + F1_NR) * 64) void fused1x1_persist
         const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.X), 0, (int)((long long)P * Ck1 * 2), 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(SRC2 ? a.X2 : a.X), 0, (int)((long long)P * (SRC2 ? Ck2 : Ck1) * 2), 0x00020000);
         // a DMA piece = 8 rows x 128 bytes; LDS slot `lane` of piece q = row 8q + (lane >> 3), physical chunk lane & 7 = logical chunk ^ ((row >> 1) & 7)
-        // (the k-tile-64 image of igemm_conv_k64_kernel); q = pw + F1_NP i has the parity of pw, so the logical chunk is the same for all of a lane's pieces
+        // (the k-tile-64 image of igemm_conv_ring_kernel); q = pw + F1_NP i has the parity of pw, so the logical chunk is the same for all of a lane's pieces
         const int r_in = lane >> 3;
         const int kc = (lane & 7) ^ (((pw & 1) << 2) | (r_in >> 1));
         constexpr int NPC = F1_TM / 8 / F1_NP;                        // pieces per producer, operand and k-step: 4

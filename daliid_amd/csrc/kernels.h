@@ -55,7 +55,7 @@ struct IGemmArgs {
     int out_relu;
     uint8_t* bits_out;        // 1 bit per output element, bit e & 7 of byte e >> 3, e = p*Cm + c (the layout of res_mask)
     const uint8_t* out_mask;  // same layout
-    // ---- second operand tensor (the SRC2 instantiations of igemm_conv_dma_kernel; 1x1 / stride 1 only) ----
+    // ---- second operand tensor (the SRC2 instantiations of igemm_conv_ring_kernel and igemm_conv_k64s_kernel; 1x1 / stride 1 only) ----
     // The GEMM's K dimension is the concatenation of X's Ck1 channels and X2's g.Ck - Ck1 channels, both [P][channels] bf16 (plain rows):
     // O = [X | X2] W^T with W [Cm][g.Ck].  Two chained data gradients that accumulate into the same output (bnlin.hip: dz (A.W3) and
     // -a2 (W3^T diag(Q) W3)) become one launch and the partial result is never stored.

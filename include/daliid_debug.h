@@ -26,6 +26,27 @@ int dali_debug_set_conv_stamps(void* dev_ptr);
 /* the split count the weight-gradient plan picks for a layer (returned as the status value, >= 1) */
 int dali_debug_wgrad_splits(int Cm, int Ntot, int P, int taps, int halo_w);
 
+/* Which entries of the kernel table (daliid_amd/csrc/conv.hip, GemmKernel::name) a forward / data-gradient / linear-layer GEMM is launched on:
+ * the launcher's parity split of a stride-2 data gradient and the kernel chooser, no launch and no HIP call, so it runs without a GPU.
+ * Problem: Cm output channels x P pixels; the geometry as dali_conv2d_fwd (mode 0: h x wd input images of ck channels) or dali_conv2d_dgrad
+ * (mode 1: h x wd images of dx, ck channels of dy) takes it, a linear layer of `rows` rows as h = wd = r = s = stride = 1, pad = 0, P = rows,
+ * ck = K; flags: what the launch carries; ck1 > 0: a second operand tensor (IGemmArgs::X2: ck1 channels in the first, x_rep weight images);
+ * n_cus: the CU count the persistent kernel's grid is sized by (a multiple of 8).  The residual is a tensor of its own (not accumulated in
+ * place), and the launcher's check of the statistics slab is not run.
+ * -> DALI_OK and the names in `out`, joined by '+' when the split makes several launches; the chooser's refusal status (message:
+ * dali_last_error) otherwise */
+enum {
+    DALI_DEBUG_CONV_STATS = 1,      /* BatchNorm statistics epilogue */
+    DALI_DEBUG_CONV_FUSED = 2,      /* fused output stage: scale, shift, ReLU */
+    DALI_DEBUG_CONV_RES = 4,        /* residual */
+    DALI_DEBUG_CONV_RES_MASK = 8,   /* 1-bit gate of the residual (dali_conv2d_dgrad) */
+    DALI_DEBUG_CONV_OUT_MASK = 16,  /* 1-bit gate of the output (fused stage) */
+    DALI_DEBUG_CONV_BITS = 32,      /* (value > 0) bits written (fused stage) */
+    DALI_DEBUG_CONV_LIN = 64        /* linear-layer extras (GELU) */
+};
+int dali_debug_conv_kernel_name(int Cm, int P, int h, int wd, int ck, int r, int s, int stride, int pad, int mode, int flags, int ck1, int x_rep,
+                                int n_cus, char* out, int cap);
+
 /* the split-K reduce alone: out[e] (+)= sum_k partial[k][e], fixed order (tests/test_gpu_conv.py, scripts/bench_reduce.py) */
 int dali_debug_splitk_reduce(void* stream, const float* partial, float* out, long long elems, int splits, int accumulate);
 

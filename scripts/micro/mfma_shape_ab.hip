@@ -1,4 +1,4 @@
-// Micro-benchmark: the fragment-read + MFMA part of the 256 x 256 k-tile-64 convolution kernel (igemm_conv_k64_kernel<4,4,2>:
+// Micro-benchmark: the fragment-read + MFMA part of the 256 x 256 k-tile-64 convolution kernel (igemm_conv_ring_kernel, table entry K64:
 // 16 waves of 64 x 64, LDS image [rows][64 bf16] with the chunk ^ ((row >> 1) & 7) swizzle, one barrier per 64-deep k-step) with
 // v_mfma_f32_16x16x32_bf16 (what every kernel in csrc/ uses) against v_mfma_f32_32x32x16_bf16 on the SAME per-wave tile, LDS image and
 // data.  No DMA refill: the operands stay in LDS, so this isolates issue slots, LDS reads and the clock the chip holds per shape

@@ -35,7 +35,7 @@ CASES = [
     (128, 32, 16, 256, 256, 3, 3, 2, 1),  # layer3 conv2 (stride 2) at full pixel count: parity-split dgrad, its 4-tap class on the specialised kernel
     (2, 16, 16, 64, 64, 3, 3, 1, 1),      # 64 -> 64 3x3 on the halo-patch kernel (igemm_conv_halo64_kernel): one 256-pixel tile per image, W = 16
     (3, 64, 32, 64, 64, 3, 3, 1, 1),      # layer1 conv2's geometry (64 x 32 images, 8 tiles each): forward and data gradient on the halo-patch kernel
-    (33, 32, 16, 160, 512, 3, 3, 1, 1),   # fwd 256x256 with Cin % 64 != 0 (K = 1440, P = 16896): the k-tile-32 16-wave kernel (igemm_conv_wg_kernel<4, 4, 4>)
+    (33, 32, 16, 160, 512, 3, 3, 1, 1),   # fwd 256x256 with Cin % 64 != 0 (K = 1440, P = 16896): the k-tile-32 16-wave 4-stage ring (table entry WG256)
     (129, 32, 16, 512, 256, 3, 3, 2, 1),  # stride-2 dgrad into 512 channels, 16512 pixels per parity class, 4-tap class K = 1024: 256x256 k-tile 64, class grid
     (65, 30, 34, 256, 128, 1, 1, 2, 0),   # strided 1x1, P = 65 x 15 x 17 = 16575: weight gradient on the pipelined 128 x 256 kernel's general (non-flat) gather
 ]

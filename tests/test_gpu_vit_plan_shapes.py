@@ -123,12 +123,12 @@ def _dgelu_bound(ref, acc):
 # 1: every ViT-B/16 linear at its plan size, bit for bit
 # ---------------------------------------------------------------------------------------------------------------------------
 # (name, rows, K, N).  Tile configuration (conv.hip conv_pick_cfg / conv_prefers_320, default environment) and epilogue paths:
-#  patch 25088 x 768 -> 768, bias:  conv_prefers_320 -> 256 x 320 k-tile 64 (igemm_conv_k64_kernel<4,4,2,4,5,1>), 3 x 79 tiles; interior
+#  patch 25088 x 768 -> 768, bias:  conv_prefers_320 -> 256 x 320 k-tile 64 (table entry K64_320: igemm_conv_ring_kernel, 16 waves of 64 x 80, Epi::LIN), 3 x 79 tiles; interior
 #        tiles: the staged column-block store (conv_epilogue_cols), the last row tile (128 of 320 rows): the general path.
-#  qkv   25216 x 768 -> 2304, bias:  256 x 256 k-tile 64 without linear extras (igemm_conv_k64_kernel<4,4,2>), 9 x 99 tiles; interior:
+#  qkv   25216 x 768 -> 2304, bias:  256 x 256 k-tile 64 without linear extras (K64), 9 x 99 tiles; interior:
 #        the lean staged store (bias folded), last row tile (128 of 256 rows): the general path.
 #  proj  25216 x 768 -> 768, bias + residual + row_scale:  256 x 320 (as patch); columns store / general path (last tile: 256 of 320 rows).
-#  fc1   25216 x 768 -> 3072, bias + GELU + O2:  256 x 256 k-tile 64 with linear extras (igemm_conv_k64_kernel<4,4,2,4,4,1>), 12 x 99
+#  fc1   25216 x 768 -> 3072, bias + GELU + O2:  256 x 256 k-tile 64 with linear extras (K64_LIN), 12 x 99
 #        tiles; interior: the half-tile "linear-layer extras" block, last row tile: the general path.
 #  fc2   25216 x 3072 -> 768, bias + residual + row_scale:  conv_pick_cfg says 256 x 256 (K >= 1024), conv_prefers_320 overrides it:
 #        256 x 320, as proj.
