@@ -93,7 +93,8 @@ _SIGNATURES = {
     "dali_layernorm_fwd": [c_void_p] * 5 + [c_int, c_int, c_float] + [c_void_p] * 3,
     "dali_layernorm_bwd": [c_void_p] * 8 + [c_int, c_int] + [c_void_p] * 3,
     "dali_attention_fwd": [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p],
-    "dali_attention_fwd_short": [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p],
+    "dali_attention_fwd_long": [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p],
+    "dali_attention_fwd_short":[c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p, c_void_p],
     "dali_attention_bwd": [c_void_p] * 6 + [c_int] * 4 + [c_float, c_void_p],
     "dali_center_loss_fwd": [c_void_p] * 6 + [c_float, c_int, c_int, c_void_p, c_void_p],
     "dali_center_loss_bwd": [c_void_p] * 6 + [c_float, c_int, c_int, c_void_p, c_float, c_void_p],

@@ -202,6 +202,8 @@ int launch_rowscale_add(hipStream_t st, const uint16_t* branch, const float* sca
                         uint16_t* out);
 int launch_expand_rowscale(hipStream_t st, const float* scale, int n_vec, int B, int T, float* out);
 int launch_attention_fwd(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse);
+// 1 <= T <= 1024, forward only: key chunks of 256 under an online softmax (launch_attention_fwd routes T > 256 here)
+int launch_attention_fwd_long(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse);
 // T <= 64 (the JPM local sequences): the 4-tile instance of the forward kernel
 int launch_attention_fwd_short(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse);
 // SIE / JPM (vit_pytorch.py:316-331, 382-396; make_models.py:221-377)

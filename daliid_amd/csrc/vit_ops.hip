@@ -812,6 +812,118 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_dkv_kernel(const uin
 template <int NTILE> constexpr size_t att2_lds() { return (size_t)2 * NTILE * 16 * ATT_LD * 2 + 2 * NTILE * 16 * 4; }
 static_assert(2 * att2_lds<16>() <= 163840, "two attention workgroups per CU");
 
+// ------------------------------------------------------------------------------------------------
+// Forward past 256 tokens (eval only; 257 = 256x256 at stride 16, 311 = 384x128 at stride 12, 577 = 384x384 at stride 16; up to ATT_FWD_MAX_T).
+// One workgroup per (batch, head, block of 128 queries): eight waves, one 16-query tile each, walk the keys in chunks of 256 = 16 tiles.  A chunk's
+// body is the NTILE = 16 instance of attention_fwd2_kernel -- s[16] in registers, S^T = K Q^T, the same plain [256][72] images of K and V -- under
+// an online softmax: per query a running maximum m and sum l (fp32); each chunk rescales l and the output accumulators by alpha = 2^(m_old - m_new),
+// adds P = 2^(s - m_new) rounded to bf16 UNNORMALISED as the operand of P V, and the one multiply by 1 / l comes last, in fp32, before the one
+// rounding of the output.  Registers: s (64) and the output accumulators (16) are live together at the end of the score phase, where
+// attention_fwd2_kernel<16, 8> holds s alone in 107 VGPRs; left to itself the scheduler fetches K and V fragments far ahead and spills 10 to 16
+// VGPRs at the 128 that two workgroups per CU allow.  The sched_barriers below keep it to one score tile at a time: 128 VGPRs, no scratch.
+//
+// Barriers: nothing between kernel entry and the end of the chunk loop depends on the wave's query tile -- no break, no return, no continue.  A wave
+// whose tile lies past T (T = 257: query block 2 holds one live query in wave 0, waves 1 .. 7 are idle) reads zero query fragments (frag_g), runs
+// every chunk with all 64 lanes, reaches both barriers of every chunk, and only its stores are predicated off (row < T).  The chunk count depends
+// on T alone, so all waves of a workgroup agree on it.
+// Who owns what: after the __shfl_xor reductions m, l and alpha of query i live in the lanes with (lane & 15) == i.  attention_fwd2_kernel's
+// O = P V leaves lane (g, i) with rows 4 g + r of O -- four OTHER queries, whose alpha would have to be fetched across lanes.  Here the two MFMA
+// operands swap places: O^T = V^T P^T.  The A and B fragments of a 16 x 16 x 32 MFMA have the same shape (index lane & 15, eight k slots per lane
+// group), so frag_tr2 of V serves as A (row = head column d) exactly as it served as B, the packed probabilities serve as B (column = query i),
+// and the accumulator of lane (g, i) holds columns 16 d + 4 g + r of query i: alpha and 1 / l are the lane's OWN, no shuffle, and a lane stores
+// four adjacent bf16 (8 bytes) per d.
+// Infinities: keys past T score -inf.  The chunks number ceil(T / 256), so each chunk's first key is a real one and its score is finite (a product
+// of finite bf16 values; an idle wave's is 0): m_new is finite from the first chunk on.  There m_old = -inf gives alpha = 2^-inf = 0 (times l = 0 and
+// o = 0), afterwards m_old is finite: (-inf) - (-inf) needs m_old = m_new = -inf and is never formed, neither in alpha nor in s - m_new.
+// ------------------------------------------------------------------------------------------------
+constexpr int ATT_FWD_MAX_T = 1024;
+constexpr int ATT_LONG_CHUNK = 256, ATT_LONG_QBLOCK = 128;
+constexpr size_t ATT_LONG_LDS = (size_t)2 * ATT_LONG_CHUNK * ATT_LD * 2;
+static_assert(ATT_LONG_LDS == 73728 && 2 * ATT_LONG_LDS <= 163840, "two long-attention workgroups per CU");
+
+__global__ __launch_bounds__(512, 4) void attention_fwd_long_kernel(const uint16_t* __restrict__ qkv, int B, int T, int H, float scale,
+                                                                    uint16_t* __restrict__ out, float* __restrict__ lse) {
+    constexpr int NTILE = ATT_LONG_CHUNK / 16;
+    extern __shared__ __attribute__((aligned(16))) uint16_t sm[];
+    uint16_t* sK = sm;
+    uint16_t* sV = sK + ATT_LONG_CHUNK * ATT_LD;
+    const int nqb = (T + ATT_LONG_QBLOCK - 1) / ATT_LONG_QBLOCK;
+    const int bh = blockIdx.x / nqb, qb = blockIdx.x - bh * nqb, b = bh / H, h = bh - b * H;
+    const int C = H * ATT_HD, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t rs = (size_t)3 * C;
+    const uint16_t* base = qkv + (size_t)b * T * rs + h * ATT_HD;
+    const int q0 = qb * ATT_LONG_QBLOCK + wave * 16;                 // may lie past T: zero fragments, no stores, every barrier
+    const bf16x8_t qa0 = frag_g(base, rs, q0, 0, T, lane), qa1 = frag_g(base, rs, q0, 32, T, lane);
+    const float sc2 = scale * 1.44269504088896f;                     // exp(x) = 2^(x log2 e)
+    float m = -__builtin_inff(), l = 0.f;                            // of query q0 + (lane & 15)
+    f32x4_t o[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};      // O^T: o[d][r] = column 16 d + 4 (lane >> 4) + r of the same query
+    for (int k0 = 0; k0 < T; k0 += ATT_LONG_CHUNK) {
+        const int left = T - k0;                                     // >= 1: keys k0 .. k0 + min(left, 256) - 1 are real
+        __syncthreads();                                             // every wave is done with the previous chunk's K and V
+        att_load_tile<ATT_LONG_CHUNK>(base + C + (size_t)k0 * rs, rs, left, sK);
+        att_load_tile<ATT_LONG_CHUNK>(base + 2 * C + (size_t)k0 * rs, rs, left, sV);
+        __syncthreads();
+        f32x4_t s[NTILE];
+        float mc = -__builtin_inff();
+#pragma unroll
+        for (int j = 0; j < NTILE; ++j) {
+            f32x4_t a = {0.f, 0.f, 0.f, 0.f};
+            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_k(sK, ATT_LD, j * 16, 0, lane), qa0, a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_k(sK, ATT_LD, j * 16, 32, lane), qa1, a, 0, 0, 0);
+            const int key0 = j * 16 + (lane >> 4) * 4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { a[r] = (key0 + r < left) ? a[r] * sc2 : -__builtin_inff(); mc = fmaxf(mc, a[r]); }
+            s[j] = a;
+            __builtin_amdgcn_sched_barrier(0);                       // one tile's K fragments in flight, and no V fragments fetched ahead (see above)
+        }
+        mc = fmaxf(mc, __shfl_xor(mc, 16, 64)); mc = fmaxf(mc, __shfl_xor(mc, 32, 64));
+        const float m_new = fmaxf(m, mc);                            // finite: the chunk's key 0 is real
+        const float alpha = __builtin_amdgcn_exp2f(m - m_new);       // first chunk: 2^-inf = 0
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[d][r] *= alpha;            // this lane's own alpha: o is transposed (see above)
+        float lc = 0.f;
+#pragma unroll
+        for (int jp = 0; jp < NTILE / 2; ++jp) {                     // a pair of score tiles: 2^(s - m), summed in fp32, rounded to bf16, into P V
+            const int j0 = 2 * jp, j1 = 2 * jp + 1;
+            float pa[4], pb[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                pa[r] = __builtin_amdgcn_exp2f(s[j0][r] - m_new); pb[r] = __builtin_amdgcn_exp2f(s[j1][r] - m_new);
+                lc += pa[r]; lc += pb[r];
+            }
+            const bf16x8_t pf = pack_frag(pa, pb);
+#pragma unroll
+            for (int d = 0; d < 4; ++d) o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr2(sV, ATT_LD, j0 * 16, j1 * 16, d * 16, lane), pf, o[d], 0, 0, 0);
+        }
+        lc += __shfl_xor(lc, 16, 64); lc += __shfl_xor(lc, 32, 64);
+        l = l * alpha + lc;
+        m = m_new;
+    }
+    const int row = q0 + (lane & 15);
+    if (row < T) {
+        const float inv_l = 1.0f / l;                                // l >= 1: the maximum's own term is 2^0
+        if (lane < 16 && lse) lse[(size_t)bh * T + row] = (m + log2f(l)) * 0.6931471805599453f;       // natural-log lse = max + log(sum)
+        uint16_t* orow = out + ((size_t)b * T + row) * C + h * ATT_HD + (lane >> 4) * 4;
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            *reinterpret_cast<uint2*>(orow + d * 16) = make_uint2(pack_bf16x2(o[d][0] * inv_l, o[d][1] * inv_l), pack_bf16x2(o[d][2] * inv_l, o[d][3] * inv_l));
+    }
+}
+int launch_attention_fwd_long(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse) {
+    if (T < 1 || T > ATT_FWD_MAX_T) {
+        set_error("attention: %d tokens exceed the limit of %d", T, ATT_FWD_MAX_T);
+        return DALI_ERR_LIMIT;
+    }
+    const int nqb = (T + ATT_LONG_QBLOCK - 1) / ATT_LONG_QBLOCK;
+    if (B < 1 || H < 1 || (int64_t)B * H * nqb > 0x7fffffff) { set_error("attention: bad batch / heads (%d, %d)", B, H); return DALI_ERR_INVALID; }
+    DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_fwd_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LONG_LDS));
+    hipLaunchKernelGGL(attention_fwd_long_kernel, dim3(B * H * nqb), dim3(512), ATT_LONG_LDS, st, qkv, B, T, H, scale, out, lse);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+
 template <int NTILE, int NW>
 static int att2_fwd_launch(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse) {
     constexpr size_t lds = att2_lds<NTILE>();
@@ -835,8 +947,7 @@ int launch_attention_fwd(hipStream_t st, const uint16_t* qkv, int B, int T, int 
     if (T <= 208) return att2_fwd_launch<13, 7>(st, qkv, B, T, H, scale, out, lse);
     if (T <= 224) return att2_fwd_launch<14, 7>(st, qkv, B, T, H, scale, out, lse);
     if (T <= 256) return att2_fwd_launch<16, 8>(st, qkv, B, T, H, scale, out, lse);
-    set_error("attention: %d tokens exceed the limit of %d", T, ATT_MAX_T);
-    return DALI_ERR_LIMIT;
+    return launch_attention_fwd_long(st, qkv, B, T, H, scale, out, lse);       // forward only, up to ATT_FWD_MAX_T; refuses beyond
 }
 // The JPM local branch runs 4 B sequences of 1 + L tokens (33 at 256x128 / stride 16, 53 at stride 12, 50 at 224x224): a 4-tile instance of the
 // same kernel, four waves, 16 tile pairs per head where the 13-tile instance walks 169.  launch_attention_fwd's routing is unchanged.
@@ -921,8 +1032,14 @@ extern "C" int dali_layernorm_bwd(dali_ctx* ctx, void* stream, const uint16_t* g
 extern "C" int dali_attention_fwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
                                   uint16_t* out, float* lse) {
     DALI_REQUIRE(ctx && qkv && out, "dali_attention_fwd: null argument");
-    DALI_REQUIRE(head_dim == ATT_HD && T > 0 && T <= ATT_MAX_T, "dali_attention_fwd: head_dim must be %d and T <= %d (got %d, %d)", ATT_HD, ATT_MAX_T, head_dim, T);
+    DALI_REQUIRE(head_dim == ATT_HD && T > 0, "dali_attention_fwd: head_dim must be %d and T >= 1 (got %d, %d)", ATT_HD, head_dim, T);
     return launch_attention_fwd((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
+}
+extern "C" int dali_attention_fwd_long(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
+                                       uint16_t* out, float* lse) {
+    DALI_REQUIRE(ctx && qkv && out, "dali_attention_fwd_long: null argument");
+    DALI_REQUIRE(head_dim == ATT_HD && T > 0, "dali_attention_fwd_long: head_dim must be %d and T >= 1 (got %d, %d)", ATT_HD, head_dim, T);
+    return launch_attention_fwd_long((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
 }
 extern "C" int dali_attention_fwd_short(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
                                         uint16_t* out, float* lse) {

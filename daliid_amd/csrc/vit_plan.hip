@@ -12,7 +12,9 @@
 //   JPM (make_models.build_transformer_local, make_models.py:221-377), eval mode only: b1 / b2 = block + norm copies, the shifted and
 //   shuffled patch tokens cut into four runs that share b2, five BatchNorm1d necks, output [B][5C].
 // A local_feature / JPM plan never runs a backward, so it reserves none of the backward's buffers (dgrad weight images, weight-gradient slab,
-// reduction partials, DropPath rows, gradient buffers) and its refresh_weights only casts.
+// reduction partials, DropPath rows, gradient buffers) and its refresh_weights only casts.  The same holds for any plan with more than 256 tokens
+// (up to 1024: 384x128 at stride 12 = 311, 256x256 at stride 16 = 257): only the attention FORWARD exists there, so a training forward and the
+// backward entries return DALI_ERR_LIMIT before their first launch.
 #include "kernels.h"
 #include "plan_table.h"
 #include <cstdio>
@@ -63,9 +65,18 @@ struct dali_vit : PlanTable {
     float *gf2 = nullptr, *fin2_mean = nullptr, *fin2_rstd = nullptr;
     int n_stages = 1;
     std::vector<int> stage_first_block;   // backward stage s runs blocks [stage_first_block[s+1], stage_first_block[s]) downwards
+    bool eval_only = false;               // local_feature / JPM, or more than VIT_TRAIN_MAX_T tokens: none of the backward's buffers
 };
 
 namespace {
+// The attention forward runs up to 1024 tokens (launch_attention_fwd), its backward up to 256: a longer plan is an eval plan.
+constexpr int VIT_MAX_T = 1024, VIT_TRAIN_MAX_T = 256;
+// the training forward and every backward entry ask this before their first launch
+int refuse_long_training(const dali_vit* n) {
+    if (n->T <= VIT_TRAIN_MAX_T) return DALI_OK;
+    set_error("training needs at most %d tokens (this plan has %d); eval mode only", VIT_TRAIN_MAX_T, n->T);
+    return DALI_ERR_LIMIT;
+}
 void add_lin(dali_vit* n, Lin& l, const std::string& name, int K, int N) {
     l.K = K; l.N = N;
     l.w_off = n->add_param(name + ".weight", {N, K});
@@ -104,7 +115,9 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
     if (n->ext.jpm) n->ext.local_feature = 1;            // make_models.py:243: the JPM base is built with local_feature = cfg.MODEL.JPM
     const int ny = (cfg->height - cfg->patch) / cfg->stride + 1, nx = (cfg->width - cfg->patch) / cfg->stride + 1;
     n->B = cfg->batch; n->np = ny * nx; n->T = n->np + 1; n->C = cfg->dim; n->H = cfg->heads; n->rows = n->B * n->T;
-    if (n->T > 256) { set_error("dali_vit_create: %d tokens exceed the attention kernel's limit of 256", n->T); delete n; return DALI_ERR_LIMIT; }
+    if (n->T > VIT_MAX_T) { set_error("dali_vit_create: %d tokens exceed the attention kernel's limit of %d", n->T, VIT_MAX_T); delete n; return DALI_ERR_LIMIT; }
+    // past VIT_TRAIN_MAX_T tokens only the attention forward exists: an eval plan, reserved like a local_feature one
+    n->eval_only = n->ext.local_feature != 0 || n->T > VIT_TRAIN_MAX_T;
     const int C = n->C, Kp = 3 * cfg->patch * cfg->patch;
     n->cls_off = n->add_param("base.cls_token", {1, 1, C});
     n->pos_off = n->add_param("base.pos_embed", {1, n->T, C});
@@ -156,7 +169,7 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
     n->reserve(n->patches, (size_t)n->B * n->np * Kp * 2);
     n->reserve(n->pe, (size_t)n->B * n->np * C * 2);
     n->reserve(n->x0, rows * C * 2);
-    const bool eval_only = n->ext.local_feature != 0;
+    const bool eval_only = n->eval_only;
     if (!eval_only) n->reserve(n->patch.wt, (size_t)Kp * C * 2);          // unused (images need no gradient) but keeps Lin uniform
     // the weight-gradient workspace is sized for every linear layer the backward runs (patch embedding, then each block's four)
     WGradNeed need = linear_wgrad_need(n->B * n->np, Kp, C, true);
@@ -238,7 +251,7 @@ extern "C" int dali_vit_refresh_weights(dali_vit* n, void* stream) {
     if (rc) return rc;
     // b1 / b2 read their bf16 weights from the same image (the cast above covers them)
     if (n->ext.jpm) DALI_HIP(hipMemcpyAsync(n->map_dev, n->map_host.data(), n->map_host.size() * 4, hipMemcpyHostToDevice, st));
-    if (n->ext.local_feature) return DALI_OK;            // eval only: no dgrad images
+    if (n->eval_only) return DALI_OK;                    // local_feature / JPM / more than 256 tokens: no dgrad images
     std::vector<TransposeJob> jobs;                      // every linear's dgrad image [K][N], batched launches (48 single launches cost 0.3 ms)
     for (auto& b : n->blocks) {
         Lin* ls[4] = {&b.qkv, &b.proj, &b.fc1, &b.fc2};
@@ -273,6 +286,7 @@ extern "C" int dali_vit_forward(dali_vit* n, void* stream, const float* images, 
 extern "C" int dali_vit_forward_ex(dali_vit* n, void* stream, const float* images, const int32_t* sie_idx, int training, float* feat, float* global_feat,
                                    float* tokens_out) {
     DALI_REQUIRE(n && n->P && images, "dali_vit_forward: null argument or net not bound");
+    if (training) { const int lim = refuse_long_training(n); if (lim) return lim; }
     const bool local = n->ext.local_feature != 0, jpm = n->ext.jpm != 0;
     if (local && !jpm) {
         // vit_pytorch.py:393-396 returns the tokens and nothing else: there is no cls feature and no neck output to write
@@ -419,7 +433,9 @@ int bwd_tokens(dali_vit* n, hipStream_t st) {
 }  // namespace
 
 extern "C" int dali_vit_backward_stages(dali_vit* n, void* stream, const float* d_feat, int stage_begin, int stage_end) {
-    DALI_REQUIRE(n && n->P && n->G, "dali_vit_backward: null argument or net not bound");
+    DALI_REQUIRE(n, "dali_vit_backward: null argument or net not bound");
+    { const int lim = refuse_long_training(n); if (lim) return lim; }
+    DALI_REQUIRE(n->P && n->G, "dali_vit_backward: null argument or net not bound");
     DALI_REQUIRE(!n->ext.local_feature, "dali_vit_backward: a local_feature / JPM net is eval only (its train-mode forward feeds an ID loss that is out of scope)");
     DALI_REQUIRE(n->fwd_training, "dali_vit_backward: the last forward was not in training mode");
     DALI_REQUIRE(stage_begin >= 0 && stage_end < n->n_stages && stage_begin <= stage_end, "dali_vit_backward: bad stage range %d..%d", stage_begin, stage_end);
@@ -440,6 +456,7 @@ extern "C" int dali_vit_backward_stages(dali_vit* n, void* stream, const float* 
 // ---- diagnostics (include/daliid_debug.h) ----
 extern "C" int dali_debug_vit_backward_block(dali_vit* n, void* stream, const float* d_feat, int block) {
     DALI_REQUIRE(n && n->P && n->G, "dali_debug_vit_backward_block: null argument or net not bound");
+    { const int lim = refuse_long_training(n); if (lim) return lim; }
     DALI_REQUIRE(!n->ext.local_feature, "dali_debug_vit_backward_block: a local_feature / JPM net is eval only");
     DALI_REQUIRE(n->fwd_training, "dali_debug_vit_backward_block: the last forward was not in training mode");
     const int depth = (int)n->blocks.size();

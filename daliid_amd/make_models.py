@@ -8,11 +8,13 @@ eval forward returns ``[B, 5 * 768]``.  SIE camera / view embeddings follow ``cf
 Out of scope: ``Backbone`` (broken in the reference, make_models.py:63) and JPM's train-mode forward (classifier scores for an
 ID loss the trainer never uses).
 """
+import os
+
 import numpy as np
 import torch
 
 from ._lib import DaliError
-from .vit_pytorch import ViTNeckNet
+from .vit_pytorch import ViTNeckNet, load_base_param
 
 _GEOM = {  # factory name -> (embed_dim, depth, heads, mlp_ratio)   (vit_pytorch.py:453-476)
     "vit_base_patch16_224_TransReID": (768, 12, 12, 4.0),
@@ -52,7 +54,7 @@ def _base_kwargs(cfg, camera_num, view_num, depth, device, seed, who):
         raise NotImplementedError("%s: transformer type %r is out of scope (head_dim 64 ViT-B only)" % (who, name))
     if getattr(cfg.MODEL, "DROP_OUT", 0.0) != 0.0 or getattr(cfg.MODEL, "ATT_DROP_RATE", 0.0) != 0.0:
         raise NotImplementedError("%s: dropout is not supported" % who)
-    if cfg.MODEL.PRETRAIN_CHOICE == 'imagenet':
+    if cfg.MODEL.PRETRAIN_CHOICE == 'imagenet' and not os.path.isfile(str(cfg.MODEL.PRETRAIN_PATH)):
         raise NotImplementedError("%s: ImageNet checkpoint loading needs a file fetched from the network; "
                                   "load a state_dict with load_state_dict instead" % who)
     dim, geom_depth, heads, ratio = _GEOM[name]
@@ -61,6 +63,15 @@ def _base_kwargs(cfg, camera_num, view_num, depth, device, seed, who):
                 num_heads=heads, mlp_ratio=ratio, num_classes=1000, drop_path_rate=cfg.MODEL.DROP_PATH, device=device, seed=seed,
                 camera=camera_num if cfg.MODEL.SIE_CAMERA else 0, view=view_num if cfg.MODEL.SIE_VIEW else 0,      # make_models.py:135-142
                 sie_xishu=cfg.MODEL.SIE_COE)
+
+
+def _load_pretrained(model, cfg):
+    """make_models.py:150-152, :245-247: with PRETRAIN_CHOICE 'imagenet' the base loads cfg.MODEL.PRETRAIN_PATH (a local file, checked in _base_kwargs)
+    through TransReID.load_param: head / dist keys skipped, pos_embed resized to this geometry."""
+    if cfg.MODEL.PRETRAIN_CHOICE == 'imagenet':
+        load_base_param(model, cfg.MODEL.PRETRAIN_PATH)
+        model._copy_jpm_branches()                       # make_models.py:247-258 copies the block and norm after the base has loaded
+        print('Loading pretrained ImageNet model......from {}'.format(cfg.MODEL.PRETRAIN_PATH))
 
 
 class _Checkpoints:
@@ -90,6 +101,7 @@ class build_transformer(_Checkpoints, ViTNeckNet):
         super().__init__(**_base_kwargs(cfg, camera_num, view_num, depth, device, seed, "build_transformer"))
         self.neck, self.neck_feat, self.cos_layer = cfg.MODEL.NECK, cfg.TEST.NECK_FEAT, cfg.MODEL.COS_LAYER
         self.num_classes, self.ID_LOSS_TYPE = num_classes, cfg.MODEL.ID_LOSS_TYPE
+        _load_pretrained(self, cfg)
 
 
 class build_transformer_local(_Checkpoints, ViTNeckNet):
@@ -112,6 +124,7 @@ class build_transformer_local(_Checkpoints, ViTNeckNet):
         print("JPM head: %d runs of %d tokens, shift %d, %d shuffle groups%s" % (divide, token_map.shape[1], shift, groups, "" if rearrange else " (not rearranged)"))
         self.neck, self.neck_feat, self.cos_layer = cfg.MODEL.NECK, cfg.TEST.NECK_FEAT, cfg.MODEL.COS_LAYER
         self.num_classes, self.ID_LOSS_TYPE = num_classes, cfg.MODEL.ID_LOSS_TYPE
+        _load_pretrained(self, cfg)
 
     def forward(self, x, label=None, cam_label=None, view_label=None):
         if self.training:

@@ -155,6 +155,18 @@ def attention_fwd_short(qkv, B, T, H, scale=None):
     return out, lse
 
 
+def attention_fwd_long(qkv, B, T, H, scale=None, with_lse=True):
+    """The chunked forward (key chunks of 256 under an online softmax), 1 <= T <= 1024; attention_fwd routes T > 256 to it.
+    with_lse=False hands the kernel a null lse and returns (out, None)."""
+    hd = qkv.shape[1] // (3 * H)
+    scale = hd ** -0.5 if scale is None else scale
+    out = torch.empty(B * T, H * hd, device=qkv.device, dtype=bf16)
+    lse = torch.empty(B * H, T, device=qkv.device, dtype=torch.float32) if with_lse else None
+    _lib.check(_lib.lib().dali_attention_fwd_long(_lib.ctx(qkv.device), _lib.stream_ptr(), _lib.ptr(qkv, bf16, "qkv"), B, T, H, hd, float(scale),
+                                                   _lib.ptr(out), _lib.ptr(lse)), "dali_attention_fwd_long")
+    return out, lse
+
+
 def jpm_head(glob, loc, necks=None):
     """glob fp32 [B, C], loc fp32 [4*B, C] -> [B, 5C] (make_models.py:351-377).  necks = (gamma, beta, running_mean, running_var), each fp32
     [5, C]: the 'after' flavour; None: the raw features ('before')."""

@@ -7,7 +7,9 @@ feature so the reference's key names (``cls_token``, ``pos_embed``, ``patch_embe
 
 Supported: drop / attn_drop = 0; SIE camera / view embeddings (vit_pytorch.py:316-331, 382-387: ``sie_embed`` added to every token as
 ``sie_xishu * sie_embed[index]``, trained through ``dali_vit_sie_grad``); ``local_feature=True`` (:393-396: ``blocks[:-1]``, all tokens, no
-final norm; eval mode only).  ``make_models.build_transformer_local`` puts the JPM head on the same plan.  DropPath (vit_pytorch.py:45-62; per-block rate
+final norm; eval mode only).  ``make_models.build_transformer_local`` puts the JPM head on the same plan.  Geometries up to 1024 tokens
+(384x128 at stride 12 = 311, 256x256 at stride 16 = 257, 384x384 at stride 16 = 577); past 256 tokens a model is eval only, its train-mode
+forward raises.  ``resize_pos_embed`` / ``TransReID.load_param`` (vit_pytorch.py:410-450) bring a checkpoint of another size in.  DropPath (vit_pytorch.py:45-62; per-block rate
 ``linspace(0, drop_path_rate, depth)``, :338) is applied in training mode: one uniform draw per (branch, sample) on the
 device per step, scale = floor(keep + u) / keep; ``drop_path_uniform`` can be set to inject the draws (parity tests hand
 the same ones to the oracle).  In eval mode it is the identity, as in the reference.
@@ -20,6 +22,9 @@ import torch
 from torch import nn
 
 from . import _lib
+
+
+TRAIN_MAX_TOKENS = 256      # the attention backward's limit; the forward alone (eval mode) runs up to 1024 tokens
 
 
 class _VitCfg(ctypes.Structure):
@@ -170,19 +175,25 @@ class ViTNeckNet(nn.Module):
                     p.fill_(1.0)                       # LayerNorm / BatchNorm weights
                 else:
                     p.zero_()                          # every bias
-            if self._ext.get("jpm"):
-                # make_models.py:249-258: b1 and b2 start as deep copies of the last block and the final norm
-                sd = self.state_dict()
-                last = "base.blocks.%d." % (self._geom[3] - 1)
-                for name in self._param_names:
-                    if name.startswith(("b1.0.", "b2.0.")):
-                        sd[name].copy_(sd[last + name[5:]])
-                    elif name.startswith(("b1.1.", "b2.1.")):
-                        sd[name].copy_(sd["base.norm." + name[5:]])
+            self._copy_jpm_branches()
             self.flat_buffers.zero_()
             for name, b in self.named_buffers():
                 if name.endswith("running_var"):
                     b.fill_(1.0)
+        self.mark_weights_changed()
+
+    def _copy_jpm_branches(self):
+        """make_models.py:249-258: b1 and b2 start as deep copies of the last block and the final norm (of the pretrained base, when one was loaded)"""
+        if not self._ext.get("jpm"):
+            return
+        with torch.no_grad():
+            sd = self.state_dict()
+            last = "base.blocks.%d." % (self._geom[3] - 1)
+            for name in self._param_names:
+                if name.startswith(("b1.0.", "b2.0.")):
+                    sd[name].copy_(sd[last + name[5:]])
+                elif name.startswith(("b1.1.", "b2.1.")):
+                    sd[name].copy_(sd["base.norm." + name[5:]])
         self.mark_weights_changed()
 
     def mark_weights_changed(self):
@@ -301,11 +312,19 @@ class ViTNeckNet(nn.Module):
             for name, p in zip(self._param_names, self.parameters()):
                 p.grad = self._grad_views[name] if p.requires_grad else None
 
+    @property
+    def num_tokens(self):
+        return int(self.base.pos_embed.shape[1])
+
     def forward(self, x, label=None, cam_label=None, view_label=None):
         """make_models.py:184-205: returns the post-neck ``feat``."""
         self._refuse_tokens_only("forward()")
         idx = self.sie_index(cam_label, view_label, x.shape[0])
         if self.training and torch.is_grad_enabled():
+            if self.num_tokens > TRAIN_MAX_TOKENS:
+                # past 256 tokens only the attention forward exists (the plan holds none of the backward's buffers)
+                raise _lib.DaliError("training needs at most %d tokens (this model has %d): it is eval mode only -- call .eval() and run under "
+                                     "torch.no_grad()" % (TRAIN_MAX_TOKENS, self.num_tokens))
             return _VitFn.apply(x, self._anchor, self, idx)
         return self._run_forward(x, self.training, sie_idx=idx)
 
@@ -351,12 +370,68 @@ class TransReID(nn.Module):
         full.update({"base." + k: v for k, v in sd.items()})
         return self.net.load_state_dict(full, strict=strict)
 
+    def load_param(self, model_path):
+        """vit_pytorch.py:410-434, see load_base_param."""
+        return load_base_param(self.net, model_path)
+
     def forward(self, x, cam_label=None, view_label=None):
         if self.local_feature:
             if self.training and torch.is_grad_enabled():
                 raise NotImplementedError("TransReID(local_feature=True) is eval only: call .eval() or run under torch.no_grad()")
             return self.net.local_tokens(x, cam_label, view_label)
         return self.net.global_feat(x, cam_label, view_label)
+
+
+def load_base_param(net, model_path):
+    """``TransReID.load_param`` (vit_pytorch.py:410-434) on the ``base.*`` entries of a ViTNeckNet: load a pretrained ViT checkpoint (a local
+    file) in place.  ``'model'`` / ``'state_dict'`` wrappers are unwrapped, keys containing ``head`` or ``dist`` are skipped, a 2-D patch
+    projection (from before the conv patchification) is reshaped, and ``pos_embed`` of another token grid is resized (resize_pos_embed).  As
+    in the reference a key this model lacks, or one whose shape does not fit, is reported and left out, not fatal; the list of those keys is
+    returned."""
+    param_dict = torch.load(model_path, map_location="cpu")
+    for wrapper in ("model", "state_dict"):
+        if wrapper in param_dict:
+            param_dict = param_dict[wrapper]
+    own = {key[len("base."):]: v for key, v in net.state_dict().items() if key.startswith("base.")}
+    ps, st = net._geom[0], net._geom[1]
+    num_y, num_x = (net.img_size[0] - ps) // st + 1, (net.img_size[1] - ps) // st + 1
+    left_out = []
+    with torch.no_grad():
+        for k, v in param_dict.items():
+            if "head" in k or "dist" in k:
+                continue
+            if "patch_embed.proj.weight" in k and v.dim() < 4:
+                O, _, H, W = own["patch_embed.proj.weight"].shape
+                v = v.reshape(O, -1, H, W)
+            elif k == "pos_embed" and v.shape != own["pos_embed"].shape:
+                if "distilled" in str(model_path):      # a distilled checkpoint carries a second (distillation) token after cls
+                    v = torch.cat([v[:, 0:1], v[:, 2:]], dim=1)
+                v = resize_pos_embed(v, own["pos_embed"], num_y, num_x)
+            if k not in own or tuple(own[k].shape) != tuple(v.shape):
+                print("load_param: left out %s: checkpoint %s vs model %s" % (k, tuple(v.shape), tuple(own[k].shape) if k in own else None))
+                left_out.append(k)
+                continue
+            own[k].copy_(v.to(own[k].device, own[k].dtype))
+    net.mark_weights_changed()
+    return left_out
+
+
+def resize_pos_embed(posemb, posemb_new, height, width):
+    """vit_pytorch.py:436-450: position embedding [1, 1 + g*g, C] of a square g x g patch grid -> [1, 1 + height*width, C].  The cls row is
+    kept, the grid is interpolated bilinearly (align_corners=False, torch's default) to height x width.  Host-side torch, on posemb's device;
+    ``posemb_new`` only has to be the target tensor (its token count must be 1 + height*width)."""
+    if posemb.dim() != 3 or posemb.shape[0] != 1:
+        raise ValueError("resize_pos_embed: posemb must be [1, tokens, C], got %s" % (tuple(posemb.shape),))
+    gs_old = int(math.sqrt(posemb.shape[1] - 1))
+    if gs_old * gs_old != posemb.shape[1] - 1:
+        raise ValueError("resize_pos_embed: %d patch tokens are not a square grid" % (posemb.shape[1] - 1))
+    if posemb_new.shape[1] != 1 + height * width:
+        raise ValueError("resize_pos_embed: the target holds %d tokens, not 1 + %d x %d" % (posemb_new.shape[1], height, width))
+    cls_row, grid = posemb[:, :1], posemb[0, 1:]
+    grid = grid.reshape(1, gs_old, gs_old, -1).permute(0, 3, 1, 2)
+    grid = torch.nn.functional.interpolate(grid, size=(height, width), mode="bilinear")
+    grid = grid.permute(0, 2, 3, 1).reshape(1, height * width, -1)
+    return torch.cat([cls_row, grid], dim=1)
 
 
 def vit_base_patch16_224_TransReID(img_size=(256, 128), stride_size=16, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.1, camera=0, view=0,

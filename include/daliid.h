@@ -437,9 +437,16 @@ int dali_layernorm_fwd(dali_ctx* ctx, void* stream, const uint16_t* x, const flo
 int dali_layernorm_bwd(dali_ctx* ctx, void* stream, const uint16_t* g, const uint16_t* x, const float* gamma, const float* mean,
                        const float* rstd, const uint16_t* add, int rows, int C, uint16_t* dx, float* dgamma, float* dbeta);
 /* Attention (vit_pytorch.py:152-164): qkv [B*T][3*H*64] -> out [B*T][H*64] = softmax(q k^T * scale) v per head, scores on chip;
- * lse [B*H][T] (row log-sum-exp) feeds the backward, which recomputes the probabilities.  T <= 208, head_dim 64. */
+ * lse [B*H][T] (row log-sum-exp, natural log; nullable in the forward) feeds the backward, which recomputes the probabilities.  head_dim 64.
+ * Forward: 1 <= T <= 1024.  T <= 256 keeps a head's K and V in LDS (one workgroup per batch and head); 256 < T <= 1024 goes to the chunked
+ * kernel of dali_attention_fwd_long; beyond 1024 DALI_ERR_LIMIT, nothing launched.  Backward: T <= 256 (a longer sequence is eval only). */
 int dali_attention_fwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
                        uint16_t* out, float* lse);
+/* The chunked forward on its own, 1 <= T <= 1024 (DALI_ERR_LIMIT beyond): one workgroup per (batch, head, 128 queries) walks the keys in
+ * chunks of 256 under an online softmax (running maximum and sum in fp32, probabilities rounded to bf16 unnormalised, one division at the
+ * end).  Same operands and layouts as dali_attention_fwd; lse may be NULL.  Not bitwise equal to the T <= 256 kernels. */
+int dali_attention_fwd_long(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
+                            uint16_t* out, float* lse);
 int dali_attention_bwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out, const float* lse,
                        int B, int T, int H, int head_dim, float scale, uint16_t* dqkv);
 /* The forward for short sequences, T <= 64 (the JPM local runs: 33 / 53 / 50 tokens): a 4-tile instance of the same kernel. */
@@ -604,7 +611,10 @@ int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void** ptr, int
 /* ---- net plan: TransReID ViT + BN neck (make_models.build_transformer.forward, make_models.py:184-205) ----- *
  * Same storage contract as dali_resnet_*.  forward: images fp32 NCHW -> feat fp32 [batch, dim] (after the
  * BatchNorm1d neck); global_feat (nullable) receives the pre-neck cls feature.  Dropout is the identity (rate 0).
- * Limits: head_dim 64, at most 256 tokens. */
+ * Limits: head_dim 64, at most 1024 tokens (DALI_ERR_LIMIT beyond).  A plan with more than 256 tokens is an EVAL plan: it reserves none of the
+ * backward's buffers, refresh_weights only casts, and dali_vit_forward_ex with training != 0, dali_vit_backward and dali_vit_backward_stages
+ * return DALI_ERR_LIMIT before any launch ("training needs at most 256 tokens (this plan has N); eval mode only").  Plans with at most 256
+ * tokens are what they were, size for size. */
 typedef struct dali_vit dali_vit;
 typedef struct {
     int batch, height, width;   /* images fp32 NCHW [batch,3,height,width] */
