@@ -1,5 +1,6 @@
-"""Mirror of the reference's ``Encoders.py`` for the path in scope: ``getDCNN("resnet50")`` and
-``ResNet50ReID`` (Encoders.py:25-48, 306-351), backed by the native HIP net plan (``dali_resnet_*`` in
+"""Mirror of the reference's ``Encoders.py`` for the paths in scope: ``getDCNN("resnet50")`` with ``ResNet50ReID`` (Encoders.py:25-48,
+306-351) and, eval only, ``getDCNN("resnet50IBN" | "resnet101IBN")`` with ``ResNet50IBNReID`` / ``ResNet101IBNReID`` (:462-603),
+backed by the native HIP net plan (``dali_resnet_*`` in
 include/daliid.h) instead of torchvision + cuDNN.
 
 What is kept from the reference surface
@@ -30,14 +31,23 @@ class _Cfg(ctypes.Structure):
                 ("layers", ctypes.c_int * 4), ("width_base", ctypes.c_int)]
 
 
+class _Ext(ctypes.Structure):
+    """dali_resnet_ext (include/daliid.h): the stages whose bottlenecks are IBN-a blocks."""
+    _fields_ = [("ibn", ctypes.c_int * 4)]
+
+
 class _Plan:
     """One dali_resnet plan for a fixed (batch, H, W)."""
 
-    def __init__(self, device, batch, height, width, layers, width_base):
+    def __init__(self, device, batch, height, width, layers, width_base, ibn=None):
         self.key = (batch, height, width)
         cfg = _Cfg(batch, height, width, (ctypes.c_int * 4)(*layers), width_base)
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib().dali_resnet_create(_lib.ctx(device), ctypes.byref(cfg), ctypes.byref(h)), "dali_resnet_create")
+        if ibn is not None:                      # dali_resnet_create_ex; all zero is dali_resnet_create's plan
+            ext = _Ext((ctypes.c_int * 4)(*[int(bool(v)) for v in ibn]))
+            _lib.check(_lib.lib().dali_resnet_create_ex(_lib.ctx(device), ctypes.byref(cfg), ctypes.byref(ext), ctypes.byref(h)), "dali_resnet_create_ex")
+        else:
+            _lib.check(_lib.lib().dali_resnet_create(_lib.ctx(device), ctypes.byref(cfg), ctypes.byref(h)), "dali_resnet_create")
         self.h = h
         pe, be, ab = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         fd, np_, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
@@ -100,6 +110,9 @@ def default_parts(map_rows):
 class ResNet50ReID(nn.Module):
     """Encoders.ResNet50ReID (Encoders.py:306-351) on the HIP net plan."""
 
+    _ibn = None                              # dali_resnet_ext.ibn of this class' plans (None: dali_resnet_create)
+    _own_prefixes = ("last_bn.",)           # what a trunk handed in as model_base does not carry
+
     def __init__(self, model_base=None, layers=(3, 4, 6, 3), width=64, device=None, seed=None):
         super().__init__()
         if device is None:
@@ -125,6 +138,8 @@ class ResNet50ReID(nn.Module):
         self._param_names = []
         self._bn_modules = []
         for name, off, numel, shape in probe.tensor_table(0):
+            if name == "last_bn.weight":
+                self._add_unplanned_modules()
             leaf, attr = self._leaf(name)
             view = self._view(self.flat_params, off, numel, shape)
             leaf.register_parameter(attr, nn.Parameter(view))
@@ -150,12 +165,16 @@ class ResNet50ReID(nn.Module):
         Anything else missing or unexpected is an error, as in a strict load."""
         sd = {k: v for k, v in sd.items() if not k.startswith("fc.")}
         res = self.load_state_dict(sd, strict=False)
-        missing = [k for k in res.missing_keys if not k.startswith("last_bn.")]
+        missing = [k for k in res.missing_keys if not k.startswith(self._own_prefixes)]
         if missing or res.unexpected_keys:
-            raise _lib.DaliError("ResNet50ReID(model_base): model_base is not a ResNet-50 trunk (missing %s, unexpected %s)"
-                                 % (missing[:4], list(res.unexpected_keys)[:4]))
+            raise _lib.DaliError("%s(model_base): model_base is not a trunk of this architecture (missing %s, unexpected %s)"
+                                 % (type(self).__name__, missing[:4], list(res.unexpected_keys)[:4]))
 
     # ---- construction helpers -------------------------------------------------------------------
+    def _add_unplanned_modules(self):
+        """Modules of the reference class that sit between ``layer4`` and ``last_bn`` in its state_dict and that no forward runs
+        (none for ResNet50ReID); called once, when the parameter table reaches ``last_bn``."""
+
     @staticmethod
     def _view(flat, off, numel, shape):
         v = flat[off:off + numel]
@@ -177,8 +196,10 @@ class ResNet50ReID(nn.Module):
         """torchvision's ResNet init: conv kaiming_normal_(fan_out, relu); BN weight 1 / bias 0; stats 0 / 1."""
         gen = torch.Generator(device="cpu")
         gen.manual_seed(int(seed) if seed is not None else int(torch.initial_seed()) & 0x7fffffff)
+        params = dict(self.named_parameters())
         with torch.no_grad():
-            for name, p in self.named_parameters():
+            for name in self._param_names:               # the plan's tensors, in table order
+                p = params[name]
                 if p.dim() == 4:
                     o, i, r, s = p.shape
                     std = (2.0 / (o * r * s)) ** 0.5
@@ -216,7 +237,7 @@ class ResNet50ReID(nn.Module):
         key = (batch, height, width)
         p = self._plans.get(key)
         if p is None:
-            p = self._plans[key] = _Plan(self._device, batch, height, width, self._layers, self._width)
+            p = self._plans[key] = _Plan(self._device, batch, height, width, self._layers, self._width, self._ibn)
         return p
 
     def _activate(self, plan):
@@ -332,6 +353,61 @@ class ResNet50ReID(nn.Module):
         return self._run_forward(x, training=self.training)
 
 
+class ResNet50IBNReID(ResNet50ReID):
+    """Encoders.ResNet50IBNReID (Encoders.py:462-531) over IBN-Net's ``resnet50_ibn_a``: the bottlenecks of layer1-3 carry ``bn1 = IBN(planes)``,
+    InstanceNorm2d (affine, per-sample statistics in eval mode too) on the first half of the channels and BatchNorm2d on the rest; layer4 is
+    plain.  State-dict keys, order and shapes are the reference's, the four modules it builds and never calls included
+    (``conv1x1_layer4``, ``conv1x1_squeeze_layer4``, ``conv1x1_expand_layer4``, ``attribute_classifier``: plain parameters outside the plan,
+    ``grad`` None).
+
+    EVAL ONLY: the plan has no half-channel batch statistics and no instance-norm backward, so a forward in train mode raises
+    ``NotImplementedError``; call ``.eval()``.  ``model_base``: an IBN-a trunk (Module or state_dict), ``fc.*`` dropped."""
+
+    _ibn = (1, 1, 1, 0)
+    _own_prefixes = ("last_bn.", "conv1x1_layer4.", "conv1x1_squeeze_layer4.", "conv1x1_expand_layer4.", "attribute_classifier.")
+
+    def __init__(self, model_base=None, layers=(3, 4, 6, 3), width=64, device=None, seed=None):
+        super().__init__(model_base, layers, width, device, seed)
+
+    def _add_unplanned_modules(self):
+        # literal shapes, as in the reference (Encoders.py:483-487), whatever `width` is
+        dev = self._device
+        self.conv1x1_layer4 = nn.Conv2d(2048, 1, (1, 1), stride=1, device=dev)
+        self.conv1x1_squeeze_layer4 = nn.Conv2d(4096, 1024, (1, 1), stride=1, device=dev)
+        self.conv1x1_expand_layer4 = nn.Conv2d(1024, 2048, (1, 1), stride=1, device=dev)
+        self.attribute_classifier = nn.Linear(2048, 88, bias=True, device=dev)
+
+    def reset_parameters(self, seed=None):
+        """The plan's tensors as ResNet50ReID (``IN.weight`` 1, ``IN.bias`` 0); the unused modules uniform in +-1/sqrt(fan_in), from the seed."""
+        super().reset_parameters(seed)
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed((int(seed) if seed is not None else int(torch.initial_seed())) + 1 & 0x7fffffff)
+        with torch.no_grad():
+            for prefix in self._own_prefixes[1:]:
+                mod = getattr(self, prefix[:-1])
+                bound = (mod.weight[0].numel()) ** -0.5
+                for p in (mod.weight, mod.bias):
+                    p.copy_(((torch.rand(p.shape, generator=gen) * 2 - 1) * bound).to(p.device))
+
+    def attach_grads(self):
+        raise NotImplementedError("%s is eval only (IBN-a blocks have no backward here): there are no gradients to attach; call .eval()" % type(self).__name__)
+
+    def forward(self, x, multipart=False, attention_map=False):
+        """-> [B, 2048].  ``multipart`` and ``attention_map`` are accepted and IGNORED, as the reference's IBN classes ignore them
+        (Encoders.py:492-515); body parts, the three poolings and the heat map come from ``forward_heads``."""
+        if self.training:
+            raise NotImplementedError("%s is eval only: training an IBN-a net needs half-channel batch statistics and an instance-norm backward, "
+                                      "which the plan does not have; call .eval()" % type(self).__name__)
+        return self._run_forward(x, training=False)
+
+
+class ResNet101IBNReID(ResNet50IBNReID):
+    """Encoders.ResNet101IBNReID (Encoders.py:534-603) over ``resnet101_ibn_a``: ResNet50IBNReID at depth (3, 4, 23, 3)."""
+
+    def __init__(self, model_base=None, layers=(3, 4, 23, 3), width=64, device=None, seed=None):
+        super().__init__(model_base, layers, width, device, seed)
+
+
 class _DataParallelShim(nn.Module):
     """Keeps the reference's ``nn.DataParallel`` object protocol (``.module``, ``module.``-prefixed keys) for a
     one-GPU-per-process design."""
@@ -357,12 +433,13 @@ def getEnsembles(gpu_indexes):
 
 def getDCNN(gpu_indexes, model_name, embedding_size=None):
     """Encoders.getDCNN (Encoders.py:25-48, 241): -> (model_online, model_momentum), both eval()."""
-    if model_name != "resnet50":
-        raise NotImplementedError("getDCNN: only model_name='resnet50' is in scope of this build (got %r)" % model_name)
+    nets = {"resnet50": ResNet50ReID, "resnet50IBN": ResNet50IBNReID, "resnet101IBN": ResNet101IBNReID}      # (the IBN-a pairs are eval only)
+    if model_name not in nets:
+        raise NotImplementedError("getDCNN: model_name must be one of %s in this build (got %r)" % (sorted(nets), model_name))
     if embedding_size not in (None, 2048):
-        raise NotImplementedError("getDCNN: embedding_size is fixed at 2048 for resnet50")
+        raise NotImplementedError("getDCNN: embedding_size is fixed at 2048 for %s" % model_name)
     dev = torch.device("cuda", gpu_indexes[0] if len(gpu_indexes) else 0)
-    model_source = _DataParallelShim(ResNet50ReID(device=dev))
-    model_momentum = _DataParallelShim(ResNet50ReID(device=dev))
+    model_source = _DataParallelShim(nets[model_name](device=dev))
+    model_momentum = _DataParallelShim(nets[model_name](device=dev))
     model_momentum.load_state_dict(model_source.state_dict())
     return model_source.eval(), model_momentum.eval()

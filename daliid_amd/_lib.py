@@ -69,6 +69,7 @@ _SIGNATURES = {
     "dali_bn_finalize": [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "dali_bn_act": [c_void_p] * 9 + [c_int, ctypes.c_int64, c_int, c_void_p, c_void_p],
+    "dali_ibn_act": [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p],
     "dali_bn_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_int64, c_int] + [c_void_p] * 16,
     "dali_maxpool_bn_fwd": [c_void_p] * 5 + [c_int] * 4 + [c_void_p, c_void_p],
     "dali_maxpool_bn_bwd": [c_void_p] * 8 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p],
@@ -117,6 +118,7 @@ _SIGNATURES = {
     "dali_gemm_profile_begin": [c_void_p, c_int],
     "dali_gemm_profile_end": [c_void_p, c_void_p, c_void_p, c_void_p],
     "dali_resnet_create": [c_void_p, c_void_p, ctypes.POINTER(c_void_p)],
+    "dali_resnet_create_ex": [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p)],
     "dali_resnet_destroy": [c_void_p],
     "dali_resnet_set_feature": [c_void_p, c_int],
     "dali_resnet_sizes": [c_void_p] + [c_void_p] * 6,

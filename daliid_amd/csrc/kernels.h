@@ -143,6 +143,9 @@ int launch_fold_cat_weights(hipStream_t st, const float* w3, const float* wd, co
                             int cin, int parts, uint16_t* wcat, float* shcat);
 int launch_bn_act(hipStream_t st, const uint16_t* raw, const float* scale, const float* shift, const uint16_t* idn, const uint16_t* raw2,
                   const float* scale2, const float* shift2, int relu, size_t elems, int C, uint16_t* y, uint8_t* mask_out);
+// IBN-a's bn1 + ReLU in one launch (dali_ibn_act): instance statistics on channels [0, c_in), the rest passes through; y may be x
+int launch_ibn_act(hipStream_t st, const uint16_t* x, int n, int hw, int C, int c_in, const float* gamma, const float* beta, float eps, int relu,
+                   uint16_t* y, float* mean, float* invstd);
 int bn_bwd_blocks(int P, int C, int* rows_per_block);
 size_t bn_bwd_partial_floats(int P, int C, bool dual);
 int launch_bn_bwd(hipStream_t st, const uint16_t* g, const uint16_t* ymask, const uint8_t* ybits, const BnBwdSide& a, const BnBwdSide* b, int relu, int P, int C,

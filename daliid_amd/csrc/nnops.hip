@@ -4,6 +4,7 @@
 // BatchNorm1d neck (Encoders.py:350), weight casts/transposes.  All activations NHWC bf16, math fp32.
 #include "kernels.h"
 #include "reduce_finish.h"
+#include <algorithm>
 
 namespace dali {
 
@@ -116,6 +117,159 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const uint16_t* __restrict_
             for (int t = 0; t < 8; ++t) m |= (v[t] > 0.f ? 1u : 0u) << t;
             mask_out[i] = (uint8_t)m;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// IBN-a's bn1 + ReLU (IBN-Net IBN.forward behind conv1): InstanceNorm2d on channels [0, c_in), per (sample, channel) over the hw
+// pixels; channels [c_in, C) pass through (their BatchNorm rode in the convolution's output stage); ReLU on all of them.
+// One workgroup owns one sample's slab of tpp 16-byte channel chunks (tpp a power of two <= 32: runs of tpp * 16 bytes per pixel) and
+// sweeps its pixels NT / tpp at a time.  NCH > 0: the slab is read once into registers (NCH chunks per thread); NCH = 0: the
+// three passes read it from memory.  Block b serves sample 8 (b / 8 groups) + b % 8 and channel group (b / 8) % groups: the groups of a
+// sample sit 8 blocks apart, which the dispatcher places on one XCD (for speed only: where a run is shorter than a 128-byte line, the
+// groups that share the line then share an L2).  The variance is centred: sum (x - mean)^2 in a second pass.  Sums: per thread in pixel order,
+// then over the lanes that share a chunk by xor shuffles, then over the waves in wave order: a fixed order that depends on
+// (hw, C) alone, so a sample's result depends neither on the batch nor on its place in it.  y may be x: a thread writes only the
+// chunks it alone has read, after its last read of them.  Every thread reaches every barrier: tail pixels and tail chunks are predicated.
+// ------------------------------------------------------------------------------------------------
+// the 8 bf16 of a chunk as 4 float pairs, so that the passes below run on the packed fp32 pipe (v_pk_add / v_pk_fma: the kernel's VALU work is
+// a third of its memory time at the plan's shapes)
+__device__ __forceinline__ void ibn_unpack(const uint4& v, f32x2_t (&f)[4]) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[j] = f32x2_t{__uint_as_float(w[j] << 16), __uint_as_float(w[j] & 0xffff0000u)};
+}
+
+// v[t] <- the sum of v[t] over the threads with the same tid % tpp; part: [NT / 64][32][2] float4 of LDS, one buffer per call site
+template <int NT>
+__device__ __forceinline__ void ibn_chunk_sum(float (&v)[8], float4* part, int tpp, int tid) {
+    for (int o = 32; o >= tpp; o >>= 1) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) v[t] += __shfl_xor(v[t], o, 64);
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane < tpp) {
+        part[(wave * 32 + lane) * 2] = make_float4(v[0], v[1], v[2], v[3]);
+        part[(wave * 32 + lane) * 2 + 1] = make_float4(v[4], v[5], v[6], v[7]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 8; ++t) v[t] = 0.f;
+    const int col = lane & (tpp - 1);
+    for (int w = 0; w < NT / 64; ++w) {
+        const float4 a = part[(w * 32 + col) * 2], b = part[(w * 32 + col) * 2 + 1];
+        v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w; v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
+    }
+}
+
+// (16 chunks per thread: at most 128 registers, so that 16 waves -- two workgroups of 512 threads, four of 256 -- share a CU)
+template <int NT, int NCH>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NCH == 16 ? 4 : 1))) void ibn_act_kernel(const uint16_t* x, int n_total, int hw, int C, int c_in, int tpp, int groups, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, float eps, int relu, uint16_t* y, float* __restrict__ mean_out,
+                                                     float* __restrict__ invstd_out) {
+    __shared__ float4 s_part[2][NT / 64 * 32 * 2];
+    const int tid = threadIdx.x;
+    constexpr bool CACHED = NCH > 0;
+    const int octet = blockIdx.x / (8 * groups), rem = blockIdx.x - octet * (8 * groups);
+    const int n = octet * 8 + (rem & 7), grp = rem >> 3;
+    const int c = (grp * tpp + (tid & (tpp - 1))) * 8;
+    const bool live = n < n_total && c < C, inorm = live && c < c_in;      // (the grid is rounded up to whole octets of samples)
+    const int p0 = tid / tpp, pstep = NT / tpp;
+    const size_t base = (size_t)(n < n_total ? n : 0) * hw * C + (c < C ? c : 0);      // (a uniform part + the thread's channel; dead threads never use it)
+    uint4 r[CACHED ? NCH : 1];
+    float m[8], q[8];
+    f32x2_t f[4], acc[4];
+    // ---- mean ----
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = f32x2_t{0.f, 0.f};
+    if constexpr (CACHED) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            const int p = p0 + k * pstep;
+            r[k] = make_uint4(0, 0, 0, 0);
+            if (live && p < hw) r[k] = *reinterpret_cast<const uint4*>(x + base + (size_t)p * C);
+        }
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (inorm && p0 + k * pstep < hw) {
+                ibn_unpack(r[k], f);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] += f[j];
+            }
+        }
+    } else if (inorm) {
+        for (int p = p0; p < hw; p += pstep) {
+            ibn_unpack(*reinterpret_cast<const uint4*>(x + base + (size_t)p * C), f);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += f[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { m[2 * j] = acc[j].x; m[2 * j + 1] = acc[j].y; }
+    ibn_chunk_sum<NT>(m, s_part[0], tpp, tid);
+    f32x2_t mean[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { mean[j] = f32x2_t{m[2 * j] / (float)hw, m[2 * j + 1] / (float)hw}; acc[j] = f32x2_t{0.f, 0.f}; }
+    // ---- centred variance: sum (x - mean)^2, the square and the add in one rounding ----
+    if constexpr (CACHED) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (inorm && p0 + k * pstep < hw) {
+                ibn_unpack(r[k], f);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const f32x2_t d = f[j] - mean[j]; acc[j] = __builtin_elementwise_fma(d, d, acc[j]); }
+            }
+        }
+    } else if (inorm) {
+        for (int p = p0; p < hw; p += pstep) {
+            ibn_unpack(*reinterpret_cast<const uint4*>(x + base + (size_t)p * C), f);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const f32x2_t d = f[j] - mean[j]; acc[j] = __builtin_elementwise_fma(d, d, acc[j]); }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { q[2 * j] = acc[j].x; q[2 * j + 1] = acc[j].y; }
+    ibn_chunk_sum<NT>(q, s_part[1], tpp, tid);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) q[t] = 1.f / sqrtf(q[t] / (float)hw + eps);
+    if (inorm && p0 == 0) {
+        float* mo = mean_out ? mean_out + (size_t)n * c_in + c : nullptr;
+        float* io = invstd_out ? invstd_out + (size_t)n * c_in + c : nullptr;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            if (mo) mo[t] = t & 1 ? mean[t >> 1].y : mean[t >> 1].x;
+            if (io) io[t] = q[t];
+        }
+    }
+    // ---- y ----
+    // fma(x - mean, invstd * gamma, beta): the scale once per channel, the product and the add in one rounding
+    f32x2_t sc[4], sh[4];
+    if (inorm) {
+        float g[8], b[8];
+        load8f(gamma + c, g); load8f(beta + c, b);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { sc[j] = f32x2_t{q[2 * j] * g[2 * j], q[2 * j + 1] * g[2 * j + 1]}; sh[j] = f32x2_t{b[2 * j], b[2 * j + 1]}; }
+    }
+    const f32x2_t floor2 = relu ? f32x2_t{0.f, 0.f} : f32x2_t{-INFINITY, -INFINITY};
+    auto emit = [&](const uint4& in, int p) {
+        ibn_unpack(in, f);
+        uint32_t o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (inorm) f[j] = __builtin_elementwise_fma(f[j] - mean[j], sc[j], sh[j]);
+            f[j] = __builtin_elementwise_max(f[j], floor2);
+            o[j] = pack_bf16x2(f[j].x, f[j].y);
+        }
+        *reinterpret_cast<uint4*>(y + base + (size_t)p * C) = make_uint4(o[0], o[1], o[2], o[3]);
+    };
+    if constexpr (CACHED) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            const int p = p0 + k * pstep;
+            if (live && p < hw) emit(r[k], p);
+        }
+    } else if (live) {
+        for (int p = p0; p < hw; p += pstep) emit(*reinterpret_cast<const uint4*>(x + base + (size_t)p * C), p);
     }
 }
 
@@ -852,6 +1006,32 @@ int launch_bn_act(hipStream_t st, const uint16_t* raw, const float* scale, const
     DALI_LAUNCH_CHECK();
     return DALI_OK;
 }
+// The slab a workgroup of ibn_act_kernel owns, from (hw, C) alone (never from n: see the kernel).  Runs of 128 bytes per pixel (8 chunks) where C
+// has them and 512 threads x 16 chunks hold the slab (hw <= 1024), else runs of 64 bytes (hw <= 2048: ResNet-50-IBN-a's largest maps at
+// 256 x 128); two such workgroups fit a CU, so that one loads while the other stores.  Small slabs take fewer registers (4 chunks per
+// thread: 8 workgroups per CU).  Beyond that the three passes re-read the tensor.
+int launch_ibn_act(hipStream_t st, const uint16_t* x, int n, int hw, int C, int c_in, const float* gamma, const float* beta, float eps, int relu,
+                   uint16_t* y, float* mean, float* invstd) {
+    const int cch = C / 8;
+    int tpp = 1;
+    while (tpp < cch && tpp < 8) tpp <<= 1;
+    const bool cached = (size_t)hw * std::min(tpp, 4) <= 512 * 16;
+    if (cached && (size_t)hw * tpp > 512 * 16) tpp = 4;
+    const size_t slab = (size_t)hw * tpp;
+    const int groups = (cch + tpp - 1) / tpp;
+    const size_t blocks = (size_t)(n + 7) / 8 * 8 * groups;
+    DALI_REQUIRE(blocks <= 0x7fffffffu, "dali_ibn_act: n * channel groups = %zu exceeds the grid", blocks);
+    const dim3 grid((unsigned)blocks);
+#define IBN_LAUNCH(NT, NCH) \
+    hipLaunchKernelGGL((ibn_act_kernel<NT, NCH>), grid, dim3(NT), 0, st, x, n, hw, C, c_in, tpp, groups, gamma, beta, eps, relu, y, mean, invstd)
+    if (!cached) IBN_LAUNCH(1024, 0);
+    else if (slab <= 256 * 4) IBN_LAUNCH(256, 4);
+    else if (slab <= 256 * 16) IBN_LAUNCH(256, 16);
+    else IBN_LAUNCH(512, 16);
+#undef IBN_LAUNCH
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
 // Number of partial blocks the reduce pass uses for a [P][C] tensor
 int bn_bwd_blocks(int P, int C, int* rows_per_block) {
     const int rif = 256 / (C / 8);
@@ -1081,6 +1261,16 @@ extern "C" int dali_bn_act(dali_ctx* ctx, void* stream, const uint16_t* raw, con
     DALI_REQUIRE(!raw2 || (scale2 && shift2), "dali_bn_act: raw2 needs scale2/shift2");
     if (pixels == 0) return DALI_OK;
     return launch_bn_act((hipStream_t)stream, raw, scale, shift, identity, raw2, scale2, shift2, relu, (size_t)pixels * C, C, y, mask_out);
+}
+
+extern "C" int dali_ibn_act(dali_ctx* ctx, void* stream, const uint16_t* x, int n, int hw, int C, int c_in, const float* gamma, const float* beta,
+                            float eps, int relu, uint16_t* y, float* mean, float* invstd) {
+    DALI_REQUIRE(n >= 1, "dali_ibn_act: n must be at least 1 (got %d)", n);
+    DALI_REQUIRE(hw >= 1, "dali_ibn_act: hw must be at least 1 (got %d)", hw);
+    DALI_REQUIRE(C > 0 && C % 8 == 0, "dali_ibn_act: C must be a positive multiple of 8 (got %d)", C);
+    DALI_REQUIRE(c_in > 0 && c_in % 8 == 0 && c_in <= C, "dali_ibn_act: c_in must be a multiple of 8 in (0, C] (got %d, C = %d)", c_in, C);
+    DALI_REQUIRE(ctx && x && gamma && beta && y, "dali_ibn_act: null argument");
+    return launch_ibn_act((hipStream_t)stream, x, n, hw, C, c_in, gamma, beta, eps, relu, y, mean, invstd);
 }
 
 extern "C" int dali_bn_bwd(dali_ctx* ctx, void* stream, const uint16_t* g, const uint16_t* ymask, const uint8_t* ybits, int relu, int64_t pixels, int C,

@@ -25,6 +25,7 @@ struct Conv {
 };
 struct Bn {
     int C;
+    int lo = 0;               // the BatchNorm covers channels [lo, C) of the coefficient arrays (an IBN block's bn1: lo = C / 2, its tensors have C - lo entries)
     int64_t g_off, b_off;     // flat params
     int64_t rm_off, rv_off;   // flat buffers
     float *scale, *shift, *mean, *invstd, *coef;   // arena, [C] each (coef [C][3])
@@ -56,6 +57,11 @@ struct Block {
     bool cat_eval = false;
     uint16_t* wcat = nullptr;
     float* shcat = nullptr;
+    // IBN-a (dali_resnet_ext): bn1 = InstanceNorm2d on channels [0, c_in) | BatchNorm2d on the rest (b1, with b1.lo = c_in)
+    bool ibn = false;
+    int c_in = 0;
+    int64_t in_g_off = 0, in_b_off = 0;                        // IN.weight / IN.bias [c_in], flat params
+    float *in_mean = nullptr, *in_invstd = nullptr;            // [N][c_in], what the last forward's dali_ibn_act launch saw
     uint16_t* dbg_d_raw1 = nullptr;                            // where the last backward of this block left d(raw1) (scratch: valid until the next block runs)
 };
 template <class F> void for_each_conv(Block& b, F f) { f(b.c1); f(b.c2); f(b.c3); if (b.has_ds) f(b.cd); }
@@ -66,6 +72,7 @@ template <class F> void for_each_bn(Block& b, F f) { f(b.b1); f(b.b2); f(b.b3); 
 struct dali_resnet : PlanTable {
     dali_ctx* ctx;
     dali_resnet_cfg cfg;
+    bool eval_only = false;                  // a plan with an IBN stage: no training forward, no backward, none of the backward's buffers
     int N, H, W;
     Conv stem; Bn stem_bn; Bn neck;
     int stem_h, stem_w, pool_h, pool_w, feat_dim, head_hw;
@@ -107,6 +114,18 @@ void add_bn(dali_resnet* net, Bn& b, const std::string& name, int C) {
     b.b_off = net->add_param(name + ".bias", {C});
     b.rm_off = net->add_buffer(name + ".running_mean", {C});
     b.rv_off = net->add_buffer(name + ".running_var", {C});
+}
+// IBN(planes) as bn1 of block b: IN.weight, IN.bias [C/2], then the BatchNorm half's tensors [C - C/2] (IBN-Net's module order)
+void add_ibn(dali_resnet* net, Block& b, const std::string& name, int C) {
+    Bn& bn = b.b1;
+    b.ibn = true; b.c_in = C / 2;
+    bn.C = C; bn.lo = b.c_in;
+    b.in_g_off = net->add_param(name + ".IN.weight", {b.c_in});
+    b.in_b_off = net->add_param(name + ".IN.bias", {b.c_in});
+    bn.g_off = net->add_param(name + ".BN.weight", {C - b.c_in});
+    bn.b_off = net->add_param(name + ".BN.bias", {C - b.c_in});
+    bn.rm_off = net->add_buffer(name + ".BN.running_mean", {C - b.c_in});
+    bn.rv_off = net->add_buffer(name + ".BN.running_var", {C - b.c_in});
 }
 void reserve_bn(dali_resnet* net, Bn& b) {
     net->reserve(b.scale, b.C * 4); net->reserve(b.shift, b.C * 4);
@@ -155,16 +174,23 @@ int run_wgrad(dali_resnet* net, hipStream_t st, const WGradDesc& d, const uint16
 }  // namespace
 
 extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dali_resnet** out) {
+    return dali_resnet_create_ex(ctx, cfg, nullptr, out);
+}
+
+extern "C" int dali_resnet_create_ex(dali_ctx* ctx, const dali_resnet_cfg* cfg, const dali_resnet_ext* ext, dali_resnet** out) {
     DALI_REQUIRE(ctx && cfg && out, "dali_resnet_create: null argument");
     DALI_REQUIRE(cfg->batch > 0 && cfg->height >= 32 && cfg->width >= 32 && cfg->height % 32 == 0 && cfg->width % 16 == 0,
                  "dali_resnet_create: bad input shape %dx%dx%d (height %% 32, width %% 16)", cfg->batch, cfg->height, cfg->width);
     DALI_REQUIRE(cfg->width_base >= 32 && cfg->width_base % 32 == 0 && cfg->width_base <= 64,
                  "dali_resnet_create: width_base must be 32 or 64 (got %d)", cfg->width_base);
     for (int i = 0; i < 4; ++i) DALI_REQUIRE(cfg->layers[i] >= 1, "dali_resnet_create: layers[%d] < 1", i);
+    DALI_REQUIRE(!ext || (cfg->width_base / 2) % 8 == 0, "dali_resnet_create_ex: an IBN block's IN half (width / 2 channels) must be a multiple of 8");
     dali_resnet* net = new (std::nothrow) dali_resnet();
     if (!net) { set_error("dali_resnet_create: out of host memory"); return DALI_ERR_NOMEM; }
     net->ctx = ctx; net->cfg = *cfg; net->N = cfg->batch; net->H = cfg->height; net->W = cfg->width;
     const int wb = cfg->width_base;
+    for (int i = 0; i < 4; ++i) net->eval_only |= ext && ext->ibn[i] != 0;
+    const bool train = !net->eval_only;
     // ---- topology + parameter table (torchvision order) ----
     add_conv(net, net->stem, "conv1", 3, wb, 7, 2, 3, net->H, net->W);
     add_bn(net, net->stem_bn, "bn1", wb);
@@ -181,7 +207,8 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
             const std::string pre = "layer" + std::to_string(li + 1) + "." + std::to_string(bi);
             b.hin = h; b.win = w; b.cin = inpl; b.width = planes; b.cout = planes * 4;
             add_conv(net, b.c1, pre + ".conv1", inpl, planes, 1, 1, 0, h, w);
-            add_bn(net, b.b1, pre + ".bn1", planes);
+            if (ext && ext->ibn[li]) add_ibn(net, b, pre + ".bn1", planes);        // (planes / 2 is a multiple of 8: width_base 32 or 64)
+            else add_bn(net, b.b1, pre + ".bn1", planes);
             add_conv(net, b.c2, pre + ".conv2", planes, planes, 3, st, 1, h, w);
             add_bn(net, b.b2, pre + ".bn2", planes);
             add_conv(net, b.c3, pre + ".conv3", planes, planes * 4, 1, 1, 0, b.c2.hout, b.c2.wout);
@@ -221,6 +248,7 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
     reserve_bn(net, net->stem_bn);
     size_t max_act = raw0_bytes, max_stat = (size_t)igemm_conv_stat_tiles(wb, (int)N * net->stem_h * net->stem_w, 224) * wb * 2 * 4;
     int stem_qpb;
+    // (an eval plan reserves what the inference forward touches and nothing else: `train` guards the rest)
     size_t max_bwd_partial = (size_t)maxpool_bn_bwd_blocks((int)N, net->stem_h, net->stem_w, wb, &stem_qpb) * wb * 2 * 4;
     // the weight-gradient slab and column-sum partials: the most any weight-gradient GEMM of the plan asks for (run_wgrad's callers)
     size_t max_slab = 0, max_cs = 256;
@@ -232,17 +260,20 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
     size_wgrad(stem_wgrad_desc(net), false);
     for (auto& b : net->blocks) {
         const size_t pin = N * b.hin * b.win, pout = N * b.hout * b.wout;
-        net->reserve(b.raw1, pin * b.width * 2);
+        if (train) net->reserve(b.raw1, pin * b.width * 2);
         net->reserve(b.a1, pin * b.width * 2);
-        net->reserve(b.raw2, pout * b.width * 2);
+        if (train) net->reserve(b.raw2, pout * b.width * 2);
         net->reserve(b.a2, pout * b.width * 2);
-        reserve_linbn(net, b.l3, b.c3, true);
-        net->reserve(b.sdz, (size_t)b.cout * 4);
-        size_wgrad(gram_desc(net, b.c3), true);
+        if (train) {
+            reserve_linbn(net, b.l3, b.c3, true);
+            net->reserve(b.sdz, (size_t)b.cout * 4);
+            size_wgrad(gram_desc(net, b.c3), true);
+        }
         net->reserve(b.y, pout * b.cout * 2);
-        net->reserve(b.ybits, pout * b.cout / 8);
+        if (train) net->reserve(b.ybits, pout * b.cout / 8);
         if (b.has_ds) net->reserve(b.rawd, pout * b.cout * 2);
-        if (b.lin_ds) {
+        if (b.ibn) { net->reserve(b.in_mean, N * b.c_in * 4); net->reserve(b.in_invstd, N * b.c_in * 4); }
+        if (b.lin_ds && train) {
             reserve_linbn(net, b.ld, b.cd, false);
             size_wgrad(gram_desc(net, b.cd), true);
         }
@@ -251,7 +282,7 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
         b.cat_eval = b.has_ds && b.cd.stride == 1 && conv_cat_act_supported(b.cout, b.width, b.cin, (int)pout, 2);
         if (b.cat_eval) { net->reserve(b.wcat, (size_t)b.cout * 2 * (b.width + b.cin) * 2); net->reserve(b.shcat, (size_t)b.cout * 4); }
         for_each_bn(b, [&](Bn& bn) { reserve_bn(net, bn); });
-        for_each_conv(b, [&](Conv& c) {
+        if (train) for_each_conv(b, [&](Conv& c) {
             net->reserve(c.wt_bf16, (size_t)c.cin * c.r * c.s * c.cout * 2);
             const int P = (int)N * c.hout * c.wout;
             max_stat = std::max(max_stat, (size_t)igemm_conv_stat_tiles(c.cout, P, c.r * c.s * c.cin) * c.cout * 2 * 4);
@@ -262,18 +293,24 @@ extern "C" int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dal
         });
     }
     net->reserve(net->feat, N * net->feat_dim * 4);
-    net->reserve(net->dfeat, N * net->feat_dim * 4);
+    if (train) net->reserve(net->dfeat, N * net->feat_dim * 4);
     net->reserve(net->head_arg, N * net->feat_dim * 2);
     net->reserve(net->neck_mean, net->feat_dim * 4);
     net->reserve(net->neck_invstd, net->feat_dim * 4);
-    net->reserve(net->stat_partial, max_stat);
-    net->reserve(net->bwd_partial, max_bwd_partial);
-    net->reserve(net->wgrad_slab, max_slab);
-    net->reserve(net->cs_partial, max_cs);
-    net->reserve(net->stem_dw_pad, (size_t)wb * 224 * 4);
-    net->reserve(net->red_scratch, reduce_scratch_bytes(net->feat_dim, 3));
-    net->gbuf_bytes = align_up(max_act, 256);
-    for (int i = 0; i < 6; ++i) net->reserve(net->gbuf[i], net->gbuf_bytes);
+    if (train) {
+        net->reserve(net->stat_partial, max_stat);
+        net->reserve(net->bwd_partial, max_bwd_partial);
+        net->reserve(net->wgrad_slab, max_slab);
+        net->reserve(net->cs_partial, max_cs);
+        net->reserve(net->stem_dw_pad, (size_t)wb * 224 * 4);
+        net->reserve(net->red_scratch, reduce_scratch_bytes(net->feat_dim, 3));
+        net->gbuf_bytes = align_up(max_act, 256);
+        for (int i = 0; i < 6; ++i) net->reserve(net->gbuf[i], net->gbuf_bytes);
+    } else {
+        // the one forward that uses the gradient buffers' region: dali_resnet_forward_heads' pooled values, up to DALI_MAX_HEADS heads
+        net->gbuf_bytes = align_up((DALI_MAX_HEADS * N * net->feat_dim * 4 + 5) / 6, 256);
+        net->reserve(net->gbuf[0], 6 * net->gbuf_bytes);
+    }
     *out = net;
     return DALI_OK;
 }
@@ -326,6 +363,15 @@ extern "C" int dali_resnet_refresh_weights(dali_resnet* net, void* stream) {
     if (rc) return rc;
     rc = launch_stem_pack_weight(st, net->P + net->stem.w_off, net->stem.cout, net->w_stem);
     if (rc) return rc;
+    if (net->eval_only) {
+        // no data-gradient images; the IN half of every IBN block's conv1 output stage is the identity (scale 1, shift 0): constants of the arena
+        for (auto& b : net->blocks) {
+            if (!b.ibn) continue;
+            DALI_HIP(hipMemsetD32Async((hipDeviceptr_t)b.b1.scale, 0x3f800000, (size_t)b.c_in, st));
+            DALI_HIP(hipMemsetD32Async((hipDeviceptr_t)b.b1.shift, 0, (size_t)b.c_in, st));
+        }
+        return DALI_OK;
+    }
     std::vector<TransposeJob> jobs;                      // every conv's dgrad image [cin][r*s][cout], one launch
     for (auto& b : net->blocks) for_each_conv(b, [&](Conv& c) { jobs.push_back(TransposeJob{c.w_bf16, c.wt_bf16, c.cout, c.r * c.s, c.cin, 0}); });
     return launch_weight_transpose_batched(st, jobs.data(), (int)jobs.size());
@@ -359,10 +405,10 @@ int bn_relu(hipStream_t st, const Bn& bn, const uint16_t* raw, size_t elems, uin
 // inference: act = relu(bn(conv(x))) leaves the GEMM directly -- the running-statistics coefficients are known before the convolution runs, so
 // they ride in the fused output stage (IGemmArgs::out_scale / out_shift / out_relu) and neither the raw output nor a bn_act pass exists
 // (getFeatures.py:56-67 forwards the whole train set this way every epoch, train_encodersKIT.py:104-110; every validate, validateModels.py:38-39)
-int conv_bn_relu_eval(dali_resnet* net, hipStream_t st, const Conv& c, const Bn& bn, const uint16_t* x, uint16_t* act) {
+int conv_bn_relu_eval(dali_resnet* net, hipStream_t st, const Conv& c, const Bn& bn, const uint16_t* x, uint16_t* act, int relu = 1) {
     IGemmArgs a{};
     a.W = c.w_bf16; a.X = x; a.O = act;
-    a.out_scale = bn.scale; a.out_shift = bn.shift; a.out_relu = 1;
+    a.out_scale = bn.scale; a.out_shift = bn.shift; a.out_relu = relu;
     a.Cm = c.cout; a.P = net->N * c.hout * c.wout;
     a.g = conv_geom(c, 0);
     return launch_igemm_conv(st, a);
@@ -462,7 +508,15 @@ int stem_forward(dali_resnet* net, hipStream_t st, const float* images, bool tr)
 int block_forward(dali_resnet* net, hipStream_t st, Block& b, const uint16_t* x, bool tr) {
     int rc;
     b.x = const_cast<uint16_t*>(x);
-    if (!tr) {
+    if (!tr && b.ibn) {
+        // IBN-a: the instance statistics of conv1's output are not known before it runs, so a1 leaves the output stage without the ReLU (identity on
+        // the IN half, bn1.BN's running-statistics coefficients on the rest) and one launch normalises the IN half and applies the ReLU in place
+        // (rounding and ReLU commute: the BN half is bit for bit what conv_bn_relu_eval gives)
+        if ((rc = conv_bn_relu_eval(net, st, b.c1, b.b1, x, b.a1, 0))) return rc;
+        if ((rc = launch_ibn_act(st, b.a1, net->N, b.hin * b.win, b.width, b.c_in, net->P + b.in_g_off, net->P + b.in_b_off, 1e-5f, 1, b.a1, b.in_mean,
+                                 b.in_invstd))) return rc;
+        if ((rc = conv_bn_relu_eval(net, st, b.c2, b.b2, b.a1, b.a2))) return rc;
+    } else if (!tr) {
         if ((rc = conv_bn_relu_eval(net, st, b.c1, b.b1, x, b.a1))) return rc;
         if ((rc = conv_bn_relu_eval(net, st, b.c2, b.b2, b.a1, b.a2))) return rc;
     } else {
@@ -497,6 +551,12 @@ int block_forward(dali_resnet* net, hipStream_t st, Block& b, const uint16_t* x,
 
 }  // namespace
 
+// training an IBN-a net needs half-channel batch statistics and an instance-norm backward, which the plan does not have
+static int eval_only_error(const char* who) {
+    set_error("%s: a plan with IBN-a stages is eval only (running statistics; no training forward, no backward)", who);
+    return DALI_ERR_LIMIT;
+}
+
 extern "C" int dali_resnet_set_feature(dali_resnet* net, int mode) {
     DALI_REQUIRE(net, "dali_resnet_set_feature: null net");
     DALI_REQUIRE(mode >= DALI_FEATURE_BOTH && mode <= DALI_FEATURE_GMP, "dali_resnet_set_feature: bad feature mode %d", mode);
@@ -512,7 +572,7 @@ int trunk_forward(dali_resnet* net, hipStream_t st, const float* images, bool tr
     int rc;
     if (!tr) {                                               // inference: every BatchNorm's scale / shift from the running statistics, one launch
         std::vector<BnEvalJob> jobs;
-        auto add = [&](Bn& b) { const BnParams p = bn_params(net, b); jobs.push_back(BnEvalJob{p.gamma, p.beta, p.rm, p.rv, b.scale, b.shift, b.C}); };
+        auto add = [&](Bn& b) { const BnParams p = bn_params(net, b); jobs.push_back(BnEvalJob{p.gamma, p.beta, p.rm, p.rv, b.scale + b.lo, b.shift + b.lo, b.C - b.lo}); };
         add(net->stem_bn);
         for (auto& b : net->blocks) for_each_bn(b, add);
         if ((rc = launch_bn_eval_coeffs_batched(st, jobs.data(), (int)jobs.size(), 1e-5f))) return rc;
@@ -531,6 +591,7 @@ int trunk_forward(dali_resnet* net, hipStream_t st, const float* images, bool tr
 
 extern "C" int dali_resnet_forward(dali_resnet* net, void* stream, const float* images, int training, float* emb) {
     DALI_REQUIRE(net && net->P && images && emb, "dali_resnet_forward: null argument or net not bound");
+    if (training && net->eval_only) return eval_only_error("dali_resnet_forward(training = 1)");
     hipStream_t st = (hipStream_t)stream;
     const bool tr = training != 0;
     const uint16_t* x;
@@ -657,7 +718,9 @@ static int stem_backward(dali_resnet* net, hipStream_t st) {
 // Runs stages [stage_begin, stage_end] of the backward pass (0: neck+head+layer4, 1: layer3, 2: layer2,
 // 3: layer1+stem).  Stage 0 consumes d_emb; later stages continue from the gradient the previous call left.
 extern "C" int dali_resnet_backward(dali_resnet* net, void* stream, const float* d_emb, int stage_begin, int stage_end) {
-    DALI_REQUIRE(net && net->P && net->G, "dali_resnet_backward: net not bound (grads required)");
+    DALI_REQUIRE(net, "dali_resnet_backward: null net");
+    if (net->eval_only) return eval_only_error("dali_resnet_backward");
+    DALI_REQUIRE(net->P && net->G, "dali_resnet_backward: net not bound (grads required)");
     DALI_REQUIRE(net->fwd_training, "dali_resnet_backward: the last forward was not in training mode");
     DALI_REQUIRE(stage_begin >= 0 && stage_end <= 3 && stage_begin <= stage_end, "dali_resnet_backward: bad stage range %d..%d", stage_begin, stage_end);
     hipStream_t st = (hipStream_t)stream;
@@ -679,7 +742,9 @@ extern "C" int dali_resnet_backward(dali_resnet* net, void* stream, const float*
 // (`grad_cur` of dali_resnet_debug_tensor) instead of one per stage.  Call with block = last block first (that call also runs the neck + head
 // backward from d_emb), then block - 1, ... down to 0, then -1 (the stem); same launches, same order as dali_resnet_backward.
 extern "C" int dali_debug_resnet_backward_block(dali_resnet* net, void* stream, const float* d_emb, int block) {
-    DALI_REQUIRE(net && net->P && net->G, "dali_debug_resnet_backward_block: net not bound (grads required)");
+    DALI_REQUIRE(net, "dali_debug_resnet_backward_block: null net");
+    if (net->eval_only) return eval_only_error("dali_debug_resnet_backward_block");
+    DALI_REQUIRE(net->P && net->G, "dali_debug_resnet_backward_block: net not bound (grads required)");
     DALI_REQUIRE(net->fwd_training, "dali_debug_resnet_backward_block: the last forward was not in training mode");
     const int nb = (int)net->blocks.size();
     if (block == -1) return stem_backward(net, (hipStream_t)stream);      // after block 0: the stem (its own call, so that block 0's scratch tensors can be read first)
@@ -694,7 +759,8 @@ extern "C" int dali_debug_resnet_backward_block(dali_resnet* net, void* stream, 
 }
 
 // Debug/inspection: device pointer + byte size of a named intermediate (valid after a forward).
-// Names: raw0, pool0, feat, grad_cur (gradient wrt the input of the last block processed by backward), block<i>.{raw1,raw2,rawd,y,d_raw1}, block<i>.bn{1,2,3,d}.{scale,shift,mean,invstd}, bn1.{...};
+// Names: raw0, pool0, feat, grad_cur (gradient wrt the input of the last block processed by backward), block<i>.{raw1,a1,raw2,rawd,y,d_raw1},
+// for an IBN block block<i>.in1.{mean,invstd} (fp32 [N][width / 2], of the last forward), block<i>.bn{1,2,3,d}.{scale,shift,mean,invstd}, bn1.{...};
 // ximg (packed image bf16 [N][H+6][W+8][4]), w_stem (bf16 [Cout][7][8][4]), d_raw0 (after a stem backward); the weight images block<i>.conv{1,2,3,d}.w
 // (bf16 [cout][r][s][cin]) and .wt (bf16 [cin][r*s][cout]), and, where the inference forward folds conv3 + downsample into one GEMM,
 // block<i>.wcat (bf16 [cout][2 (w + cin)]: W3 hi | W3 lo | Wd hi | Wd lo) and block<i>.shcat (fp32 [cout])
@@ -724,8 +790,11 @@ extern "C" int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void
                 Block& b = net->blocks[bi];
                 const std::string f = n.substr(dot + 1);
                 const size_t pin = N * b.hin * b.win, pout = N * b.hout * b.wout;
-                if (f == "raw1") { *ptr = b.raw1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }
-                if (f == "raw2") { *ptr = b.raw2; *bytes = (int64_t)(pout * b.width * 2); return DALI_OK; }
+                if (f == "a1") { *ptr = b.a1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }
+                if (f == "in1.mean" && b.ibn) { *ptr = b.in_mean; *bytes = (int64_t)(N * b.c_in * 4); return DALI_OK; }
+                if (f == "in1.invstd" && b.ibn) { *ptr = b.in_invstd; *bytes = (int64_t)(N * b.c_in * 4); return DALI_OK; }
+                if (f == "raw1" && b.raw1) { *ptr = b.raw1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }
+                if (f == "raw2" && b.raw2) { *ptr = b.raw2; *bytes = (int64_t)(pout * b.width * 2); return DALI_OK; }
                 if (f == "rawd" && b.has_ds) { *ptr = b.rawd; *bytes = (int64_t)(pout * b.cout * 2); return DALI_OK; }
                 if (f == "y") { *ptr = b.y; *bytes = (int64_t)(pout * b.cout * 2); return DALI_OK; }
                 if (f == "d_raw1" && b.dbg_d_raw1) { *ptr = b.dbg_d_raw1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }

@@ -182,6 +182,26 @@ def bn_act(raw, scale, shift, identity=None, raw2=None, scale2=None, shift2=None
     return (y, mask) if want_mask else y
 
 
+def ibn_act(x, c_in, gamma, beta, eps=1e-5, relu=True, out=None, want_stats=False):
+    """IBN-a's bn1 + ReLU (dali_ibn_act): x bf16 [n, ..., C]; InstanceNorm (biased variance over the pixels of each sample, affine
+    gamma / beta fp32 [c_in]) on channels [0, c_in), the others pass through, ReLU on all of them with ``relu``.  ``out``: where to
+    write (``out=x`` works in place).  -> y, or (y, mean, invstd) fp32 [n, c_in] with ``want_stats``."""
+    if x.dim() < 2:
+        raise _lib.DaliError("ibn_act: x must be [n, ..., C], got %s" % (tuple(x.shape),))
+    n, C = x.shape[0], x.shape[-1]
+    hw = x.numel() // (n * C) if n * C else 0
+    y = torch.empty_like(x) if out is None else out
+    if y.shape != x.shape:
+        raise _lib.DaliError("ibn_act: out must have x's shape")
+    mean = invstd = None
+    if want_stats:
+        mean, invstd = torch.empty(n, c_in, device=x.device, dtype=torch.float32), torch.empty(n, c_in, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().dali_ibn_act(_lib.ctx(x.device), _lib.stream_ptr(), _lib.ptr(x, bf16, "x"), n, hw, C, int(c_in),
+                                        _lib.ptr(gamma, torch.float32, "gamma"), _lib.ptr(beta, torch.float32, "beta"), float(eps), int(relu),
+                                        _lib.ptr(y, bf16, "out"), _lib.ptr(mean), _lib.ptr(invstd)), "dali_ibn_act")
+    return (y, mean, invstd) if want_stats else y
+
+
 def bn_bwd(g, raw_a, mean_a, invstd_a, scale_a, shift_a=None, ymask=None, relu=True, side_b=None, want_dz=False, ybits=None):
     """-> (draw_a, dgamma_a, dbeta_a[, draw_b, dgamma_b, dbeta_b][, dz])"""
     C = g.shape[-1]

@@ -350,6 +350,17 @@ int dali_bn_finalize(dali_ctx* ctx, void* stream, const float* partial, int tile
 int dali_bn_act(dali_ctx* ctx, void* stream, const uint16_t* raw, const float* scale, const float* shift,
                 const uint16_t* identity, const uint16_t* raw2, const float* scale2, const float* shift2, int relu,
                 int64_t pixels, int C, uint16_t* y, uint8_t* mask_out);
+/* IBN-a's bn1 + ReLU on an NHWC map (IBN-Net IBN.forward; Bottleneck_IBN: conv1 -> bn1 -> relu).
+ * x, y bf16 [n][hw][C]; y may be x.  Channels [0, c_in): per (sample, channel) over the hw pixels
+ *   mean = sum x / hw, var = sum (x - mean)^2 / hw (biased), invstd = 1 / sqrt(var + eps),
+ *   y = fma(x - mean, invstd * gamma[c], beta[c])     (fp32, then one rounding to bf16)
+ * Channels [c_in, C): y = x (the BatchNorm half arrives already affine from the convolution's output stage).
+ * relu != 0: max(y, 0) on every channel.  mean, invstd: optional fp32 [n][c_in] outputs (may be NULL).
+ * C % 8 == 0, c_in % 8 == 0, 0 < c_in <= C, n >= 1, hw >= 1; anything else DALI_ERR_INVALID before any launch.
+ * One launch, no atomics: bitwise reproducible, and a sample's result depends neither on n nor on its place in the batch.  The tensor
+ * is read once and written once while hw * min(C, 32) <= 65536 (up to 2048 pixels at 32 channels and more); larger maps are read three times. */
+int dali_ibn_act(dali_ctx* ctx, void* stream, const uint16_t* x, int n, int hw, int C, int c_in, const float* gamma, const float* beta,
+                 float eps, int relu, uint16_t* y, float* mean, float* invstd);
 /* Backward of z = bn(raw) followed by an optional ReLU whose mask is the bit mask ybits (dali_bn_act's mask_out) or
  * (ymask > 0) if one of them is given (they are exclusive), else (raw*scale+shift > 0).  g = gradient after the ReLU.  Writes d(raw) (bf16), dgamma, dbeta; with a second side
  * (raw_b...) the same masked gradient also flows through a second BatchNorm (the downsample branch).  dz_out
@@ -572,7 +583,16 @@ typedef struct {
     int width_base;             /* 64 for ResNet-50 (32 allowed for test-size nets) */
 } dali_resnet_cfg;
 
+/* IBN-a (IBN-Net resnet50_ibn_a / resnet101_ibn_a under Encoders.ResNet50IBNReID / ResNet101IBNReID, Encoders.py:462-603): ibn[s] != 0 makes
+ * every bottleneck of stage s (layer s+1) an IBN-a block, whose bn1 is InstanceNorm2d (affine) on the first width / 2 channels and BatchNorm2d
+ * on the rest.  Its tensors are "layerL.B.bn1.IN.weight", ".IN.bias" [w/2], ".bn1.BN.weight", ".BN.bias" [w - w/2] and the buffers
+ * ".bn1.BN.running_mean", ".running_var"; IBN-a proper is {1,1,1,0}.  All zero (or a null ext) = dali_resnet_create, size for size.
+ * A plan with an IBN stage is an EVAL plan: conv1 writes its output through the output stage (identity on the IN half, the running
+ * statistics' coefficients on the BN half), then one dali_ibn_act launch in place.  It reserves none of the backward's buffers, and
+ * dali_resnet_forward with training != 0 and dali_resnet_backward return DALI_ERR_LIMIT before any launch ("... eval only"). */
+typedef struct { int ibn[4]; } dali_resnet_ext;
 int dali_resnet_create(dali_ctx* ctx, const dali_resnet_cfg* cfg, dali_resnet** out);
+int dali_resnet_create_ex(dali_ctx* ctx, const dali_resnet_cfg* cfg, const dali_resnet_ext* ext, dali_resnet** out);
 int dali_resnet_destroy(dali_resnet* net);
 int dali_resnet_sizes(const dali_resnet* net, int64_t* param_elems, int64_t* buffer_elems, int64_t* arena_bytes,
                       int* feat_dim, int* n_params, int* n_buffers);
