@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops_nn
+from .plan_net import PlanHandle, PlanNet
 
 
 class _Cfg(ctypes.Structure):
@@ -36,62 +37,11 @@ class _Ext(ctypes.Structure):
     _fields_ = [("ibn", ctypes.c_int * 4)]
 
 
-class _Plan:
-    """One dali_resnet plan for a fixed (batch, H, W)."""
-
-    def __init__(self, device, batch, height, width, layers, width_base, ibn=None):
-        self.key = (batch, height, width)
-        cfg = _Cfg(batch, height, width, (ctypes.c_int * 4)(*layers), width_base)
-        h = ctypes.c_void_p()
-        if ibn is not None:                      # dali_resnet_create_ex; all zero is dali_resnet_create's plan
-            ext = _Ext((ctypes.c_int * 4)(*[int(bool(v)) for v in ibn]))
-            _lib.check(_lib.lib().dali_resnet_create_ex(_lib.ctx(device), ctypes.byref(cfg), ctypes.byref(ext), ctypes.byref(h)), "dali_resnet_create_ex")
-        else:
-            _lib.check(_lib.lib().dali_resnet_create(_lib.ctx(device), ctypes.byref(cfg), ctypes.byref(h)), "dali_resnet_create")
-        self.h = h
-        pe, be, ab = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        fd, np_, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        _lib.check(_lib.lib().dali_resnet_sizes(h, ctypes.byref(pe), ctypes.byref(be), ctypes.byref(ab), ctypes.byref(fd),
-                                                 ctypes.byref(np_), ctypes.byref(nb)), "dali_resnet_sizes")
-        self.param_elems, self.buffer_elems, self.arena_bytes = pe.value, be.value, ab.value
-        self.feat_dim, self.n_params, self.n_buffers = fd.value, np_.value, nb.value
-
-    def tensor_table(self, kind):
-        out = []
-        name = ctypes.create_string_buffer(128)
-        off, numel, ndim = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
-        shape = (ctypes.c_int * 4)()
-        for i in range(self.n_params if kind == 0 else self.n_buffers):
-            _lib.check(_lib.lib().dali_resnet_tensor_info(self.h, kind, i, name, 128, ctypes.byref(off), ctypes.byref(numel),
-                                                           shape, ctypes.byref(ndim)), "dali_resnet_tensor_info")
-            out.append((name.value.decode(), off.value, numel.value, tuple(shape[:ndim.value])))
-        return out
-
-    def stage_range(self, stage):
-        b, e = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(_lib.lib().dali_resnet_stage_param_range(self.h, stage, ctypes.byref(b), ctypes.byref(e)), "stage_param_range")
-        return b.value, e.value
-
-    def __del__(self):
-        try:
-            _lib.lib().dali_resnet_destroy(self.h)
-        except Exception:
-            pass
-
-
-class _NetFn(torch.autograd.Function):
-    """autograd glue: forward = one C-ABI call, backward = one call per stage (+ optional gradient hook per stage)."""
-
-    @staticmethod
-    def forward(ctx, x, anchor, net):
-        ctx.net = net
-        return net._run_forward(x, training=True)
-
-    @staticmethod
-    def backward(ctx, d_emb):
-        net = ctx.net
-        net._run_backward(d_emb.contiguous())
-        return None, torch.zeros_like(net._anchor), None
+def _Plan(device, batch, height, width, layers, width_base, ibn=None):
+    """One dali_resnet plan for a fixed (batch, H, W).  ``ibn`` given: dali_resnet_create_ex (all zero is dali_resnet_create's plan)."""
+    cfg = _Cfg(batch, height, width, (ctypes.c_int * 4)(*layers), width_base)
+    ext = None if ibn is None else _Ext((ctypes.c_int * 4)(*[int(bool(v)) for v in ibn]))
+    return PlanHandle("resnet", device, cfg, ext)
 
 
 _FEATURE_MODES = {"both": 0, "gap": 1, "gmp": 2}        # dali_feature in include/daliid.h
@@ -107,56 +57,23 @@ def default_parts(map_rows):
     return (0, R // 2), (R // 4, R // 4 + R // 2), (R // 2, R)
 
 
-class ResNet50ReID(nn.Module):
+class ResNet50ReID(PlanNet):
     """Encoders.ResNet50ReID (Encoders.py:306-351) on the HIP net plan."""
 
     _ibn = None                              # dali_resnet_ext.ibn of this class' plans (None: dali_resnet_create)
     _own_prefixes = ("last_bn.",)           # what a trunk handed in as model_base does not carry
 
     def __init__(self, model_base=None, layers=(3, 4, 6, 3), width=64, device=None, seed=None):
-        super().__init__()
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-        if device is None:
-            raise _lib.DaliError("ResNet50ReID needs a gfx950 GPU; there is no CPU path")
-        self._device = torch.device(device)
+        super().__init__(device)
         self._layers, self._width = tuple(layers), int(width)
-        self._plans = {}
-        self._arena = None
-        self._last_plan = None
-        self._refreshed = (None, -1)
-        self.grad_stage_hook = None          # callable(stage, begin, end) after each backward stage (DP all-reduce)
         self.feature = "both"               # head pooling: "both" | "gap" | "gmp" (evaluateCleanATModels.py:249-256, :335-340)
-        probe = self._plan(1, 32, 32)
-        self.feat_dim = probe.feat_dim
-        dev = self._device
-        self.flat_params = torch.zeros(probe.param_elems, device=dev, dtype=torch.float32)
-        self.flat_grads = torch.zeros(probe.param_elems, device=dev, dtype=torch.float32)
-        self.flat_buffers = torch.zeros(probe.buffer_elems, device=dev, dtype=torch.float32)
-        self._anchor = torch.zeros(1, device=dev, requires_grad=True)
-        self._grad_views = {}
-        self._param_names = []
-        self._bn_modules = []
-        for name, off, numel, shape in probe.tensor_table(0):
-            if name == "last_bn.weight":
-                self._add_unplanned_modules()
-            leaf, attr = self._leaf(name)
-            view = self._view(self.flat_params, off, numel, shape)
-            leaf.register_parameter(attr, nn.Parameter(view))
-            self._grad_views[name] = self._view(self.flat_grads, off, numel, shape)
-            self._param_names.append(name)
-        table1 = probe.tensor_table(1)
-        self.flat_nbt = torch.zeros(sum(1 for t in table1 if t[0].endswith("running_var")), dtype=torch.long, device=dev)
-        for name, off, numel, shape in table1:
-            leaf, attr = self._leaf(name)
-            leaf.register_buffer(attr, self._view(self.flat_buffers, off, numel, shape))
-            if attr == "running_var":                    # all num_batches_tracked counters are views of ONE int64 vector
-                leaf.register_buffer("num_batches_tracked", self.flat_nbt[len(self._bn_modules)])
-                self._bn_modules.append(leaf)
+        self._register_plan_tensors(self._plan(1, 32, 32))
         self.reset_parameters(seed)
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module.mark_weights_changed())
         if model_base is not None:
             self._load_base(model_base.state_dict() if isinstance(model_base, nn.Module) else model_base)
+
+    def _make_plan(self, batch, height, width):
+        return _Plan(self._device, batch, height, width, self._layers, self._width, self._ibn)
 
     def _load_base(self, sd):
         """``ResNet50ReID(model_base)`` as the reference calls it (Encoders.py:33-37, 306-328): model_base is a torchvision ``resnet50``,
@@ -170,27 +87,13 @@ class ResNet50ReID(nn.Module):
             raise _lib.DaliError("%s(model_base): model_base is not a trunk of this architecture (missing %s, unexpected %s)"
                                  % (type(self).__name__, missing[:4], list(res.unexpected_keys)[:4]))
 
-    # ---- construction helpers -------------------------------------------------------------------
-    def _add_unplanned_modules(self):
-        """Modules of the reference class that sit between ``layer4`` and ``last_bn`` in its state_dict and that no forward runs
-        (none for ResNet50ReID); called once, when the parameter table reaches ``last_bn``."""
-
     @staticmethod
     def _view(flat, off, numel, shape):
         v = flat[off:off + numel]
-        if len(shape) == 4:                       # logical OIHW over OHWI storage (channels_last)
+        if len(shape) == 4:                       # a conv weight: logical OIHW over OHWI storage (channels_last)
             o, i, r, s = shape
             return v.view(o, r, s, i).permute(0, 3, 1, 2)
         return v.view(*shape)
-
-    def _leaf(self, dotted):
-        parts = dotted.split(".")
-        mod = self
-        for p in parts[:-1]:
-            if p not in mod._modules:
-                mod.add_module(p, nn.Module())
-            mod = mod._modules[p]
-        return mod, parts[-1]
 
     def reset_parameters(self, seed=None):
         """torchvision's ResNet init: conv kaiming_normal_(fan_out, relu); BN weight 1 / bias 0; stats 0 / 1."""
@@ -215,46 +118,6 @@ class ResNet50ReID(nn.Module):
                     b.zero_()
         self.mark_weights_changed()
 
-    @property
-    def _weights_version(self):
-        # every in-place write through any parameter view (optimizer step, copy_, load_state_dict) bumps the version
-        # counter the views share with the flat buffer; kernels that write it behind torch's back call
-        # mark_weights_changed()
-        return self.flat_params._version
-
-    def mark_weights_changed(self):
-        torch.autograd.graph.increment_version(self.flat_params)
-
-    def _apply(self, fn, recurse=True):
-        # parameters are views into flat storages owned by this module: device / dtype moves are not supported
-        probe = fn(torch.zeros(1, device=self._device))
-        if probe.device != self._device or probe.dtype != torch.float32:
-            raise _lib.DaliError("ResNet50ReID lives on %s in fp32 storage; .to()/.half()/.cpu() are not supported" % self._device)
-        return self
-
-    # ---- plans ---------------------------------------------------------------------------------------
-    def _plan(self, batch, height, width):
-        key = (batch, height, width)
-        p = self._plans.get(key)
-        if p is None:
-            p = self._plans[key] = _Plan(self._device, batch, height, width, self._layers, self._width, self._ibn)
-        return p
-
-    def _activate(self, plan):
-        if self._arena is None or self._arena.numel() < plan.arena_bytes:
-            self._arena = None
-            torch.cuda.synchronize(self._device)
-            self._arena = torch.empty(plan.arena_bytes + 256, device=self._device, dtype=torch.uint8)
-            self._refreshed = (None, -1)
-        L = _lib.lib()
-        if self._last_plan is not plan:
-            _lib.check(L.dali_resnet_bind(plan.h, _lib.ptr(self.flat_params), _lib.ptr(self.flat_grads), _lib.ptr(self.flat_buffers),
-                                          _lib.ptr(self._arena), self._arena.numel()), "dali_resnet_bind")
-            self._last_plan = plan
-        if self._refreshed != (plan.key, self._weights_version):
-            _lib.check(L.dali_resnet_refresh_weights(plan.h, _lib.stream_ptr()), "dali_resnet_refresh_weights")
-            self._refreshed = (plan.key, self._weights_version)
-
     def _run_forward(self, x, training):
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.DaliError("expected images [B,3,H,W], got %s" % (tuple(x.shape),))
@@ -264,12 +127,10 @@ class ResNet50ReID(nn.Module):
         emb = torch.empty(x.shape[0], plan.feat_dim, device=self._device, dtype=torch.float32)
         if self.feature not in _FEATURE_MODES:
             raise _lib.DaliError("feature must be 'both', 'gap' or 'gmp' (got %r)" % (self.feature,))
-        _lib.check(_lib.lib().dali_resnet_set_feature(plan.h, _FEATURE_MODES[self.feature]), "dali_resnet_set_feature")
-        _lib.check(_lib.lib().dali_resnet_forward(plan.h, _lib.stream_ptr(), _lib.ptr(x), int(training), _lib.ptr(emb)),
-                   "dali_resnet_forward")
+        plan.call("set_feature", _FEATURE_MODES[self.feature])
+        plan.call("forward", _lib.stream_ptr(), _lib.ptr(x), int(training), _lib.ptr(emb))
         if training:
-            self.flat_nbt += 1
-            self._bwd_plan = plan
+            self._trained(plan)
         return emb
 
     def _eval_only(self, what):
@@ -279,7 +140,7 @@ class ResNet50ReID(nn.Module):
     def head_map(self, height, width, batch=1):
         """(rows, columns) of the layer4 map for images of height x width: what the row ranges of ``forward_heads`` count."""
         h, w = ctypes.c_int(), ctypes.c_int()
-        _lib.check(_lib.lib().dali_resnet_head_map(self._plan(batch, height, width).h, ctypes.byref(h), ctypes.byref(w)), "dali_resnet_head_map")
+        self._plan(batch, height, width).call("head_map", ctypes.byref(h), ctypes.byref(w))
         return h.value, w.value
 
     def forward_heads(self, x, heads, heatmap=False):
@@ -299,40 +160,12 @@ class ResNet50ReID(nn.Module):
             emb = torch.empty(nh, x.shape[0], plan.feat_dim, device=self._device, dtype=torch.float32)
             heat = torch.empty((x.shape[0],) + self.head_map(x.shape[2], x.shape[3], x.shape[0]), device=self._device,
                                dtype=torch.float32) if heatmap else None
-            _lib.check(_lib.lib().dali_resnet_forward_heads(plan.h, _lib.stream_ptr(), _lib.ptr(x), specs, nh, _lib.ptr(emb), _lib.ptr(heat)),
-                       "dali_resnet_forward_heads")
+            plan.call("forward_heads", _lib.stream_ptr(), _lib.ptr(x), specs, nh, _lib.ptr(emb), _lib.ptr(heat))
         return (emb, heat) if heatmap else emb
-
-    n_bwd_stages = 4          # 0: neck + head + layer4, 1: layer3, 2: layer2, 3: layer1 + stem (dali_resnet_backward)
-
-    def _run_backward(self, d_emb):
-        for stage in range(self.n_bwd_stages):
-            self._backward_stage(d_emb, stage)
-        self.attach_grads()
-
-    def _backward_stage(self, d_emb, stage):
-        plan = self._bwd_plan
-        if plan is not self._last_plan:
-            raise _lib.DaliError("backward() after another forward of a different shape is not supported")
-        _lib.check(_lib.lib().dali_resnet_backward(plan.h, _lib.stream_ptr(), _lib.ptr(d_emb, torch.float32, "d_emb"), stage, stage),
-                   "dali_resnet_backward")
-        if self.grad_stage_hook is not None:
-            b, e = plan.stage_range(stage)
-            self.grad_stage_hook(stage, b, e)
-
-    def attach_grads(self):
-        """Point every parameter's .grad at its view of the flat gradient buffer (torch optimizers read .grad)."""
-        for name, p in zip(self._param_names, self.parameters()):
-            p.grad = self._grad_views[name]
-
-    def stage_ranges(self, batch, height, width):
-        plan = self._plan(batch, height, width)
-        return [plan.stage_range(s) for s in range(4)]
 
     def debug_tensor(self, name, dtype, shape):
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_int64()
-        _lib.check(_lib.lib().dali_resnet_debug_tensor(self._last_plan.h, name.encode(), ctypes.byref(ptr), ctypes.byref(nbytes)),
-                   "dali_resnet_debug_tensor")
+        self._last_plan.call("debug_tensor", name.encode(), ctypes.byref(ptr), ctypes.byref(nbytes))
         off = ptr.value - self._arena.data_ptr()
         return self._arena[off:off + nbytes.value].view(dtype).view(*shape).clone()
 
@@ -349,7 +182,7 @@ class ResNet50ReID(nn.Module):
             self._eval_only("forward(attention_map=True)")
             return self.forward_heads(x, [("gmp", None)], heatmap=True)[1][0]
         if self.training and torch.is_grad_enabled():
-            return _NetFn.apply(x, self._anchor, self)
+            return self._forward_with_grad(x)
         return self._run_forward(x, training=self.training)
 
 
@@ -369,7 +202,10 @@ class ResNet50IBNReID(ResNet50ReID):
     def __init__(self, model_base=None, layers=(3, 4, 6, 3), width=64, device=None, seed=None):
         super().__init__(model_base, layers, width, device, seed)
 
-    def _add_unplanned_modules(self):
+    def _before_param(self, name):
+        """The modules of the reference class that sit between ``layer4`` and ``last_bn`` in its state_dict and that no forward runs."""
+        if name != "last_bn.weight":
+            return
         # literal shapes, as in the reference (Encoders.py:483-487), whatever `width` is
         dev = self._device
         self.conv1x1_layer4 = nn.Conv2d(2048, 1, (1, 1), stride=1, device=dev)

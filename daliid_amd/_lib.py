@@ -206,11 +206,12 @@ def ctx(device=None, lane=0):
     key = device if lane == 0 else (device, lane)
     c = _ctxs.get(key)
     if c is None:
+        L = lib()                  # loaded before _lock is taken: lib() takes the same (non-reentrant) lock when it has to load
         with _lock:
             c = _ctxs.get(key)
             if c is None:
                 h = c_void_p()
-                check(lib().dali_ctx_create(device, ctypes.byref(h)), "dali_ctx_create")
+                check(L.dali_ctx_create(device, ctypes.byref(h)), "dali_ctx_create")
                 c = _ctxs[key] = h
     return c
 

@@ -201,7 +201,7 @@ class trainer(object):
         local = extractFeatures(selected_images[lo:hi], self.img_height, self.img_width, self.model_online, 500, gpu_index=self.gpu_indexes[0],
                                 keep_on_device=True)
         if local.shape[0] == 0:
-            local = local.new_zeros(0, getattr(self._net, "feat_dim", None) or self._net.in_planes)
+            local = local.new_zeros(0, self._net.feat_dim)
         self.last_inference_rows = hi - lo
         return parallel.all_gather_rows(local.float().contiguous(), bounds, self.process_group)
 

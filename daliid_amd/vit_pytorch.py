@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .plan_net import PlanHandle, PlanNet
 
 
 TRAIN_MAX_TOKENS = 256      # the attention backward's limit; the forward alone (eval mode) runs up to 1024 tokens
@@ -36,61 +37,18 @@ class _VitExt(ctypes.Structure):
                 ("divide", ctypes.c_int), ("token_map", ctypes.c_void_p), ("neck_after", ctypes.c_int), ("id_classes", ctypes.c_int)]
 
 
-class _VitPlan:
-    def __init__(self, device, cfg_tuple, ext=None):
-        cfg = _VitCfg(*cfg_tuple)
-        ext = dict(ext or {})
-        token_map = ext.pop("token_map", None)           # int32 [divide, L] on the host; the plan copies it during the call
-        if token_map is not None:
-            token_map = np.ascontiguousarray(token_map, dtype=np.int32)
-            ext["divide"], ext["token_map"] = token_map.shape[0], token_map.ctypes.data
-        ext = _VitExt(**ext)
-        h = ctypes.c_void_p()
-        _lib.check(_lib.lib().dali_vit_create_ex(_lib.ctx(device), ctypes.byref(cfg), ctypes.byref(ext), ctypes.byref(h)), "dali_vit_create_ex")
-        self.h = h
-        pe, be, ab = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        fd, np_, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        _lib.check(_lib.lib().dali_vit_sizes(h, ctypes.byref(pe), ctypes.byref(be), ctypes.byref(ab), ctypes.byref(fd), ctypes.byref(np_),
-                                              ctypes.byref(nb)), "dali_vit_sizes")
-        self.param_elems, self.buffer_elems, self.arena_bytes = pe.value, be.value, ab.value
-        self.feat_dim, self.n_params, self.n_buffers = fd.value, np_.value, nb.value
-
-        self.n_stages = int(_lib.lib().dali_vit_num_stages(h))
-
-    def stage_range(self, stage):
-        b, e = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(_lib.lib().dali_vit_stage_param_range(self.h, stage, ctypes.byref(b), ctypes.byref(e)), "dali_vit_stage_param_range")
-        return b.value, e.value
-
-    def tensor_table(self, kind):
-        out, name = [], ctypes.create_string_buffer(128)
-        off, numel, ndim, shape = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int(), (ctypes.c_int * 4)()
-        for i in range(self.n_params if kind == 0 else self.n_buffers):
-            _lib.check(_lib.lib().dali_vit_tensor_info(self.h, kind, i, name, 128, ctypes.byref(off), ctypes.byref(numel), shape,
-                                                        ctypes.byref(ndim)), "dali_vit_tensor_info")
-            out.append((name.value.decode(), off.value, numel.value, tuple(shape[:ndim.value])))
-        return out
-
-    def __del__(self):
-        try:
-            _lib.lib().dali_vit_destroy(self.h)
-        except Exception:
-            pass
+def _VitPlan(device, cfg_tuple, ext=None):
+    """One dali_vit plan for a fixed batch, always through dali_vit_create_ex (nothing set is dali_vit_create's plan).  ``ext``: a dict of
+    dali_vit_ext's fields; ``token_map`` is int32 [divide, L] on the host, the plan copies it during the call."""
+    ext = dict(ext or {})
+    token_map = ext.pop("token_map", None)
+    if token_map is not None:
+        token_map = np.ascontiguousarray(token_map, dtype=np.int32)
+        ext["divide"], ext["token_map"] = token_map.shape[0], token_map.ctypes.data
+    return PlanHandle("vit", device, _VitCfg(*cfg_tuple), _VitExt(**ext))
 
 
-class _VitFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, anchor, net, sie_idx=None):
-        ctx.net = net
-        return net._run_forward(x, True, sie_idx=sie_idx)
-
-    @staticmethod
-    def backward(ctx, d_feat):
-        ctx.net._run_backward(d_feat.contiguous())
-        return None, torch.zeros_like(ctx.net._anchor), None, None
-
-
-class ViTNeckNet(nn.Module):
+class ViTNeckNet(PlanNet):
     """TransReID encoder + BatchNorm1d neck on the HIP plan; state_dict keys as make_models.build_transformer
     (``base.*``, ``bottleneck.*``).  ``camera`` / ``view`` > 1 add the SIE parameter ``base.sie_embed`` (vit_pytorch.py:316-331);
     ``jpm`` (a dict of dali_vit_ext's JPM fields: ``token_map``, ``neck_after``, ``id_classes``; set by make_models.build_transformer_local) adds ``b1.*``, ``b2.*``, ``classifier*`` and
@@ -98,7 +56,7 @@ class ViTNeckNet(nn.Module):
 
     def __init__(self, img_size=(224, 224), patch_size=16, stride_size=16, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.0,
                  num_classes=1000, drop_path_rate=0.0, device=None, seed=None, camera=0, view=0, sie_xishu=1.0, local_feature=False, jpm=None):
-        super().__init__()
+        super().__init__(device)
         self.cam_num, self.view_num, self.sie_xishu = int(camera), int(view), float(sie_xishu)
         # vit_pytorch.py:317-331: one row per (camera, view) pair, per camera, or per view
         n_sie = camera * view if camera > 1 and view > 1 else camera if camera > 1 else view if view > 1 else 0
@@ -107,38 +65,13 @@ class ViTNeckNet(nn.Module):
         if jpm:
             self._ext.update(jpm=1, **jpm)
         self._sie_idx = None
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-        if device is None:
-            raise _lib.DaliError("the ViT path needs a gfx950 GPU; there is no CPU path")
-        self._device = torch.device(device)
         self.img_size = (img_size, img_size) if isinstance(img_size, int) else tuple(img_size)
         self._geom = (patch_size, stride_size, embed_dim, depth, num_heads, int(embed_dim * mlp_ratio), num_classes)
         self.drop_path_rate = float(drop_path_rate)
         self.drop_path_uniform = None            # optional [2*depth, B] uniform draws in [0,1) used instead of torch.rand (tests)
         self._dp_scales = None
         self.in_planes = embed_dim
-        self._plans, self._arena, self._last_plan, self._refreshed = {}, None, None, (None, -1)
-        probe = self._plan(1)
-        dev = self._device
-        self.flat_params = torch.zeros(probe.param_elems, device=dev)
-        self.flat_grads = torch.zeros(probe.param_elems, device=dev)
-        self.flat_buffers = torch.zeros(probe.buffer_elems, device=dev)
-        self.flat_nbt = torch.zeros(sum(1 for t in probe.tensor_table(1) if t[0].endswith("running_var")), dtype=torch.long, device=dev)
-        self._anchor = torch.zeros(1, device=dev, requires_grad=True)
-        self._grad_views, self._param_names = {}, []
-        for name, off, numel, shape in probe.tensor_table(0):
-            leaf, attr = self._leaf(name)
-            leaf.register_parameter(attr, nn.Parameter(self.flat_params[off:off + numel].view(*shape)))
-            self._grad_views[name] = self.flat_grads[off:off + numel].view(*shape)
-            self._param_names.append(name)
-        n_necks = 0
-        for name, off, numel, shape in probe.tensor_table(1):
-            leaf, attr = self._leaf(name)
-            leaf.register_buffer(attr, self.flat_buffers[off:off + numel].view(*shape))
-            if attr == "running_var":
-                leaf.register_buffer("num_batches_tracked", self.flat_nbt[n_necks])
-                n_necks += 1
+        self._register_plan_tensors(self._plan(1))            # every tensor in its stored order, the 4-D patch projection included
         for name, p in self.named_parameters():
             if name.startswith("bottleneck") and name.endswith(".bias"):
                 p.requires_grad_(False)                                              # make_models.py:181, :290-304
@@ -146,15 +79,10 @@ class ViTNeckNet(nn.Module):
         # reference, so torch.optim.Adam skips it (no weight decay either)
         self._no_grad_params = ("base.fc.weight", "base.fc.bias")
         self.reset_parameters(seed)
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module.mark_weights_changed())
 
-    def _leaf(self, dotted):
-        parts, mod = dotted.split("."), self
-        for p in parts[:-1]:
-            if p not in mod._modules:
-                mod.add_module(p, nn.Module())
-            mod = mod._modules[p]
-        return mod, parts[-1]
+    def _make_plan(self, batch):
+        ps, st, dim, depth, heads, hidden, ncls = self._geom
+        return _VitPlan(self._device, (batch, self.img_size[0], self.img_size[1], ps, st, dim, depth, heads, hidden, ncls), self._ext)
 
     def reset_parameters(self, seed=None):
         """vit_pytorch.py:350-361 + PatchEmbed_overlap init (:268-271) + weights_init_kaiming on the neck (make_models.py:182)."""
@@ -196,38 +124,6 @@ class ViTNeckNet(nn.Module):
                     sd[name].copy_(sd["base.norm." + name[5:]])
         self.mark_weights_changed()
 
-    def mark_weights_changed(self):
-        torch.autograd.graph.increment_version(self.flat_params)
-
-    def _apply(self, fn, recurse=True):
-        probe = fn(torch.zeros(1, device=self._device))
-        if probe.device != self._device or probe.dtype != torch.float32:
-            raise _lib.DaliError("this module lives on %s in fp32 storage; .to()/.half()/.cpu() are not supported" % self._device)
-        return self
-
-    def _plan(self, batch):
-        p = self._plans.get(batch)
-        if p is None:
-            ps, st, dim, depth, heads, hidden, ncls = self._geom
-            p = self._plans[batch] = _VitPlan(self._device, (batch, self.img_size[0], self.img_size[1], ps, st, dim, depth, heads, hidden, ncls), self._ext)
-        return p
-
-    def _activate(self, plan):
-        if self._arena is None or self._arena.numel() < plan.arena_bytes:
-            self._arena = None
-            torch.cuda.synchronize(self._device)
-            self._arena = torch.empty(plan.arena_bytes + 256, device=self._device, dtype=torch.uint8)
-            self._refreshed = (None, -1)
-        L = _lib.lib()
-        if self._last_plan is not plan:
-            _lib.check(L.dali_vit_bind(plan.h, _lib.ptr(self.flat_params), _lib.ptr(self.flat_grads), _lib.ptr(self.flat_buffers),
-                                       _lib.ptr(self._arena), self._arena.numel()), "dali_vit_bind")
-            self._last_plan = plan
-        key = (id(plan), self.flat_params._version)
-        if self._refreshed != key:
-            _lib.check(L.dali_vit_refresh_weights(plan.h, _lib.stream_ptr()), "dali_vit_refresh_weights")
-            self._refreshed = key
-
     def sie_index(self, cam_label, view_label, batch):
         """vit_pytorch.py:382-389: the row of ``sie_embed`` per sample, ``cam * view_num + view``, ``cam`` or ``view``, validated on the host
         -> int32 [batch] on the device (None for a model without SIE).  Labels: an int, a numpy array or a tensor of length ``batch``."""
@@ -259,23 +155,20 @@ class ViTNeckNet(nn.Module):
         plan = self._plan(x.shape[0])
         self._activate(plan)
         self._dp_scales = self._draw_drop_path(x.shape[0]) if training else None
-        _lib.check(_lib.lib().dali_vit_set_drop_path(plan.h, _lib.ptr(self._dp_scales)), "dali_vit_set_drop_path")
+        plan.call("set_drop_path", _lib.ptr(self._dp_scales))
         if self._ext["n_sie"] and sie_idx is None:
             raise _lib.DaliError("this model has SIE embeddings: forward() needs cam_label / view_label")
         if training:
             self._sie_idx = sie_idx                  # the backward's sie_grad reads it
         if want_tokens:
             tokens = torch.empty(x.shape[0], self.base.pos_embed.shape[1], self.in_planes, device=self._device)
-            _lib.check(_lib.lib().dali_vit_forward_ex(plan.h, _lib.stream_ptr(), _lib.ptr(x), _lib.ptr(sie_idx), 0, None, None, _lib.ptr(tokens)),
-                       "dali_vit_forward_ex")
+            plan.call("forward_ex", _lib.stream_ptr(), _lib.ptr(x), _lib.ptr(sie_idx), 0, None, None, _lib.ptr(tokens))
             return tokens
         feat = torch.empty(x.shape[0], plan.feat_dim, device=self._device)
         gf = torch.empty(x.shape[0], self.in_planes, device=self._device) if want_global else None
-        _lib.check(_lib.lib().dali_vit_forward_ex(plan.h, _lib.stream_ptr(), _lib.ptr(x), _lib.ptr(sie_idx), int(training), _lib.ptr(feat), _lib.ptr(gf),
-                                                  None), "dali_vit_forward_ex")
+        plan.call("forward_ex", _lib.stream_ptr(), _lib.ptr(x), _lib.ptr(sie_idx), int(training), _lib.ptr(feat), _lib.ptr(gf), None)
         if training:
-            self.flat_nbt += 1
-            self._bwd_plan = plan
+            self._trained(plan)
         return (feat, gf) if want_global else feat
 
     def _draw_drop_path(self, batch):
@@ -293,25 +186,6 @@ class ViTNeckNet(nn.Module):
         keep = 1.0 - dpr
         return ((keep + u.to(self._device, torch.float32)).floor() / keep).contiguous()
 
-    # the trainer / data-parallel reducer drive the backward per stage (= gradient bucket): groups of blocks, last group first
-    @property
-    def n_bwd_stages(self):
-        return self._bwd_plan.n_stages
-
-    def _backward_stage(self, d_feat, stage):
-        plan = self._bwd_plan
-        if plan is not self._last_plan:
-            raise _lib.DaliError("backward() after another forward of a different shape is not supported")
-        _lib.check(_lib.lib().dali_vit_backward_stages(plan.h, _lib.stream_ptr(), _lib.ptr(d_feat, torch.float32, "d_feat"), stage, stage),
-                   "dali_vit_backward_stages")
-
-    def _run_backward(self, d_feat, attach=True):
-        for stage in range(self.n_bwd_stages):
-            self._backward_stage(d_feat, stage)
-        if attach:
-            for name, p in zip(self._param_names, self.parameters()):
-                p.grad = self._grad_views[name] if p.requires_grad else None
-
     @property
     def num_tokens(self):
         return int(self.base.pos_embed.shape[1])
@@ -325,7 +199,7 @@ class ViTNeckNet(nn.Module):
                 # past 256 tokens only the attention forward exists (the plan holds none of the backward's buffers)
                 raise _lib.DaliError("training needs at most %d tokens (this model has %d): it is eval mode only -- call .eval() and run under "
                                      "torch.no_grad()" % (TRAIN_MAX_TOKENS, self.num_tokens))
-            return _VitFn.apply(x, self._anchor, self, idx)
+            return self._forward_with_grad(x, sie_idx=idx)
         return self._run_forward(x, self.training, sie_idx=idx)
 
     def global_feat(self, x, cam_label=None, view_label=None):

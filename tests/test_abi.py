@@ -55,3 +55,27 @@ def test_product_never_imports_oracle():
             if f.endswith(".py"):
                 src = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), f
+
+
+_CTX_FIRST = """
+import sys
+sys.path.insert(0, %r)
+import torch
+torch.cuda.is_available = lambda: True            # no GPU needed: the call may fail in dali_ctx_create, it must come back
+torch.cuda.current_device = lambda: 0
+from daliid_amd import _lib
+try:
+    _lib.ctx(0)
+except _lib.DaliError:
+    pass
+print("came back")
+"""
+
+
+def test_ctx_as_the_first_call_of_a_process_comes_back():
+    """``_lib.ctx`` creates a context under the lock that ``_lib.lib`` takes to load the library: as the first call of a fresh process
+    (a net built before anything else touched the library) it must load first, not wait for its own lock."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, "-c", _CTX_FIRST % ROOT], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "came back" in out.stdout, out.stderr[-400:]
