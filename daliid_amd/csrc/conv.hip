@@ -229,21 +229,28 @@ __device__ __forceinline__ float row16_reduce8(const float (&v)[8], int lane) {
 // workgroup lifetime in VALU / LDS-crossbar work (statistics by 128 ds_bpermute shuffles, per-element predicates and
 // 64-bit address arithmetic, 8-byte stores scattered over 16 cache lines per instruction) while the stores themselves
 // drained in 0.2 us.  Hence: statistics first, reduced with DPP row rotates; barriers that order LDS traffic only (a
-// __syncthreads() would wait for the global stores); and for interior tiles of the plain convolution a lean path that
-// stages the tile through LDS as [pixel][TM channels] bf16 and writes 16 bytes per lane, TM/8 adjacent lanes covering
-// one pixel's contiguous TM*2 bytes, without per-element predicates.  Values and rounding are identical on every path.
+// __syncthreads() would wait for the global stores); and for interior tiles a staged path that puts the tile through
+// LDS as [pixel][TM channels] bf16 and writes 16 bytes per lane, TM/8 adjacent lanes covering one pixel's contiguous
+// TM*2 bytes, without per-element predicates.
 // Generic over the block shape: TM x TN tile, WNW waves along n, NT threads; this wave sits at (wm, wn) and owns an
 // (FM*16) x (FN*16) sub-tile.
+//
+// The arithmetic of the output stage is written once (OutStage: affine, bias, O2, GELU, GELU', row factor, residual, ReLU, the one rounding,
+// the output gate, the mask bits, in that order) and every store path calls it: conv_epilogue_cols (8 channels at a time, the 256 x 320 tile),
+// epi_store_staged (4 at a time, half tiles through LDS; its kinds CONV, PARITY, LIN, FUSED, FUSED_LEAN) and epi_store_general (edge tiles and
+// whatever the staged paths refuse).  What stays per path is staging, addressing, barriers, prefetch and where an operand is fetched from (the
+// path's operand source: ColsSrc, StagedSrc, GeneralSrc).  Values and rounding are the same on every path, with one recorded exception:
+// out_shift together with bias under the fused modes, where the staged store folds the bias into the shift first (see epi_store_staged).
 //
 // What an instantiation's output stage compiles in (conv_epilogue_g; the kernels' MODE / EPI parameter, which the GemmKernel table names for
 // every entry).  Each mode is its own instantiation so that the hot convolution kernels compile none of the others' code: code that is never
 // executed still cost their register allocation 0.4-0.8 ms per ResNet step.
 enum class Epi : int {
-    CONV = 0,        // convolution only: the lean staged store (+ residual, + residual mask); no linear-layer extras compiled in at all
-    LIN = 1,         // linear-layer extras (GELU, pre-activation copy O2, GELU' factor, DropPath row factor) in a staged block and in the general path
-    GENERAL = 2,     // the lean store, the extras in the general path only: kernels without a LIN variant
-    FUSED = 3,       // the fused output stage (IGemmArgs::out_scale ... out_mask) in a staged block and in the general path
-    PARITY = 4,      // the lean store with the output addressing of a stride-2 data gradient's parity class (GatherGeom::sub)
+    CONV = 0,        // convolution only: the staged store's CONV kind (+ bias, + residual, + residual mask); no linear-layer extras compiled in at all
+    LIN = 1,         // linear-layer extras (GELU, pre-activation copy O2, GELU' factor, DropPath row factor) in the staged store's LIN kind and in the general path
+    GENERAL = 2,     // the CONV kind, the extras in the general path only: kernels without a LIN variant
+    FUSED = 3,       // the fused output stage (IGemmArgs::out_scale ... out_mask) in the staged store's FUSED kind and in the general path
+    PARITY = 4,      // the CONV kind with the output addressing of a stride-2 data gradient's parity class (GatherGeom::sub)
     FUSED_LEAN = 5,  // the fused stage WITHOUT residual, masks and mask bits (scale / shift / bias / ReLU only): the inference forward's conv + BatchNorm
                      // + ReLU launches on the 3x3 and narrow kernels, whose register budgets the full stage's residual prefetch overflowed
 };
@@ -285,22 +292,170 @@ __device__ __forceinline__ void unpack4(uint2 q, float (&f)[4]) {
 __device__ __forceinline__ uint2 pack4(const float (&v)[4]) { return make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])); }
 // this lane's 4 channels of every 16-row block of a per-channel vector (bias, scale, shift); `vec` points at the lane's first channel
 template <int FM>
-__device__ __forceinline__ void load_rows4(float4 (&d)[FM], const float* vec) {
+__device__ __forceinline__ void load_rows4(float (&d)[FM][4], const float* vec) {
 #pragma unroll
-    for (int i = 0; i < FM; ++i) d[i] = *reinterpret_cast<const float4*>(vec + i * 16);
+    for (int i = 0; i < FM; ++i) {
+        const float4 q = *reinterpret_cast<const float4*>(vec + i * 16);
+        d[i][0] = q.x; d[i][1] = q.y; d[i][2] = q.z; d[i][3] = q.w;
+    }
 }
 // bit 0 / bit 1: the low / high bf16 half of w is > 0
 __device__ __forceinline__ unsigned pos_bits_bf16x2(uint32_t w) {
     return ((int)(int16_t)(w & 0xffffu) > 0 ? 1u : 0u) | (((int)w >> 16) > 0 ? 2u : 0u);
 }
+// the same helpers by the number of channels, for OutStage: N = 4 in a uint2, N = 8 in a uint4
+template <int N> struct Bf16xN;
+template <> struct Bf16xN<4> { using type = uint2; };
+template <> struct Bf16xN<8> { using type = uint4; };
+__device__ __forceinline__ void unpack_n(uint2 q, float (&f)[4]) { unpack4(q, f); }
+__device__ __forceinline__ void unpack_n(const uint4& q, float (&f)[8]) { unpack8(q, f); }
+__device__ __forceinline__ uint2 pack_n(const float (&v)[4]) { return pack4(v); }
+__device__ __forceinline__ uint4 pack_n(const float (&v)[8]) { return pack8(v); }
+__device__ __forceinline__ void gate_n(uint2& v, unsigned m) { v.x = gate_bf16x2(v.x, m); v.y = gate_bf16x2(v.y, m >> 2); }      // (bits 0-3 of m)
+__device__ __forceinline__ void gate_n(uint4& v, unsigned m) { gate_bf16x8(v, m); }
+__device__ __forceinline__ unsigned pos_bits_n(uint2 v) { return pos_bits_bf16x2(v.x) | (pos_bits_bf16x2(v.y) << 2); }
+__device__ __forceinline__ unsigned pos_bits_n(const uint4& v) {
+    return pos_bits_bf16x2(v.x) | (pos_bits_bf16x2(v.y) << 2) | (pos_bits_bf16x2(v.z) << 4) | (pos_bits_bf16x2(v.w) << 6);
+}
+// N consecutive floats of a per-channel vector (16-byte loads)
+template <int N>
+__device__ __forceinline__ void load_nf(const float* p, float (&f)[N]) {
+#pragma unroll
+    for (int q = 0; q < N; q += 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p + q);
+        f[q] = t.x; f[q + 1] = t.y; f[q + 2] = t.z; f[q + 3] = t.w;
+    }
+}
+
+// ---- The output stage: N adjacent channels of one pixel, from the fp32 accumulators to the bf16 that O receives.  Every store path below calls
+// it, and it is the only code in this file that knows the order of the steps; a path owns where the operands come from (LDS slot, register
+// prefetch, global load), its barriers, its addresses and its stamps.  MODE: what is compiled in, as the general path of that instantiation has
+// it (CONV stands for CONV and PARITY alike).  Src is the path's operand source: has_x() says whether operand x is there, x(value&) fetches
+// it at the moment the stage wants it, so that a path's loads stay where they were (fetched ahead of the stage they stayed live across it:
+// spills and lost occupancy in a dozen kernels); a source that answers has_x() with a constant compiles the step in or out.
+//   1  v = acc * scale + shift        fused modes
+//   2  v += bias
+//   3  O2 receives v                  (Src::o2; the staged linear path sends O2 in a pass of its own, from pre())
+//   4  v = gelu(v)
+//      Src::load_inputs()             a source whose dact and res are one quad in LDS reads it here, once (read where each is wanted, the
+//                                     two reads cost K64S_LIN and WG128_LIN a spilled register each)
+//   5  v *= gelu'(dact)
+//   6  v *= row_scale
+//   7  v += (res_scale *) res         res gated by res_mask
+//   8  v = max(v, 0)
+//   9  the one rounding to bf16
+//   10 the out_mask gate              gate(): the staged fused path rounds a quad into LDS and gates the 16-byte chunk it reads back
+//   11 bits_out from the gated value
+template <Epi MODE, int N>
+struct OutStage {
+    using Pack = typename Bf16xN<N>::type;
+    static constexpr bool AFFINE = epi_fused(MODE), EXTRAS = MODE == Epi::LIN || MODE == Epi::GENERAL, RES = MODE != Epi::FUSED_LEAN,
+                          RES_MASK = RES && MODE != Epi::FUSED, FULL = MODE == Epi::FUSED;
+    template <class Src>
+    static __device__ __forceinline__ void pre(float (&v)[N], const Src& s) {            // steps 1-2
+        float f[N];
+        if constexpr (AFFINE) {
+            if (s.has_scale()) {
+                s.scale(f);
+#pragma unroll
+                for (int t = 0; t < N; ++t) v[t] *= f[t];
+            }
+            if (s.has_shift()) {
+                s.shift(f);
+#pragma unroll
+                for (int t = 0; t < N; ++t) v[t] += f[t];
+            }
+        }
+        if (s.has_bias()) {
+            s.bias(f);
+#pragma unroll
+            for (int t = 0; t < N; ++t) v[t] += f[t];
+        }
+    }
+    template <class Src>
+    static __device__ __forceinline__ Pack run(float (&v)[N], const Src& s) {            // steps 1-9
+        pre(v, s);
+        if constexpr (EXTRAS) {
+            if (s.want_o2()) s.o2(pack_n(v));
+            if (s.gelu()) {
+#pragma unroll
+                for (int t = 0; t < N; ++t) v[t] = gelu_f(v[t]);
+            }
+        }
+        s.load_inputs();
+        if constexpr (EXTRAS) {
+            if (s.has_dact()) {
+                Pack xv;
+                s.dact(xv);
+                float x[N];
+                unpack_n(xv, x);
+#pragma unroll
+                for (int t = 0; t < N; ++t) v[t] *= gelu_grad_f(x[t]);
+            }
+            if (s.has_row_scale()) {
+                float rs;
+                s.row_scale(rs);
+#pragma unroll
+                for (int t = 0; t < N; ++t) v[t] *= rs;
+            }
+        }
+        if constexpr (RES) {
+            if (s.has_res()) {
+                Pack rv;
+                s.res(rv);
+                if constexpr (RES_MASK) if (s.has_res_mask()) { unsigned m; s.res_mask(m); gate_n(rv, m); }
+                float r[N], f[N];
+                unpack_n(rv, r);
+                if constexpr (FULL) if (s.has_res_scale()) {
+                    s.res_scale(f);
+#pragma unroll
+                    for (int t = 0; t < N; ++t) r[t] *= f[t];
+                }
+#pragma unroll
+                for (int t = 0; t < N; ++t) v[t] += r[t];
+            }
+        }
+        if constexpr (AFFINE) if (s.relu()) {
+#pragma unroll
+            for (int t = 0; t < N; ++t) v[t] = fmaxf(v[t], 0.f);
+        }
+        return pack_n(v);
+    }
+    // steps 10-11 on a rounded value: gates w in place, returns its N mask bits
+    static __device__ __forceinline__ unsigned gate(Pack& w, bool mask_on, const unsigned& mask) {      // (mask: read only under mask_on)
+        if (mask_on) gate_n(w, mask);
+        return pos_bits_n(w);
+    }
+};
+
 // Staged store, one 16-pixel column block of every wave at a time (any FN; used by the 256 x 320 tile, FN = 5).  The staging is a pure
 // transpose: the WNW * 16 pixels of step j go through LDS as [pixel][TM channels] fp32 accumulators, and the thread that reads 8 adjacent
-// channels of a pixel back applies the whole output stage to them -- bias, pre-activation copy (O2), GELU, GELU' factor, DropPath row
-// factor, residual (+ mask) -- with its residual / GELU' argument chunk (16 bytes, requested before the staging so that the transpose
-// hides its latency) and stores 16 bytes.  One rounding to bf16 at the end, as on every other path; interior tiles, natural output
-// addressing, Cm % 8 == 0.  (Its own geometry: fp32 by column block, not the half tiles of EpiStage below.)
-template <int TM, int TN, int FM_, int FN_, int WNW, int NT>
+// channels of a pixel back runs the output stage on them with its residual / GELU' argument chunk (16 bytes, requested before the staging so
+// that the transpose hides its latency) and stores 16 bytes.  Interior tiles, natural output addressing, Cm % 8 == 0, no fused mode.
+// (Its own geometry: fp32 by column block, not the half tiles of EpiStage below.)
+// Its operands: the per-channel vectors, the row factor and the mask byte from global memory at byte offset `ob` of the 8-channel chunk; the
+// residual / GELU' argument chunk from the prefetch register.
+struct ColsSrc {
+    const IGemmArgs& a; const float* bias_c; const uint4& tin; uint32_t ob;
+    __device__ __forceinline__ void load_inputs() const {}
+    __device__ __forceinline__ bool has_bias() const { return bias_c != nullptr; }
+    __device__ __forceinline__ void bias(float (&f)[8]) const { load_nf(bias_c, f); }
+    __device__ __forceinline__ bool want_o2() const { return a.O2 != nullptr; }
+    __device__ __forceinline__ void o2(const uint4& w) const { *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O2) + ob) = w; }
+    __device__ __forceinline__ bool gelu() const { return a.act == 1; }
+    __device__ __forceinline__ bool has_dact() const { return a.dact_pre != nullptr; }
+    __device__ __forceinline__ void dact(uint4& x) const { x = tin; }
+    __device__ __forceinline__ bool has_row_scale() const { return a.row_scale != nullptr; }
+    __device__ __forceinline__ void row_scale(float& rs) const { rs = a.row_scale[ob / ((uint32_t)a.Cm * 2u)]; }
+    __device__ __forceinline__ bool has_res() const { return a.Res != nullptr; }
+    __device__ __forceinline__ void res(uint4& r) const { r = tin; }
+    // (reachable: dali_conv2d_dgrad with a masked residual at a shape conv_prefers_320 takes, e.g. 1x1 / stride 1, 512 channels, 32896 pixels)
+    __device__ __forceinline__ bool has_res_mask() const { return a.res_mask != nullptr; }
+    __device__ __forceinline__ void res_mask(unsigned& m) const { m = a.res_mask[ob >> 4]; }
+};
+template <Epi MODE, int TM, int TN, int FM_, int FN_, int WNW, int NT>
 __device__ __forceinline__ void conv_epilogue_cols(const IGemmArgs& a, f32x4_t (&acc)[FM_][FN_], int tm, int tn, uint16_t* smem, int wm, int wn) {
+    static_assert(!epi_fused(MODE), "the column-block store has no fused output stage");
     constexpr int ROWB = TM * 4 + 16, ROWS = WNW * 16, CPR = TM / 8, ITERS = ROWS * CPR / NT;       // +16: 16 rows of 16-byte writes cover all banks once
     static_assert(ROWS * CPR % NT == 0 && NT % CPR == 0, "staged store: threads must tile the column block evenly");
     const int lane = threadIdx.x & 63;
@@ -328,47 +483,19 @@ __device__ __forceinline__ void conv_epilogue_cols(const IGemmArgs& a, f32x4_t (
         for (int it = 0; it < ITERS; ++it) {
             const int lp = lp0 + it * (NT / CPR);
             float v[8];
+            // (16-byte stores into v: read element by element the 8 values stop travelling as two quads and this kernel spills 8 registers)
             *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(stage + lp * ROWB + ch * 32);
             *reinterpret_cast<float4*>(v + 4) = *reinterpret_cast<const float4*>(stage + lp * ROWB + ch * 32 + 16);
-            if (bias_c) {
-                const float4 b0 = *reinterpret_cast<const float4*>(bias_c), b1 = *reinterpret_cast<const float4*>(bias_c + 4);
-                v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-            }
-            if (a.O2) *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O2) + gofs[it]) = pack8(v);
-            if (a.act == 1) {
-#pragma unroll
-                for (int t = 0; t < 8; ++t) v[t] = gelu_f(v[t]);
-            }
-            if (a.dact_pre) {
-                float x8[8];
-                unpack8(tin[it], x8);
-#pragma unroll
-                for (int t = 0; t < 8; ++t) v[t] *= gelu_grad_f(x8[t]);
-            }
-            if (a.row_scale) {
-                const float rs = a.row_scale[gofs[it] / ((uint32_t)a.Cm * 2u)];
-#pragma unroll
-                for (int t = 0; t < 8; ++t) v[t] *= rs;
-            }
-            if (a.Res) {
-                uint4 rv = tin[it];
-                // (reachable: dali_conv2d_dgrad with a masked residual at a shape conv_prefers_320 takes, e.g. 1x1 / stride 1, 512 channels, 32896 pixels)
-                if (a.res_mask) gate_bf16x8(rv, a.res_mask[gofs[it] >> 4]);
-                float r8[8];
-                unpack8(rv, r8);
-#pragma unroll
-                for (int t = 0; t < 8; ++t) v[t] += r8[t];
-            }
-            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + gofs[it]) = pack8(v);
+            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + gofs[it]) = OutStage<MODE, 8>::run(v, ColsSrc{a, bias_c, tin[it], gofs[it]});
         }
         if (j + 1 < FN_) lds_barrier();                  // the read-out is done before the next column block overwrites the stage
     }
 }
 
-// The staged half-tile store's geometry, shared by the lean, linear-extras and fused paths.  The tile's pixels leave in two halves (the first
-// FN / 2 of every wave's 16-pixel column blocks, then the rest).  A half goes through LDS as [pixel][TM channels] bf16: every lane puts its
-// accumulator quads into `slot(jj, i)`; after a barrier a thread owns the 16-byte chunk `ch` of rows row(0), row(1), ..., CPR adjacent lanes
-// covering one pixel's contiguous TM * 2 bytes.  An input tile (residual, GELU' argument) comes in the same way and is read back from the slots.
+// The staged half-tile store's geometry.  The tile's pixels leave in two halves (the first FN / 2 of every wave's 16-pixel column blocks, then
+// the rest).  A half goes through LDS as [pixel][TM channels] bf16: every lane puts its accumulator quads into `slot(jj, i)`; after a barrier
+// a thread owns the 16-byte chunk `ch` of rows row(0), row(1), ..., CPR adjacent lanes covering one pixel's contiguous TM * 2 bytes.  An input
+// tile (residual, GELU' argument) comes in the same way and is read back from the slots.
 constexpr int epi_stage_bytes(int TM, int TN) { return (TN / 2) * (TM * 2 + 32); }      // the LDS image of a half; the statistics' partial sums sit behind it
 template <bool SUB, int TM, int TN, int FM, int FN, int WNW, int NT>      // SUB: output rows through a parity class's scattered pixels (out_pixel)
 struct EpiStage {
@@ -397,7 +524,7 @@ struct EpiStage {
         if constexpr (SUB) return (out_pixel(a.g, tn * TN + h * WROWS + pixel(it)) * a.Cm + tm * TM + ch * 8) * 2;
         else return ((size_t)(tn * TN + h * WROWS) * a.Cm + tm * TM + ch * 8) * 2 + (size_t)pixel(it) * a.Cm * 2;
     }
-    // that chunk of tensor `src`; the staged chunk -> `dst`.  (The loops over `it` stay in the store paths, inside their loop over the halves: a
+    // that chunk of tensor `src`; the staged chunk -> `dst`.  (The loops over `it` stay in the store path, inside its loop over the halves: a
     // member holding the loop is unrolled before it is inlined, its chunk addresses are then hoisted out of the half loop and stay live across
     // both halves: 105 -> 122 VGPRs for the 128 x 128 tile of igemm_conv_ring_kernel, DMA128.)
     __device__ __forceinline__ uint4 in(const uint16_t* src, int h, int it) const {
@@ -438,154 +565,89 @@ __device__ __forceinline__ void epi_stats(const IGemmArgs& a, f32x4_t (&acc)[FM]
         }
     }
 }       // no barrier: the staged stores do not touch `red`
-// ---- lean path: plain convolution (optionally + bias, + residual, + residual mask), interior tile ----
-// SUB (Epi::PARITY): the output addressing of a stride-2 data gradient's parity class: the pixel rows of the tile scatter to every second
-// position of every second image row, each still TM * 2 contiguous bytes.  Its own instantiations (the sub-problems went through the general
-// path before: 8-byte stores per lane, per-element residual loads; layer2's downsample data gradient 169 us against 71 us forward), so that
-// the hot convolution instantiations stay as they are.
-template <bool SUB, int TM, int TN, int FM, int FN, int WNW, int NT>
-__device__ __forceinline__ void epi_store_lean(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wn, int mb) {
-    using Stage = EpiStage<SUB, TM, TN, FM, FN, WNW, NT>;
-    constexpr int ITERS = Stage::ITERS;
-    const Stage st(a, tm, tn, smem, wn, mb);
-    float4 bias4[FM];                                           // this lane's 4 channels of every 16-row block (linear layers; folded in here)
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-        bias4[i] = a.bias ? *reinterpret_cast<const float4*>(a.bias + tm * TM + mb + i * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (a.Res) {
-            unsigned rm[ITERS];                                 // (mask bytes requested together: see the fused output stage below)
-            if (a.res_mask) {
-#pragma unroll
-                for (int it = 0; it < ITERS; ++it) rm[it] = a.res_mask[st.offset(h, it) >> 4];
-            }
-#pragma unroll
-            for (int it = 0; it < ITERS; ++it) {
-                uint4 rv = st.in(a.Res, h, it);
-                if (a.res_mask) gate_bf16x8(rv, rm[it]);
-                *st.chunk(it) = rv;
-            }
-            lds_barrier_vm();                                   // the loaded residual is visible to every wave
-        }
-#pragma unroll
-        for (int jj = 0; jj < Stage::HFN; ++jj) {
-            const int j = h * Stage::HFN + jj;
-#pragma unroll
-            for (int i = 0; i < FM; ++i) {
-                float v[4] = {acc[i][j][0] + bias4[i].x, acc[i][j][1] + bias4[i].y, acc[i][j][2] + bias4[i].z, acc[i][j][3] + bias4[i].w};
-                uint2* slot = st.slot(jj, i);
-                if (a.Res) {
-                    float r4[4];
-                    unpack4(*slot, r4);
-                    v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3];
-                }
-                *slot = pack4(v);
-            }
-        }
-        lds_barrier();
-        conv_stamp(a, 6 + 2 * h);   // half staged
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) st.out(a.O, h, it);
-        conv_stamp(a, 7 + 2 * h);   // half's stores issued
-        if (h == 0) lds_barrier();                              // the LDS reads are done before the second half overwrites them
-    }
-}
-// ---- linear-layer extras (Epi::LIN): GELU, pre-activation copy, GELU' factor, DropPath row factor; interior tile, natural addressing ----
-// A second staged block, kept apart so that the convolutions' path stays as lean as it was (folding them into one block cost the ResNet step
-// 0.8 ms), and only in the LIN instantiations of the kernels (compiled into every kernel it changed the convolutions' register allocation and
-// cost the ResNet step 0.4 ms even when never taken).  No residual mask: conv_choose refuses res_mask beside an extra.
-template <int TM, int TN, int FM, int FN, int WNW, int NT>
-__device__ __forceinline__ void epi_store_lin(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wn, int mb) {
-    using Stage = EpiStage<false, TM, TN, FM, FN, WNW, NT>;
+// ---- The staged half-tile store of an interior tile whose pixels are whole 16-byte chunks (Cm % 8 == 0).  One skeleton per half -- optional
+// O2 pass, optional input tile into the slots, the output stage quad by quad, barrier, read-out -- and KIND says, while compiling, what hangs
+// on it; each kind is its own instantiation and compiles none of the others' code:
+//   CONV        plain convolution (+ bias, + residual, + residual mask: the mask gates the residual chunk on its way into LDS).
+//   PARITY      the same with the output addressing of a stride-2 data gradient's parity class: the pixel rows of the tile scatter to every
+//               second position of every second image row, each still TM * 2 contiguous bytes.  (The sub-problems went through the general
+//               path before: 8-byte stores per lane, per-element residual loads; layer2's downsample data gradient 169 us against 71 us forward.)
+//   LIN         the linear-layer extras: GELU, pre-activation copy, GELU' factor, DropPath row factor; one input tile (residual or GELU'
+//               argument).  No residual mask: conv_choose refuses res_mask beside an extra.
+//   FUSED       the fused output stage (see IGemmArgs); the residual tile of both halves prefetched into registers, the mask bytes of a half
+//               requested together, out_mask and bits_out at the read-out.  No residual mask: conv_choose refuses it beside a fused-stage field.
+//   FUSED_LEAN  scale / shift / bias / ReLU only.
+// The stamps stay out of the fused kinds, which never had them (their kernels sit at their register budgets).
+// (Earlier measurements against folding these paths -- 0.8 ms and 0.4 ms per ResNet step -- were of run-time branches inside one instantiation:
+// code that is never executed still cost the register allocation.  Here every branch on the kind is compile-time, and none of the three former
+// functions (lean, linear extras, fused) had to stay apart: no kernel gained a spill or lost occupancy, docs/experiments.md has the table.)
+// Its operands, for one accumulator quad: scale and the additive vector from this lane's registers (always there: 1 and 0 when the launch has
+// none), the input tile's quad from the LDS slot the result then overwrites, the row factor and res_scale from global memory.
+template <bool FUSED>
+struct StagedSrc {
+    const IGemmArgs& a; const float (&mul)[4]; const float (&add)[4];
+    const uint2* slot; bool res_on, dact_on;
+    int pix, c;               // the quad's pixel and first channel
+    mutable uint2 in_q;       // the input tile's quad (residual or GELU' argument: the staged store takes one input tile)
+    __device__ __forceinline__ void load_inputs() const { if (res_on || dact_on) in_q = *slot; }
+    __device__ __forceinline__ void copy4(const float (&s)[4], float (&f)[4]) const { f[0] = s[0]; f[1] = s[1]; f[2] = s[2]; f[3] = s[3]; }
+    __device__ __forceinline__ bool has_scale() const { return true; }
+    __device__ __forceinline__ void scale(float (&f)[4]) const { copy4(mul, f); }
+    __device__ __forceinline__ bool has_shift() const { return true; }
+    __device__ __forceinline__ void shift(float (&f)[4]) const { copy4(add, f); }                   // (the bias is folded in: see epi_store_staged)
+    __device__ __forceinline__ bool has_bias() const { return !FUSED; }
+    __device__ __forceinline__ void bias(float (&f)[4]) const { copy4(add, f); }
+    __device__ __forceinline__ bool want_o2() const { return false; }                               // (a pass of its own)
+    __device__ __forceinline__ void o2(uint2) const {}
+    __device__ __forceinline__ bool gelu() const { return a.act == 1; }
+    __device__ __forceinline__ bool has_dact() const { return dact_on; }
+    __device__ __forceinline__ void dact(uint2& x) const { x = in_q; }
+    // DropPath: the whole branch output (bias included) times its sample's factor
+    __device__ __forceinline__ bool has_row_scale() const { return a.row_scale != nullptr; }
+    __device__ __forceinline__ void row_scale(float& rs) const { rs = a.row_scale[pix]; }
+    __device__ __forceinline__ bool has_res() const { return res_on; }
+    __device__ __forceinline__ void res(uint2& r) const { r = in_q; }
+    __device__ __forceinline__ bool has_res_mask() const { return false; }                          // (gated on its way into LDS)
+    __device__ __forceinline__ void res_mask(unsigned&) const {}
+    // (loaded per use: L1-resident; held across the tile it cost 16 registers and spills)
+    __device__ __forceinline__ bool has_res_scale() const { return a.res_scale != nullptr; }
+    __device__ __forceinline__ void res_scale(float (&f)[4]) const { load_nf(a.res_scale + c, f); }
+    __device__ __forceinline__ bool relu() const { return a.out_relu != 0; }
+};
+template <Epi KIND, int TM, int TN, int FM, int FN, int WNW, int NT>
+__device__ __forceinline__ void epi_store_staged(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wn, int mb) {
+    constexpr bool LIN = KIND == Epi::LIN, FUSED = epi_fused(KIND), FULL = KIND == Epi::FUSED, LEAN = !LIN && !FUSED;
+    using Stage = EpiStage<KIND == Epi::PARITY, TM, TN, FM, FN, WNW, NT>;
+    using Out = OutStage<KIND == Epi::PARITY ? Epi::CONV : KIND, 4>;
     constexpr int ITERS = Stage::ITERS;
     const Stage st(a, tm, tn, smem, wn, mb);
     const int lane = threadIdx.x & 63;
-    float4 bias4[FM];                                           // this lane's 4 channels of every 16-row block
+    // this lane's 4 channels of every 16-row block: `add` is the bias, under the fused kinds the shift; `mul` the fused kinds' scale
+    float mul[FM][4], add[FM][4];
 #pragma unroll
     for (int i = 0; i < FM; ++i)
-        bias4[i] = a.bias ? *reinterpret_cast<const float4*>(a.bias + tm * TM + mb + i * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const uint16_t* in_tile = a.Res ? a.Res : a.dact_pre;       // optional input tile (residual / GELU' argument) staged through LDS in the output layout
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (a.O2) {                                             // pre-activation copy (kept for the backward) goes out first
+        for (int t = 0; t < 4; ++t) { mul[i][t] = 1.f; add[i][t] = 0.f; }
+    if constexpr (FUSED) {
+        if (a.out_scale) load_rows4(mul, a.out_scale + tm * TM + mb);        // one branch per batch of loads (as for the mask bytes below)
+        if (a.out_shift) load_rows4(add, a.out_shift + tm * TM + mb);
+        // THE ONE RECORDED DISAGREEMENT between the store paths: here the bias is folded into the shift first, acc * scale + (shift + bias), and
+        // the stage gets no bias; epi_store_general passes both, (acc * scale + shift) + bias.  With out_shift and bias both set (every block
+        // with a downsample branch) an edge tile's rows round differently from an interior tile's.  Kept as it was; closing it changes bits.
+        if (a.bias) {
+            float bi[FM][4];
+            load_rows4(bi, a.bias + tm * TM + mb);
 #pragma unroll
-            for (int jj = 0; jj < Stage::HFN; ++jj) {
-                const int j = h * Stage::HFN + jj;
+            for (int i = 0; i < FM; ++i)
 #pragma unroll
-                for (int i = 0; i < FM; ++i) {
-                    const float v[4] = {acc[i][j][0] + bias4[i].x, acc[i][j][1] + bias4[i].y, acc[i][j][2] + bias4[i].z, acc[i][j][3] + bias4[i].w};
-                    *st.slot(jj, i) = pack4(v);
-                }
-            }
-            lds_barrier();
-#pragma unroll
-            for (int it = 0; it < ITERS; ++it) st.out(a.O2, h, it);
-            lds_barrier();
+                for (int t = 0; t < 4; ++t) add[i][t] += bi[i][t];
         }
-        if (in_tile) {
-#pragma unroll
-            for (int it = 0; it < ITERS; ++it) *st.chunk(it) = st.in(in_tile, h, it);
-            lds_barrier_vm();                                   // the loaded tile is visible to every wave
-        }
-#pragma unroll
-        for (int jj = 0; jj < Stage::HFN; ++jj) {
-            const int j = h * Stage::HFN + jj;
-#pragma unroll
-            for (int i = 0; i < FM; ++i) {
-                float v[4] = {acc[i][j][0] + bias4[i].x, acc[i][j][1] + bias4[i].y, acc[i][j][2] + bias4[i].z, acc[i][j][3] + bias4[i].w};
-                uint2* slot = st.slot(jj, i);
-                if (a.act == 1) {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) v[t] = gelu_f(v[t]);
-                }
-                if (a.row_scale) {                              // DropPath: the whole branch output (bias included) times its sample's factor
-                    const float rs = a.row_scale[tn * TN + h * Stage::WROWS + wn * (FN * 16) + jj * 16 + (lane & 15)];
-                    v[0] *= rs; v[1] *= rs; v[2] *= rs; v[3] *= rs;
-                }
-                if (in_tile) {
-                    float x4[4];
-                    unpack4(*slot, x4);
-                    if (a.Res) {
-                        v[0] += x4[0]; v[1] += x4[1]; v[2] += x4[2]; v[3] += x4[3];
-                    } else {
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) v[t] *= gelu_grad_f(x4[t]);
-                    }
-                }
-                *slot = pack4(v);
-            }
-        }
-        lds_barrier();
-        conv_stamp(a, 6 + 2 * h);   // half staged
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it) st.out(a.O, h, it);
-        conv_stamp(a, 7 + 2 * h);   // half's stores issued
-        if (h == 0) lds_barrier();                              // the LDS reads are done before the second half overwrites them
+    } else {
+        if (a.bias) load_rows4(add, a.bias + tm * TM + mb);
     }
-}
-// ---- fused output stage (see IGemmArgs; Epi::FUSED, and FULL = false: Epi::FUSED_LEAN), staged like the lean path; interior tile, natural
-// addressing.  No residual mask: conv_choose refuses res_mask beside a fused-stage field.
-template <bool FULL, int TM, int TN, int FM, int FN, int WNW, int NT>
-__device__ __forceinline__ void epi_store_fused(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wn, int mb) {
-    using Stage = EpiStage<false, TM, TN, FM, FN, WNW, NT>;
-    constexpr int ITERS = Stage::ITERS;
-    const Stage st(a, tm, tn, smem, wn, mb);
-    const uint16_t* const Res = FULL ? a.Res : nullptr;
-    const uint8_t* const out_mask = FULL ? a.out_mask : nullptr;
-    uint8_t* const bits_out = FULL ? a.bits_out : nullptr;
-    float4 sc4[FM], sh4[FM];
-#pragma unroll
-    for (int i = 0; i < FM; ++i) { sc4[i] = make_float4(1.f, 1.f, 1.f, 1.f); sh4[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
-    if (a.out_scale) load_rows4(sc4, a.out_scale + tm * TM + mb);        // one branch per batch of loads (as for the mask bytes below)
-    if (a.out_shift) load_rows4(sh4, a.out_shift + tm * TM + mb);
-    if (a.bias) {
-        float4 bi4[FM];
-        load_rows4(bi4, a.bias + tm * TM + mb);
-#pragma unroll
-        for (int i = 0; i < FM; ++i) { sh4[i].x += bi4[i].x; sh4[i].y += bi4[i].y; sh4[i].z += bi4[i].z; sh4[i].w += bi4[i].w; }
-    }
-    // the residual tile of BOTH halves is requested up front: the second half's loads fly while the first half is formed and stored
+    const uint16_t* const Res = KIND == Epi::FUSED_LEAN ? nullptr : a.Res;
+    const uint16_t* const in_tile = LIN && !a.Res ? a.dact_pre : Res;        // the input tile staged through LDS in the output layout
+    // FUSED: the residual tile of BOTH halves is requested up front: the second half's loads fly while the first half is formed and stored
     // (requested per half they exposed one HBM round trip per half: these kernels are short-K, their epilogue is most of their time)
     constexpr bool PRE = FULL && NT == 256;          // (the 512-thread 128 x 256 kernel would leave its 128-register budget = two workgroups per CU)
     uint4 rpre[2][PRE ? ITERS : 1];
@@ -599,60 +661,106 @@ __device__ __forceinline__ void epi_store_fused(const IGemmArgs& a, f32x4_t (&ac
     for (int h = 0; h < 2; ++h) {
         // the mask bytes of this half, requested together and early: "if (mask) m = mask[..]" inside the unrolled loops below compiled to a
         // branch and a wait around every byte load (up to 16 dependent round trips per tile; MI355X guide, the per-element select trap)
-        unsigned om[ITERS];
-        if (out_mask) {
+        unsigned om[ITERS], rm[ITERS];
+        if constexpr (FULL) if (a.out_mask) {
 #pragma unroll
-            for (int it = 0; it < ITERS; ++it) om[it] = out_mask[st.offset(h, it) >> 4];
+            for (int it = 0; it < ITERS; ++it) om[it] = a.out_mask[st.offset(h, it) >> 4];
         }
-        if (Res) {
+        if constexpr (LIN) if (a.O2) {                          // pre-activation copy (kept for the backward) goes out first
+#pragma unroll
+            for (int jj = 0; jj < Stage::HFN; ++jj) {
+                const int j = h * Stage::HFN + jj;
+#pragma unroll
+                for (int i = 0; i < FM; ++i) {
+                    float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+                    Out::pre(v, StagedSrc<FUSED>{a, mul[i], add[i], nullptr, false, false, 0, 0, uint2{}});
+                    *st.slot(jj, i) = pack4(v);
+                }
+            }
+            lds_barrier();
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) st.out(a.O2, h, it);
+            lds_barrier();
+        }
+        if (in_tile) {
+            if constexpr (LEAN) if (a.res_mask) {
+#pragma unroll
+                for (int it = 0; it < ITERS; ++it) rm[it] = a.res_mask[st.offset(h, it) >> 4];
+            }
 #pragma unroll
             for (int it = 0; it < ITERS; ++it) {
                 uint4 rv;
                 if constexpr (PRE) rv = rpre[h][it];
-                else rv = st.in(Res, h, it);
+                else rv = st.in(in_tile, h, it);
+                if constexpr (LEAN) if (a.res_mask) gate_bf16x8(rv, rm[it]);
                 *st.chunk(it) = rv;
             }
             if constexpr (PRE) lds_barrier();                   // (the register dependence waits for the loads of this half only)
-            else lds_barrier_vm();
+            else lds_barrier_vm();                              // the loaded tile is visible to every wave
         }
 #pragma unroll
         for (int jj = 0; jj < Stage::HFN; ++jj) {
             const int j = h * Stage::HFN + jj;
 #pragma unroll
             for (int i = 0; i < FM; ++i) {
-                float v[4] = {acc[i][j][0] * sc4[i].x + sh4[i].x, acc[i][j][1] * sc4[i].y + sh4[i].y, acc[i][j][2] * sc4[i].z + sh4[i].z, acc[i][j][3] * sc4[i].w + sh4[i].w};
+                float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
                 uint2* slot = st.slot(jj, i);
-                if (Res) {
-                    float r4[4];
-                    unpack4(*slot, r4);
-                    if (a.res_scale) {                          // (loaded per use: L1-resident; held across the tile it cost 16 registers and spills)
-                        const float4 rs = *reinterpret_cast<const float4*>(a.res_scale + tm * TM + mb + i * 16);
-                        v[0] += rs.x * r4[0]; v[1] += rs.y * r4[1]; v[2] += rs.z * r4[2]; v[3] += rs.w * r4[3];
-                    } else {
-                        v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3];
-                    }
-                }
-                if (a.out_relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-                *slot = pack4(v);
+                const int pix = tn * TN + h * Stage::WROWS + wn * (FN * 16) + jj * 16 + (lane & 15);
+                *slot = Out::run(v, StagedSrc<FUSED>{a, mul[i], add[i], slot, Res != nullptr, LIN && !a.Res && a.dact_pre, pix, tm * TM + mb + i * 16, uint2{}});
             }
         }
         lds_barrier();
+        if constexpr (!FUSED) conv_stamp(a, 6 + 2 * h);         // half staged
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
-            const size_t ob = st.offset(h, it);
-            uint4 v = *st.chunk(it);
-            if (out_mask) gate_bf16x8(v, om[it]);
-            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + ob) = v;
-            if (bits_out) bits_out[ob >> 4] = (uint8_t)(pos_bits_bf16x2(v.x) | (pos_bits_bf16x2(v.y) << 2) | (pos_bits_bf16x2(v.z) << 4) | (pos_bits_bf16x2(v.w) << 6));
+            if constexpr (FULL) {
+                const size_t ob = st.offset(h, it);
+                uint4 w = *st.chunk(it);
+                const unsigned bits = OutStage<KIND, 8>::gate(w, a.out_mask != nullptr, om[it]);       // (the whole 16-byte chunk: N = 8)
+                *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.O) + ob) = w;
+                if (a.bits_out) a.bits_out[ob >> 4] = (uint8_t)bits;
+            } else {
+                st.out(a.O, h, it);
+            }
         }
-        if (h == 0) lds_barrier();
+        if constexpr (!FUSED) conv_stamp(a, 7 + 2 * h);         // half's stores issued
+        if (h == 0) lds_barrier();                              // the LDS reads are done before the second half overwrites them
     }
 }
 // ---- general path: edge tiles, Cm % 8 != 0, parity sub-problems outside Epi::PARITY, the linear layers' extras outside Epi::LIN; 8-byte
-// stores with per-element predicates.  What MODE compiles in: the extras under LIN and GENERAL, the fused stage under FUSED, its scale / shift /
-// ReLU under FUSED_LEAN; the residual everywhere but FUSED_LEAN, its mask everywhere but FUSED (dali_conv2d_dgrad's edge tiles).
+// stores with per-element predicates, operands straight from global memory.  What MODE compiles in is OutStage<MODE>'s table: the extras under
+// LIN and GENERAL, the fused stage under FUSED, its scale / shift / ReLU under FUSED_LEAN; the residual everywhere but FUSED_LEAN, its mask
+// everywhere but FUSED (dali_conv2d_dgrad's edge tiles).
+// Its operands: everything from global memory, for the 4 channels from c of pixel p = element e of the output.
+struct GeneralSrc {
+    const IGemmArgs& a; int p, c; size_t e;
+    // e is a multiple of 4: this lane's nibble of the mask byte
+    __device__ __forceinline__ unsigned mask_nibble(const uint8_t* src) const { return src[e >> 3] >> (e & 4); }
+    __device__ __forceinline__ void load_inputs() const {}
+    __device__ __forceinline__ bool has_scale() const { return a.out_scale != nullptr; }
+    __device__ __forceinline__ void scale(float (&f)[4]) const { load_nf(a.out_scale + c, f); }
+    __device__ __forceinline__ bool has_shift() const { return a.out_shift != nullptr; }            // shift AND bias reach the stage: see epi_store_staged
+    __device__ __forceinline__ void shift(float (&f)[4]) const { load_nf(a.out_shift + c, f); }
+    __device__ __forceinline__ bool has_bias() const { return a.bias != nullptr; }
+    __device__ __forceinline__ void bias(float (&f)[4]) const { load_nf(a.bias + c, f); }
+    __device__ __forceinline__ bool want_o2() const { return a.O2 != nullptr; }
+    __device__ __forceinline__ void o2(uint2 w) const { *reinterpret_cast<uint2*>(a.O2 + e) = w; }
+    __device__ __forceinline__ bool gelu() const { return a.act == 1; }
+    __device__ __forceinline__ bool has_dact() const { return a.dact_pre != nullptr; }
+    __device__ __forceinline__ void dact(uint2& x) const { x = *reinterpret_cast<const uint2*>(a.dact_pre + e); }
+    __device__ __forceinline__ bool has_row_scale() const { return a.row_scale != nullptr; }
+    __device__ __forceinline__ void row_scale(float& rs) const { rs = a.row_scale[p]; }
+    __device__ __forceinline__ bool has_res() const { return a.Res != nullptr; }
+    __device__ __forceinline__ void res(uint2& r) const { r = *reinterpret_cast<const uint2*>(a.Res + e); }
+    __device__ __forceinline__ bool has_res_mask() const { return a.res_mask != nullptr; }
+    __device__ __forceinline__ void res_mask(unsigned& m) const { m = mask_nibble(a.res_mask); }
+    __device__ __forceinline__ bool has_res_scale() const { return a.res_scale != nullptr; }
+    __device__ __forceinline__ void res_scale(float (&f)[4]) const { load_nf(a.res_scale + c, f); }
+    __device__ __forceinline__ bool relu() const { return a.out_relu != 0; }
+};
 template <Epi MODE, int TM, int TN, int FM, int FN>
 __device__ __forceinline__ void epi_store_general(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, int mb, int nb) {
+    using Out = OutStage<MODE == Epi::PARITY ? Epi::CONV : MODE, 4>;
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
@@ -664,58 +772,17 @@ __device__ __forceinline__ void epi_store_general(const IGemmArgs& a, f32x4_t (&
             unsigned nib = 0;
             if (p < a.P && c < a.Cm) {      // Cm is a multiple of 4: the 4 channels are all valid
                 float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                const size_t o = opix * a.Cm + c;
-                if constexpr (epi_fused(MODE)) {
-                    if (a.out_scale) { const float4 sv = *reinterpret_cast<const float4*>(a.out_scale + c); v[0] *= sv.x; v[1] *= sv.y; v[2] *= sv.z; v[3] *= sv.w; }
-                    if (a.out_shift) { const float4 sv = *reinterpret_cast<const float4*>(a.out_shift + c); v[0] += sv.x; v[1] += sv.y; v[2] += sv.z; v[3] += sv.w; }
+                const size_t e = opix * a.Cm + c;
+                const GeneralSrc s{a, p, c, e};
+                uint2 ov = Out::run(v, s);
+                if constexpr (Out::FULL) {
+                    unsigned m = 0;
+                    if (a.out_mask) m = s.mask_nibble(a.out_mask);
+                    nib = Out::gate(ov, a.out_mask != nullptr, m);
                 }
-                if (a.bias) {
-                    const float4 bv = *reinterpret_cast<const float4*>(a.bias + c);
-                    v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-                }
-                if constexpr (MODE == Epi::LIN || MODE == Epi::GENERAL) {
-                    if (a.O2) *reinterpret_cast<uint2*>(a.O2 + o) = pack4(v);
-                    if (a.act == 1) {
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) v[t] = gelu_f(v[t]);
-                    }
-                    if (a.dact_pre) {
-                        float x4[4];
-                        unpack4(*reinterpret_cast<const uint2*>(a.dact_pre + o), x4);
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) v[t] *= gelu_grad_f(x4[t]);
-                    }
-                    if (a.row_scale) {
-                        const float rs = a.row_scale[p];
-                        v[0] *= rs; v[1] *= rs; v[2] *= rs; v[3] *= rs;
-                    }
-                }
-                if (MODE != Epi::FUSED_LEAN && a.Res) {
-                    uint2 rv = *reinterpret_cast<const uint2*>(a.Res + o);
-                    if constexpr (MODE != Epi::FUSED) if (a.res_mask) {         // o is a multiple of 4: this lane's nibble of the mask byte
-                        const unsigned m = a.res_mask[o >> 3] >> (o & 4);
-                        rv.x = gate_bf16x2(rv.x, m); rv.y = gate_bf16x2(rv.y, m >> 2);
-                    }
-                    float r4[4];
-                    unpack4(rv, r4);
-                    if constexpr (MODE == Epi::FUSED) if (a.res_scale) {
-                        const float4 rs = *reinterpret_cast<const float4*>(a.res_scale + c);
-                        r4[0] *= rs.x; r4[1] *= rs.y; r4[2] *= rs.z; r4[3] *= rs.w;
-                    }
-                    v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3];
-                }
-                if constexpr (epi_fused(MODE)) if (a.out_relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-                uint2 ov = pack4(v);
-                if constexpr (MODE == Epi::FUSED) {
-                    if (a.out_mask) {
-                        const unsigned m = a.out_mask[o >> 3] >> (o & 4);
-                        ov.x = gate_bf16x2(ov.x, m); ov.y = gate_bf16x2(ov.y, m >> 2);
-                    }
-                    nib = pos_bits_bf16x2(ov.x) | (pos_bits_bf16x2(ov.y) << 2);
-                }
-                *reinterpret_cast<uint2*>(a.O + o) = ov;
+                *reinterpret_cast<uint2*>(a.O + e) = ov;
             }
-            if constexpr (MODE == Epi::FUSED) {
+            if constexpr (Out::FULL) {
                 // this lane's 4 mask bits and those of lane ^ 16 (the other half of the same byte: Cm % 8 == 0 is required) -> one byte store
                 const unsigned other = __shfl_xor(nib, 16, 64);
                 if (a.bits_out && p < a.P && c < a.Cm && ((lane >> 4) & 1) == 0) a.bits_out[(opix * a.Cm + c) >> 3] = (uint8_t)(nib | (other << 4));
@@ -729,7 +796,7 @@ __device__ __forceinline__ void epi_store_general(const IGemmArgs& a, f32x4_t (&
 // last fragment read), so smem is free.
 template <int TM, int TN, int FM, int FN, int WNW, int NT, Epi MODE = Epi::GENERAL>
 __device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&acc)[FM][FN], int tm, int tn, uint16_t* smem, int wm, int wn) {
-    constexpr bool EVEN = FN % 2 == 0;       // the half-tile stores split every wave's column blocks in two; odd FN: conv_epilogue_cols
+    constexpr bool EVEN = FN % 2 == 0;       // the half-tile store splits every wave's column blocks in two; odd FN: conv_epilogue_cols
     constexpr bool FUSED = epi_fused(MODE), SUB = MODE == Epi::PARITY;
     const int lane = threadIdx.x & 63;
     const int mb = wm * (FM * 16) + (lane >> 4) * 4, nb = wn * (FN * 16) + (lane & 15);      // this lane's first channel / pixel inside the tile
@@ -737,18 +804,20 @@ __device__ __forceinline__ void conv_epilogue_g(const IGemmArgs& a, f32x4_t (&ac
     conv_stamp(a, 5);     // stats done
     const bool interior = (tm + 1) * TM <= a.Cm && (tn + 1) * TN <= a.P;
     const bool chunks = (a.Cm & 7) == 0;                                                    // a pixel's channels are whole 16-byte chunks
-    const bool extras = a.O2 || a.act != 0 || a.dact_pre || a.row_scale;                    // a linear layer's (bias alone is folded into the lean path)
+    const bool extras = a.O2 || a.act != 0 || a.dact_pre || a.row_scale;                    // a linear layer's (bias alone rides in the CONV kind)
     const bool plain = !FUSED && !extras && (SUB || !a.g.sub) && chunks;
     const bool in_once = !(a.Res && a.dact_pre);                                            // the staged extras take one input tile
     if constexpr (!EVEN) {
-        if (interior && !FUSED && !a.g.sub && chunks && in_once && (unsigned long long)a.P * a.Cm * 2ull < 0xffffffffull)
-            return conv_epilogue_cols<TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wm, wn);
+        constexpr bool HAS_EXTRAS = MODE == Epi::LIN || MODE == Epi::GENERAL;               // (conv_choose sends extras to those modes only)
+        if constexpr (!FUSED)
+        if (interior && (HAS_EXTRAS || !extras) && !a.g.sub && chunks && in_once && (unsigned long long)a.P * a.Cm * 2ull < 0xffffffffull)
+            return conv_epilogue_cols<MODE, TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wm, wn);
     } else if constexpr (FUSED) {
-        if (interior && !a.g.sub && chunks) return epi_store_fused<MODE == Epi::FUSED, TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
+        if (interior && !a.g.sub && chunks) return epi_store_staged<MODE, TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
     } else {
-        if (interior && plain) return epi_store_lean<SUB, TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
+        if (interior && plain) return epi_store_staged<SUB ? Epi::PARITY : Epi::CONV, TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
         if constexpr (MODE == Epi::LIN)
-            if (interior && !plain && !a.g.sub && chunks && in_once) return epi_store_lin<TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
+            if (interior && !plain && !a.g.sub && chunks && in_once) return epi_store_staged<Epi::LIN, TM, TN, FM, FN, WNW, NT>(a, acc, tm, tn, smem, wn, mb);
     }
     epi_store_general<MODE, TM, TN, FM, FN>(a, acc, tm, tn, mb, nb);
 }

@@ -1,9 +1,10 @@
-"""A/B of two library builds on the kernels of nnops.hip / vit_ops.hip (select the build with DALIID_LIB; one process per build):
+"""A/B of two library builds on the kernels of nnops.hip / vit_ops.hip / conv.hip (select the build with DALIID_LIB; one process per build):
 
   python scripts/ab_nnops.py bits OUT.json [ODD_DIR]   sha256 of every output on seeded inputs: bn_bwd (three mask modes, single / dual, with / without
                                                        dz), maxpool_bn_bwd, bn_act, head pool, LayerNorm, attention, linear bias gradients (colsum),
-                                                       bnlin (transposed weights), one ResNet and one ViT train step (features + every gradient);
-                                                       the odd-sided max-pool outputs go to ODD_DIR as .npz
+                                                       bnlin (transposed weights), the conv / conv1x1_* / linear single ops (every output stage of
+                                                       conv.hip, edge shapes included), one ResNet and one ViT train step (features + every gradient),
+                                                       one ResNet eval forward; the odd-sided max-pool outputs go to ODD_DIR as .npz
   python scripts/ab_nnops.py cmp A.json B.json [ODD_DIR_A ODD_DIR_B]   differing arrays; ulp distances of the odd-sided max-pool outputs
   python scripts/ab_nnops.py time [N H W C]            maxpool_bn_bwd (default 256x63x33x64, the odd path): 5 runs of 20 launches, us per launch
 """
@@ -37,6 +38,65 @@ def _pool_inputs(shape, g):
     raw, mean, invstd, scale, shift = _bn_inputs(n * h * w, C, g)
     dp = torch.randn(n, (h + 1) // 2, (w + 1) // 2, C, generator=g).to(bf16)
     return [t.cuda() for t in (raw.view(n, h, w, C), mean, invstd, scale, shift, dp)]
+
+
+def _pack_bits(b):
+    b = b.flatten().to(torch.int32).view(-1, 8)
+    return (b << torch.arange(8, dtype=torch.int32, device=b.device)).sum(1).to(torch.uint8)
+
+
+def _conv_bits(put, ops_nn, ops_vit, g):
+    """every output stage of conv.hip's forward / data-gradient / linear GEMMs: the convolution single ops over the shapes of tests/test_gpu_conv.py,
+    the conv1x1_* and linear single ops over its 1x1 / stride-1 shapes and over edge and 256 x 320-tile shapes (out_shift with bias included)"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("conv_cases", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "test_gpu_conv.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+
+    def rnd(*shape, s=1.0):
+        return (torch.randn(shape, generator=g) * s).to(bf16).cuda()
+
+    def vec(n, lo=0.5, hi=1.5):
+        return (lo + (hi - lo) * torch.rand(n, generator=g)).cuda()
+
+    def keep(n):
+        return _pack_bits(torch.rand(n, generator=g) < 0.6).cuda()
+
+    def try_put(name, fn):
+        """an entry point that refuses a shape is recorded as refused (both builds must then refuse it)"""
+        from daliid_amd import _lib
+        try:
+            put(name, fn())
+        except _lib.DaliError as e:
+            put(name + " refused", (torch.tensor([len(str(e))]),))
+
+    flat = [(300, 32, 136), (300, 32, 64), (300, 32, 72), (25216, 768, 3072), (25216, 3072, 768), (32896, 512, 512)]
+    for n, h, w, cin, cout, r, s, stride, pad in mod.CASES:
+        name = "conv %s" % ((n, h, w, cin, cout, r, s, stride, pad),)
+        ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+        x, wt_f, wt_d = rnd(n, h, w, cin), rnd(cout, r, s, cin, s=0.1), rnd(cin, r, s, cout, s=0.1)
+        dy, res = rnd(n, ho, wo, cout), rnd(n, h, w, cin)
+        try_put(name + " fwd", lambda: ops_nn.conv2d_fwd(x, wt_f, stride, pad, want_stats=True))
+        try_put(name + " fwd in_bn", lambda: ops_nn.conv2d_fwd(x, wt_f, stride, pad, in_scale=vec(cin), in_shift=vec(cin, -0.5, 0.5), in_relu=True, want_stats=True))
+        try_put(name + " bn_act", lambda: (ops_nn.conv2d_bn_act(x, wt_f, vec(cout), vec(cout, -0.5, 0.5), stride, pad, relu=True),))
+        try_put(name + " dgrad", lambda: (ops_nn.conv2d_dgrad(dy, wt_d, (h, w), stride, pad),))
+        try_put(name + " dgrad res mask", lambda: (ops_nn.conv2d_dgrad(dy, wt_d, (h, w), stride, pad, residual=res, residual_mask=keep(res.numel())),))
+        if r == 1 and stride == 1:
+            flat.append((n * h * w, cin, cout))
+    for P, cin, cout in flat:
+        name = "flat %dx%dx%d" % (P, cin, cout)
+        x, w, res = rnd(P, cin), rnd(cout, cin, s=cin ** -0.5), rnd(P, cout)
+        sc, sh, bi, rsc = vec(cout), vec(cout, -0.5, 0.5), vec(cout, -0.5, 0.5), vec(cout)
+        try_put(name + " fused full", lambda: ops_nn.conv1x1_fused(x, w, out_scale=sc, out_shift=sh, residual=res, res_scale=rsc, relu=True, want_bits=True,
+                                                                   out_mask=keep(P * cout)))
+        try_put(name + " fused shift+bias", lambda: ops_nn.conv1x1_fused(x, w, out_scale=sc, out_shift=sh, bias=bi, residual=res, res_scale=rsc, relu=True, want_bits=True))
+        try_put(name + " fused bias", lambda: (ops_nn.conv1x1_fused(x, w, out_scale=sc, bias=bi, relu=True), ops_nn.conv1x1_fused(x, w, out_shift=sh)))
+        if cin % 64 == 0:
+            x1, x2 = x[:, :cin // 2].contiguous(), x[:, cin // 2:].contiguous()
+            try_put(name + " cat", lambda: (ops_nn.conv1x1_cat(x1, x2, w, bias=bi),))
+        try_put(name + " linear", lambda: ops_vit.linear_fwd(x, w, bias=bi, act=1, want_pre=True) + (ops_vit.linear_fwd(x, w, bias=bi, residual=res), ops_vit.linear_fwd(x, w)))
+        try_put(name + " linear scaled", lambda: (ops_vit.linear_fwd_scaled(x, w, vec(P, 0.0, 1.2), bias=bi, residual=res), ops_vit.linear_fwd_scaled(x, w, vec(P), bias=bi, act=1)))
+        try_put(name + " linear dgrad", lambda: (ops_vit.linear_dgrad(x, w, gelu_pre=res), ops_vit.linear_dgrad(x, w, residual=res)))
 
 
 def run_bits(out_json, odd_dir):
@@ -102,6 +162,7 @@ def run_bits(out_json, odd_dir):
         fwd = ops_nn.bnlin_fwd(a, W, (torch.rand(C, generator=g) + 0.5).cuda(), torch.randn(C, generator=g).cuda())
         bwd = ops_nn.bnlin_bwd(torch.randn(P, C, generator=g).to(bf16).cuda(), a, W, fwd)
         put("bnlin %d %d %d" % (P, C, w), [fwd[k] for k in sorted(fwd)] + [bwd[k] for k in sorted(bwd)])
+    _conv_bits(put, ops_nn, ops_vit, g)
     for name, net, img in [("resnet", Encoders.ResNet50ReID(seed=2), (32, 3, 256, 128)),
                            ("vit", vit_pytorch.ViTNeckNet(img_size=(224, 224), num_classes=10, seed=3), (16, 3, 224, 224))]:
         net.train()
@@ -110,6 +171,9 @@ def run_bits(out_json, odd_dir):
         for s in range(net.n_bwd_stages if name == "vit" else 4):
             net._backward_stage(d, s)
         put(name + " train step", (emb, net.flat_grads, net.flat_buffers))
+        if name == "resnet":
+            net.eval()
+            put("resnet eval forward", (net._run_forward(torch.randn(img, generator=g).cuda(), False),))
     torch.cuda.synchronize()
     json.dump(res, open(out_json, "w"), indent=0)
     print("%d arrays hashed with %s" % (len(res), os.environ.get("DALIID_LIB", "the tree's library")))
