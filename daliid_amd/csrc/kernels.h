@@ -209,6 +209,8 @@ int launch_attention_fwd(hipStream_t st, const uint16_t* qkv, int B, int T, int 
 int launch_attention_fwd_long(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse);
 // T <= 64 (the JPM local sequences): the 4-tile instance of the forward kernel
 int launch_attention_fwd_short(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse);
+// head_dim 96 (qkv [B*T][3*H*96]), 1 <= T <= 1024, forward only: the chunked kernel with key chunks of 128, at every length
+int launch_attention_fwd_hd96(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse);
 // SIE / JPM (vit_pytorch.py:316-331, 382-396; make_models.py:221-377)
 int launch_assemble_tokens_sie(hipStream_t st, const uint16_t* pe, const float* cls, const float* pos, const float* sie, const int32_t* idx, int n_sie,
                                float coef, int B, int T, int C, uint16_t* x);

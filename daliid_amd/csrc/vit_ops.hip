@@ -283,14 +283,23 @@ typedef short s16x8v __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ bf16x8_t frag_k(const uint16_t* base, int ld, int row0, int k0, int lane) {
     return *reinterpret_cast<const bf16x8_t*>(base + (row0 + (lane & 15)) * ld + k0 + 8 * (lane >> 4));
 }
-template <int TP>
+// LDS row pitch of a [T][HD] image, in bf16: HD + 8.  The pitch is an odd number of 16-byte slots (9 at 64, 13 at 96), so the sixteen consecutive
+// rows that frag_k's lanes with one value of lane >> 4 read at one column (16 bytes each) fall into sixteen different slots of the 256-byte bank
+// row (9 r and 13 r mod 16 are permutations of 0 .. 15), where the unpadded pitches (8 and 12 slots) would stack them two- and four-deep; and it
+// is a multiple of 16 bytes (144, 208), so the 16-byte writes of att_load_tile, the 16-byte reads of frag_k and the 8-byte transposing reads of
+// frag_tr2 (columns in steps of four bf16) all stay aligned.  (The hardware serves a 16-byte read in groups of lanes that mix two values of
+// lane >> 4; by that grouping neither pitch is free of two-way conflicts, docs/experiments.md.)
+template <int HD> constexpr int att_ld() { return HD + 8; }
+static_assert(att_ld<ATT_HD>() == ATT_LD && (att_ld<96>() * 2) % 16 == 0 && (att_ld<96>() / 8) % 2 == 1, "LDS row pitch: whole, odd count of 16-byte slots");
+template <int TP, int HD = ATT_HD>
 __device__ __forceinline__ void att_load_tile(const uint16_t* __restrict__ src, size_t row_stride, int T, uint16_t* dst) {
-    // [T][64] bf16 from global (row stride in elements) -> LDS [TP][ATT_LD], rows >= T zeroed
-    for (int i = threadIdx.x; i < TP * 8; i += blockDim.x) {
-        const int row = i >> 3, ch = i & 7;
+    // [T][HD] bf16 from global (row stride in elements) -> LDS [TP][att_ld<HD>()], rows >= T zeroed
+    constexpr unsigned CH = HD / 8;
+    for (int i = threadIdx.x; i < TP * (int)CH; i += blockDim.x) {
+        const int row = (unsigned)i / CH, ch = (unsigned)i % CH;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (row < T) v = *reinterpret_cast<const uint4*>(src + (size_t)row * row_stride + ch * 8);
-        *reinterpret_cast<uint4*>(dst + row * ATT_LD + ch * 8) = v;
+        *reinterpret_cast<uint4*>(dst + row * att_ld<HD>() + ch * 8) = v;
     }
 }
 
@@ -838,38 +847,61 @@ static_assert(2 * att2_lds<16>() <= 163840, "two attention workgroups per CU");
 // ------------------------------------------------------------------------------------------------
 constexpr int ATT_FWD_MAX_T = 1024;
 constexpr int ATT_LONG_CHUNK = 256, ATT_LONG_QBLOCK = 128;
-constexpr size_t ATT_LONG_LDS = (size_t)2 * ATT_LONG_CHUNK * ATT_LD * 2;
+template <int HD, int CHUNK> constexpr size_t att_long_lds() { return (size_t)2 * CHUNK * att_ld<HD>() * 2; }
+constexpr size_t ATT_LONG_LDS = att_long_lds<ATT_HD, ATT_LONG_CHUNK>();
 static_assert(ATT_LONG_LDS == 73728 && 2 * ATT_LONG_LDS <= 163840, "two long-attention workgroups per CU");
+// ------------------------------------------------------------------------------------------------
+// head_dim 96 (ViT-Small: dim 768, 8 heads; eval only): the same kernel as the instance <96, 128>, for EVERY length from 1 to ATT_FWD_MAX_T --
+// 129 tokens (256x128 at stride 16), 211 (stride 12), the JPM runs of 33 / 53, and everything past 256.  What HD changes: a query tile is three
+// k-blocks of 32 (three fragments, three MFMAs per score tile), the output is six 16-column accumulators, and the LDS rows are att_ld<96>() = 104
+// bf16 apart.  Why chunks of 128 there (arithmetic, not measurement): at 256 keys the two images take 2 x 256 x 104 x 2 B = 106496 B, one workgroup
+// per CU; and s[16] (64 VGPRs) + o[6] (24) + the query (12) would sit on top of a body that at HD 64 already fills the 128 VGPRs two workgroups of
+// 512 threads allow.  At 128 keys the images take 53248 B (two workgroups: 106496 of 163840) and s[8] is 32 VGPRs.
+// The three arguments above hold for it unchanged, per chunk of 128: nothing before the end of the chunk loop depends on the wave's query tile, and
+// the chunk count ceil(T / 128) depends on T alone, so no wave leaves the loop early and every wave reaches both barriers of every chunk; chunk c
+// starts at key 128 c < T, a real key with a finite score, so m_new is finite from the first chunk on and (-inf) - (-inf) is never formed; and
+// O^T = V^T P^T leaves lane (g, i) with columns 16 d + 4 g + r (d = 0 .. 5) of query i, so alpha and 1 / l are the lane's own.
+// ------------------------------------------------------------------------------------------------
+constexpr int ATT_HD96 = 96, ATT_HD96_CHUNK = 128;
+static_assert(2 * att_long_lds<ATT_HD96, ATT_HD96_CHUNK>() <= 163840, "two head-dim-96 attention workgroups per CU");
 
+template <int HD, int CHUNK>
 __global__ __launch_bounds__(512, 4) void attention_fwd_long_kernel(const uint16_t* __restrict__ qkv, int B, int T, int H, float scale,
                                                                     uint16_t* __restrict__ out, float* __restrict__ lse) {
-    constexpr int NTILE = ATT_LONG_CHUNK / 16;
+    static_assert((HD == 64 || HD == 96) && CHUNK % 32 == 0, "two or three k-blocks of 32, score tiles in pairs");
+    constexpr int NTILE = CHUNK / 16, LD = att_ld<HD>(), NK = HD / 32, ND = HD / 16;
     extern __shared__ __attribute__((aligned(16))) uint16_t sm[];
     uint16_t* sK = sm;
-    uint16_t* sV = sK + ATT_LONG_CHUNK * ATT_LD;
+    uint16_t* sV = sK + CHUNK * LD;
     const int nqb = (T + ATT_LONG_QBLOCK - 1) / ATT_LONG_QBLOCK;
     const int bh = blockIdx.x / nqb, qb = blockIdx.x - bh * nqb, b = bh / H, h = bh - b * H;
-    const int C = H * ATT_HD, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int C = H * HD, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t rs = (size_t)3 * C;
-    const uint16_t* base = qkv + (size_t)b * T * rs + h * ATT_HD;
+    const uint16_t* base = qkv + (size_t)b * T * rs + h * HD;
     const int q0 = qb * ATT_LONG_QBLOCK + wave * 16;                 // may lie past T: zero fragments, no stores, every barrier
-    const bf16x8_t qa0 = frag_g(base, rs, q0, 0, T, lane), qa1 = frag_g(base, rs, q0, 32, T, lane);
+    // the k-blocks are written out, here and in the score tile below: as loops over kb they compile to another instruction stream at HD 64
+    bf16x8_t qa[NK];
+    qa[0] = frag_g(base, rs, q0, 0, T, lane); qa[1] = frag_g(base, rs, q0, 32, T, lane);
+    if constexpr (NK > 2) qa[2] = frag_g(base, rs, q0, 64, T, lane);
     const float sc2 = scale * 1.44269504088896f;                     // exp(x) = 2^(x log2 e)
     float m = -__builtin_inff(), l = 0.f;                            // of query q0 + (lane & 15)
-    f32x4_t o[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};      // O^T: o[d][r] = column 16 d + 4 (lane >> 4) + r of the same query
-    for (int k0 = 0; k0 < T; k0 += ATT_LONG_CHUNK) {
-        const int left = T - k0;                                     // >= 1: keys k0 .. k0 + min(left, 256) - 1 are real
+    f32x4_t o[ND];                                                   // O^T: o[d][r] = column 16 d + 4 (lane >> 4) + r of the same query
+#pragma unroll
+    for (int d = 0; d < ND; ++d) o[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < T; k0 += CHUNK) {
+        const int left = T - k0;                                     // >= 1: keys k0 .. k0 + min(left, CHUNK) - 1 are real
         __syncthreads();                                             // every wave is done with the previous chunk's K and V
-        att_load_tile<ATT_LONG_CHUNK>(base + C + (size_t)k0 * rs, rs, left, sK);
-        att_load_tile<ATT_LONG_CHUNK>(base + 2 * C + (size_t)k0 * rs, rs, left, sV);
+        att_load_tile<CHUNK, HD>(base + C + (size_t)k0 * rs, rs, left, sK);
+        att_load_tile<CHUNK, HD>(base + 2 * C + (size_t)k0 * rs, rs, left, sV);
         __syncthreads();
         f32x4_t s[NTILE];
         float mc = -__builtin_inff();
 #pragma unroll
         for (int j = 0; j < NTILE; ++j) {
             f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_k(sK, ATT_LD, j * 16, 0, lane), qa0, a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_k(sK, ATT_LD, j * 16, 32, lane), qa1, a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_k(sK, LD, j * 16, 0, lane), qa[0], a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_k(sK, LD, j * 16, 32, lane), qa[1], a, 0, 0, 0);
+            if constexpr (NK > 2) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_k(sK, LD, j * 16, 64, lane), qa[2], a, 0, 0, 0);
             const int key0 = j * 16 + (lane >> 4) * 4;
 #pragma unroll
             for (int r = 0; r < 4; ++r) { a[r] = (key0 + r < left) ? a[r] * sc2 : -__builtin_inff(); mc = fmaxf(mc, a[r]); }
@@ -880,7 +912,7 @@ __global__ __launch_bounds__(512, 4) void attention_fwd_long_kernel(const uint16
         const float m_new = fmaxf(m, mc);                            // finite: the chunk's key 0 is real
         const float alpha = __builtin_amdgcn_exp2f(m - m_new);       // first chunk: 2^-inf = 0
 #pragma unroll
-        for (int d = 0; d < 4; ++d)
+        for (int d = 0; d < ND; ++d)
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[d][r] *= alpha;            // this lane's own alpha: o is transposed (see above)
         float lc = 0.f;
@@ -895,7 +927,7 @@ __global__ __launch_bounds__(512, 4) void attention_fwd_long_kernel(const uint16
             }
             const bf16x8_t pf = pack_frag(pa, pb);
 #pragma unroll
-            for (int d = 0; d < 4; ++d) o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr2(sV, ATT_LD, j0 * 16, j1 * 16, d * 16, lane), pf, o[d], 0, 0, 0);
+            for (int d = 0; d < ND; ++d) o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr2(sV, LD, j0 * 16, j1 * 16, d * 16, lane), pf, o[d], 0, 0, 0);
         }
         lc += __shfl_xor(lc, 16, 64); lc += __shfl_xor(lc, 32, 64);
         l = l * alpha + lc;
@@ -905,23 +937,32 @@ __global__ __launch_bounds__(512, 4) void attention_fwd_long_kernel(const uint16
     if (row < T) {
         const float inv_l = 1.0f / l;                                // l >= 1: the maximum's own term is 2^0
         if (lane < 16 && lse) lse[(size_t)bh * T + row] = (m + log2f(l)) * 0.6931471805599453f;       // natural-log lse = max + log(sum)
-        uint16_t* orow = out + ((size_t)b * T + row) * C + h * ATT_HD + (lane >> 4) * 4;
+        uint16_t* orow = out + ((size_t)b * T + row) * C + h * HD + (lane >> 4) * 4;
 #pragma unroll
-        for (int d = 0; d < 4; ++d)
+        for (int d = 0; d < ND; ++d)
             *reinterpret_cast<uint2*>(orow + d * 16) = make_uint2(pack_bf16x2(o[d][0] * inv_l, o[d][1] * inv_l), pack_bf16x2(o[d][2] * inv_l, o[d][3] * inv_l));
     }
 }
-int launch_attention_fwd_long(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse) {
+template <int HD, int CHUNK>
+static int att_long_launch(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse) {
     if (T < 1 || T > ATT_FWD_MAX_T) {
         set_error("attention: %d tokens exceed the limit of %d", T, ATT_FWD_MAX_T);
         return DALI_ERR_LIMIT;
     }
+    constexpr size_t lds = att_long_lds<HD, CHUNK>();
     const int nqb = (T + ATT_LONG_QBLOCK - 1) / ATT_LONG_QBLOCK;
     if (B < 1 || H < 1 || (int64_t)B * H * nqb > 0x7fffffff) { set_error("attention: bad batch / heads (%d, %d)", B, H); return DALI_ERR_INVALID; }
-    DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_fwd_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LONG_LDS));
-    hipLaunchKernelGGL(attention_fwd_long_kernel, dim3(B * H * nqb), dim3(512), ATT_LONG_LDS, st, qkv, B, T, H, scale, out, lse);
+    DALI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_fwd_long_kernel<HD, CHUNK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((attention_fwd_long_kernel<HD, CHUNK>), dim3(B * H * nqb), dim3(512), lds, st, qkv, B, T, H, scale, out, lse);
     DALI_LAUNCH_CHECK();
     return DALI_OK;
+}
+int launch_attention_fwd_long(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse) {
+    return att_long_launch<ATT_HD, ATT_LONG_CHUNK>(st, qkv, B, T, H, scale, out, lse);
+}
+// head_dim 96, 1 <= T <= 1024: every length runs the chunked kernel (there is no one-pass instance and no backward at this width)
+int launch_attention_fwd_hd96(hipStream_t st, const uint16_t* qkv, int B, int T, int H, float scale, uint16_t* out, float* lse) {
+    return att_long_launch<ATT_HD96, ATT_HD96_CHUNK>(st, qkv, B, T, H, scale, out, lse);
 }
 
 template <int NTILE, int NW>
@@ -1032,19 +1073,25 @@ extern "C" int dali_layernorm_bwd(dali_ctx* ctx, void* stream, const uint16_t* g
 extern "C" int dali_attention_fwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
                                   uint16_t* out, float* lse) {
     DALI_REQUIRE(ctx && qkv && out, "dali_attention_fwd: null argument");
-    DALI_REQUIRE(head_dim == ATT_HD && T > 0, "dali_attention_fwd: head_dim must be %d and T >= 1 (got %d, %d)", ATT_HD, head_dim, T);
+    DALI_REQUIRE(head_dim == ATT_HD || head_dim == ATT_HD96, "dali_attention_fwd: head_dim must be 64 or 96 (got %d)", head_dim);
+    DALI_REQUIRE(T > 0, "dali_attention_fwd: T >= 1 (got %d)", T);
+    if (head_dim == ATT_HD96) return launch_attention_fwd_hd96((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
     return launch_attention_fwd((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
 }
 extern "C" int dali_attention_fwd_long(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
                                        uint16_t* out, float* lse) {
     DALI_REQUIRE(ctx && qkv && out, "dali_attention_fwd_long: null argument");
-    DALI_REQUIRE(head_dim == ATT_HD && T > 0, "dali_attention_fwd_long: head_dim must be %d and T >= 1 (got %d, %d)", ATT_HD, head_dim, T);
+    DALI_REQUIRE(head_dim == ATT_HD || head_dim == ATT_HD96, "dali_attention_fwd_long: head_dim must be 64 or 96 (got %d)", head_dim);
+    DALI_REQUIRE(T > 0, "dali_attention_fwd_long: T >= 1 (got %d)", T);
+    if (head_dim == ATT_HD96) return launch_attention_fwd_hd96((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
     return launch_attention_fwd_long((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
 }
 extern "C" int dali_attention_fwd_short(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
                                         uint16_t* out, float* lse) {
     DALI_REQUIRE(ctx && qkv && out, "dali_attention_fwd_short: null argument");
-    DALI_REQUIRE(head_dim == ATT_HD && T > 0 && T <= ATT_SHORT_T, "dali_attention_fwd_short: head_dim must be %d and T <= %d (got %d, %d)", ATT_HD, ATT_SHORT_T, head_dim, T);
+    DALI_REQUIRE(head_dim == ATT_HD || head_dim == ATT_HD96, "dali_attention_fwd_short: head_dim must be 64 or 96 (got %d)", head_dim);
+    DALI_REQUIRE(T > 0 && T <= ATT_SHORT_T, "dali_attention_fwd_short: T must be 1 .. %d (got %d)", ATT_SHORT_T, T);
+    if (head_dim == ATT_HD96) return launch_attention_fwd_hd96((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
     return launch_attention_fwd_short((hipStream_t)stream, qkv, B, T, H, scale, out, lse);
 }
 extern "C" int dali_attention_bwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out, const float* lse,

@@ -14,9 +14,14 @@
 // A local_feature / JPM plan never runs a backward, so it reserves none of the backward's buffers (dgrad weight images, weight-gradient slab,
 // reduction partials, DropPath rows, gradient buffers) and its refresh_weights only casts.  The same holds for any plan with more than 256 tokens
 // (up to 1024: 384x128 at stride 12 = 311, 256x256 at stride 16 = 257): only the attention FORWARD exists there, so a training forward and the
-// backward entries return DALI_ERR_LIMIT before their first launch.
+// backward entries return DALI_ERR_LIMIT before their first launch.  And for a plan with head_dim 96 (ViT-Small, vit_pytorch.py:461-468: dim 768,
+// 8 heads): at that width only the chunked attention forward exists (launch_attention_fwd_hd96), whatever the token count.
+//   no_qkv_bias (vit_pytorch.py:147, qkv_bias=False): no block has an "attn.qkv.bias" parameter; the qkv GEMM runs without a bias and its
+//   weight gradient without a column sum.  qk_scale (vit_pytorch.py:145): the attention scale, 0 = head_dim ** -0.5; the plan keeps ONE scale
+//   (att_scale) for the forward and the backward.  Both are independent of head_dim and train at head_dim 64.
 #include "kernels.h"
 #include "plan_table.h"
+#include <cmath>
 #include <cstdio>
 #include <new>
 #include <string>
@@ -38,7 +43,8 @@ struct Neck { int64_t g, b, rm, rv; };
 struct dali_vit : PlanTable {
     dali_ctx* ctx;
     dali_vit_cfg cfg;
-    int B, T, np, C, H, rows;
+    int B, T, np, C, H, rows, hd;
+    float att_scale;                      // vit_pytorch.py:145: qk_scale or head_dim ** -0.5 (exactly 0.125f at head_dim 64), forward and backward
     int64_t cls_off, pos_off, fcw_off, fcb_off;
     Lin patch; Ln fin; std::vector<VBlock> blocks;
     int64_t neck_g, neck_b, neck_rm, neck_rv;
@@ -65,24 +71,33 @@ struct dali_vit : PlanTable {
     float *gf2 = nullptr, *fin2_mean = nullptr, *fin2_rstd = nullptr;
     int n_stages = 1;
     std::vector<int> stage_first_block;   // backward stage s runs blocks [stage_first_block[s+1], stage_first_block[s]) downwards
-    bool eval_only = false;               // local_feature / JPM, or more than VIT_TRAIN_MAX_T tokens: none of the backward's buffers
+    bool eval_only = false;               // local_feature / JPM, more than VIT_TRAIN_MAX_T tokens, or head_dim 96: none of the backward's buffers
 };
 
 namespace {
 // The attention forward runs up to 1024 tokens (launch_attention_fwd), its backward up to 256: a longer plan is an eval plan.
-constexpr int VIT_MAX_T = 1024, VIT_TRAIN_MAX_T = 256;
-// the training forward and every backward entry ask this before their first launch
+// At head_dim 96 only the attention forward exists, at any length: such a plan is an eval plan too.
+constexpr int VIT_MAX_T = 1024, VIT_TRAIN_MAX_T = 256, VIT_TRAIN_HD = 64, VIT_EVAL_HD = 96;
+// the training forward and every backward entry ask this before their first launch (the token check first)
 int refuse_long_training(const dali_vit* n) {
-    if (n->T <= VIT_TRAIN_MAX_T) return DALI_OK;
-    set_error("training needs at most %d tokens (this plan has %d); eval mode only", VIT_TRAIN_MAX_T, n->T);
-    return DALI_ERR_LIMIT;
+    if (n->T > VIT_TRAIN_MAX_T) {
+        set_error("training needs at most %d tokens (this plan has %d); eval mode only", VIT_TRAIN_MAX_T, n->T);
+        return DALI_ERR_LIMIT;
+    }
+    if (n->hd != VIT_TRAIN_HD) {
+        set_error("training needs head_dim %d (this plan has %d); eval mode only", VIT_TRAIN_HD, n->hd);
+        return DALI_ERR_LIMIT;
+    }
+    return DALI_OK;
 }
-void add_lin(dali_vit* n, Lin& l, const std::string& name, int K, int N) {
+void add_lin(dali_vit* n, Lin& l, const std::string& name, int K, int N, bool bias = true) {
     l.K = K; l.N = N;
     l.w_off = n->add_param(name + ".weight", {N, K});
-    l.b_off = n->add_param(name + ".bias", {N});
+    l.b_off = bias ? n->add_param(name + ".bias", {N}) : -1;          // -1: no such parameter (lin_bias / lin_dbias hand out null)
     l.w = l.wt = nullptr;
 }
+const float* lin_bias(const dali_vit* n, const Lin& l) { return l.b_off >= 0 ? n->P + l.b_off : nullptr; }
+float* lin_dbias(const dali_vit* n, const Lin& l) { return l.b_off >= 0 ? n->G + l.b_off : nullptr; }
 void add_ln(dali_vit* n, Ln& l, const std::string& name, int C) {
     l.g_off = n->add_param(name + ".weight", {C});
     l.b_off = n->add_param(name + ".bias", {C});
@@ -90,7 +105,7 @@ void add_ln(dali_vit* n, Ln& l, const std::string& name, int C) {
 void add_block(dali_vit* n, VBlock& b, const std::string& pre) {
     const int C = n->C;
     add_ln(n, b.n1, pre + ".norm1", C);
-    add_lin(n, b.qkv, pre + ".attn.qkv", C, 3 * C);
+    add_lin(n, b.qkv, pre + ".attn.qkv", C, 3 * C, !n->ext.no_qkv_bias);
     add_lin(n, b.proj, pre + ".attn.proj", C, C);
     add_ln(n, b.n2, pre + ".norm2", C);
     add_lin(n, b.fc1, pre + ".mlp.fc1", C, n->cfg.mlp_hidden);
@@ -107,7 +122,10 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
     DALI_REQUIRE(ctx && cfg && ext && out, "dali_vit_create: null argument");
     DALI_REQUIRE(cfg->batch > 0 && cfg->patch % 8 == 0 && cfg->stride > 0 && cfg->height >= cfg->patch && cfg->width >= cfg->patch,
                  "dali_vit_create: bad geometry");
-    DALI_REQUIRE(cfg->dim % 64 == 0 && cfg->heads * 64 == cfg->dim && cfg->dim <= 2048, "dali_vit_create: head_dim must be 64 (dim=%d heads=%d)", cfg->dim, cfg->heads);
+    DALI_REQUIRE(cfg->heads > 0 && cfg->dim > 0 && cfg->dim <= 2048 && cfg->dim % cfg->heads == 0 &&
+                 (cfg->dim / cfg->heads == VIT_TRAIN_HD || cfg->dim / cfg->heads == VIT_EVAL_HD),
+                 "dali_vit_create: head_dim = dim / heads must be %d or %d (dim=%d heads=%d)", VIT_TRAIN_HD, VIT_EVAL_HD, cfg->dim, cfg->heads);
+    DALI_REQUIRE(ext->qk_scale >= 0.0f && ext->qk_scale < 1e30f, "dali_vit_create: qk_scale must be positive, or 0 for head_dim ** -0.5");
     DALI_REQUIRE(cfg->depth >= 1 && cfg->mlp_hidden % 32 == 0 && cfg->mlp_hidden > 0, "dali_vit_create: bad depth / mlp_hidden");
     dali_vit* n = new (std::nothrow) dali_vit();
     if (!n) { set_error("dali_vit_create: out of host memory"); return DALI_ERR_NOMEM; }
@@ -115,9 +133,11 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
     if (n->ext.jpm) n->ext.local_feature = 1;            // make_models.py:243: the JPM base is built with local_feature = cfg.MODEL.JPM
     const int ny = (cfg->height - cfg->patch) / cfg->stride + 1, nx = (cfg->width - cfg->patch) / cfg->stride + 1;
     n->B = cfg->batch; n->np = ny * nx; n->T = n->np + 1; n->C = cfg->dim; n->H = cfg->heads; n->rows = n->B * n->T;
+    n->hd = cfg->dim / cfg->heads;
+    n->att_scale = ext->qk_scale > 0.0f ? ext->qk_scale : n->hd == VIT_TRAIN_HD ? 0.125f : 1.0f / sqrtf((float)n->hd);
     if (n->T > VIT_MAX_T) { set_error("dali_vit_create: %d tokens exceed the attention kernel's limit of %d", n->T, VIT_MAX_T); delete n; return DALI_ERR_LIMIT; }
-    // past VIT_TRAIN_MAX_T tokens only the attention forward exists: an eval plan, reserved like a local_feature one
-    n->eval_only = n->ext.local_feature != 0 || n->T > VIT_TRAIN_MAX_T;
+    // past VIT_TRAIN_MAX_T tokens, and at head_dim 96, only the attention forward exists: an eval plan, reserved like a local_feature one
+    n->eval_only = n->ext.local_feature != 0 || n->T > VIT_TRAIN_MAX_T || n->hd != VIT_TRAIN_HD;
     const int C = n->C, Kp = 3 * cfg->patch * cfg->patch;
     n->cls_off = n->add_param("base.cls_token", {1, 1, C});
     n->pos_off = n->add_param("base.pos_embed", {1, n->T, C});
@@ -251,7 +271,7 @@ extern "C" int dali_vit_refresh_weights(dali_vit* n, void* stream) {
     if (rc) return rc;
     // b1 / b2 read their bf16 weights from the same image (the cast above covers them)
     if (n->ext.jpm) DALI_HIP(hipMemcpyAsync(n->map_dev, n->map_host.data(), n->map_host.size() * 4, hipMemcpyHostToDevice, st));
-    if (n->eval_only) return DALI_OK;                    // local_feature / JPM / more than 256 tokens: no dgrad images
+    if (n->eval_only) return DALI_OK;                    // local_feature / JPM / more than 256 tokens / head_dim 96: no dgrad images
     std::vector<TransposeJob> jobs;                      // every linear's dgrad image [K][N], batched launches (48 single launches cost 0.3 ms)
     for (auto& b : n->blocks) {
         Lin* ls[4] = {&b.qkv, &b.proj, &b.fc1, &b.fc2};
@@ -264,13 +284,14 @@ namespace {
 // one transformer block (vit_pytorch.py:166-184) on `rows` = seqs * T token rows; dp_att / dp_mlp: DropPath factors per row or null
 int run_block(dali_vit* n, hipStream_t st, VBlock& b, const uint16_t* x, int rows, int seqs, int T, const float* dp_att, const float* dp_mlp, bool short_att) {
     const int C = n->C, Hd = n->cfg.mlp_hidden;
-    const float eps = 1e-6f, scale = 0.125f;           // head_dim 64 -> 64^-0.5
+    const float eps = 1e-6f, scale = n->att_scale;
     int rc;
     b.x_in = const_cast<uint16_t*>(x);
     if ((rc = launch_layernorm_fwd(st, x, n->P + b.n1.g_off, n->P + b.n1.b_off, rows, C, eps, b.h1, b.n1.mean, b.n1.rstd, nullptr))) return rc;
-    if ((rc = launch_linear_fwd(st, b.h1, b.qkv.w, n->P + b.qkv.b_off, 0, nullptr, b.qkv_o, nullptr, nullptr, rows, C, 3 * C))) return rc;
-    if ((rc = short_att ? launch_attention_fwd_short(st, b.qkv_o, seqs, T, n->H, scale, b.att, b.lse)
-                        : launch_attention_fwd(st, b.qkv_o, seqs, T, n->H, scale, b.att, b.lse))) return rc;
+    if ((rc = launch_linear_fwd(st, b.h1, b.qkv.w, lin_bias(n, b.qkv), 0, nullptr, b.qkv_o, nullptr, nullptr, rows, C, 3 * C))) return rc;
+    if ((rc = n->hd == VIT_EVAL_HD ? launch_attention_fwd_hd96(st, b.qkv_o, seqs, T, n->H, scale, b.att, b.lse)
+              : short_att        ? launch_attention_fwd_short(st, b.qkv_o, seqs, T, n->H, scale, b.att, b.lse)
+                                 : launch_attention_fwd(st, b.qkv_o, seqs, T, n->H, scale, b.att, b.lse))) return rc;
     // x_mid = x + s[b] * proj(...): the per-row factor rides in the GEMM's epilogue (IGemmArgs::row_scale)
     if ((rc = launch_linear_fwd(st, b.att, b.proj.w, n->P + b.proj.b_off, 0, x, b.x_mid, nullptr, nullptr, rows, C, C, dp_att))) return rc;
     if ((rc = launch_layernorm_fwd(st, b.x_mid, n->P + b.n2.g_off, n->P + b.n2.b_off, rows, C, eps, b.h2, b.n2.mean, b.n2.rstd, nullptr))) return rc;
@@ -349,7 +370,7 @@ extern "C" int dali_vit_forward_ex(dali_vit* n, void* stream, const float* image
 namespace {
 int lin_bwd(dali_vit* n, hipStream_t st, const Lin& l, const uint16_t* x, const uint16_t* dy, const uint16_t* gelu_pre, uint16_t* dx, int rows) {
     int rc;
-    if ((rc = launch_linear_wgrad(st, x, dy, n->G + l.w_off, rows, l.K, l.N, WGradBufs{n->slab, n->partial, n->scratch}, n->G + l.b_off))) return rc;
+    if ((rc = launch_linear_wgrad(st, x, dy, n->G + l.w_off, rows, l.K, l.N, WGradBufs{n->slab, n->partial, n->scratch}, lin_dbias(n, l)))) return rc;
     if (dx) return launch_linear_fwd(st, dy, l.wt, nullptr, 0, nullptr, dx, nullptr, gelu_pre, rows, l.N, l.K);
     return DALI_OK;
 }
@@ -410,7 +431,7 @@ int bwd_block(dali_vit* n, hipStream_t st, int i) {
     d_branch = t3;
     if (dp) { if ((rc = launch_rowscale_add(st, t3, s_att, n->B, n->T, C, nullptr, t2))) return rc; d_branch = t2; }
     if ((rc = lin_bwd(n, st, b.proj, b.att, d_branch, nullptr, t1, rows))) return rc;          // t1 = d_att
-    if ((rc = launch_attention_bwd(st, b.qkv_o, b.att, t1, b.lse, n->B, n->T, n->H, 0.125f, t2))) return rc;   // t2 = d_qkv
+    if ((rc = launch_attention_bwd(st, b.qkv_o, b.att, t1, b.lse, n->B, n->T, n->H, n->att_scale, t2))) return rc;   // t2 = d_qkv
     if ((rc = lin_bwd(n, st, b.qkv, b.h1, t2, nullptr, t1, rows))) return rc;                  // t1 = d_h1
     return launch_layernorm_bwd(st, t1, b.x_in, n->P + b.n1.g_off, b.n1.mean, b.n1.rstd, t3, rows, C, dx, n->G + b.n1.g_off,
                                 n->G + b.n1.b_off, n->partial, n->scratch);                    // dx = dx_in

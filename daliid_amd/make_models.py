@@ -2,7 +2,8 @@
 (make_models.py:399-410) -> ``build_transformer`` (:121-218): TransReID ViT encoder + BatchNorm1d neck with frozen bias,
 ``forward(x, label=None, cam_label=None, view_label=None)`` returning the post-neck ``feat`` (:184-205), or, with ``cfg.MODEL.JPM``,
 ``build_transformer_local`` (:221-389): the JPM head (global branch + four shuffled local runs through a shared block, five necks) whose
-eval forward returns ``[B, 5 * 768]``.  SIE camera / view embeddings follow ``cfg.MODEL.SIE_CAMERA`` / ``SIE_VIEW`` / ``SIE_COE``.
+eval forward returns ``[B, 5 * 768]``.  ``cfg.MODEL.TRANSFORMER_TYPE`` takes the reference's four names (make_models.py:392-397): ViT-B/16 under
+two of them, DeiT-Small (dim 384, trains) and ViT-Small (head_dim 96: eval only; JPM in eval).  SIE camera / view embeddings follow ``cfg.MODEL.SIE_CAMERA`` / ``SIE_VIEW`` / ``SIE_COE``.
 
 ``cfg`` is the same yacs-like attribute tree the reference reads (cfg.MODEL.*, cfg.TEST.NECK_FEAT, cfg.INPUT.SIZE_TRAIN).
 Out of scope: ``Backbone`` (broken in the reference, make_models.py:63) and JPM's train-mode forward (classifier scores for an
@@ -16,9 +17,11 @@ import torch
 from ._lib import DaliError
 from .vit_pytorch import ViTNeckNet, load_base_param
 
-_GEOM = {  # factory name -> (embed_dim, depth, heads, mlp_ratio)   (vit_pytorch.py:453-476)
-    "vit_base_patch16_224_TransReID": (768, 12, 12, 4.0),
-    "deit_base_patch16_224_TransReID": (768, 12, 12, 4.0),
+_GEOM = {  # factory name -> (embed_dim, depth, heads, mlp_ratio, qkv_bias, qk_scale)   (vit_pytorch.py:453-476, make_models.py:392-397)
+    "vit_base_patch16_224_TransReID": (768, 12, 12, 4.0, True, None),
+    "deit_base_patch16_224_TransReID": (768, 12, 12, 4.0, True, None),
+    "vit_small_patch16_224_TransReID": (768, 8, 8, 3.0, False, 768 ** -0.5),       # head_dim 96: eval only
+    "deit_small_patch16_224_TransReID": (384, 12, 6, 4.0, True, None),             # in_planes 384 (make_models.py:148-149)
 }
 
 
@@ -51,18 +54,18 @@ def jpm_token_map(n_patches, shift, groups, divide=4, rearrange=True):
 def _base_kwargs(cfg, camera_num, view_num, depth, device, seed, who):
     name = cfg.MODEL.TRANSFORMER_TYPE
     if name not in _GEOM:
-        raise NotImplementedError("%s: transformer type %r is out of scope (head_dim 64 ViT-B only)" % (who, name))
+        raise NotImplementedError("%s: transformer type %r is out of scope (admitted: %s)" % (who, name, ", ".join(_GEOM)))
     if getattr(cfg.MODEL, "DROP_OUT", 0.0) != 0.0 or getattr(cfg.MODEL, "ATT_DROP_RATE", 0.0) != 0.0:
         raise NotImplementedError("%s: dropout is not supported" % who)
     if cfg.MODEL.PRETRAIN_CHOICE == 'imagenet' and not os.path.isfile(str(cfg.MODEL.PRETRAIN_PATH)):
         raise NotImplementedError("%s: ImageNet checkpoint loading needs a file fetched from the network; "
                                   "load a state_dict with load_state_dict instead" % who)
-    dim, geom_depth, heads, ratio = _GEOM[name]
+    dim, geom_depth, heads, ratio, qkv_bias, qk_scale = _GEOM[name]
     print('using Transformer_type: {} as a backbone'.format(name))
     return dict(img_size=cfg.INPUT.SIZE_TRAIN, patch_size=16, stride_size=cfg.MODEL.STRIDE_SIZE, embed_dim=dim, depth=geom_depth if depth is None else depth,
                 num_heads=heads, mlp_ratio=ratio, num_classes=1000, drop_path_rate=cfg.MODEL.DROP_PATH, device=device, seed=seed,
                 camera=camera_num if cfg.MODEL.SIE_CAMERA else 0, view=view_num if cfg.MODEL.SIE_VIEW else 0,      # make_models.py:135-142
-                sie_xishu=cfg.MODEL.SIE_COE)
+                sie_xishu=cfg.MODEL.SIE_COE, qkv_bias=qkv_bias, qk_scale=qk_scale)
 
 
 def _load_pretrained(model, cfg):
@@ -111,6 +114,10 @@ class build_transformer_local(_Checkpoints, ViTNeckNet):
 
     def __init__(self, num_classes, camera_num, view_num, cfg, factory=None, rearrange=True, device=None, seed=None, depth=None):
         kw = _base_kwargs(cfg, camera_num, view_num, depth, device, seed, "build_transformer_local")
+        if kw["embed_dim"] != 768:
+            raise NotImplementedError("build_transformer_local: JPM with %s is out of scope: the reference builds 768-wide necks there "
+                                      "(in_planes = 768, make_models.py:229) over a %d-wide base and fails on its first forward"
+                                      % (cfg.MODEL.TRANSFORMER_TYPE, kw["embed_dim"]))
         if cfg.MODEL.ID_LOSS_TYPE in ('arcface', 'cosface', 'amsoftmax', 'circle'):
             raise NotImplementedError("build_transformer_local: margin classifiers (ID_LOSS_TYPE %r) are out of scope" % cfg.MODEL.ID_LOSS_TYPE)
         groups, shift, divide = int(cfg.MODEL.SHUFFLE_GROUP), int(cfg.MODEL.SHIFT_NUM), int(cfg.MODEL.DEVIDE_LENGTH)

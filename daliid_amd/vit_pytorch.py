@@ -1,5 +1,5 @@
 """Mirror of the reference's ``vit_pytorch.py`` for the path in scope: the ``TransReID`` encoder
-(vit_pytorch.py:291-408) and its factory ``vit_base_patch16_224_TransReID`` (:453-459), on the native HIP ViT plan
+(vit_pytorch.py:291-408) and its factories ``vit_base_`` / ``vit_small_`` / ``deit_small_patch16_224_TransReID`` (:453-476), on the native HIP ViT plan
 (``dali_vit_*``).  ``make_models.build_transformer`` (the BN-neck wrapper the reference actually instantiates,
 make_models.py:121-205) is the module that owns the plan; ``TransReID`` here is the same plan exposed at the pre-neck
 feature so the reference's key names (``cls_token``, ``pos_embed``, ``patch_embed.proj.*``, ``blocks.N.*``, ``norm.*``,
@@ -9,7 +9,8 @@ Supported: drop / attn_drop = 0; SIE camera / view embeddings (vit_pytorch.py:31
 ``sie_xishu * sie_embed[index]``, trained through ``dali_vit_sie_grad``); ``local_feature=True`` (:393-396: ``blocks[:-1]``, all tokens, no
 final norm; eval mode only).  ``make_models.build_transformer_local`` puts the JPM head on the same plan.  Geometries up to 1024 tokens
 (384x128 at stride 12 = 311, 256x256 at stride 16 = 257, 384x384 at stride 16 = 577); past 256 tokens a model is eval only, its train-mode
-forward raises.  ``resize_pos_embed`` / ``TransReID.load_param`` (vit_pytorch.py:410-450) bring a checkpoint of another size in.  DropPath (vit_pytorch.py:45-62; per-block rate
+forward raises.  Head widths 64 and 96: ``qkv_bias=False`` and a set ``qk_scale`` (vit_pytorch.py:145-147) work at both; at head_dim 96 (ViT-Small:
+dim 768, 8 heads) only the attention forward exists, so such a model is eval only as well.  ``resize_pos_embed`` / ``TransReID.load_param`` (vit_pytorch.py:410-450) bring a checkpoint of another size in.  DropPath (vit_pytorch.py:45-62; per-block rate
 ``linspace(0, drop_path_rate, depth)``, :338) is applied in training mode: one uniform draw per (branch, sample) on the
 device per step, scale = floor(keep + u) / keep; ``drop_path_uniform`` can be set to inject the draws (parity tests hand
 the same ones to the oracle).  In eval mode it is the identity, as in the reference.
@@ -26,6 +27,7 @@ from .plan_net import PlanHandle, PlanNet
 
 
 TRAIN_MAX_TOKENS = 256      # the attention backward's limit; the forward alone (eval mode) runs up to 1024 tokens
+TRAIN_HEAD_DIM = 64         # the attention backward's head width; the forward alone also runs at 96
 
 
 class _VitCfg(ctypes.Structure):
@@ -34,7 +36,8 @@ class _VitCfg(ctypes.Structure):
 
 class _VitExt(ctypes.Structure):
     _fields_ = [("n_sie", ctypes.c_int), ("sie_coef", ctypes.c_float), ("local_feature", ctypes.c_int), ("jpm", ctypes.c_int),
-                ("divide", ctypes.c_int), ("token_map", ctypes.c_void_p), ("neck_after", ctypes.c_int), ("id_classes", ctypes.c_int)]
+                ("divide", ctypes.c_int), ("token_map", ctypes.c_void_p), ("neck_after", ctypes.c_int), ("id_classes", ctypes.c_int),
+                ("no_qkv_bias", ctypes.c_int), ("qk_scale", ctypes.c_float)]
 
 
 def _VitPlan(device, cfg_tuple, ext=None):
@@ -52,16 +55,20 @@ class ViTNeckNet(PlanNet):
     """TransReID encoder + BatchNorm1d neck on the HIP plan; state_dict keys as make_models.build_transformer
     (``base.*``, ``bottleneck.*``).  ``camera`` / ``view`` > 1 add the SIE parameter ``base.sie_embed`` (vit_pytorch.py:316-331);
     ``jpm`` (a dict of dali_vit_ext's JPM fields: ``token_map``, ``neck_after``, ``id_classes``; set by make_models.build_transformer_local) adds ``b1.*``, ``b2.*``, ``classifier*`` and
-    ``bottleneck_1..4`` and makes the output [B, 5 * embed_dim]."""
+    ``bottleneck_1..4`` and makes the output [B, 5 * embed_dim].  ``qkv_bias=False`` drops every ``attn.qkv.bias``; ``qk_scale`` replaces the attention
+    scale ``head_dim ** -0.5`` (vit_pytorch.py:145-147).  ``embed_dim // num_heads`` is 64 or 96; a 96-wide model is eval only."""
 
     def __init__(self, img_size=(224, 224), patch_size=16, stride_size=16, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.0,
-                 num_classes=1000, drop_path_rate=0.0, device=None, seed=None, camera=0, view=0, sie_xishu=1.0, local_feature=False, jpm=None):
+                 num_classes=1000, drop_path_rate=0.0, device=None, seed=None, camera=0, view=0, sie_xishu=1.0, local_feature=False, jpm=None,
+                 qkv_bias=True, qk_scale=None):
         super().__init__(device)
         self.cam_num, self.view_num, self.sie_xishu = int(camera), int(view), float(sie_xishu)
         # vit_pytorch.py:317-331: one row per (camera, view) pair, per camera, or per view
         n_sie = camera * view if camera > 1 and view > 1 else camera if camera > 1 else view if view > 1 else 0
         self.local_feature = bool(local_feature or jpm)
-        self._ext = dict(n_sie=int(n_sie), sie_coef=float(sie_xishu), local_feature=int(self.local_feature))
+        self._ext = dict(n_sie=int(n_sie), sie_coef=float(sie_xishu), local_feature=int(self.local_feature),
+                         no_qkv_bias=int(not qkv_bias), qk_scale=float(qk_scale or 0.0))          # `qk_scale or`, as vit_pytorch.py:145
+        self.head_dim = embed_dim // max(int(num_heads), 1)
         if jpm:
             self._ext.update(jpm=1, **jpm)
         self._sie_idx = None
@@ -199,6 +206,10 @@ class ViTNeckNet(PlanNet):
                 # past 256 tokens only the attention forward exists (the plan holds none of the backward's buffers)
                 raise _lib.DaliError("training needs at most %d tokens (this model has %d): it is eval mode only -- call .eval() and run under "
                                      "torch.no_grad()" % (TRAIN_MAX_TOKENS, self.num_tokens))
+            if self.head_dim != TRAIN_HEAD_DIM:
+                # at head_dim 96 only the attention forward exists (the plan holds none of the backward's buffers)
+                raise _lib.DaliError("training needs head_dim %d (this model has %d): it is eval mode only -- call .eval() and run under "
+                                     "torch.no_grad()" % (TRAIN_HEAD_DIM, self.head_dim))
             return self._forward_with_grad(x, sie_idx=idx)
         return self._run_forward(x, self.training, sie_idx=idx)
 
@@ -226,12 +237,12 @@ class TransReID(nn.Module):
                  mlp_ratio=4., qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0., camera=0, view=0, drop_path_rate=0.,
                  hybrid_backbone=None, norm_layer=None, local_feature=False, sie_xishu=1.0, device=None, seed=None):
         super().__init__()
-        if in_chans != 3 or not qkv_bias or qk_scale is not None or hybrid_backbone is not None:
-            raise NotImplementedError("TransReID: only in_chans=3, qkv_bias=True, default qk_scale, no hybrid backbone are in scope")
+        if in_chans != 3 or hybrid_backbone is not None:
+            raise NotImplementedError("TransReID: only in_chans=3 and no hybrid backbone are in scope")
         if drop_rate != 0. or attn_drop_rate != 0.:
             raise NotImplementedError("TransReID: dropout is not supported (the reference's callers use 0)")
         self.net = ViTNeckNet(img_size, patch_size, stride_size, embed_dim, depth, num_heads, mlp_ratio, num_classes, drop_path_rate, device, seed,
-                              camera=camera, view=view, sie_xishu=sie_xishu, local_feature=local_feature)
+                              camera=camera, view=view, sie_xishu=sie_xishu, local_feature=local_feature, qkv_bias=qkv_bias, qk_scale=qk_scale)
         self.local_feature, self.cam_num, self.view_num, self.sie_xishu = bool(local_feature), camera, view, sie_xishu
         self.num_features = self.embed_dim = embed_dim
         self.num_classes = num_classes
@@ -313,4 +324,22 @@ def vit_base_patch16_224_TransReID(img_size=(256, 128), stride_size=16, drop_rat
     """vit_pytorch.py:453-459."""
     return TransReID(img_size=img_size, patch_size=16, stride_size=stride_size, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4, qkv_bias=True,
                      camera=camera, view=view, drop_path_rate=drop_path_rate, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate,
+                     sie_xishu=sie_xishu, local_feature=local_feature, **kwargs)
+
+
+def vit_small_patch16_224_TransReID(img_size=(256, 128), stride_size=16, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.1, camera=0, view=0,
+                                    local_feature=False, sie_xishu=1.5, **kwargs):
+    """vit_pytorch.py:461-468: dim 768, depth 8, 8 heads (head_dim 96), MLP ratio 3, no qkv bias, and the scale of the FULL width, 768 ** -0.5.
+    Eval only (there is no attention backward at head_dim 96)."""
+    kwargs.setdefault('qk_scale', 768 ** -0.5)
+    return TransReID(img_size=img_size, patch_size=16, stride_size=stride_size, embed_dim=768, depth=8, num_heads=8, mlp_ratio=3., qkv_bias=False,
+                     drop_path_rate=drop_path_rate, camera=camera, view=view, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate,
+                     sie_xishu=sie_xishu, local_feature=local_feature, **kwargs)
+
+
+def deit_small_patch16_224_TransReID(img_size=(256, 128), stride_size=16, drop_path_rate=0.1, drop_rate=0.0, attn_drop_rate=0.0, camera=0, view=0,
+                                     local_feature=False, sie_xishu=1.5, **kwargs):
+    """vit_pytorch.py:470-476: dim 384, depth 12, 6 heads (head_dim 64), MLP ratio 4; trains and evaluates."""
+    return TransReID(img_size=img_size, patch_size=16, stride_size=stride_size, embed_dim=384, depth=12, num_heads=6, mlp_ratio=4, qkv_bias=True,
+                     drop_path_rate=drop_path_rate, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, camera=camera, view=view,
                      sie_xishu=sie_xishu, local_feature=local_feature, **kwargs)

@@ -448,19 +448,24 @@ int dali_layernorm_fwd(dali_ctx* ctx, void* stream, const uint16_t* x, const flo
 int dali_layernorm_bwd(dali_ctx* ctx, void* stream, const uint16_t* g, const uint16_t* x, const float* gamma, const float* mean,
                        const float* rstd, const uint16_t* add, int rows, int C, uint16_t* dx, float* dgamma, float* dbeta);
 /* Attention (vit_pytorch.py:152-164): qkv [B*T][3*H*64] -> out [B*T][H*64] = softmax(q k^T * scale) v per head, scores on chip;
- * lse [B*H][T] (row log-sum-exp, natural log; nullable in the forward) feeds the backward, which recomputes the probabilities.  head_dim 64.
+ * lse [B*H][T] (row log-sum-exp, natural log; nullable in the forward) feeds the backward, which recomputes the probabilities.
+ * head_dim 64 (forward and backward) or 96 (forward only: 64 above stands for head_dim); any other width is refused before a launch
+ * ("head_dim must be 64 or 96 (got N)").
  * Forward: 1 <= T <= 1024.  T <= 256 keeps a head's K and V in LDS (one workgroup per batch and head); 256 < T <= 1024 goes to the chunked
- * kernel of dali_attention_fwd_long; beyond 1024 DALI_ERR_LIMIT, nothing launched.  Backward: T <= 256 (a longer sequence is eval only). */
+ * kernel of dali_attention_fwd_long; beyond 1024 DALI_ERR_LIMIT, nothing launched.  At head_dim 96 every length, through any of the three
+ * forward entries, runs the chunked kernel's 96-wide instance (key chunks of 128).  Backward: head_dim 64 and T <= 256 only. */
 int dali_attention_fwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
                        uint16_t* out, float* lse);
 /* The chunked forward on its own, 1 <= T <= 1024 (DALI_ERR_LIMIT beyond): one workgroup per (batch, head, 128 queries) walks the keys in
  * chunks of 256 under an online softmax (running maximum and sum in fp32, probabilities rounded to bf16 unnormalised, one division at the
- * end).  Same operands and layouts as dali_attention_fwd; lse may be NULL.  Not bitwise equal to the T <= 256 kernels. */
+ * end).  Same operands and layouts as dali_attention_fwd; lse may be NULL.  Not bitwise equal to the T <= 256 kernels.  head_dim 96: chunks
+ * of 128. */
 int dali_attention_fwd_long(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
                             uint16_t* out, float* lse);
 int dali_attention_bwd(dali_ctx* ctx, void* stream, const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out, const float* lse,
                        int B, int T, int H, int head_dim, float scale, uint16_t* dqkv);
-/* The forward for short sequences, T <= 64 (the JPM local runs: 33 / 53 / 50 tokens): a 4-tile instance of the same kernel. */
+/* The forward for short sequences, T <= 64 (the JPM local runs: 33 / 53 / 50 tokens): a 4-tile instance of the same kernel (head_dim 96:
+ * the chunked kernel, under the same limit). */
 int dali_attention_fwd_short(dali_ctx* ctx, void* stream, const uint16_t* qkv, int B, int T, int H, int head_dim, float scale,
                              uint16_t* out, float* lse);
 
@@ -631,10 +636,12 @@ int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void** ptr, int
 /* ---- net plan: TransReID ViT + BN neck (make_models.build_transformer.forward, make_models.py:184-205) ----- *
  * Same storage contract as dali_resnet_*.  forward: images fp32 NCHW -> feat fp32 [batch, dim] (after the
  * BatchNorm1d neck); global_feat (nullable) receives the pre-neck cls feature.  Dropout is the identity (rate 0).
- * Limits: head_dim 64, at most 1024 tokens (DALI_ERR_LIMIT beyond).  A plan with more than 256 tokens is an EVAL plan: it reserves none of the
- * backward's buffers, refresh_weights only casts, and dali_vit_forward_ex with training != 0, dali_vit_backward and dali_vit_backward_stages
- * return DALI_ERR_LIMIT before any launch ("training needs at most 256 tokens (this plan has N); eval mode only").  Plans with at most 256
- * tokens are what they were, size for size. */
+ * Limits: head_dim = dim / heads is 64 or 96, at most 1024 tokens (DALI_ERR_LIMIT beyond).  A plan with more than 256 tokens is an EVAL plan:
+ * it reserves none of the backward's buffers, refresh_weights only casts, and dali_vit_forward_ex with training != 0, dali_vit_backward and
+ * dali_vit_backward_stages return DALI_ERR_LIMIT before any launch ("training needs at most 256 tokens (this plan has N); eval mode only").
+ * A plan with head_dim 96 (ViT-Small: dim 768, 8 heads) is an eval plan in the same way -- only the attention forward exists at that width --
+ * and its refusal reads "training needs head_dim 64 (this plan has 96); eval mode only"; the token check comes first.  Plans with at most 256
+ * tokens and head_dim 64 are what they were, size for size. */
 typedef struct dali_vit dali_vit;
 typedef struct {
     int batch, height, width;   /* images fp32 NCHW [batch,3,height,width] */
@@ -649,7 +656,9 @@ typedef struct {
  *   jpm (make_models.build_transformer_local, make_models.py:221-377; implies local_feature; eval only): parameters "b1.0.*", "b1.1.*",
  *   "b2.0.*", "b2.1.*", "classifier*.weight" [id_classes, dim] (unused), "bottleneck", "bottleneck_1..4"; feat is [batch, 5*dim].
  *   The shift + group shuffle of the patch tokens (shuffle_unit, make_models.py:8-25) does not depend on the data: the caller computes it once
- *   (daliid_amd.make_models.jpm_token_map) and hands it in as token_map; the plan copies it. */
+ *   (daliid_amd.make_models.jpm_token_map) and hands it in as token_map; the plan copies it.
+ *   no_qkv_bias / qk_scale: ViT-Small's Attention (vit_pytorch.py:461-468: no qkv bias, scale 768 ** -0.5); independent of head_dim, they
+ *   train at head_dim 64. */
 typedef struct {
     int n_sie;                  /* rows of sie_embed; 0 = no SIE */
     float sie_coef;             /* cfg.MODEL.SIE_COE */
@@ -658,6 +667,8 @@ typedef struct {
     const int32_t* token_map;   /* jpm: host int32 [divide][L], L = n_patches / divide: the token (1 .. n_patches; 0 is cls) at place j of run i */
     int neck_after;             /* cfg.TEST.NECK_FEAT == 'after' */
     int id_classes;             /* rows of the unused classifier weights (the training set's identities) */
+    int no_qkv_bias;            /* qkv_bias=False (vit_pytorch.py:147): no "attn.qkv.bias" parameter in any block, b1.0 / b2.0 included */
+    float qk_scale;             /* the attention scale (vit_pytorch.py:145), forward and backward; 0 = head_dim ** -0.5 */
 } dali_vit_ext;
 int dali_vit_create(dali_ctx* ctx, const dali_vit_cfg* cfg, dali_vit** out);
 int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const dali_vit_ext* ext, dali_vit** out);
