@@ -1,6 +1,7 @@
 // rank.hip -- the market1501 CMC/mAP arithmetic of torchreid.metrics.evaluate_rank (validateModels.py:68) on a distance matrix, without a
 //   full row sort: dali_rank_eval on one GPU, dali_rank_shard_matches / _bins / _finish with the gallery sharded over ranks.  The stages
 //   the two paths share (identity slice, lower bound among the sorted match keys, bins -> AP) are one function each, below.
+//   dali_rank_eval_inp: mINP (mean inverse negative penalty) from the same query kernels on one GPU; the sharded path is out of its scope.
 #include "block_prims.h"
 
 namespace dali {
@@ -52,9 +53,11 @@ __device__ __forceinline__ int rank_lower_bound(const unsigned long long* s_key,
 // matches with a smaller key, so the (1-based) position of the j-th match is the inclusive prefix sum; taken in sequential chunks of 256
 // with a carry.  The float arithmetic and its order -- per-thread partial sums over the chunks, wave_sum, four wave partials added in
 // order, one division by np -- exist only here: whatever bins the whole-gallery and the sharded path agree on give the same bits.
+// last / n_rel (nullable; compile-time null for CMC / mAP): the 0-based position of the LAST match, where the scan ends, and np.
 template <class LoadBin>
 __device__ __forceinline__ void rank_ap_tail(LoadBin load_bin, int np, int* s_scan, float* s_red, int tid, float* __restrict__ ap,
-                                             int32_t* __restrict__ first) {
+                                             int32_t* __restrict__ first, int32_t* __restrict__ last = nullptr,
+                                             int32_t* __restrict__ n_rel = nullptr) {
     float ap_part = 0.f;
     int carry = 0;
     for (int base = 0; base < np; base += 256) {
@@ -62,6 +65,7 @@ __device__ __forceinline__ void rank_ap_tail(LoadBin load_bin, int np, int* s_sc
         const int pos = carry + block_scan_incl_256(s_scan, (t < np) ? load_bin(t) : 0, tid);
         if (t < np) ap_part += (float)(t + 1) / (float)pos;
         if (t == 0) *first = pos - 1;
+        if (last && t == np - 1) *last = pos - 1;
         carry += s_scan[255];
         __syncthreads();
     }
@@ -69,6 +73,7 @@ __device__ __forceinline__ void rank_ap_tail(LoadBin load_bin, int np, int* s_sc
     if ((tid & 63) == 0) s_red[tid >> 6] = ap_part;
     __syncthreads();
     if (tid == 0) *ap = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (float)np;
+    if (n_rel && tid == 0) *n_rel = np;
 }
 
 // ---- gallery index by identity: info = {min pid, max pid}; counts/starts over [min, max]; order = gallery positions grouped by pid ----
@@ -104,13 +109,16 @@ __global__ __launch_bounds__(256) void rank_index_scatter_kernel(const int32_t* 
 }
 
 // PASS 0: every query, LDS for PCAP = RANK_PSMALL; larger identities set pending[q].  PASS 1: only the pending queries, PCAP = RANK_PMAX.
-template <int PCAP, int PASS>
+// INP (dali_rank_eval_inp): also last_rank[q] / n_rel[q], the position of the query's last match and its number of matches (-1 / 0 for an
+// invalid query); without it the two pointers are never read and the kernel is what it was.
+template <int PCAP, int PASS, bool INP>
 __global__ __launch_bounds__(256) void rank_query_kernel(const float* __restrict__ distmat, const int32_t* __restrict__ q_pids,
                                                           const int32_t* __restrict__ q_cams, const int32_t* __restrict__ g_cams,
                                                           const int32_t* __restrict__ info, const int32_t* __restrict__ starts,
                                                           const int32_t* __restrict__ order, int nq, int ng,
                                                           float* __restrict__ ap_out, int32_t* __restrict__ first_rank,
-                                                          int32_t* __restrict__ pending, int32_t* __restrict__ status) {
+                                                          int32_t* __restrict__ pending, int32_t* __restrict__ status,
+                                                          int32_t* __restrict__ last_rank, int32_t* __restrict__ n_rel) {
     __shared__ unsigned long long s_key[PCAP];    // (orderable distance bits << 32) | gallery index: one 8-byte LDS read per compare
     __shared__ unsigned s_cell[RANK_BINS];
     __shared__ int s_cnt[PCAP + 1];
@@ -124,15 +132,16 @@ __global__ __launch_bounds__(256) void rank_query_kernel(const float* __restrict
     const int qp = q_pids[q], qc = q_cams[q];
     // 1. this query's identity slice of the gallery index: matches (other camera) and junk (same camera)
     int sb, se;
-    if (!rank_identity_slice(info, starts, qp, sb, se)) { if (tid == 0) { ap_out[q] = 0.f; first_rank[q] = -1; } return; }
+    auto invalid = [&]() { ap_out[q] = 0.f; first_rank[q] = -1; if constexpr (INP) { last_rank[q] = -1; n_rel[q] = 0; } };
+    if (!rank_identity_slice(info, starts, qp, sb, se)) { if (tid == 0) invalid(); return; }
     const int nsame = se - sb;
     if (nsame == 0) {
-        if (tid == 0) { ap_out[q] = 0.f; first_rank[q] = -1; if (PASS == 0) pending[q] = 0; }
+        if (tid == 0) { invalid(); if (PASS == 0) pending[q] = 0; }
         return;
     }
     if (nsame > PCAP) {
         if (tid == 0) {
-            ap_out[q] = 0.f; first_rank[q] = -1;
+            invalid();
             if (PASS == 0) pending[q] = 1; else atomicMax(status, 1);
         }
         return;
@@ -147,7 +156,7 @@ __global__ __launch_bounds__(256) void rank_query_kernel(const float* __restrict
     __syncthreads();
     const int np = s_n, nj = s_nj;
     if (np == 0) {
-        if (tid == 0) { ap_out[q] = 0.f; first_rank[q] = -1; }
+        if (tid == 0) invalid();
         return;
     }
     const bool vec = (ng & 3) == 0 && (reinterpret_cast<uintptr_t>(drow) & 15) == 0;
@@ -207,7 +216,39 @@ __global__ __launch_bounds__(256) void rank_query_kernel(const float* __restrict
     for (int t = tid; t < nj; t += 256) bin(drow[s_junk[t]], s_junk[t], -1);
     __syncthreads();
     // 4. inclusive scan of the bins + AP
-    rank_ap_tail([&](int t) { return s_cnt[t]; }, np, s_scan, s_red, tid, &ap_out[q], &first_rank[q]);
+    if constexpr (INP) rank_ap_tail([&](int t) { return s_cnt[t]; }, np, s_scan, s_red, tid, &ap_out[q], &first_rank[q], &last_rank[q], &n_rel[q]);
+    else rank_ap_tail([&](int t) { return s_cnt[t]; }, np, s_scan, s_red, tid, &ap_out[q], &first_rank[q]);
+}
+
+// Single-block deterministic reduction of dali_rank_eval_inp: inp[q] = n_rel / (last_rank + 1), one fp32 division (0 for an invalid
+// query), and the mean over the valid queries of the same quotient taken in fp64.
+__global__ __launch_bounds__(256) void rank_inp_reduce_kernel(const int32_t* __restrict__ last_rank, const int32_t* __restrict__ n_rel, int nq,
+                                                               float* __restrict__ inp, double* __restrict__ minp64, int32_t* __restrict__ num_valid) {
+    __shared__ double s_sum[256];
+    __shared__ int s_valid[256];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    int nv = 0;
+    for (int q = tid; q < nq; q += 256) {
+        const int lr = last_rank[q], nr = n_rel[q];
+        if (lr >= 0) {
+            inp[q] = __fdiv_rn((float)nr, (float)(lr + 1));
+            s += (double)nr / (double)(lr + 1);
+            ++nv;
+        } else {
+            inp[q] = 0.f;
+        }
+    }
+    s_sum[tid] = s; s_valid[tid] = nv;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) { s_sum[tid] += s_sum[tid + o]; s_valid[tid] += s_valid[tid + o]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        num_valid[0] = s_valid[0];
+        minp64[0] = s_valid[0] > 0 ? s_sum[0] / (double)s_valid[0] : 0.0;
+    }
 }
 
 // Single-block deterministic reduction: CMC curve + mAP over valid queries.
@@ -425,6 +466,38 @@ extern "C" int dali_rank_shard_finish(dali_ctx* ctx, void* stream, const int32_t
     return DALI_OK;
 }
 
+// The per-query stage of dali_rank_eval / dali_rank_eval_inp: status cleared, the gallery index by identity (counting sort over [min pid,
+// max pid]) in the context workspace behind the ap / first_rank scratch, then the two-tier query launches.
+template <bool INP>
+static int rank_queries(dali_ctx* ctx, hipStream_t st, const float* distmat, const int32_t* q_pids, const int32_t* g_pids, const int32_t* q_camids,
+                        const int32_t* g_camids, int nq, int ng, float* ap, int32_t* first_rank, int32_t* last_rank, int32_t* n_rel,
+                        int32_t* status, float*& ap_buf, int32_t*& fr_buf) {
+    ap_buf = ap;
+    fr_buf = first_rank;
+    DALI_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+    const size_t head = (!ap || !first_rank) ? align_up((size_t)nq * 4, 256) * 2 : 0;
+    const size_t b_info = 256, b_order = align_up((size_t)ng * 4, 256), b_pend = align_up((size_t)nq * 4, 256);
+    const size_t b_tab = align_up(((size_t)RANK_MAX_PID_RANGE + 1) * 4, 256);
+    char* ws = static_cast<char*>(workspace(ctx, head + b_info + b_order + b_pend + 3 * b_tab));
+    if (!ws) return DALI_ERR_NOMEM;
+    if (!ap) ap_buf = reinterpret_cast<float*>(ws);
+    if (!first_rank) fr_buf = reinterpret_cast<int32_t*>(ws + align_up((size_t)nq * 4, 256));
+    int32_t* info = reinterpret_cast<int32_t*>(ws + head);
+    int32_t* order = reinterpret_cast<int32_t*>(ws + head + b_info);
+    int32_t* pending = reinterpret_cast<int32_t*>(ws + head + b_info + b_order);
+    int32_t* counts = reinterpret_cast<int32_t*>(ws + head + b_info + b_order + b_pend);
+    int32_t* starts = counts + b_tab / 4;
+    int32_t* cursor = starts + b_tab / 4;
+    if (int rc = build_gallery_index(st, g_pids, ng, info, counts, starts, cursor, order, status)) return rc;
+    hipLaunchKernelGGL((rank_query_kernel<RANK_PSMALL, 0, INP>), dim3(nq), dim3(256), 0, st, distmat, q_pids, q_camids, g_camids, info, starts, order,
+                       nq, ng, ap_buf, fr_buf, pending, status, last_rank, n_rel);
+    DALI_LAUNCH_CHECK();
+    hipLaunchKernelGGL((rank_query_kernel<RANK_PMAX, 1, INP>), dim3(nq), dim3(256), 0, st, distmat, q_pids, q_camids, g_camids, info, starts, order,
+                       nq, ng, ap_buf, fr_buf, pending, status, last_rank, n_rel);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+
 extern "C" int dali_rank_eval(dali_ctx* ctx, void* stream, const float* distmat, const int32_t* q_pids,
                               const int32_t* g_pids, const int32_t* q_camids, const int32_t* g_camids, int nq, int ng,
                               int max_rank, float* cmc, float* mAP, double* map64, int32_t* num_valid, float* ap,
@@ -434,33 +507,29 @@ extern "C" int dali_rank_eval(dali_ctx* ctx, void* stream, const float* distmat,
     DALI_REQUIRE(nq > 0 && ng > 0, "dali_rank_eval: bad shape nq=%d ng=%d", nq, ng);
     DALI_REQUIRE(max_rank > 0 && max_rank <= 1024, "dali_rank_eval: max_rank %d outside 1..1024", max_rank);
     hipStream_t st = (hipStream_t)stream;
-    float* ap_buf = ap;
-    int32_t* fr_buf = first_rank;
-    // gallery index by identity (counting sort over [min pid, max pid]) in the context workspace, behind the ap / first_rank scratch
-    DALI_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
-    {
-        const size_t head = (!ap || !first_rank) ? align_up((size_t)nq * 4, 256) * 2 : 0;
-        const size_t b_info = 256, b_order = align_up((size_t)ng * 4, 256), b_pend = align_up((size_t)nq * 4, 256);
-        const size_t b_tab = align_up(((size_t)RANK_MAX_PID_RANGE + 1) * 4, 256);
-        char* ws = static_cast<char*>(workspace(ctx, head + b_info + b_order + b_pend + 3 * b_tab));
-        if (!ws) return DALI_ERR_NOMEM;
-        if (!ap) ap_buf = reinterpret_cast<float*>(ws);
-        if (!first_rank) fr_buf = reinterpret_cast<int32_t*>(ws + align_up((size_t)nq * 4, 256));
-        int32_t* info = reinterpret_cast<int32_t*>(ws + head);
-        int32_t* order = reinterpret_cast<int32_t*>(ws + head + b_info);
-        int32_t* pending = reinterpret_cast<int32_t*>(ws + head + b_info + b_order);
-        int32_t* counts = reinterpret_cast<int32_t*>(ws + head + b_info + b_order + b_pend);
-        int32_t* starts = counts + b_tab / 4;
-        int32_t* cursor = starts + b_tab / 4;
-        if (int rc = build_gallery_index(st, g_pids, ng, info, counts, starts, cursor, order, status)) return rc;
-        hipLaunchKernelGGL((rank_query_kernel<RANK_PSMALL, 0>), dim3(nq), dim3(256), 0, st, distmat, q_pids, q_camids, g_camids, info, starts, order,
-                           nq, ng, ap_buf, fr_buf, pending, status);
-        DALI_LAUNCH_CHECK();
-        hipLaunchKernelGGL((rank_query_kernel<RANK_PMAX, 1>), dim3(nq), dim3(256), 0, st, distmat, q_pids, q_camids, g_camids, info, starts, order,
-                           nq, ng, ap_buf, fr_buf, pending, status);
-        DALI_LAUNCH_CHECK();
-    }
+    float* ap_buf;
+    int32_t* fr_buf;
+    if (int rc = rank_queries<false>(ctx, st, distmat, q_pids, g_pids, q_camids, g_camids, nq, ng, ap, first_rank, nullptr, nullptr, status, ap_buf, fr_buf))
+        return rc;
     hipLaunchKernelGGL(rank_reduce_kernel, dim3(1), dim3(256), 0, st, ap_buf, fr_buf, nq, max_rank, cmc, mAP, map64, num_valid);
+    DALI_LAUNCH_CHECK();
+    return DALI_OK;
+}
+
+// mINP beside dali_rank_eval (include/daliid.h): the same query kernels, keeping where the scan of rank_ap_tail ends.  One GPU only:
+// the sharded path (dali_rank_shard_*) has no INP entry.
+extern "C" int dali_rank_eval_inp(dali_ctx* ctx, void* stream, const float* distmat, const int32_t* q_pids, const int32_t* g_pids,
+                                  const int32_t* q_camids, const int32_t* g_camids, int nq, int ng, float* inp, int32_t* last_rank,
+                                  int32_t* n_rel, double* minp64, int32_t* num_valid, int32_t* status) {
+    DALI_REQUIRE(ctx && distmat && q_pids && g_pids && q_camids && g_camids && inp && last_rank && n_rel && minp64 && num_valid && status,
+                 "dali_rank_eval_inp: null argument");
+    DALI_REQUIRE(nq > 0 && ng > 0, "dali_rank_eval_inp: bad shape nq=%d ng=%d", nq, ng);
+    hipStream_t st = (hipStream_t)stream;
+    float* ap_buf;
+    int32_t* fr_buf;
+    if (int rc = rank_queries<true>(ctx, st, distmat, q_pids, g_pids, q_camids, g_camids, nq, ng, nullptr, nullptr, last_rank, n_rel, status, ap_buf, fr_buf))
+        return rc;
+    hipLaunchKernelGGL(rank_inp_reduce_kernel, dim3(1), dim3(256), 0, st, last_rank, n_rel, nq, inp, minp64, num_valid);
     DALI_LAUNCH_CHECK();
     return DALI_OK;
 }

@@ -212,6 +212,126 @@ def rank_eval(distmat, q_pids, g_pids, q_camids, g_camids, max_rank=50, return_p
     return res
 
 
+def rank_eval_inp(distmat, q_pids, g_pids, q_camids, g_camids, return_per_query=False):
+    """mINP (mean inverse negative penalty) under ``rank_eval``'s protocol and key order (include/daliid.h, dali_rank_eval_inp): per query
+    INP = matches / (1-based position of the LAST match among the kept gallery entries); the mean over the valid queries, in fp64.
+    -> mINP float [, inp float32 [nq], last_rank int32 [nq] (0-based, -1 = invalid query), n_rel int32 [nq]] as numpy.  Raises what
+    ``rank_eval`` raises."""
+    dev = distmat.device
+    nq, ng = distmat.shape
+    qp, gp = factorize_ids(q_pids, g_pids)
+    qc, gc = factorize_ids(q_camids, g_camids)
+    qp, gp, qc, gc = (torch.from_numpy(a).to(dev) for a in (qp, gp, qc, gc))
+    inp = torch.empty(nq, device=dev, dtype=torch.float32)
+    last_rank = torch.empty(nq, device=dev, dtype=torch.int32)
+    n_rel = torch.empty(nq, device=dev, dtype=torch.int32)
+    minp64 = torch.empty(1, device=dev, dtype=torch.float64)
+    nvalid = torch.empty(1, device=dev, dtype=torch.int32)
+    status = torch.empty(1, device=dev, dtype=torch.int32)
+    _lib.check(_lib.lib().dali_rank_eval_inp(_lib.ctx(dev), _lib.stream_ptr(), _lib.ptr(distmat, torch.float32, "distmat"),
+                                              _lib.ptr(qp, torch.int32), _lib.ptr(gp, torch.int32), _lib.ptr(qc, torch.int32),
+                                              _lib.ptr(gc, torch.int32), nq, ng, _lib.ptr(inp), _lib.ptr(last_rank), _lib.ptr(n_rel),
+                                              _lib.ptr(minp64), _lib.ptr(nvalid), _lib.ptr(status)), "dali_rank_eval_inp")
+    st = int(status.item())
+    if st != 0:
+        raise _lib.DaliError("dali_rank_eval_inp: " + ("a query's identity has more than 4096 gallery entries (documented limit)" if st == 1 else
+                                                       "identity codes span more than 2^20 values (documented limit)"))
+    if int(nvalid.item()) == 0:
+        raise AssertionError("Error: all query identities do not appear in gallery")
+    minp = float(minp64.item())
+    if return_per_query:
+        return minp, inp.cpu().numpy(), last_rank.cpu().numpy(), n_rel.cpu().numpy()
+    return minp
+
+
+QE_ALPHA_MAX = 16         # integer exponents the combine kernel builds by repeated multiplication (include/daliid.h, dali_qe_combine)
+QE_TIMES_MAX = 8
+
+
+def _qe_alpha(alpha, who):
+    if isinstance(alpha, bool) or float(alpha) != int(alpha) or not 0 <= int(alpha) <= QE_ALPHA_MAX:
+        raise ValueError("%s: alpha=%r: only integer exponents 0..%d are built (non-integer exponents are not built)" % (who, alpha, QE_ALPHA_MAX))
+    return int(alpha)
+
+
+def _qe_combine(pool, idx, val, alpha, val_is_distance, out, status):
+    """dali_qe_combine on checked tensors; ``status`` (device int32 [1]) collects out-of-range indices and is not read here."""
+    n, k = idx.shape
+    if n > 0:
+        _lib.check(_lib.lib().dali_qe_combine(_lib.ctx(pool.device), _lib.stream_ptr(), _lib.ptr(pool, torch.float32, "pool"), pool.shape[0],
+                                              pool.shape[1], _lib.ptr(idx, torch.int32, "idx"), _lib.ptr(val, torch.float32, "val"), n, k,
+                                              int(bool(val_is_distance)), alpha, _lib.ptr(out, torch.float32, "out"), _lib.ptr(status)),
+                   "dali_qe_combine")
+    return out
+
+
+def qe_combine(pool, idx, val, alpha=3, val_is_distance=False, out=None):
+    """out[i] = (1 / k) * sum_j w_ij * pool[idx[i, j]], w = s ** alpha by repeated multiplication, s = val (or 1 - val for
+    ``val_is_distance``), in the fixed fp32 order of include/daliid.h (dali_qe_combine).  pool fp32 [n_pool, d], idx int32 [n, k],
+    val fp32 [n, k], all CUDA and contiguous; ``out`` fp32 [n, d] must not overlap ``pool``.  An index outside the pool is skipped by the
+    kernel and raises ``DaliError`` here (one read of the status word)."""
+    if pool.dim() != 2 or idx.dim() != 2 or val.dim() != 2:
+        raise ValueError("qe_combine: pool, idx and val must be 2-D")
+    if tuple(idx.shape) != tuple(val.shape):
+        raise ValueError("qe_combine: idx %s and val %s differ in shape" % (tuple(idx.shape), tuple(val.shape)))
+    alpha = _qe_alpha(alpha, "qe_combine")
+    if not pool.is_cuda or pool.dtype != torch.float32:
+        raise _lib.DaliError("qe_combine: pool must be a CUDA float32 tensor")
+    n, d = idx.shape[0], pool.shape[1]
+    if out is None:
+        out = torch.empty(n, d, device=pool.device, dtype=torch.float32)
+    elif tuple(out.shape) != (n, d):
+        raise ValueError("qe_combine: out must be [%d, %d], got %s" % (n, d, tuple(out.shape)))
+    status = torch.zeros(1, device=pool.device, dtype=torch.int32)
+    _qe_combine(pool, idx, val, alpha, val_is_distance, out, status)
+    if n > 0 and int(status.item()) != 0:
+        raise _lib.DaliError("dali_qe_combine: a neighbour index lies outside the pool of %d rows (its term was skipped)" % pool.shape[0])
+    return out
+
+
+def query_expansion(q, g, k=10, alpha=3.0, times=1, expand="all", precision="bf16x3"):
+    """Average / alpha-weighted query expansion and database augmentation without the (Nq + Ng)^2 similarity matrix: every feature row is
+    replaced by the mean of its k nearest rows (itself included) weighted by cosine similarity ** alpha, ``times`` times.
+    expand="all" (fast-reid's aqe): the pool is [q; g], every row is expanded, the result is split back at Nq.  expand="gallery" (DBA): the
+    pool is g, only gallery rows are expanded and ``q`` is returned as it came.  Each iteration: PreparedRows(feat, normalize=True) ->
+    pairdist_topk(P, P, k, "cosine") (ascending distance, ties by ascending index) -> dali_qe_combine on the UN-normalised current
+    features with weights (1 - distance) ** alpha.  Nothing synchronises inside the loop; the status word is read once at the end.
+    -> (q', g') fp32 CUDA tensors."""
+    who = "query_expansion"
+    if expand not in ("all", "gallery"):
+        raise ValueError("%s: expand must be 'all' or 'gallery', got %r" % (who, expand))
+    alpha = _qe_alpha(alpha, who)
+    if isinstance(times, bool) or int(times) != times or not 1 <= int(times) <= QE_TIMES_MAX:
+        raise ValueError("%s: times=%r outside 1..%d" % (who, times, QE_TIMES_MAX))
+    if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise ValueError("%s: q %s and g %s must be 2-D with one width" % (who, tuple(q.shape), tuple(g.shape)))
+    if not q.is_cuda or not g.is_cuda:
+        raise _lib.DaliError("%s: q and g must be CUDA tensors" % who)
+    nq = q.shape[0]
+    if expand == "all":
+        feat = torch.cat([q.to(torch.float32), g.to(torch.float32)])
+        own = [feat]                             # the two buffers that ping-pong; the caller's gallery is never one of them
+    else:
+        feat, own = g.to(torch.float32).contiguous(), []
+    if feat.shape[0] == 0:
+        raise ValueError("%s: nothing to expand (empty pool)" % who)
+    k = _topk_k(k, feat.shape[0], None, who)
+    status = torch.zeros(1, device=feat.device, dtype=torch.int32)
+    for _ in range(int(times)):
+        out = next((b for b in own if b is not feat), None)
+        if out is None:
+            out = torch.empty_like(feat)
+            own.append(out)
+        P = PreparedRows(feat, normalize=True, precision=precision)
+        dist, idx = pairdist_topk(P, P, k, metric="cosine")
+        feat = _qe_combine(feat, idx, dist, alpha, True, out, status)
+    if int(status.item()) != 0:
+        raise _lib.DaliError("dali_qe_combine: a neighbour index lies outside the pool (its term was skipped)")
+    if expand == "all":
+        return feat[:nq], feat[nq:]
+    return q, feat
+
+
 RANK_PMAX = 4096          # matches + junk of one query the ranking kernels hold in LDS (csrc/rank.hip)
 
 

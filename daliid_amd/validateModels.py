@@ -14,6 +14,8 @@ class validateModels:
     precision = "bf16x3"          # "bf16" trades ~1e-4 absolute distance error for ~2x distance throughput
     distmat_on_cpu = False        # the reference returns a CPU tensor (validateModels.py:58); 4 GB at config-5 size
     cam_label_of = view_label_of = None      # setSIE
+    query_expansion = None        # setQueryExpansion
+    report_minp = False           # True: calculateMetrics also computes mINP, prints it and leaves it in self.mINP
 
     def setParameters(self, img_height, img_width, rerank, gpu_index):
         self.img_height = img_height
@@ -25,6 +27,23 @@ class validateModels:
         """For a model with SIE embeddings: callables from a subset (the rows handed to ``validate`` / ``validate_sharded`` / ``retrieve``) to the integer camera /
         view label of every row.  Without this call nothing changes."""
         self.cam_label_of, self.view_label_of = cam_label_of, view_label_of
+
+    def setQueryExpansion(self, k=10, alpha=3.0, times=1, expand="all"):
+        """Query expansion (expand="all": AQE / alpha-QE over [queries; gallery]) or database augmentation (expand="gallery") of the
+        extracted features before ``distance`` in ``validate`` / ``retrieve`` / ``retrieve_features`` (ops_eval.query_expansion); with
+        ``rerank`` the three blocks are computed from the expanded features.  ``setQueryExpansion(None)`` switches it off.  Without this
+        call nothing changes."""
+        if k is None:
+            self.query_expansion = None
+            return
+        if expand not in ("all", "gallery"):
+            raise ValueError("setQueryExpansion: expand must be 'all' or 'gallery', got %r" % (expand,))
+        self.query_expansion = dict(k=k, alpha=alpha, times=times, expand=expand)
+
+    def _expand(self, queries_fvs, gallery_fvs):
+        if self.query_expansion is None:
+            return queries_fvs, gallery_fvs
+        return ops_eval.query_expansion(queries_fvs, gallery_fvs, precision=self.precision, **self.query_expansion)
 
     def _features(self, subset, model):
         side = {}
@@ -38,6 +57,7 @@ class validateModels:
         model.eval()
         queries_fvs = self._features(queries, model)
         gallery_fvs = self._features(gallery, model)
+        queries_fvs, gallery_fvs = self._expand(queries_fvs, gallery_fvs)
         distmat = self.distance(queries_fvs, gallery_fvs)
         if getattr(self, "rerank", False):
             # validateModels.py:49-53 (commented out in the reference): every block is the same cosine distance, so the three agree
@@ -64,6 +84,9 @@ class validateModels:
         if getattr(self, "rerank", False):   # raised on every rank before any collective
             raise NotImplementedError("validate_sharded: re-ranking needs every gallery row's neighbourhood on one device; "
                                       "use validate() for rerank=True")
+        if self.query_expansion is not None:   # likewise: on every rank, before any collective
+            raise NotImplementedError("validate_sharded: query expansion needs every row's neighbours on one device; "
+                                      "use validate(), or setQueryExpansion(None)")
         world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         rank = dist.get_rank(process_group) if dist.is_initialized() else 0
         model.eval()
@@ -96,6 +119,7 @@ class validateModels:
         return self.retrieve_features(queries_fvs, gallery_fvs, k)
 
     def retrieve_features(self, queries_fvs, gallery_fvs, k=50):
+        queries_fvs, gallery_fvs = self._expand(queries_fvs, gallery_fvs)
         distances, indices = ops_eval.pairdist_topk(queries_fvs.contiguous(), gallery_fvs.contiguous(), k, metric="cosine",
                                                     precision=self.precision, normalize=True)
         return indices, distances
@@ -111,6 +135,9 @@ class validateModels:
         cmc, mAP = ops_eval.rank_eval(distmat, queries[:, 1], gallery[:, 1], queries[:, 2], gallery[:, 2], max_rank=50)
         print('** Results **')
         print('mAP: {:.2%}'.format(mAP))
+        if self.report_minp:
+            self.mINP = ops_eval.rank_eval_inp(distmat, queries[:, 1], gallery[:, 1], queries[:, 2], gallery[:, 2])
+            print('mINP: {:.2%}'.format(self.mINP))
         print('Ranks:')
         for r in ranks:
             if r <= len(cmc):

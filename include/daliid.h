@@ -114,6 +114,20 @@ int dali_rank_eval(dali_ctx* ctx, void* stream, const float* distmat, const int3
                    int max_rank, float* cmc, float* mAP, double* map64, int32_t* num_valid,
                    float* ap, int32_t* first_rank, int32_t* status);
 
+/* mINP, the mean inverse negative penalty that AGW / fast-reid style evaluations report next to mAP and Rank-1, under the protocol,
+ * key order (distance, gallery index), limits and status codes of dali_rank_eval, whose inputs it takes.  Per query, among the kept
+ * gallery entries (junk removed):
+ *   n_rel[q]     int32: the number of matches;                 last_rank[q]  int32: 0-based position of the LAST match, -1 = invalid query
+ *   inp[q]       fp32 : (float)n_rel / (float)(last_rank + 1), one IEEE fp32 division; 0 for an invalid query
+ *   minp64[1]    fp64 : the mean over the valid queries of n_rel / (last_rank + 1) with the quotient taken in fp64 (not of the rounded
+ *                       fp32 inp), summed by one workgroup in a fixed order; 0 without a valid query
+ *   num_valid[1] int32: queries with at least one match after junk removal.
+ * The same two-tier query kernels as dali_rank_eval (which this call leaves bit for bit what it was), keeping the position on which
+ * their scan ends.  status[0] as for dali_rank_eval.  Nothing synchronises.  One GPU only: the sharded path has no such entry. */
+int dali_rank_eval_inp(dali_ctx* ctx, void* stream, const float* distmat, const int32_t* q_pids, const int32_t* g_pids,
+                       const int32_t* q_camids, const int32_t* g_camids, int nq, int ng, float* inp, int32_t* last_rank,
+                       int32_t* n_rel, double* minp64, int32_t* num_valid, int32_t* status);
+
 /* Gallery-sharded evaluation over N ranks (validateModels.py:41-47,61-69 with the gallery split across GPUs): each rank holds
  * dist_shard [nq][ng] = the distances of ALL queries to ITS gallery slice, whose first entry has global index g_offset.  Three calls with
  * two collectives of the caller's between them (the mirror: ops_eval.rank_eval_sharded over torch.distributed):
@@ -209,6 +223,28 @@ size_t dali_pairdist_topk_scratch_bytes(int nq, int ng, int d, int k, int boot_c
 int dali_pairdist_topk(dali_ctx* ctx, void* stream, const void* q_image, const float* q_sq, const void* g_image, const float* g_sq,
                        int nq, int ng, int d, int metric, int precision, int k, int largest, int g_offset, int accumulate,
                        int64_t* keys, int boot_cols, int chunk_cols, int cand_cap, int32_t* stats);
+
+/* Query expansion (AQE / alpha-QE) and database augmentation (DBA): the gather-and-combine step.  Every output row is the weighted mean
+ * of k pool rows, the neighbour lists being those of dali_pairdist_topk (so no similarity matrix exists at any size); the mirror's
+ * ops_eval.query_expansion composes prepare -> top-k -> combine, `times` times.
+ *   pool [n_pool][d] fp32   the rows that are gathered (the un-normalised current features)
+ *   idx  [n][k] int32, val [n][k] fp32   row-major neighbour lists; val is a similarity, or a cosine distance when val_is_distance != 0
+ *   out  [n][d] fp32        must not overlap pool (address ranges are compared: DALI_ERR_INVALID)
+ * THE ARITHMETIC, every operation an IEEE fp32 operation rounded to nearest, no fused multiply-add, in this order (a numpy float32
+ * emulation reproduces it bit for bit).  For row i, element c:
+ *   s_j = val_is_distance ? 1.0f - val[i][j] : val[i][j]
+ *   w_j = 1.0f when alpha == 0, else ((s_j * s_j) * s_j) ...         alpha - 1 multiplications, left to right (a negative similarity
+ *                                                                    keeps its sign for odd alpha: no clamp, no powf)
+ *   acc = 0.0f;  for j = 0 .. k-1 ascending:  acc = acc + (w_j * pool[idx[i][j]][c])
+ *   out[i][c] = acc * (1.0f / (float)k)                              the reciprocal rounded once
+ * An index < 0 or >= n_pool is never dereferenced: its term is skipped (the divisor stays k) and status[0] (device int32) is raised to 1
+ * with atomicMax.  The call never clears status: the caller zeroes it, and one word may collect several calls.
+ * Refused before any launch (DALI_ERR_INVALID, the message names the value): k < 1, k > 128, alpha outside 0..16, d < 1, a null
+ * pointer, out overlapping pool, and n_pool < 1 with n > 0.  n == 0 launches nothing.  Rows are read 16 bytes per lane when d % 4 == 0
+ * and pool and out are 16-byte aligned, 4 bytes per lane otherwise (4-byte alignment is required).  No atomics on out: bitwise
+ * identical results run to run.  Nothing synchronises; no workspace. */
+int dali_qe_combine(dali_ctx* ctx, void* stream, const float* pool, int n_pool, int d, const int32_t* idx, const float* val, int n, int k,
+                    int val_is_distance, int alpha, float* out, int32_t* status);
 
 /* Weibull meta-recognition score fusion: libmr.FitHigh / libmr.wscore and Meta_Recognition.metarec / mrfuse (evaluate.py:394-627), the
  * `1.0 - meta_rec.mrfuse(1 - d_backbone, 1 - d_head01, 1 - d_head02)` line evaluate.py:277 leaves commented out.  Every gallery column of a
