@@ -10,6 +10,7 @@
 // head = global avg-pool + global max-pool -> BatchNorm1d.
 #include "kernels.h"
 #include "plan_table.h"
+#include "../../include/daliid_debug.h"
 #include <cstring>
 #include <new>
 
@@ -97,6 +98,10 @@ struct dali_resnet : PlanTable {
     uint16_t* dbg_d_raw0 = nullptr;          // where the last stem backward left d(raw0) (scratch: valid until the next backward runs)
     bool fwd_training = false;
     int feature_mode = DALI_FEATURE_BOTH;
+    // diagnostics (dali_debug_resnet_backward_block_snap): where snap_keep copies the backward's intermediates; null in every other call
+    char* snap = nullptr;
+    int64_t snap_cap = 0, snap_used = 0;
+    int64_t* snap_offsets = nullptr;
 };
 
 namespace {
@@ -441,6 +446,22 @@ int cat_gemm(dali_resnet* net, hipStream_t st, const Conv& c, int mode, const ui
     return launch_igemm_conv(st, a);
 }
 
+// Diagnostics: while dali_debug_resnet_backward_block_snap runs, keep a copy of an intermediate that the backward overwrites later (device to
+// device, on the launches' own stream, right after the launch that produced it).  In every other call net->snap is null and this returns at once.
+int snap_keep(dali_resnet* net, hipStream_t st, int slot, const void* src, size_t bytes) {
+    if (!net->snap) return DALI_OK;
+    const int64_t off = (int64_t)align_up((size_t)net->snap_used, 256);
+    if (off + (int64_t)bytes > net->snap_cap) {
+        set_error("dali_debug_resnet_backward_block_snap: snapshot buffer too small (slot %d needs bytes %lld .. %lld of %lld)", slot, (long long)off,
+                  (long long)(off + (int64_t)bytes), (long long)net->snap_cap);
+        return DALI_ERR_INVALID;
+    }
+    DALI_HIP(hipMemcpyAsync(net->snap + off, src, bytes, hipMemcpyDeviceToDevice, st));
+    net->snap_offsets[slot] = off;
+    net->snap_used = off + (int64_t)bytes;
+    return DALI_OK;
+}
+
 // The moments of x, the input of the 1x1 convolution c: gram = x^T x with m2 = colsum(x) on the same GEMM; from them the batch statistics of
 // bn(c(x)) (l.stats) or only Ut for the backward
 int linbn_fwd(dali_resnet* net, hipStream_t st, LinBn& l, const Conv& c, Bn& bn, const uint16_t* x) {
@@ -454,10 +475,12 @@ int linbn_fwd(dali_resnet* net, hipStream_t st, LinBn& l, const Conv& c, Bn& bn,
 }
 // G0 = dz^T x into c's gradient slot (with s_dz = colsum(dz) on the GEMM when sum_dz, else s_dz is read), finished in place by the row kernel
 // together with dgamma / dbeta, the data-gradient image l.wd and l.bvec
-int linbn_bwd(dali_resnet* net, hipStream_t st, LinBn& l, const Conv& c, const Bn& bn, const uint16_t* dz, const uint16_t* x, float* s_dz, bool sum_dz) {
+int linbn_bwd(dali_resnet* net, hipStream_t st, LinBn& l, const Conv& c, const Bn& bn, const uint16_t* dz, const uint16_t* x, float* s_dz, bool sum_dz,
+              int snap_slot) {
     const WGradDesc d = conv_wgrad_desc(net, c);
     int rc;
     if ((rc = run_wgrad(net, st, d, dz, x, net->G + c.w_off, sum_dz ? s_dz : nullptr))) return rc;
+    if ((rc = snap_keep(net, st, snap_slot, net->G + c.w_off, (size_t)l.C * l.w * 4))) return rc;
     const int ld = l.C + l.w;
     return launch_bnlin_bwd(st, c.w_bf16, c.wt_bf16, l.ut, l.m2, s_dz, l.C, l.w, (double)d.P, bn.scale, bn.mean, bn.invstd, net->G + c.w_off, net->G + bn.g_off,
                             net->G + bn.b_off, l.wd, l.wd + l.C, l.bvec, l.qk, ld, ld);
@@ -641,7 +664,7 @@ static int block_backward(dali_resnet* net, hipStream_t st, Block& b, const uint
     uint16_t* d_rawd = nullptr;
     // bn3 + conv3 through the moments of a2 (bnlin.hip): no reduce / apply passes over [P][cout] tensors, conv3's raw output does not exist.
     // G0 = dz^T a2 goes into the gradient slot with s = colsum(dz) riding on the GEMM
-    if ((rc = linbn_bwd(net, st, b.l3, b.c3, b.b3, dz, b.a2, b.sdz, true))) return rc;
+    if ((rc = linbn_bwd(net, st, b.l3, b.c3, b.b3, dz, b.a2, b.sdz, true, DALI_SNAP_G0_CONV3))) return rc;
     uint16_t* d_a2 = next_gbuf(net, dz);
     uint16_t* scratch_a = next_gbuf(net, dz, d_a2);
     {   // d_a2 = dz (A.W3) + W3^T Kc - a2 (W3^T diag(Q) W3) as ONE GEMM over K = cout + w: [dz | a2] against the concatenated image
@@ -649,23 +672,28 @@ static int block_backward(dali_resnet* net, hipStream_t st, Block& b, const uint
         IGemmArgs stage{};
         stage.bias = b.l3.bvec;
         if ((rc = cat_gemm(net, st, b.c3, 1, b.l3.wd, dz, b.cout, b.a2, b.width, b.width, d_a2, stage))) return rc;
+        if ((rc = snap_keep(net, st, DALI_SNAP_D_A2, d_a2, (size_t)Pout * b.width * 2))) return rc;
     }
     if (b.lin_ds) {
         // downsample branch through the moments of x: G0d = dz^T x into the gradient slot (s = colsum(dz) is bn3's), finished in place by the row
         // kernel together with dgamma / dbeta and the two data-gradient images; the data gradient itself follows conv1's below
-        if ((rc = linbn_bwd(net, st, b.ld, b.cd, b.bd, dz, b.x, b.sdz, false))) return rc;
+        if ((rc = linbn_bwd(net, st, b.ld, b.cd, b.bd, dz, b.x, b.sdz, false, DALI_SNAP_G0_DS))) return rc;
     } else if (b.has_ds) {                                    // the downsample BatchNorm: its own two passes over (dz, rawd)
         d_rawd = next_gbuf(net, dz, d_a2, scratch_a);
         if ((rc = bn_bwd(net, st, b.bd, b.rawd, dz, 0, Pout, d_rawd))) return rc;
+        if ((rc = snap_keep(net, st, DALI_SNAP_D_RAWD, d_rawd, (size_t)Pout * b.cout * 2))) return rc;
     }
     // bn2 + relu, in place.  The ReLU mask is recomputed from raw2 (raw*scale+shift > 0 <=> a2 > 0: bf16 rounding cannot
     // flush a positive fp32 to zero) instead of reading a2: one tensor read less in each of the two passes.
     if ((rc = bn_bwd(net, st, b.b2, b.raw2, d_a2, 1, Pout, d_a2))) return rc;
+    if ((rc = snap_keep(net, st, DALI_SNAP_D_RAW2, d_a2, (size_t)Pout * b.width * 2))) return rc;
     // conv2
     if ((rc = conv_wgrad(net, st, b.c2, b.a1, d_a2))) return rc;
     uint16_t* d_a1 = scratch_a;
     if ((rc = conv_dgrad(net, st, b.c2, d_a2, nullptr, d_a1))) return rc;
+    if ((rc = snap_keep(net, st, DALI_SNAP_D_A1, d_a1, (size_t)Pin * b.width * 2))) return rc;
     if ((rc = bn_bwd(net, st, b.b1, b.raw1, d_a1, 1, Pin, d_a1))) return rc;
+    if ((rc = snap_keep(net, st, DALI_SNAP_D_RAW1, d_a1, (size_t)Pin * b.width * 2))) return rc;
     b.dbg_d_raw1 = d_a1;
     // conv1 (+ identity / downsample branch); the result is masked with the previous block's ReLU bits
     if ((rc = conv_wgrad(net, st, b.c1, b.x, d_a1))) return rc;
@@ -673,6 +701,7 @@ static int block_backward(dali_resnet* net, hipStream_t st, Block& b, const uint
     if (b.lin_ds) {
         // dx = d_a1 W1 + [dz | x] [(A_d.Wd)^T | -(Wd^T diag(Q_d) Wd)] + Wd^T Kc: conv1's data gradient, then the branch's two-operand GEMM on top of it
         if ((rc = conv_dgrad(net, st, b.c1, d_a1, nullptr, dx, prev_bits))) return rc;
+        if ((rc = snap_keep(net, st, DALI_SNAP_DX_CONV1, dx, (size_t)Pin * b.cin * 2))) return rc;
         IGemmArgs stage{};
         stage.Res = dx; stage.bias = b.ld.bvec;
         if ((rc = cat_gemm(net, st, b.cd, 1, b.ld.wd, dz, b.cout, b.x, b.cin, b.cin, dx, stage))) return rc;
@@ -682,6 +711,7 @@ static int block_backward(dali_resnet* net, hipStream_t st, Block& b, const uint
         // even-even quarter of the positions receives a contribution (launch_igemm_conv's parity split).  (a + b) * m = a * m + b * m:
         // both launches apply the mask.
         if ((rc = conv_dgrad(net, st, b.c1, d_a1, nullptr, dx, prev_bits))) return rc;
+        if ((rc = snap_keep(net, st, DALI_SNAP_DX_CONV1, dx, (size_t)Pin * b.cin * 2))) return rc;
         if ((rc = conv_dgrad(net, st, b.cd, d_rawd, dx, dx, prev_bits))) return rc;
     } else {
         if ((rc = conv_dgrad(net, st, b.c1, d_a1, dz, dx, prev_bits))) return rc;             // identity path: + dz
@@ -700,7 +730,7 @@ static int head_backward(dali_resnet* net, hipStream_t st, const float* d_emb) {
     if ((rc = launch_head_pool_bwd(st, net->dfeat, net->head_arg, net->N, net->head_hw, net->feat_dim, net->feature_mode, net->cur_dy,
                                    net->blocks.back().ybits))) return rc;
     net->cur_dy_bytes = (int64_t)net->N * net->head_hw * net->feat_dim * 2;
-    return DALI_OK;
+    return snap_keep(net, st, DALI_SNAP_HEAD_DZ, net->cur_dy, (size_t)net->cur_dy_bytes);
 }
 
 // maxpool + stem BN backward, then the stem weight gradient (no data gradient: images need none)
@@ -711,7 +741,9 @@ static int stem_backward(dali_resnet* net, hipStream_t st) {
                                     net->N, net->stem_h, net->stem_w, net->stem.cout, net->bwd_partial, net->stem_bn.coef,
                                     net->G + net->stem_bn.g_off, net->G + net->stem_bn.b_off, d_raw0, net->red_scratch))) return rc;
     net->dbg_d_raw0 = d_raw0;
+    if ((rc = snap_keep(net, st, DALI_SNAP_D_RAW0, d_raw0, (size_t)net->N * net->stem_h * net->stem_w * net->stem.cout * 2))) return rc;
     if ((rc = run_wgrad(net, st, stem_wgrad_desc(net), d_raw0, net->ximg, net->stem_dw_pad))) return rc;
+    if ((rc = snap_keep(net, st, DALI_SNAP_STEM_DW_PAD, net->stem_dw_pad, (size_t)net->stem.cout * 224 * 4))) return rc;
     return launch_stem_unpack_wgrad(st, net->stem_dw_pad, net->stem.cout, net->G + net->stem.w_off);
 }
 
@@ -741,7 +773,7 @@ extern "C" int dali_resnet_backward(dali_resnet* net, void* stream, const float*
 // Diagnostic (include/daliid_debug.h): the backward pass ONE bottleneck at a time, so that a test can read the gradient entering every block
 // (`grad_cur` of dali_resnet_debug_tensor) instead of one per stage.  Call with block = last block first (that call also runs the neck + head
 // backward from d_emb), then block - 1, ... down to 0, then -1 (the stem); same launches, same order as dali_resnet_backward.
-extern "C" int dali_debug_resnet_backward_block(dali_resnet* net, void* stream, const float* d_emb, int block) {
+static int debug_backward_block(dali_resnet* net, void* stream, const float* d_emb, int block) {
     DALI_REQUIRE(net, "dali_debug_resnet_backward_block: null net");
     if (net->eval_only) return eval_only_error("dali_debug_resnet_backward_block");
     DALI_REQUIRE(net->P && net->G, "dali_debug_resnet_backward_block: net not bound (grads required)");
@@ -757,9 +789,27 @@ extern "C" int dali_debug_resnet_backward_block(dali_resnet* net, void* stream, 
     }
     return block_backward(net, st, net->blocks[block], block > 0 ? net->blocks[block - 1].ybits : nullptr);
 }
+extern "C" int dali_debug_resnet_backward_block(dali_resnet* net, void* stream, const float* d_emb, int block) {
+    return debug_backward_block(net, stream, d_emb, block);
+}
+// Diagnostic (include/daliid_debug.h): the same call with snap_keep switched on: the backward's in-place intermediates are copied into `snap` as
+// they are produced (offsets[DALI_SNAP_*]: where, or -1)
+extern "C" int dali_debug_resnet_backward_block_snap(dali_resnet* net, void* stream, const float* d_emb, int block, void* snap, int64_t snap_bytes,
+                                                      int64_t* offsets) {
+    DALI_REQUIRE(net && snap && offsets && snap_bytes > 0, "dali_debug_resnet_backward_block_snap: null argument");
+    for (int i = 0; i < DALI_SNAP_COUNT; ++i) offsets[i] = -1;
+    net->snap = static_cast<char*>(snap); net->snap_cap = snap_bytes; net->snap_used = 0; net->snap_offsets = offsets;
+    const int rc = debug_backward_block(net, stream, d_emb, block);
+    net->snap = nullptr; net->snap_cap = 0; net->snap_offsets = nullptr;
+    return rc;
+}
 
 // Debug/inspection: device pointer + byte size of a named intermediate (valid after a forward).
-// Names: raw0, pool0, feat, grad_cur (gradient wrt the input of the last block processed by backward), block<i>.{raw1,a1,raw2,rawd,y,d_raw1},
+// Names: raw0, pool0, pool_arg (uint8, the max-pool's tap), feat, head_arg (int16), neck.{mean,invstd}, dfeat (after a backward's head call),
+// grad_cur (gradient wrt the input of the last block processed by backward), block<i>.{raw1,a1,raw2,a2,rawd,y,d_raw1}, of a training plan
+// block<i>.ybits (the ReLU mask of y, one bit per element), block<i>.sdz (colsum(dz), after the block's backward) and the moments scheme's
+// block<i>.l3.{gram,m2,ut,wd,bvec,qk} (LinBn; wd, bvec, qk after the block's backward), the same under block<i>.ld. where the downsample
+// branch's backward runs through the moments of x,
 // for an IBN block block<i>.in1.{mean,invstd} (fp32 [N][width / 2], of the last forward), block<i>.bn{1,2,3,d}.{scale,shift,mean,invstd}, bn1.{...};
 // ximg (packed image bf16 [N][H+6][W+8][4]), w_stem (bf16 [Cout][7][8][4]), d_raw0 (after a stem backward); the weight images block<i>.conv{1,2,3,d}.w
 // (bf16 [cout][r][s][cin]) and .wt (bf16 [cin][r*s][cout]), and, where the inference forward folds conv3 + downsample into one GEMM,
@@ -777,6 +827,11 @@ extern "C" int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void
     if (n == "raw0") { *ptr = net->raw0; *bytes = (int64_t)(N * net->stem_h * net->stem_w * net->stem.cout * 2); return DALI_OK; }
     if (n == "pool0") { *ptr = net->pool0; *bytes = (int64_t)(N * net->pool_h * net->pool_w * net->stem.cout * 2); return DALI_OK; }
     if (n == "grad_cur" && net->cur_dy) { *ptr = net->cur_dy; *bytes = net->cur_dy_bytes; return DALI_OK; }
+    if (n == "pool_arg") { *ptr = net->pool_arg; *bytes = (int64_t)(N * net->pool_h * net->pool_w * net->stem.cout); return DALI_OK; }
+    if (n == "head_arg") { *ptr = net->head_arg; *bytes = (int64_t)(N * net->feat_dim * 2); return DALI_OK; }
+    if (n == "neck.mean") { *ptr = net->neck_mean; *bytes = (int64_t)net->feat_dim * 4; return DALI_OK; }
+    if (n == "neck.invstd") { *ptr = net->neck_invstd; *bytes = (int64_t)net->feat_dim * 4; return DALI_OK; }
+    if (n == "dfeat" && net->dfeat) { *ptr = net->dfeat; *bytes = (int64_t)(N * net->feat_dim * 4); return DALI_OK; }
     if (n == "feat") { *ptr = net->feat; *bytes = (int64_t)(N * net->feat_dim * 4); return DALI_OK; }
     if (n == "ximg") { *ptr = net->ximg; *bytes = (int64_t)(N * (net->H + 6) * (net->W + 8) * 4 * 2); return DALI_OK; }
     if (n == "w_stem") { *ptr = net->w_stem; *bytes = (int64_t)net->stem.cout * 224 * 2; return DALI_OK; }
@@ -790,6 +845,22 @@ extern "C" int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void
                 Block& b = net->blocks[bi];
                 const std::string f = n.substr(dot + 1);
                 const size_t pin = N * b.hin * b.win, pout = N * b.hout * b.wout;
+                if (f == "a2") { *ptr = b.a2; *bytes = (int64_t)(pout * b.width * 2); return DALI_OK; }
+                if (f == "ybits" && b.ybits) { *ptr = b.ybits; *bytes = (int64_t)(pout * b.cout / 8); return DALI_OK; }
+                if (f == "sdz" && b.sdz) { *ptr = b.sdz; *bytes = (int64_t)b.cout * 4; return DALI_OK; }
+                if ((f.rfind("l3.", 0) == 0 || f.rfind("ld.", 0) == 0) && (f[1] == '3' ? b.l3.gram != nullptr : (b.lin_ds && b.ld.gram != nullptr))) {
+                    const LinBn& l = f[1] == '3' ? b.l3 : b.ld;
+                    const std::string q = f.substr(3);
+                    const int64_t w = l.w, C = l.C;
+                    void* p = nullptr; int64_t nb = 0;
+                    if (q == "gram") { p = l.gram; nb = w * w * 4; }
+                    else if (q == "m2") { p = l.m2; nb = w * 4; }
+                    else if (q == "ut") { p = l.ut; nb = w * C * 4; }
+                    else if (q == "wd") { p = l.wd; nb = w * (C + w) * 2; }
+                    else if (q == "bvec") { p = l.bvec; nb = w * 4; }
+                    else if (q == "qk") { p = l.qk; nb = C * 8; }
+                    if (p) { *ptr = p; *bytes = nb; return DALI_OK; }
+                }
                 if (f == "a1") { *ptr = b.a1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }
                 if (f == "in1.mean" && b.ibn) { *ptr = b.in_mean; *bytes = (int64_t)(N * b.c_in * 4); return DALI_OK; }
                 if (f == "in1.invstd" && b.ibn) { *ptr = b.in_invstd; *bytes = (int64_t)(N * b.c_in * 4); return DALI_OK; }

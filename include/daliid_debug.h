@@ -55,6 +55,28 @@ int dali_debug_splitk_reduce(void* stream, const float* partial, float* out, lon
  * in the same order as dali_resnet_backward (tests/test_gpu_resnet_blocks.py, the batch-256 composition check) */
 struct dali_resnet;
 int dali_debug_resnet_backward_block(struct dali_resnet* net, void* stream, const float* d_emb, int block);
+/* The same call (same helper, same launches, same order) that also KEEPS the intermediates which the backward overwrites in place (d_a2 becomes
+ * d_raw2 and then dx; G0 = dz^T a2 is finished inside the gradient slot): each one is copied, device to device on the same stream right after
+ * the launch that produces it, into `snap` (device memory, snap_bytes long).  offsets[slot] receives the byte offset of the copy inside snap
+ * (256-byte aligned), or -1 where this call does not produce that tensor.  Sizes are those of the tensor: bf16 [pixels][channels] for the
+ * activations' gradients, fp32 [cout][cin] for an unfinished G0, fp32 [Cout][224] for the padded stem weight gradient.
+ * DALI_ERR_INVALID when snap is too small (nothing after the tensor that did not fit is meaningful) (tests/test_gpu_resnet_plan.py) */
+enum {
+    DALI_SNAP_D_A2 = 0,         /* output of the [dz | a2] GEMM: the gradient of a2 */
+    DALI_SNAP_D_RAW2,           /* after bn2 + ReLU backward */
+    DALI_SNAP_D_A1,             /* conv2's data gradient */
+    DALI_SNAP_D_RAW1,           /* after bn1 + ReLU backward */
+    DALI_SNAP_D_RAWD,           /* downsample BatchNorm backward (blocks with a branch that does not run through the moments of x) */
+    DALI_SNAP_DX_CONV1,         /* dx after conv1's data gradient, before the downsample branch accumulates into it (blocks with a branch) */
+    DALI_SNAP_G0_CONV3,         /* dz^T a2 as the weight-gradient GEMM leaves it in conv3's gradient slot */
+    DALI_SNAP_G0_DS,            /* dz^T x in the downsample convolution's slot (the net's first block: branch through the moments of x) */
+    DALI_SNAP_D_RAW0,           /* block = -1: the stem's d(raw0) */
+    DALI_SNAP_STEM_DW_PAD,      /* block = -1: the stem weight gradient on the padded [Cout][7][8][4] layout, before the unpack */
+    DALI_SNAP_HEAD_DZ,          /* last block: the masked gradient of the last block's output, as the head pooling's backward leaves it */
+    DALI_SNAP_COUNT
+};
+int dali_debug_resnet_backward_block_snap(struct dali_resnet* net, void* stream, const float* d_emb, int block, void* snap, int64_t snap_bytes,
+                                          int64_t* offsets);
 
 /* the ViT plan's backward ONE piece at a time: block = depth runs the head only (neck, final LayerNorm on the cls rows, memset + scatter of
  * their gradient into the token gradient), depth-1 .. 0 runs that one transformer block, -1 the token tail (assemble_tokens_bwd, the patch

@@ -18,6 +18,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from resnet_checks import _assert_within, _bn1d_check_y, _draw_bound_check, _pack_bits, _ulp      # shared with tests/test_gpu_resnet_plan.py
 from vit_checks import check_bn1d_bwd, check_layernorm_fwd
 
 pytestmark = pytest.mark.gpu
@@ -59,28 +60,8 @@ def _dev(t):
     return t.cuda().to(bf16)
 
 
-def _pack_bits(b):
-    """bool [.., 8k] -> bytes: bit t of byte i = b.flatten()[8i + t] (the kernels' mask layout)"""
-    w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=b.device)
-    return (b.reshape(-1, 8).to(torch.uint8) * w).sum(1, dtype=torch.uint8)
-
-
-def _ulp(a):
-    """fp32 ulp of |a| (float64 numpy in and out)"""
-    return np.spacing(np.abs(np.asarray(a, dtype=np.float64)).astype(np.float32)).astype(np.float64)
-
-
 def _rows(P, C):
     return max(1, CHUNK // C)
-
-
-def _assert_within(got, ref, bound, what):
-    err = (got - ref).abs()
-    bad = err > bound
-    if bad.any():
-        i = int(torch.argmax((err - bound).flatten()))
-        raise AssertionError("%s: %d elements off; worst at %d: got %r, ref %r, bound %r" % (
-            what, int(bad.sum()), i, float(got.flatten()[i]), float(ref.flatten()[i]), float(bound.flatten()[i])))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -348,23 +329,6 @@ def test_bn_act_plan_sizes(nn, shape):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 5: BatchNorm backward (single / dual, three mask sources)
 # ---------------------------------------------------------------------------------------------------------------------------
-def _draw_bound_check(got, dz, raw, mean, invstd, scale, S1, S2, N, what):
-    """draw against the unfolded fp64 formula  scale * (dz - S1/N - xhat * S2/N),  xhat = (raw - mean) * invstd.
-    The kernel computes the folded form  o = A*dz + K - Q*raw  (FinBnBwd: A = scale, Q = fp32(scale*invstd*S2/N),
-    K = fp32(Q64*mean - scale*S1/N), both rounded once from fp64), in fp32 without contraction, then rounds o to bf16:
-      A*dz exact (power-of-two scale, integer dz);  rounding K, Q: u|K|, u|Q*raw|;  the add: u(|A dz| + |K|);
-      Q*raw: u|Q*raw|;  the subtraction: u(|A dz| + |K| + |Q raw|)   ->  |o - draw64| <= E = 2u(|A dz| + 2|K| + 2|Q raw|)
-      bf16(o): within HB|o| <= HB(|draw64| + E)                 ->  |out - draw64| <= HB|draw64| + (1 + HB) E"""
-    scale64 = scale.double()
-    q = scale64 * invstd.double() * (S2 / N)
-    K = q * mean.double() - scale64 * (S1 / N)
-    dzd = dz.double()
-    rawd = raw.double()
-    ref = scale64 * (dzd - S1 / N - (rawd - mean.double()) * invstd.double() * (S2 / N))
-    E = 2 * U * ((scale64 * dzd).abs() + 2 * K.abs() + 2 * (q * rawd).abs())
-    _assert_within(got.double(), ref, HB * ref.abs() + (1 + HB) * E, what)
-
-
 def _check_bwd_full(out, d, sums, what):
     _check_bwd_sums(out, d, sums, what)
     P, C = d["P"], d["C"]
@@ -540,14 +504,6 @@ def _bn1d_inputs(N, C, key):
     beta = torch.randn(C, generator=g)
     rm, rv = _ints(-2, 2, (C,), g).float(), _ints(1, 6, (C,), g).float()     # integers: (1 - MOM) * r is exact
     return g, x, gamma, beta, rm, rv
-
-
-def _bn1d_check_y(y, x, mean, inv, gamma, beta, what):
-    """y = x*sc + sh, sc = fp32(gamma*invstd), sh = fp32(beta - mean*sc): counting the roundings of invstd (<= 2.5u in eval, 1u in
-    training), sc, mean, both products, sh and the sum gives <= 8u (|x sc| + |mean sc| + |beta|)"""
-    sc = gamma.double() * inv
-    ref = x.double() * sc + (beta.double() - mean * sc)
-    _assert_within(y.cpu().double(), ref, 8 * U * ((x.double() * sc).abs() + (mean * sc).abs() + beta.double().abs()), what)
 
 
 @pytest.mark.parametrize("shape", [(256, 2048), (37, 2040)], ids=["256x2048", "37x2040_ragged"])
