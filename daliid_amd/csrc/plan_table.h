@@ -1,22 +1,24 @@
 // plan_table.h -- what the net plans (resnet_plan.hip, vit_plan.hip) share: the table of named tensors in the flat fp32 parameter / buffer
-// storages, and the byte arena whose offsets become pointers at bind().
+// storages, and the table of named tensors in the byte arena, whose offsets become pointers at bind().
 #pragma once
 #include "common.h"
 #include <cstdio>
 #include <initializer_list>
 #include <string>
-#include <utility>
 #include <vector>
 
 namespace dali {
 
 struct TensorInfo { std::string name; int64_t offset, numel; int shape[4]; int ndim; };
+// A named tensor of the arena.  offset >= 0: reserved, bind_arena sets *slot = arena + offset.  offset -1: a view, a name for storage that lies
+// inside a reserved tensor; whoever aliases it sets the slot.  A slot that is (still) null: this plan does not hold the tensor.
+struct ArenaEntry { std::string name; void** slot; int64_t offset; size_t bytes; };
 
 struct PlanTable {
     std::vector<TensorInfo> params, buffers;
     int64_t param_elems = 0, buffer_elems = 0;
     size_t arena_bytes = 0;
-    std::vector<std::pair<void**, size_t>> fixups;       // arena offsets, resolved by bind_arena
+    std::vector<ArenaEntry> arena_entries;               // every arena tensor is declared once, here: name, pointer and size
 
     // appends a tensor to `v` (params with param_elems, buffers with buffer_elems); returns its element offset
     static int64_t add_tensor(std::vector<TensorInfo>& v, int64_t& total, const std::string& name, std::initializer_list<int> shape) {
@@ -37,11 +39,13 @@ struct PlanTable {
 
     // `bytes` of the arena (256-byte aligned) for ptr, which bind_arena sets
     template <class T>
-    void reserve(T*& ptr, size_t bytes) {
-        fixups.emplace_back(reinterpret_cast<void**>(&ptr), arena_bytes);
+    void reserve(const std::string& name, T*& ptr, size_t bytes) {
+        arena_entries.push_back({name, reinterpret_cast<void**>(&ptr), (int64_t)arena_bytes, bytes});
         arena_bytes = align_up(arena_bytes + bytes, 256);
     }
-    void bind_arena(char* arena) { for (auto& f : fixups) *f.first = arena + f.second; }
+    template <class T>
+    void view(const std::string& name, T*& ptr, size_t bytes) { arena_entries.push_back({name, reinterpret_cast<void**>(&ptr), -1, bytes}); }
+    void bind_arena(char* arena) { for (auto& e : arena_entries) if (e.offset >= 0) *e.slot = arena + e.offset; }
 
     // the bodies of dali_*_sizes and dali_*_tensor_info
     int sizes(int feat, int64_t* param_elems_out, int64_t* buffer_elems_out, int64_t* arena_bytes_out, int* feat_dim, int* n_params, int* n_buffers) const {
@@ -61,6 +65,21 @@ struct PlanTable {
         snprintf(name, name_cap, "%s", t.name.c_str());
         *offset = t.offset; *numel = t.numel; *ndim = t.ndim;
         for (int i = 0; i < 4; ++i) shape4[i] = t.shape[i];
+        return DALI_OK;
+    }
+    // the bodies of dali_*_debug_tensor and dali_debug_*_arena_entry
+    int arena_tensor(const char* who, const char* name, void** ptr, int64_t* bytes) const {
+        for (const ArenaEntry& e : arena_entries)
+            if (e.name == name && *e.slot) { *ptr = *e.slot; *bytes = (int64_t)e.bytes; return DALI_OK; }
+        set_error("%s: unknown tensor '%s', or one this plan does not hold", who, name);
+        return DALI_ERR_INVALID;
+    }
+    int arena_entry(const char* who, int index, char* name, int name_cap, int64_t* offset, int64_t* bytes, int* reserved) const {
+        DALI_REQUIRE(name && offset && bytes && reserved, "%s: null argument", who);
+        DALI_REQUIRE(index >= 0 && index < (int)arena_entries.size(), "%s: index %d out of range", who, index);
+        const ArenaEntry& e = arena_entries[index];
+        snprintf(name, name_cap, "%s", e.name.c_str());
+        *offset = e.offset; *bytes = (int64_t)e.bytes; *reserved = e.offset >= 0;
         return DALI_OK;
     }
 };

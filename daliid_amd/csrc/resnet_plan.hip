@@ -12,6 +12,7 @@
 #include "plan_table.h"
 #include "../../include/daliid_debug.h"
 #include <cstring>
+#include <memory>
 #include <new>
 
 using namespace dali;
@@ -65,8 +66,9 @@ struct Block {
     float *in_mean = nullptr, *in_invstd = nullptr;            // [N][c_in], what the last forward's dali_ibn_act launch saw
     uint16_t* dbg_d_raw1 = nullptr;                            // where the last backward of this block left d(raw1) (scratch: valid until the next block runs)
 };
-template <class F> void for_each_conv(Block& b, F f) { f(b.c1); f(b.c2); f(b.c3); if (b.has_ds) f(b.cd); }
-template <class F> void for_each_bn(Block& b, F f) { f(b.b1); f(b.b2); f(b.b3); if (b.has_ds) f(b.bd); }
+// f(layer, its name inside the block's arena names)
+template <class F> void for_each_conv(Block& b, F f) { f(b.c1, "conv1"); f(b.c2, "conv2"); f(b.c3, "conv3"); if (b.has_ds) f(b.cd, "convd"); }
+template <class F> void for_each_bn(Block& b, F f) { f(b.b1, "bn1"); f(b.b2, "bn2"); f(b.b3, "bn3"); if (b.has_ds) f(b.bd, "bnd"); }
 
 }  // namespace
 
@@ -132,18 +134,19 @@ void add_ibn(dali_resnet* net, Block& b, const std::string& name, int C) {
     bn.rm_off = net->add_buffer(name + ".BN.running_mean", {C - b.c_in});
     bn.rv_off = net->add_buffer(name + ".BN.running_var", {C - b.c_in});
 }
-void reserve_bn(dali_resnet* net, Bn& b) {
-    net->reserve(b.scale, b.C * 4); net->reserve(b.shift, b.C * 4);
-    net->reserve(b.mean, b.C * 4); net->reserve(b.invstd, b.C * 4);
-    net->reserve(b.coef, b.C * 12);
+// The arena tensors of a layer, named `name`.<field> (PlanTable::reserve: what dali_resnet_debug_tensor answers)
+void reserve_bn(dali_resnet* net, Bn& b, const std::string& name) {
+    net->reserve(name + ".scale", b.scale, b.C * 4); net->reserve(name + ".shift", b.shift, b.C * 4);
+    net->reserve(name + ".mean", b.mean, b.C * 4); net->reserve(name + ".invstd", b.invstd, b.C * 4);
+    net->reserve(name + ".coef", b.coef, b.C * 12);
 }
-void reserve_linbn(dali_resnet* net, LinBn& l, const Conv& c, bool stats) {
+void reserve_linbn(dali_resnet* net, LinBn& l, const Conv& c, bool stats, const std::string& name) {
     l.w = c.cin; l.C = c.cout; l.stats = stats;
-    net->reserve(l.gram, (size_t)l.w * l.w * 4); net->reserve(l.m2, (size_t)l.w * 4);
-    net->reserve(l.bvec, (size_t)l.w * 4); net->reserve(l.qk, (size_t)l.C * 8);
-    net->reserve(l.wd, (size_t)l.w * (l.C + l.w) * 2);
-    net->reserve(l.ut, (size_t)l.w * l.C * 4);
-    if (stats) net->reserve(l.dot, (size_t)(l.w / 32) * l.C * 12);
+    net->reserve(name + ".gram", l.gram, (size_t)l.w * l.w * 4); net->reserve(name + ".m2", l.m2, (size_t)l.w * 4);
+    net->reserve(name + ".bvec", l.bvec, (size_t)l.w * 4); net->reserve(name + ".qk", l.qk, (size_t)l.C * 8);
+    net->reserve(name + ".wd", l.wd, (size_t)l.w * (l.C + l.w) * 2);
+    net->reserve(name + ".ut", l.ut, (size_t)l.w * l.C * 4);
+    if (stats) net->reserve(name + ".dot", l.dot, (size_t)(l.w / 32) * l.C * 12);
 }
 
 // (gamma, beta) in the flat parameters, (running_mean, running_var) in the flat buffers
@@ -190,7 +193,8 @@ extern "C" int dali_resnet_create_ex(dali_ctx* ctx, const dali_resnet_cfg* cfg, 
                  "dali_resnet_create: width_base must be 32 or 64 (got %d)", cfg->width_base);
     for (int i = 0; i < 4; ++i) DALI_REQUIRE(cfg->layers[i] >= 1, "dali_resnet_create: layers[%d] < 1", i);
     DALI_REQUIRE(!ext || (cfg->width_base / 2) % 8 == 0, "dali_resnet_create_ex: an IBN block's IN half (width / 2 channels) must be a multiple of 8");
-    dali_resnet* net = new (std::nothrow) dali_resnet();
+    std::unique_ptr<dali_resnet> owner(new (std::nothrow) dali_resnet());
+    dali_resnet* net = owner.get();
     if (!net) { set_error("dali_resnet_create: out of host memory"); return DALI_ERR_NOMEM; }
     net->ctx = ctx; net->cfg = *cfg; net->N = cfg->batch; net->H = cfg->height; net->W = cfg->width;
     const int wb = cfg->width_base;
@@ -243,14 +247,15 @@ extern "C" int dali_resnet_create_ex(dali_ctx* ctx, const dali_resnet_cfg* cfg, 
 
     // ---- arena layout ----
     const size_t N = net->N;
-    net->reserve(net->wbf16_flat, (size_t)net->param_elems * 2);
-    net->reserve(net->w_stem, (size_t)wb * 224 * 2);
-    net->reserve(net->ximg, N * (net->H + 6) * (net->W + 8) * 4 * 2);
+    net->reserve("wbf16", net->wbf16_flat, (size_t)net->param_elems * 2);
+    net->reserve("w_stem", net->w_stem, (size_t)wb * 224 * 2);
+    net->reserve("ximg", net->ximg, N * (net->H + 6) * (net->W + 8) * 4 * 2);
     const size_t raw0_bytes = N * net->stem_h * net->stem_w * wb * 2;
-    net->reserve(net->raw0, raw0_bytes);
-    net->reserve(net->pool0, N * net->pool_h * net->pool_w * wb * 2);
-    net->reserve(net->pool_arg, N * net->pool_h * net->pool_w * wb);
-    reserve_bn(net, net->stem_bn);
+    net->reserve("raw0", net->raw0, raw0_bytes);
+    net->view("d_raw0", net->dbg_d_raw0, raw0_bytes);
+    net->reserve("pool0", net->pool0, N * net->pool_h * net->pool_w * wb * 2);
+    net->reserve("pool_arg", net->pool_arg, N * net->pool_h * net->pool_w * wb);
+    reserve_bn(net, net->stem_bn, "bn1");
     size_t max_act = raw0_bytes, max_stat = (size_t)igemm_conv_stat_tiles(wb, (int)N * net->stem_h * net->stem_w, 224) * wb * 2 * 4;
     int stem_qpb;
     // (an eval plan reserves what the inference forward touches and nothing else: `train` guards the rest)
@@ -263,32 +268,38 @@ extern "C" int dali_resnet_create_ex(dali_ctx* ctx, const dali_resnet_cfg* cfg, 
         max_cs = std::max(max_cs, need.colsum_floats * 4);
     };
     size_wgrad(stem_wgrad_desc(net), false);
-    for (auto& b : net->blocks) {
+    for (size_t bi = 0; bi < net->blocks.size(); ++bi) {
+        Block& b = net->blocks[bi];
+        const std::string pre = "block" + std::to_string(bi) + ".";
         const size_t pin = N * b.hin * b.win, pout = N * b.hout * b.wout;
-        if (train) net->reserve(b.raw1, pin * b.width * 2);
-        net->reserve(b.a1, pin * b.width * 2);
-        if (train) net->reserve(b.raw2, pout * b.width * 2);
-        net->reserve(b.a2, pout * b.width * 2);
+        if (train) net->reserve(pre + "raw1", b.raw1, pin * b.width * 2);
+        net->view(pre + "d_raw1", b.dbg_d_raw1, pin * b.width * 2);
+        net->reserve(pre + "a1", b.a1, pin * b.width * 2);
+        if (train) net->reserve(pre + "raw2", b.raw2, pout * b.width * 2);
+        net->reserve(pre + "a2", b.a2, pout * b.width * 2);
         if (train) {
-            reserve_linbn(net, b.l3, b.c3, true);
-            net->reserve(b.sdz, (size_t)b.cout * 4);
+            reserve_linbn(net, b.l3, b.c3, true, pre + "l3");
+            net->reserve(pre + "sdz", b.sdz, (size_t)b.cout * 4);
             size_wgrad(gram_desc(net, b.c3), true);
         }
-        net->reserve(b.y, pout * b.cout * 2);
-        if (train) net->reserve(b.ybits, pout * b.cout / 8);
-        if (b.has_ds) net->reserve(b.rawd, pout * b.cout * 2);
-        if (b.ibn) { net->reserve(b.in_mean, N * b.c_in * 4); net->reserve(b.in_invstd, N * b.c_in * 4); }
+        net->reserve(pre + "y", b.y, pout * b.cout * 2);
+        if (train) net->reserve(pre + "ybits", b.ybits, pout * b.cout / 8);
+        if (b.has_ds) net->reserve(pre + "rawd", b.rawd, pout * b.cout * 2);
+        if (b.ibn) { net->reserve(pre + "in1.mean", b.in_mean, N * b.c_in * 4); net->reserve(pre + "in1.invstd", b.in_invstd, N * b.c_in * 4); }
         if (b.lin_ds && train) {
-            reserve_linbn(net, b.ld, b.cd, false);
+            reserve_linbn(net, b.ld, b.cd, false, pre + "ld");
             size_wgrad(gram_desc(net, b.cd), true);
         }
         // (split weight image, 2 parts: folding the scales into ONE bf16 image is a coherent 2^-9 perturbation of the weights, which moved the mAP of
         //  separated identities by 1.1e-3 against the oracle; hi + lo images are fp32-grade.  K = 2 (w + cin) <= 256: layer1's first block.)
         b.cat_eval = b.has_ds && b.cd.stride == 1 && conv_cat_act_supported(b.cout, b.width, b.cin, (int)pout, 2);
-        if (b.cat_eval) { net->reserve(b.wcat, (size_t)b.cout * 2 * (b.width + b.cin) * 2); net->reserve(b.shcat, (size_t)b.cout * 4); }
-        for_each_bn(b, [&](Bn& bn) { reserve_bn(net, bn); });
-        if (train) for_each_conv(b, [&](Conv& c) {
-            net->reserve(c.wt_bf16, (size_t)c.cin * c.r * c.s * c.cout * 2);
+        if (b.cat_eval) { net->reserve(pre + "wcat", b.wcat, (size_t)b.cout * 2 * (b.width + b.cin) * 2); net->reserve(pre + "shcat", b.shcat, (size_t)b.cout * 4); }
+        for_each_bn(b, [&](Bn& bn, const char* name) { reserve_bn(net, bn, pre + name); });
+        for_each_conv(b, [&](Conv& c, const char* name) {
+            const size_t w_bytes = (size_t)c.cin * c.r * c.s * c.cout * 2;
+            net->view(pre + name + ".w", c.w_bf16, w_bytes);             // in the flat bf16 cast (bind)
+            if (!train) return;
+            net->reserve(pre + name + ".wt", c.wt_bf16, w_bytes);
             const int P = (int)N * c.hout * c.wout;
             max_stat = std::max(max_stat, (size_t)igemm_conv_stat_tiles(c.cout, P, c.r * c.s * c.cin) * c.cout * 2 * 4);
             size_wgrad(conv_wgrad_desc(net, c), &c == &b.c3);      // conv3's carries s_dz = colsum(dz)
@@ -297,26 +308,26 @@ extern "C" int dali_resnet_create_ex(dali_ctx* ctx, const dali_resnet_cfg* cfg, 
             max_bwd_partial = std::max(max_bwd_partial, bn_bwd_partial_floats(P, c.cout, true) * 4);
         });
     }
-    net->reserve(net->feat, N * net->feat_dim * 4);
-    if (train) net->reserve(net->dfeat, N * net->feat_dim * 4);
-    net->reserve(net->head_arg, N * net->feat_dim * 2);
-    net->reserve(net->neck_mean, net->feat_dim * 4);
-    net->reserve(net->neck_invstd, net->feat_dim * 4);
+    net->reserve("feat", net->feat, N * net->feat_dim * 4);
+    if (train) net->reserve("dfeat", net->dfeat, N * net->feat_dim * 4);
+    net->reserve("head_arg", net->head_arg, N * net->feat_dim * 2);
+    net->reserve("neck.mean", net->neck_mean, net->feat_dim * 4);
+    net->reserve("neck.invstd", net->neck_invstd, net->feat_dim * 4);
     if (train) {
-        net->reserve(net->stat_partial, max_stat);
-        net->reserve(net->bwd_partial, max_bwd_partial);
-        net->reserve(net->wgrad_slab, max_slab);
-        net->reserve(net->cs_partial, max_cs);
-        net->reserve(net->stem_dw_pad, (size_t)wb * 224 * 4);
-        net->reserve(net->red_scratch, reduce_scratch_bytes(net->feat_dim, 3));
+        net->reserve("stat_partial", net->stat_partial, max_stat);
+        net->reserve("bwd_partial", net->bwd_partial, max_bwd_partial);
+        net->reserve("wgrad_slab", net->wgrad_slab, max_slab);
+        net->reserve("cs_partial", net->cs_partial, max_cs);
+        net->reserve("stem_dw_pad", net->stem_dw_pad, (size_t)wb * 224 * 4);
+        net->reserve("red_scratch", net->red_scratch, reduce_scratch_bytes(net->feat_dim, 3));
         net->gbuf_bytes = align_up(max_act, 256);
-        for (int i = 0; i < 6; ++i) net->reserve(net->gbuf[i], net->gbuf_bytes);
+        for (int i = 0; i < 6; ++i) net->reserve("gbuf" + std::to_string(i), net->gbuf[i], net->gbuf_bytes);
     } else {
         // the one forward that uses the gradient buffers' region: dali_resnet_forward_heads' pooled values, up to DALI_MAX_HEADS heads
         net->gbuf_bytes = align_up((DALI_MAX_HEADS * N * net->feat_dim * 4 + 5) / 6, 256);
-        net->reserve(net->gbuf[0], 6 * net->gbuf_bytes);
+        net->reserve("gbuf0", net->gbuf[0], 6 * net->gbuf_bytes);
     }
-    *out = net;
+    *out = owner.release();
     return DALI_OK;
 }
 
@@ -355,7 +366,7 @@ extern "C" int dali_resnet_bind(dali_resnet* net, float* params, float* grads, f
     net->P = params; net->G = grads; net->B = buffers; net->arena = static_cast<char*>(arena);
     net->bind_arena(net->arena);
     // bf16 weight images alias the flat bf16 cast (same offsets as the fp32 flat buffer)
-    for (auto& b : net->blocks) for_each_conv(b, [&](Conv& c) { c.w_bf16 = net->wbf16_flat + c.w_off; });
+    for (auto& b : net->blocks) for_each_conv(b, [&](Conv& c, const char*) { c.w_bf16 = net->wbf16_flat + c.w_off; });
     return DALI_OK;
 }
 
@@ -378,7 +389,7 @@ extern "C" int dali_resnet_refresh_weights(dali_resnet* net, void* stream) {
         return DALI_OK;
     }
     std::vector<TransposeJob> jobs;                      // every conv's dgrad image [cin][r*s][cout], one launch
-    for (auto& b : net->blocks) for_each_conv(b, [&](Conv& c) { jobs.push_back(TransposeJob{c.w_bf16, c.wt_bf16, c.cout, c.r * c.s, c.cin, 0}); });
+    for (auto& b : net->blocks) for_each_conv(b, [&](Conv& c, const char*) { jobs.push_back(TransposeJob{c.w_bf16, c.wt_bf16, c.cout, c.r * c.s, c.cin, 0}); });
     return launch_weight_transpose_batched(st, jobs.data(), (int)jobs.size());
 }
 
@@ -595,7 +606,7 @@ int trunk_forward(dali_resnet* net, hipStream_t st, const float* images, bool tr
     int rc;
     if (!tr) {                                               // inference: every BatchNorm's scale / shift from the running statistics, one launch
         std::vector<BnEvalJob> jobs;
-        auto add = [&](Bn& b) { const BnParams p = bn_params(net, b); jobs.push_back(BnEvalJob{p.gamma, p.beta, p.rm, p.rv, b.scale + b.lo, b.shift + b.lo, b.C - b.lo}); };
+        auto add = [&](Bn& b, const char* = nullptr) { const BnParams p = bn_params(net, b); jobs.push_back(BnEvalJob{p.gamma, p.beta, p.rm, p.rv, b.scale + b.lo, b.shift + b.lo, b.C - b.lo}); };
         add(net->stem_bn);
         for (auto& b : net->blocks) for_each_bn(b, add);
         if ((rc = launch_bn_eval_coeffs_batched(st, jobs.data(), (int)jobs.size(), 1e-5f))) return rc;
@@ -804,86 +815,27 @@ extern "C" int dali_debug_resnet_backward_block_snap(dali_resnet* net, void* str
     return rc;
 }
 
-// Debug/inspection: device pointer + byte size of a named intermediate (valid after a forward).
-// Names: raw0, pool0, pool_arg (uint8, the max-pool's tap), feat, head_arg (int16), neck.{mean,invstd}, dfeat (after a backward's head call),
-// grad_cur (gradient wrt the input of the last block processed by backward), block<i>.{raw1,a1,raw2,a2,rawd,y,d_raw1}, of a training plan
-// block<i>.ybits (the ReLU mask of y, one bit per element), block<i>.sdz (colsum(dz), after the block's backward) and the moments scheme's
-// block<i>.l3.{gram,m2,ut,wd,bvec,qk} (LinBn; wd, bvec, qk after the block's backward), the same under block<i>.ld. where the downsample
-// branch's backward runs through the moments of x,
-// for an IBN block block<i>.in1.{mean,invstd} (fp32 [N][width / 2], of the last forward), block<i>.bn{1,2,3,d}.{scale,shift,mean,invstd}, bn1.{...};
-// ximg (packed image bf16 [N][H+6][W+8][4]), w_stem (bf16 [Cout][7][8][4]), d_raw0 (after a stem backward); the weight images block<i>.conv{1,2,3,d}.w
-// (bf16 [cout][r][s][cin]) and .wt (bf16 [cin][r*s][cout]), and, where the inference forward folds conv3 + downsample into one GEMM,
-// block<i>.wcat (bf16 [cout][2 (w + cin)]: W3 hi | W3 lo | Wd hi | Wd lo) and block<i>.shcat (fp32 [cout])
+// Debug/inspection: device pointer + byte size of a named arena tensor of a bound plan (intermediates: valid after a forward).  Every name is
+// declared where dali_resnet_create_ex reserves the tensor; a tensor that this plan does not hold (an eval-only plan reserves none of the
+// backward's) is refused like an unknown name.
+// Names: wbf16 (the bf16 cast of the flat parameters), ximg (packed image bf16 [N][H+6][W+8][4]), w_stem (bf16 [Cout][7][8][4]), raw0, pool0,
+// pool_arg (uint8, the max-pool's tap), bn1.{scale,shift,mean,invstd,coef}, feat, head_arg (int16), neck.{mean,invstd}, gbuf0 (an eval-only plan:
+// the whole region dali_resnet_forward_heads pools into); of a training plan dfeat (after a backward's head call), d_raw0 (after a stem backward),
+// grad_cur (gradient wrt the input of the last block processed by backward) and the scratch stat_partial, bwd_partial, wgrad_slab, cs_partial,
+// stem_dw_pad, red_scratch, gbuf0 .. gbuf5;
+// block<i>.{a1,a2,y}, .rawd (with a downsample branch), .bn{1,2,3,d}.{scale,shift,mean,invstd,coef}, the weight images .conv{1,2,3,d}.w (bf16
+// [cout][r][s][cin]); for an IBN block .in1.{mean,invstd} (fp32 [N][width / 2], of the last forward); where the inference forward folds conv3 +
+// downsample into one GEMM .wcat (bf16 [cout][2 (w + cin)]: W3 hi | W3 lo | Wd hi | Wd lo) and .shcat (fp32 [cout]); of a training plan
+// .{raw1,raw2}, .d_raw1 (after the block's backward), .ybits (the ReLU mask of y, one bit per element), .sdz (colsum(dz), after the block's
+// backward), .conv{1,2,3,d}.wt (bf16 [cin][r*s][cout]) and the moments scheme's .l3.{gram,m2,ut,wd,bvec,qk,dot} (LinBn; wd, bvec, qk after the
+// block's backward), the same without dot under .ld. where the downsample branch's backward runs through the moments of x
 extern "C" int dali_resnet_debug_tensor(dali_resnet* net, const char* name, void** ptr, int64_t* bytes) {
     DALI_REQUIRE(net && name && ptr && bytes && net->arena, "dali_resnet_debug_tensor: bad argument / net not bound");
-    const std::string n(name);
-    const size_t N = net->N;
-    auto bn_field = [&](Bn& b, const std::string& f) -> bool {
-        float* p = f == "scale" ? b.scale : f == "shift" ? b.shift : f == "mean" ? b.mean : f == "invstd" ? b.invstd : nullptr;
-        if (!p) return false;
-        *ptr = p; *bytes = (int64_t)b.C * 4;
-        return true;
-    };
-    if (n == "raw0") { *ptr = net->raw0; *bytes = (int64_t)(N * net->stem_h * net->stem_w * net->stem.cout * 2); return DALI_OK; }
-    if (n == "pool0") { *ptr = net->pool0; *bytes = (int64_t)(N * net->pool_h * net->pool_w * net->stem.cout * 2); return DALI_OK; }
-    if (n == "grad_cur" && net->cur_dy) { *ptr = net->cur_dy; *bytes = net->cur_dy_bytes; return DALI_OK; }
-    if (n == "pool_arg") { *ptr = net->pool_arg; *bytes = (int64_t)(N * net->pool_h * net->pool_w * net->stem.cout); return DALI_OK; }
-    if (n == "head_arg") { *ptr = net->head_arg; *bytes = (int64_t)(N * net->feat_dim * 2); return DALI_OK; }
-    if (n == "neck.mean") { *ptr = net->neck_mean; *bytes = (int64_t)net->feat_dim * 4; return DALI_OK; }
-    if (n == "neck.invstd") { *ptr = net->neck_invstd; *bytes = (int64_t)net->feat_dim * 4; return DALI_OK; }
-    if (n == "dfeat" && net->dfeat) { *ptr = net->dfeat; *bytes = (int64_t)(N * net->feat_dim * 4); return DALI_OK; }
-    if (n == "feat") { *ptr = net->feat; *bytes = (int64_t)(N * net->feat_dim * 4); return DALI_OK; }
-    if (n == "ximg") { *ptr = net->ximg; *bytes = (int64_t)(N * (net->H + 6) * (net->W + 8) * 4 * 2); return DALI_OK; }
-    if (n == "w_stem") { *ptr = net->w_stem; *bytes = (int64_t)net->stem.cout * 224 * 2; return DALI_OK; }
-    if (n == "d_raw0" && net->dbg_d_raw0) { *ptr = net->dbg_d_raw0; *bytes = (int64_t)(N * net->stem_h * net->stem_w * net->stem.cout * 2); return DALI_OK; }
-    if (n.rfind("bn1.", 0) == 0 && bn_field(net->stem_bn, n.substr(4))) return DALI_OK;
-    if (n.rfind("block", 0) == 0) {
-        const size_t dot = n.find('.');
-        if (dot != std::string::npos) {
-            const int bi = atoi(n.substr(5, dot - 5).c_str());
-            if (bi >= 0 && bi < (int)net->blocks.size()) {
-                Block& b = net->blocks[bi];
-                const std::string f = n.substr(dot + 1);
-                const size_t pin = N * b.hin * b.win, pout = N * b.hout * b.wout;
-                if (f == "a2") { *ptr = b.a2; *bytes = (int64_t)(pout * b.width * 2); return DALI_OK; }
-                if (f == "ybits" && b.ybits) { *ptr = b.ybits; *bytes = (int64_t)(pout * b.cout / 8); return DALI_OK; }
-                if (f == "sdz" && b.sdz) { *ptr = b.sdz; *bytes = (int64_t)b.cout * 4; return DALI_OK; }
-                if ((f.rfind("l3.", 0) == 0 || f.rfind("ld.", 0) == 0) && (f[1] == '3' ? b.l3.gram != nullptr : (b.lin_ds && b.ld.gram != nullptr))) {
-                    const LinBn& l = f[1] == '3' ? b.l3 : b.ld;
-                    const std::string q = f.substr(3);
-                    const int64_t w = l.w, C = l.C;
-                    void* p = nullptr; int64_t nb = 0;
-                    if (q == "gram") { p = l.gram; nb = w * w * 4; }
-                    else if (q == "m2") { p = l.m2; nb = w * 4; }
-                    else if (q == "ut") { p = l.ut; nb = w * C * 4; }
-                    else if (q == "wd") { p = l.wd; nb = w * (C + w) * 2; }
-                    else if (q == "bvec") { p = l.bvec; nb = w * 4; }
-                    else if (q == "qk") { p = l.qk; nb = C * 8; }
-                    if (p) { *ptr = p; *bytes = nb; return DALI_OK; }
-                }
-                if (f == "a1") { *ptr = b.a1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }
-                if (f == "in1.mean" && b.ibn) { *ptr = b.in_mean; *bytes = (int64_t)(N * b.c_in * 4); return DALI_OK; }
-                if (f == "in1.invstd" && b.ibn) { *ptr = b.in_invstd; *bytes = (int64_t)(N * b.c_in * 4); return DALI_OK; }
-                if (f == "raw1" && b.raw1) { *ptr = b.raw1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }
-                if (f == "raw2" && b.raw2) { *ptr = b.raw2; *bytes = (int64_t)(pout * b.width * 2); return DALI_OK; }
-                if (f == "rawd" && b.has_ds) { *ptr = b.rawd; *bytes = (int64_t)(pout * b.cout * 2); return DALI_OK; }
-                if (f == "y") { *ptr = b.y; *bytes = (int64_t)(pout * b.cout * 2); return DALI_OK; }
-                if (f == "d_raw1" && b.dbg_d_raw1) { *ptr = b.dbg_d_raw1; *bytes = (int64_t)(pin * b.width * 2); return DALI_OK; }
-                if (f == "wcat" && b.cat_eval) { *ptr = b.wcat; *bytes = (int64_t)b.cout * 2 * (b.width + b.cin) * 2; return DALI_OK; }
-                if (f == "shcat" && b.cat_eval) { *ptr = b.shcat; *bytes = (int64_t)b.cout * 4; return DALI_OK; }
-                if (f.rfind("conv", 0) == 0 && f.size() > 6 && f[5] == '.') {
-                    Conv* c = f[4] == '1' ? &b.c1 : f[4] == '2' ? &b.c2 : f[4] == '3' ? &b.c3 : (f[4] == 'd' && b.has_ds) ? &b.cd : nullptr;
-                    const std::string img = f.substr(6);
-                    uint16_t* p = !c ? nullptr : img == "w" ? c->w_bf16 : img == "wt" ? c->wt_bf16 : nullptr;
-                    if (p) { *ptr = p; *bytes = (int64_t)c->cout * c->r * c->s * c->cin * 2; return DALI_OK; }
-                }
-                if (f.rfind("bn", 0) == 0 && f.size() > 4) {
-                    Bn* bn = f[2] == '1' ? &b.b1 : f[2] == '2' ? &b.b2 : f[2] == '3' ? &b.b3 : (f[2] == 'd' && b.has_ds) ? &b.bd : nullptr;
-                    if (bn && bn_field(*bn, f.substr(4))) return DALI_OK;
-                }
-            }
-        }
-    }
-    set_error("dali_resnet_debug_tensor: unknown tensor '%s'", name);
-    return DALI_ERR_INVALID;
+    // the one name that is no fixed tensor: it moves through the gradient buffers and changes its size from block to block
+    if (!strcmp(name, "grad_cur") && net->cur_dy) { *ptr = net->cur_dy; *bytes = net->cur_dy_bytes; return DALI_OK; }
+    return net->arena_tensor("dali_resnet_debug_tensor", name, ptr, bytes);
+}
+extern "C" int dali_debug_resnet_arena_entry(const dali_resnet* net, int index, char* name, int name_cap, int64_t* offset, int64_t* bytes, int* reserved) {
+    DALI_REQUIRE(net, "dali_debug_resnet_arena_entry: null net");
+    return net->arena_entry("dali_debug_resnet_arena_entry", index, name, name_cap, offset, bytes, reserved);
 }

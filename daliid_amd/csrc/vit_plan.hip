@@ -23,6 +23,7 @@
 #include "plan_table.h"
 #include <cmath>
 #include <cstdio>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -111,6 +112,22 @@ void add_block(dali_vit* n, VBlock& b, const std::string& pre) {
     add_lin(n, b.fc1, pre + ".mlp.fc1", C, n->cfg.mlp_hidden);
     add_lin(n, b.fc2, pre + ".mlp.fc2", n->cfg.mlp_hidden, C);
 }
+// f(linear layer, its name inside the block's arena names)
+template <class F> void for_each_lin(VBlock& b, F f) { f(b.qkv, "qkv"); f(b.proj, "proj"); f(b.fc1, "fc1"); f(b.fc2, "fc2"); }
+// The thirteen activation and statistic tensors of a block that runs on `rows` token rows = seqs sequences of T tokens, as `prefix`<field>
+void reserve_block_acts(dali_vit* n, VBlock& b, const std::string& prefix, size_t rows, size_t seqs, size_t T) {
+    const size_t C = n->C, Hd = n->cfg.mlp_hidden;
+    n->reserve(prefix + "h1", b.h1, rows * C * 2); n->reserve(prefix + "qkv", b.qkv_o, rows * 3 * C * 2); n->reserve(prefix + "att", b.att, rows * C * 2);
+    n->reserve(prefix + "x_mid", b.x_mid, rows * C * 2); n->reserve(prefix + "h2", b.h2, rows * C * 2); n->reserve(prefix + "pre1", b.pre1, rows * Hd * 2);
+    n->reserve(prefix + "act1", b.act1, rows * Hd * 2); n->reserve(prefix + "x_out", b.x_out, rows * C * 2);
+    n->reserve(prefix + "lse", b.lse, seqs * n->H * T * 4);
+    n->reserve(prefix + "n1.mean", b.n1.mean, rows * 4); n->reserve(prefix + "n1.rstd", b.n1.rstd, rows * 4);
+    n->reserve(prefix + "n2.mean", b.n2.mean, rows * 4); n->reserve(prefix + "n2.rstd", b.n2.rstd, rows * 4);
+}
+// `prefix`{qkv,proj,fc1,fc2}.w: the block's forward weight images, views into the flat bf16 cast (dali_vit_bind sets them)
+void name_block_weights(dali_vit* n, VBlock& b, const std::string& prefix) {
+    for_each_lin(b, [&](Lin& l, const char* name) { n->view(prefix + name + ".w", l.w, (size_t)l.K * l.N * 2); });
+}
 }  // namespace
 
 extern "C" int dali_vit_create(dali_ctx* ctx, const dali_vit_cfg* cfg, dali_vit** out) {
@@ -127,7 +144,8 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
                  "dali_vit_create: head_dim = dim / heads must be %d or %d (dim=%d heads=%d)", VIT_TRAIN_HD, VIT_EVAL_HD, cfg->dim, cfg->heads);
     DALI_REQUIRE(ext->qk_scale >= 0.0f && ext->qk_scale < 1e30f, "dali_vit_create: qk_scale must be positive, or 0 for head_dim ** -0.5");
     DALI_REQUIRE(cfg->depth >= 1 && cfg->mlp_hidden % 32 == 0 && cfg->mlp_hidden > 0, "dali_vit_create: bad depth / mlp_hidden");
-    dali_vit* n = new (std::nothrow) dali_vit();
+    std::unique_ptr<dali_vit> owner(new (std::nothrow) dali_vit());
+    dali_vit* n = owner.get();
     if (!n) { set_error("dali_vit_create: out of host memory"); return DALI_ERR_NOMEM; }
     n->ctx = ctx; n->cfg = *cfg; n->ext = *ext;
     if (n->ext.jpm) n->ext.local_feature = 1;            // make_models.py:243: the JPM base is built with local_feature = cfg.MODEL.JPM
@@ -135,13 +153,13 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
     n->B = cfg->batch; n->np = ny * nx; n->T = n->np + 1; n->C = cfg->dim; n->H = cfg->heads; n->rows = n->B * n->T;
     n->hd = cfg->dim / cfg->heads;
     n->att_scale = ext->qk_scale > 0.0f ? ext->qk_scale : n->hd == VIT_TRAIN_HD ? 0.125f : 1.0f / sqrtf((float)n->hd);
-    if (n->T > VIT_MAX_T) { set_error("dali_vit_create: %d tokens exceed the attention kernel's limit of %d", n->T, VIT_MAX_T); delete n; return DALI_ERR_LIMIT; }
+    if (n->T > VIT_MAX_T) { set_error("dali_vit_create: %d tokens exceed the attention kernel's limit of %d", n->T, VIT_MAX_T); return DALI_ERR_LIMIT; }
     // past VIT_TRAIN_MAX_T tokens, and at head_dim 96, only the attention forward exists: an eval plan, reserved like a local_feature one
     n->eval_only = n->ext.local_feature != 0 || n->T > VIT_TRAIN_MAX_T || n->hd != VIT_TRAIN_HD;
     const int C = n->C, Kp = 3 * cfg->patch * cfg->patch;
     n->cls_off = n->add_param("base.cls_token", {1, 1, C});
     n->pos_off = n->add_param("base.pos_embed", {1, n->T, C});
-    if (ext->n_sie < 0) { set_error("dali_vit_create: n_sie = %d", ext->n_sie); delete n; return DALI_ERR_INVALID; }
+    DALI_REQUIRE(ext->n_sie >= 0, "dali_vit_create: n_sie = %d", ext->n_sie);
     if (ext->n_sie > 0) n->sie_off = n->add_param("base.sie_embed", {ext->n_sie, 1, C});      // vit_pytorch.py:316-331
     n->patch.K = Kp; n->patch.N = C;
     n->patch.w_off = n->add_param("base.patch_embed.proj.weight", {C, 3, cfg->patch, cfg->patch});
@@ -153,16 +171,13 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
     n->fcb_off = n->add_param("base.fc.bias", {cfg->num_classes});
     if (n->ext.jpm) {
         // make_models.py:249-258, 279-288: b1 / b2 = (block, norm) copies, then the five unused classifiers, in the state dict's order
-        if (n->ext.id_classes < 1) { set_error("dali_vit_create: JPM needs id_classes >= 1 (the classifiers' rows)"); delete n; return DALI_ERR_INVALID; }
-        if (n->ext.divide != 4) { set_error("dali_vit_create: JPM needs divide = 4, the reference's forward cuts four runs (got %d)", n->ext.divide); delete n; return DALI_ERR_INVALID; }
+        DALI_REQUIRE(n->ext.id_classes >= 1, "dali_vit_create: JPM needs id_classes >= 1 (the classifiers' rows)");
+        DALI_REQUIRE(n->ext.divide == 4, "dali_vit_create: JPM needs divide = 4, the reference's forward cuts four runs (got %d)", n->ext.divide);
         // the token map (shift + group shuffle, make_models.jpm_token_map) is the caller's: [divide][L] token indices, each a patch token 1 .. np
         n->L = n->np / n->ext.divide;
         bool map_ok = n->ext.token_map != nullptr && n->L >= 1;
         for (int i = 0; map_ok && i < n->ext.divide * n->L; ++i) map_ok = n->ext.token_map[i] >= 1 && n->ext.token_map[i] <= n->np;
-        if (!map_ok) {
-            set_error("dali_vit_create: JPM needs token_map [%d][%d] with entries in 1 .. %d", n->ext.divide, n->L, n->np);
-            delete n; return DALI_ERR_INVALID;
-        }
+        DALI_REQUIRE(map_ok, "dali_vit_create: JPM needs token_map [%d][%d] with entries in 1 .. %d", n->ext.divide, n->L, n->np);
         n->map_host.assign(n->ext.token_map, n->ext.token_map + (size_t)n->ext.divide * n->L);
         n->ext.token_map = nullptr;                      // copied: the caller's array need not outlive this call
         n->Tl = 1 + n->L; n->rows2 = n->ext.divide * n->B * n->Tl;
@@ -185,53 +200,53 @@ extern "C" int dali_vit_create_ex(dali_ctx* ctx, const dali_vit_cfg* cfg, const 
     for (int s = 0; s <= n->n_stages; ++s) n->stage_first_block[s] = cfg->depth - (int)((int64_t)cfg->depth * s / n->n_stages);
 
     const size_t rows = n->rows, Hd = cfg->mlp_hidden;
-    n->reserve(n->wbf16, (size_t)n->param_elems * 2);
-    n->reserve(n->patches, (size_t)n->B * n->np * Kp * 2);
-    n->reserve(n->pe, (size_t)n->B * n->np * C * 2);
-    n->reserve(n->x0, rows * C * 2);
+    // ---- arena layout: every tensor under the name dali_debug_vit_tensor answers to ----
+    n->reserve("wbf16", n->wbf16, (size_t)n->param_elems * 2);
+    n->reserve("patches", n->patches, (size_t)n->B * n->np * Kp * 2);
+    n->reserve("pe", n->pe, (size_t)n->B * n->np * C * 2);
+    n->reserve("x0", n->x0, rows * C * 2);
     const bool eval_only = n->eval_only;
-    if (!eval_only) n->reserve(n->patch.wt, (size_t)Kp * C * 2);          // unused (images need no gradient) but keeps Lin uniform
+    n->view("patch.w", n->patch.w, (size_t)Kp * C * 2);
+    if (!eval_only) n->reserve("patch.wt", n->patch.wt, (size_t)Kp * C * 2);          // unused (images need no gradient) but keeps Lin uniform
     // the weight-gradient workspace is sized for every linear layer the backward runs (patch embedding, then each block's four)
     WGradNeed need = linear_wgrad_need(n->B * n->np, Kp, C, true);
     size_t part = std::max(layernorm_bwd_partial_floats((int)rows, C), colsum_partial_floats((int)rows, (int)std::max<size_t>(Hd, 3 * C)));
-    for (auto& b : n->blocks) {
-        n->reserve(b.h1, rows * C * 2); n->reserve(b.qkv_o, rows * 3 * C * 2); n->reserve(b.att, rows * C * 2);
-        n->reserve(b.x_mid, rows * C * 2); n->reserve(b.h2, rows * C * 2); n->reserve(b.pre1, rows * Hd * 2);
-        n->reserve(b.act1, rows * Hd * 2); n->reserve(b.x_out, rows * C * 2);
-        n->reserve(b.lse, (size_t)n->B * n->H * n->T * 4);
-        n->reserve(b.n1.mean, rows * 4); n->reserve(b.n1.rstd, rows * 4); n->reserve(b.n2.mean, rows * 4); n->reserve(b.n2.rstd, rows * 4);
-        Lin* ls[4] = {&b.qkv, &b.proj, &b.fc1, &b.fc2};
-        for (Lin* l : ls) {
-            if (!eval_only) n->reserve(l->wt, (size_t)l->K * l->N * 2);
-            const WGradNeed ln = linear_wgrad_need((int)rows, l->K, l->N, true);
+    for (int i = 0; i < cfg->depth; ++i) {
+        VBlock& b = n->blocks[i];
+        const std::string pre = "block" + std::to_string(i) + ".";
+        reserve_block_acts(n, b, pre, rows, n->B, n->T);
+        name_block_weights(n, b, pre);
+        for_each_lin(b, [&](Lin& l, const char* name) {
+            if (!eval_only) n->reserve(pre + name + ".wt", l.wt, (size_t)l.K * l.N * 2);
+            const WGradNeed ln = linear_wgrad_need((int)rows, l.K, l.N, true);
             need = WGradNeed{std::max(need.slab_bytes, ln.slab_bytes), std::max(need.colsum_floats, ln.colsum_floats)};
-        }
+        });
     }
-    n->reserve(n->cls_rows, (size_t)n->B * C * 2); n->reserve(n->dcls_rows, (size_t)n->B * C * 2); n->reserve(n->dgf16, (size_t)n->B * C * 2);
-    n->reserve(n->gf, (size_t)n->B * C * 4); n->reserve(n->dgf, (size_t)n->B * C * 4);
-    n->reserve(n->neck_mean, C * 4); n->reserve(n->neck_invstd, C * 4);
-    n->reserve(n->fin_mean, n->B * 4); n->reserve(n->fin_rstd, n->B * 4);
+    n->reserve("cls_rows", n->cls_rows, (size_t)n->B * C * 2); n->reserve("dcls_rows", n->dcls_rows, (size_t)n->B * C * 2);
+    n->reserve("dgf16", n->dgf16, (size_t)n->B * C * 2);
+    n->reserve("gf", n->gf, (size_t)n->B * C * 4); n->reserve("dgf", n->dgf, (size_t)n->B * C * 4);
+    n->reserve("neck.mean", n->neck_mean, C * 4); n->reserve("neck.invstd", n->neck_invstd, C * 4);
+    n->reserve("fin.mean", n->fin_mean, n->B * 4); n->reserve("fin.rstd", n->fin_rstd, n->B * 4);
     if (!eval_only) {
-        n->reserve(n->slab, need.slab_bytes); n->reserve(n->partial, std::max(part, need.colsum_floats) * 4);
-        n->reserve(n->dp_rows, (size_t)2 * cfg->depth * rows * 4);
+        n->reserve("slab", n->slab, need.slab_bytes); n->reserve("partial", n->partial, std::max(part, need.colsum_floats) * 4);
+        n->reserve("dp_rows", n->dp_rows, (size_t)2 * cfg->depth * rows * 4);
     }
-    n->reserve(n->scratch, reduce_scratch_bytes((int)std::max<size_t>(Hd, 3 * C), 2));
-    for (int i = 0; i < 4 && !eval_only; ++i) n->reserve(n->gbuf[i], rows * std::max<size_t>(Hd, 3 * C) * 2);
+    n->reserve("scratch", n->scratch, reduce_scratch_bytes((int)std::max<size_t>(Hd, 3 * C), 2));
+    for (int i = 0; i < 4 && !eval_only; ++i) n->reserve("gbuf" + std::to_string(i), n->gbuf[i], rows * std::max<size_t>(Hd, 3 * C) * 2);
+    // between two pieces of the backward the token gradient lies in gbuf[0]; the token tail hands its patch rows to the patch weight gradient in gbuf[1]
+    n->view("grad_cur", n->gbuf[0], rows * C * 2);
+    n->view("dpe", n->gbuf[1], (size_t)n->B * n->np * C * 2);
     if (n->ext.jpm) {
         // b1 runs on the B*T rows in the buffers of the idle blocks[depth-1] (bind); b2 gets its own for the divide * B sequences of 1 + L tokens
-        VBlock& b = n->b2;
-        const size_t r2 = n->rows2, seqs = (size_t)n->ext.divide * n->B;
-        n->reserve(n->jseq, r2 * C * 2);
-        n->reserve(b.h1, r2 * C * 2); n->reserve(b.qkv_o, r2 * 3 * C * 2); n->reserve(b.att, r2 * C * 2);
-        n->reserve(b.x_mid, r2 * C * 2); n->reserve(b.h2, r2 * C * 2); n->reserve(b.pre1, r2 * Hd * 2);
-        n->reserve(b.act1, r2 * Hd * 2); n->reserve(b.x_out, r2 * C * 2);
-        n->reserve(b.lse, seqs * n->H * n->Tl * 4);
-        n->reserve(b.n1.mean, r2 * 4); n->reserve(b.n1.rstd, r2 * 4); n->reserve(b.n2.mean, r2 * 4); n->reserve(b.n2.rstd, r2 * 4);
-        n->reserve(n->cls2, seqs * C * 2); n->reserve(n->gf2, seqs * C * 4);
-        n->reserve(n->fin2_mean, seqs * 4); n->reserve(n->fin2_rstd, seqs * 4);
-        n->reserve(n->map_dev, n->map_host.size() * 4);
+        const size_t seqs = (size_t)n->ext.divide * n->B;
+        n->reserve("jseq", n->jseq, (size_t)n->rows2 * C * 2);
+        reserve_block_acts(n, n->b2, "b2.", n->rows2, seqs, n->Tl);
+        n->reserve("cls2", n->cls2, seqs * C * 2); n->reserve("gf2", n->gf2, seqs * C * 4);
+        n->reserve("fin2.mean", n->fin2_mean, seqs * 4); n->reserve("fin2.rstd", n->fin2_rstd, seqs * 4);
+        n->reserve("map_dev", n->map_dev, n->map_host.size() * 4);
+        name_block_weights(n, n->b1, "b1."); name_block_weights(n, n->b2, "b2.");
     }
-    *out = n;
+    *out = owner.release();
     return DALI_OK;
 }
 
@@ -252,15 +267,17 @@ extern "C" int dali_vit_bind(dali_vit* n, float* params, float* grads, float* bu
     DALI_REQUIRE(arena_bytes >= n->arena_bytes, "dali_vit_bind: arena too small (%zu < %zu)", arena_bytes, n->arena_bytes);
     n->P = params; n->G = grads; n->Bf = buffers; n->arena = static_cast<char*>(arena);
     n->bind_arena(n->arena);
-    n->patch.w = n->wbf16 + n->patch.w_off;
-    for (auto& b : n->blocks) { b.qkv.w = n->wbf16 + b.qkv.w_off; b.proj.w = n->wbf16 + b.proj.w_off; b.fc1.w = n->wbf16 + b.fc1.w_off; b.fc2.w = n->wbf16 + b.fc2.w_off; }
+    // the forward weight images lie in the flat bf16 cast, at the offsets of the fp32 parameters
+    auto bind_w = [&](Lin& l, const char* = nullptr) { l.w = n->wbf16 + l.w_off; };
+    bind_w(n->patch);
+    for (auto& b : n->blocks) for_each_lin(b, bind_w);
     if (n->ext.jpm) {
         const VBlock& idle = n->blocks.back();           // local_feature never runs it: b1, its copy, works in its buffers
         VBlock& b = n->b1;
         b.h1 = idle.h1; b.qkv_o = idle.qkv_o; b.att = idle.att; b.x_mid = idle.x_mid; b.h2 = idle.h2; b.pre1 = idle.pre1; b.act1 = idle.act1;
         b.x_out = idle.x_out; b.lse = idle.lse;
         b.n1.mean = idle.n1.mean; b.n1.rstd = idle.n1.rstd; b.n2.mean = idle.n2.mean; b.n2.rstd = idle.n2.rstd;
-        for (VBlock* v : {&n->b1, &n->b2}) { v->qkv.w = n->wbf16 + v->qkv.w_off; v->proj.w = n->wbf16 + v->proj.w_off; v->fc1.w = n->wbf16 + v->fc1.w_off; v->fc2.w = n->wbf16 + v->fc2.w_off; }
+        for_each_lin(n->b1, bind_w); for_each_lin(n->b2, bind_w);
     }
     return DALI_OK;
 }
@@ -273,10 +290,7 @@ extern "C" int dali_vit_refresh_weights(dali_vit* n, void* stream) {
     if (n->ext.jpm) DALI_HIP(hipMemcpyAsync(n->map_dev, n->map_host.data(), n->map_host.size() * 4, hipMemcpyHostToDevice, st));
     if (n->eval_only) return DALI_OK;                    // local_feature / JPM / more than 256 tokens / head_dim 96: no dgrad images
     std::vector<TransposeJob> jobs;                      // every linear's dgrad image [K][N], batched launches (48 single launches cost 0.3 ms)
-    for (auto& b : n->blocks) {
-        Lin* ls[4] = {&b.qkv, &b.proj, &b.fc1, &b.fc2};
-        for (Lin* l : ls) jobs.push_back(TransposeJob{l->w, l->wt, l->N, 1, l->K, 0});          // [N][K] -> [K][N]
-    }
+    for (auto& b : n->blocks) for_each_lin(b, [&](Lin& l, const char*) { jobs.push_back(TransposeJob{l.w, l.wt, l.N, 1, l.K, 0}); });   // [N][K] -> [K][N]
     return launch_weight_transpose_batched(st, jobs.data(), (int)jobs.size());
 }
 
@@ -490,62 +504,16 @@ extern "C" int dali_debug_vit_backward_block(dali_vit* n, void* stream, const fl
     return block >= 0 ? bwd_block(n, st, block) : bwd_tokens(n, st);
 }
 
+// every name is declared where dali_vit_create_ex reserves the tensor; one that this plan did not reserve (dgrad images, DropPath rows, gradient
+// buffers of an eval-only plan) was never bound and is refused like an unknown name
 extern "C" int dali_debug_vit_tensor(const dali_vit* n, const char* name, void** ptr, int64_t* bytes) {
     DALI_REQUIRE(n && name && ptr && bytes, "dali_debug_vit_tensor: null argument");
     DALI_REQUIRE(n->arena, "dali_debug_vit_tensor: net not bound");
-    const size_t rows = n->rows, C = n->C, Hd = n->cfg.mlp_hidden, B = n->B;
-    const void* p = nullptr; size_t sz = 0;
-    auto is = [&](const char* s) { return std::string(name) == s; };
-    if (is("patches")) { p = n->patches; sz = B * n->np * (size_t)n->patch.K * 2; }
-    else if (is("pe")) { p = n->pe; sz = B * n->np * C * 2; }
-    else if (is("x0")) { p = n->x0; sz = rows * C * 2; }
-    else if (is("cls_rows")) { p = n->cls_rows; sz = B * C * 2; }
-    else if (is("dcls_rows")) { p = n->dcls_rows; sz = B * C * 2; }
-    else if (is("gf")) { p = n->gf; sz = B * C * 4; }
-    else if (is("dgf")) { p = n->dgf; sz = B * C * 4; }
-    else if (is("fin.mean")) { p = n->fin_mean; sz = B * 4; }
-    else if (is("fin.rstd")) { p = n->fin_rstd; sz = B * 4; }
-    else if (is("neck.mean")) { p = n->neck_mean; sz = C * 4; }
-    else if (is("neck.invstd")) { p = n->neck_invstd; sz = C * 4; }
-    else if (is("dp_rows")) { p = n->dp_rows; sz = 2 * n->blocks.size() * rows * 4; }
-    else if (is("wbf16")) { p = n->wbf16; sz = (size_t)n->param_elems * 2; }
-    else if (is("grad_cur")) { p = n->gbuf[0]; sz = rows * C * 2; }
-    else if (is("dpe")) { p = n->gbuf[1]; sz = B * n->np * C * 2; }                  // what the token tail hands to the patch weight gradient
-    else {
-        int bi = -1, used = 0;
-        if (sscanf(name, "block%d.%n", &bi, &used) < 1 || used == 0 || bi < 0 || bi >= (int)n->blocks.size()) {
-            set_error("dali_debug_vit_tensor: unknown tensor '%s'", name); return DALI_ERR_INVALID;
-        }
-        const VBlock& b = n->blocks[bi];
-        const std::string f = name + used;
-        const Lin* l = nullptr;
-        if (f == "h1") { p = b.h1; sz = rows * C * 2; }
-        else if (f == "qkv") { p = b.qkv_o; sz = rows * 3 * C * 2; }
-        else if (f == "att") { p = b.att; sz = rows * C * 2; }
-        else if (f == "x_mid") { p = b.x_mid; sz = rows * C * 2; }
-        else if (f == "h2") { p = b.h2; sz = rows * C * 2; }
-        else if (f == "pre1") { p = b.pre1; sz = rows * Hd * 2; }
-        else if (f == "act1") { p = b.act1; sz = rows * Hd * 2; }
-        else if (f == "x_out") { p = b.x_out; sz = rows * C * 2; }
-        else if (f == "lse") { p = b.lse; sz = B * n->H * (size_t)n->T * 4; }
-        else if (f == "n1.mean") { p = b.n1.mean; sz = rows * 4; }
-        else if (f == "n1.rstd") { p = b.n1.rstd; sz = rows * 4; }
-        else if (f == "n2.mean") { p = b.n2.mean; sz = rows * 4; }
-        else if (f == "n2.rstd") { p = b.n2.rstd; sz = rows * 4; }
-        else if (f.rfind("qkv.", 0) == 0) l = &b.qkv;
-        else if (f.rfind("proj.", 0) == 0) l = &b.proj;
-        else if (f.rfind("fc1.", 0) == 0) l = &b.fc1;
-        else if (f.rfind("fc2.", 0) == 0) l = &b.fc2;
-        if (l) {
-            const std::string leaf = f.substr(f.find('.') + 1);
-            sz = (size_t)l->K * l->N * 2;
-            if (leaf == "w") p = l->w; else if (leaf == "wt") p = l->wt;
-        }
-    }
-    // a name the plan did not reserve (dgrad images, DropPath rows, gradient buffers of an eval-only plan) was never bound: still null
-    if (!p) { set_error("dali_debug_vit_tensor: unknown tensor '%s', or one this plan does not hold", name); return DALI_ERR_INVALID; }
-    *ptr = const_cast<void*>(p); *bytes = (int64_t)sz;
-    return DALI_OK;
+    return n->arena_tensor("dali_debug_vit_tensor", name, ptr, bytes);
+}
+extern "C" int dali_debug_vit_arena_entry(const dali_vit* n, int index, char* name, int name_cap, int64_t* offset, int64_t* bytes, int* reserved) {
+    DALI_REQUIRE(n, "dali_debug_vit_arena_entry: null net");
+    return n->arena_entry("dali_debug_vit_arena_entry", index, name, name_cap, offset, bytes, reserved);
 }
 
 extern "C" int dali_vit_backward(dali_vit* n, void* stream, const float* d_feat) {

@@ -84,12 +84,35 @@ int dali_debug_resnet_backward_block_snap(struct dali_resnet* net, void* stream,
  * (tests/test_gpu_vit_plan.py).  d_feat is read by the head call only */
 struct dali_vit;
 int dali_debug_vit_backward_block(struct dali_vit* net, void* stream, const float* d_feat, int block);
-/* device pointer and byte size of a named arena tensor of a bound ViT plan, valid after a forward: patches, pe, x0, cls_rows, gf, dgf, dcls_rows,
- * fin.mean, fin.rstd, neck.mean, neck.invstd, dp_rows, wbf16, grad_cur (the token gradient between two pieces of the backward), dpe (the patch
- * rows of it, as the token tail hands them to the patch weight gradient), block<i>.{h1,qkv,att,x_mid,h2,pre1,act1,x_out,lse,n1.mean,n1.rstd,
- * n2.mean,n2.rstd} and block<i>.{qkv,proj,fc1,fc2}.{w,wt}.  DALI_ERR_INVALID for an unknown name and for one the plan did not reserve (wt,
- * dp_rows, grad_cur, dpe of an eval-only plan) */
+/* device pointer and byte size of a named arena tensor of a bound ViT plan (intermediates: valid after a forward).  The names are those under
+ * which dali_vit_create_ex reserves the tensors:
+ *   wbf16 (the bf16 cast of the flat parameters), patches, pe, x0, patch.w, cls_rows, dcls_rows, dgf16, gf, dgf, neck.mean, neck.invstd, fin.mean,
+ *   fin.rstd, scratch; block<i>.{h1,qkv,att,x_mid,h2,pre1,act1,x_out,lse,n1.mean,n1.rstd,n2.mean,n2.rstd} (qkv: the activation) and the forward
+ *   weight images block<i>.{qkv,proj,fc1,fc2}.w (they lie inside wbf16);
+ *   of a training plan only: patch.wt and block<i>.{qkv,proj,fc1,fc2}.wt (the transposed images), slab, partial, dp_rows, gbuf0 .. gbuf3,
+ *   grad_cur (the token gradient between two pieces of the backward: the head of gbuf0) and dpe (the patch rows of it, as the token tail hands
+ *   them to the patch weight gradient: the head of gbuf1);
+ *   of a JPM plan: jseq, b2.{h1 .. n2.rstd as a block's}, cls2, gf2, fin2.mean, fin2.rstd, map_dev and {b1,b2}.{qkv,proj,fc1,fc2}.w (b1 works in the
+ *   buffers of the idle last block: its activations are block<depth-1>.*).
+ * DALI_ERR_INVALID for an unknown name and for one this plan does not hold (wt, dp_rows, grad_cur, dpe of an eval-only plan) */
 int dali_debug_vit_tensor(const struct dali_vit* net, const char* name, void** ptr, int64_t* bytes);
+
+/* The arena of a plan as a table, one entry per index 0, 1, ... (DALI_ERR_INVALID past the last): every tensor that dali_*_create_ex reserves,
+ * in the order of the arena (reserved = 1: `offset` bytes from the arena's base, 256-byte aligned, `bytes` long; the reservations do not overlap
+ * and their 256-aligned sizes add up to the plan's arena_bytes), and every view (reserved = 0, offset = -1): a name for storage inside a
+ * reserved tensor (a weight image inside wbf16, grad_cur, dpe, the ResNet's d_raw0 and block<i>.d_raw1 inside the gradient buffers) whose
+ * pointer is set later or never.  Every entry's name is what dali_resnet_debug_tensor / dali_debug_vit_tensor answers to, with these bytes; an
+ * entry is listed whether or not the plan is bound (tests/test_gpu_plan_arena.py).
+ * The ResNet's names (shapes: the comment above dali_resnet_debug_tensor, daliid_amd/csrc/resnet_plan.hip):
+ *   wbf16, w_stem, ximg, raw0, pool0, pool_arg, bn1.{scale,shift,mean,invstd,coef}, feat, head_arg, neck.mean, neck.invstd, gbuf0;
+ *   block<i>.{a1,a2,y}, .rawd (with a downsample branch), .bn{1,2,3,d}.{scale,shift,mean,invstd,coef}, .conv{1,2,3,d}.w, .in1.{mean,invstd} (an IBN
+ *   block), .wcat and .shcat (where the inference forward folds conv3 + downsample into one GEMM);
+ *   of a training plan only: d_raw0, dfeat, stat_partial, bwd_partial, wgrad_slab, cs_partial, stem_dw_pad, red_scratch, gbuf1 .. gbuf5,
+ *   block<i>.{raw1,raw2,d_raw1,ybits,sdz}, .conv{1,2,3,d}.wt, .l3.{gram,m2,bvec,qk,wd,ut,dot} and, where the downsample branch's backward runs
+ *   through the moments of x, .ld.{gram,m2,bvec,qk,wd,ut};
+ *   grad_cur, which dali_resnet_debug_tensor also answers, is no entry: it moves and changes its size from block to block */
+int dali_debug_resnet_arena_entry(const struct dali_resnet* net, int index, char* name, int name_cap, int64_t* offset, int64_t* bytes, int* reserved);
+int dali_debug_vit_arena_entry(const struct dali_vit* net, int index, char* name, int name_cap, int64_t* offset, int64_t* bytes, int* reserved);
 
 /* pieces that only the net plan reaches, on their own (tests/test_gpu_plan_only.py) */
 struct dali_ctx;
