@@ -41,6 +41,10 @@ _SIGNATURES = {
                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "dali_rank_eval_inp": [c_void_p] * 7 + [c_int, c_int] + [c_void_p] * 6,
     "dali_qe_combine": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    "dali_pool_rows": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p],
+    "dali_segment_reduce2d": [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                              ctypes.c_int64, c_int, c_int, c_void_p],
+    "dali_open_set_search": [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_int64] + [c_void_p] * 7,
     "dali_rank_shard_matches": [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3,
     "dali_rank_shard_bins": [c_void_p] * 7 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p],
     "dali_rank_shard_finish": [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6,

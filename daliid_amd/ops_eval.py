@@ -767,3 +767,317 @@ def mr_fuse(score_list, topk=20, use_columns=False, killscale=1.0, out_dtype=tor
     if stats and int(torch.stack(stats)[:, 0].max()) != 0:
         raise ValueError("mr_fuse: input contains NaN or infinity")
     return out
+
+
+# ---- template (set) evaluation (include/daliid.h, dali_pool_rows / dali_segment_reduce2d / dali_open_set_search) ----
+_POOL_MODE = {"mean": 0, "max": 1}
+_SEG_MODE = {"min": 0, "max": 1, "mean": 2}
+_TPL_STATUS = {1: "a row number lies outside the rows", 2: "the bounds do not increase inside their range", 3: "row numbers and bounds lie outside their ranges"}
+
+
+def template_index(keys):
+    """Host: group rows into templates by key.  ``keys``: a 1-D array of any dtype (strings included) or a tuple of such columns (rows
+    are equal when every column is).  Templates are numbered in the order of their first appearance, members keep their original row
+    order.  -> (order int32 [n]: row numbers grouped by template, bounds int32 [T + 1], first int64 [T]: the first member of every
+    template) -- the ``order`` / ``bounds`` convention of ``class_targets``."""
+    cols = list(keys) if isinstance(keys, tuple) else [keys]
+    if not cols:
+        raise ValueError("template_index: no key column")
+    code = None
+    for col in cols:
+        col = np.asarray(col)
+        if col.ndim != 1:
+            raise ValueError("template_index: a key column must be 1-D, got shape %s" % (col.shape,))
+        if code is not None and col.shape[0] != code.shape[0]:
+            raise ValueError("template_index: key columns of %d and %d rows" % (code.shape[0], col.shape[0]))
+        _, inv = np.unique(col, return_inverse=True)
+        inv = inv.reshape(-1).astype(np.int64)
+        if code is None:
+            code = inv
+        else:                      # the pair (code so far, this column) renumbered densely: no product of cardinalities can overflow
+            _, code = np.unique(np.stack([code, inv], axis=1), axis=0, return_inverse=True)
+            code = code.reshape(-1).astype(np.int64)
+    n = code.shape[0]
+    if n == 0:
+        return np.zeros(0, np.int32), np.zeros(1, np.int32), np.zeros(0, np.int64)
+    _, first_of, inv = np.unique(code, return_index=True, return_inverse=True)
+    by_first = np.argsort(first_of, kind="stable")
+    number = np.empty_like(by_first)
+    number[by_first] = np.arange(by_first.size)
+    t = number[inv.reshape(-1)]
+    order = np.argsort(t, kind="stable").astype(np.int32)
+    bounds = np.concatenate([[0], np.cumsum(np.bincount(t))]).astype(np.int32)
+    return order, bounds, first_of[by_first].astype(np.int64)
+
+
+def _check_bounds(bounds, n, who, what):
+    """Host check of a bounds array: strictly increasing from 0 to n.  -> numpy int32."""
+    b = np.asarray(bounds)
+    if b.ndim != 1 or b.size < 2 or not np.issubdtype(b.dtype, np.integer):
+        raise ValueError("%s: %s must be a 1-D integer array of at least 2 entries" % (who, what))
+    b = b.astype(np.int64)
+    if b[0] != 0 or b[-1] != n:
+        raise ValueError("%s: %s run from %d to %d, not from 0 to %d" % (who, what, b[0], b[-1], n))
+    if np.any(np.diff(b) <= 0):
+        raise ValueError("%s: %s must increase strictly (template %d is empty)" % (who, what, int(np.nonzero(np.diff(b) <= 0)[0][0])))
+    return b.astype(np.int32)
+
+
+def _device_bounds(bounds, n, dev, who, what):
+    """A host array is checked here and uploaded; a CUDA int32 tensor is taken as it is (the kernels compare every bound with its range
+    and report through the status word)."""
+    if isinstance(bounds, torch.Tensor) and bounds.is_cuda:
+        if bounds.dtype != torch.int32 or bounds.dim() != 1 or bounds.numel() < 2 or not bounds.is_contiguous():
+            raise ValueError("%s: %s on the device must be a contiguous 1-D int32 tensor of at least 2 entries" % (who, what))
+        return bounds
+    if isinstance(bounds, torch.Tensor):
+        bounds = bounds.numpy()
+    return torch.from_numpy(_check_bounds(bounds, n, who, what)).to(dev)
+
+
+def _tpl_status(status, who):
+    st = int(status.item())
+    if st != 0:
+        raise _lib.DaliError("%s: %s (skipped, never read)" % (who, _TPL_STATUS.get(st, "status %d" % st)))
+
+
+def pool_templates(fvs, order, bounds, mode="mean", weights=None):
+    """Feature-level pooling of CUDA fp32 rows ``fvs`` [n, d] into one row per template (include/daliid.h, dali_pool_rows), in the fixed
+    fp32 order documented there.  ``order`` / ``bounds``: as ``template_index`` returns them (host arrays are checked here; CUDA int32
+    tensors are taken as they are and checked by the kernel).  mode: "mean" (with ``weights`` fp32 [n] indexed by row: the weighted mean
+    sum w f / sum w), "max", "magnitude" (weights = the rows' L2 norms, ``l2norm_rows(..., return_norms=True)``: the reference's
+    confidence-by-magnitude inside a template) or "unit_mean" (weights = the reciprocal norms: the mean of the unit vectors; a zero row
+    gives NaN).  -> fp32 [T, d] on the device."""
+    who = "pool_templates"
+    if mode not in ("mean", "max", "magnitude", "unit_mean"):
+        raise ValueError("%s: mode must be 'mean', 'max', 'magnitude' or 'unit_mean', got %r" % (who, mode))
+    if weights is not None and mode != "mean":
+        raise ValueError("%s: weights go with mode='mean' only (mode=%r brings its own or takes none)" % (who, mode))
+    if not isinstance(fvs, torch.Tensor) or fvs.dim() != 2:
+        raise ValueError("%s: fvs must be a 2-D tensor" % who)
+    if not fvs.is_cuda or fvs.dtype != torch.float32:
+        raise _lib.DaliError("%s: fvs must be a CUDA float32 tensor" % who)
+    n, d = fvs.shape
+    if n == 0 or d == 0:
+        raise ValueError("%s: nothing to pool (fvs is %d x %d)" % (who, n, d))
+    dev = fvs.device
+    fvs = fvs.contiguous()
+    if isinstance(order, torch.Tensor) and order.is_cuda:
+        if order.dtype != torch.int32 or order.dim() != 1 or not order.is_contiguous():
+            raise ValueError("%s: order on the device must be a contiguous 1-D int32 tensor" % who)
+        order_d = order
+    else:
+        o = np.asarray(order.numpy() if isinstance(order, torch.Tensor) else order)
+        if o.ndim != 1 or not np.issubdtype(o.dtype, np.integer) or o.size != n:
+            raise ValueError("%s: order must hold one integer row number per row (%d)" % (who, n))
+        if o.min() < 0 or o.max() >= n:
+            raise ValueError("%s: order holds a row number outside 0..%d" % (who, n - 1))
+        order_d = torch.from_numpy(o.astype(np.int32)).to(dev)
+    if order_d.numel() != n:
+        raise ValueError("%s: order has %d entries for %d rows" % (who, order_d.numel(), n))
+    bounds_d = _device_bounds(bounds, n, dev, who, "bounds")
+    T = bounds_d.numel() - 1
+    if mode in ("magnitude", "unit_mean"):
+        _, norms = l2norm_rows(fvs, return_norms=True)
+        weights = norms if mode == "magnitude" else torch.reciprocal(norms)
+    elif weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.numel() != n:
+            raise ValueError("%s: weights must be a tensor of one weight per row (%d)" % (who, n))
+        weights = weights.reshape(-1).contiguous()
+    out = torch.empty(T, d, device=dev, dtype=torch.float32)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    _lib.check(_lib.lib().dali_pool_rows(_lib.ctx(dev), _lib.stream_ptr(), _lib.ptr(fvs), n, d, _lib.ptr(order_d), _lib.ptr(bounds_d), T,
+                                         _lib.ptr(weights, torch.float32, "weights"), _POOL_MODE["max" if mode == "max" else "mean"],
+                                         _lib.ptr(out), _lib.ptr(status)), "dali_pool_rows")
+    _tpl_status(status, who)
+    return out
+
+
+def segment_reduce2d(distmat, row_bounds, col_bounds, mode, out=None, out_row0=0, out_col0=0, _status=None):
+    """Score-level linkage (include/daliid.h, dali_segment_reduce2d): entry (a, b) of the result is the "min" / "max" / "mean" of the
+    sub-matrix rows(a) x cols(b) of the CUDA fp32 ``distmat``, whose rows and columns are cut into contiguous segments by ``row_bounds``
+    [Tr + 1] / ``col_bounds`` [Tc + 1] (host arrays are checked here; CUDA int32 tensors are taken as they are).  ``distmat`` may be a
+    column slice of a wider matrix (read by its pitch).  ``out``: a CUDA fp32 matrix that receives the [Tr, Tc] block at
+    (out_row0, out_col0); its other entries are left as they are.  -> out (a new [Tr, Tc] tensor without ``out``).  ``_status``: a device
+    status word the caller reads itself (link_templates: once for all its blocks)."""
+    who = "segment_reduce2d"
+    if mode not in _SEG_MODE:
+        raise ValueError("%s: mode must be 'min', 'max' or 'mean', got %r" % (who, mode))
+    if not isinstance(distmat, torch.Tensor) or distmat.dim() != 2:
+        raise ValueError("%s: distmat must be a 2-D tensor" % who)
+    if not distmat.is_cuda or distmat.dtype != torch.float32:
+        raise _lib.DaliError("%s: distmat must be a CUDA float32 tensor" % who)
+    rows, cols = distmat.shape
+    if rows == 0 or cols == 0:
+        raise ValueError("%s: empty matrix (%d x %d)" % (who, rows, cols))
+    if not (distmat.stride(1) == 1 and (rows == 1 or distmat.stride(0) >= cols)):
+        distmat = distmat.contiguous()
+    ld = max(int(distmat.stride(0)), cols) if rows > 1 else cols
+    dev = distmat.device
+    rb = _device_bounds(row_bounds, rows, dev, who, "row_bounds")
+    cb = _device_bounds(col_bounds, cols, dev, who, "col_bounds")
+    Tr, Tc = rb.numel() - 1, cb.numel() - 1
+    if out is None:
+        if out_row0 or out_col0:
+            raise ValueError("%s: out_row0 / out_col0 without out" % who)
+        out = torch.empty(Tr, Tc, device=dev, dtype=torch.float32)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dim() != 2 or not out.is_cuda or out.dtype != torch.float32 or out.stride(1) != 1 \
+                or (out.shape[0] > 1 and out.stride(0) < out.shape[1]):
+            raise ValueError("%s: out must be a 2-D CUDA float32 matrix with contiguous rows" % who)
+        if out_row0 < 0 or out_col0 < 0 or out_row0 + Tr > out.shape[0] or out_col0 + Tc > out.shape[1]:
+            raise ValueError("%s: the %d x %d block at (%d, %d) does not lie inside out %s" % (who, Tr, Tc, out_row0, out_col0, tuple(out.shape)))
+    out_ld = max(int(out.stride(0)), out.shape[1]) if out.shape[0] > 1 else out.shape[1]
+    status = torch.zeros(1, device=dev, dtype=torch.int32) if _status is None else _status
+    _lib.check(_lib.lib().dali_segment_reduce2d(_lib.ctx(dev), _lib.stream_ptr(), _lib.c_void_p(distmat.data_ptr()), rows, cols, ld, _lib.ptr(rb), Tr,
+                                                _lib.ptr(cb), Tc, _SEG_MODE[mode], _lib.c_void_p(out.data_ptr()), out.shape[0], out_ld,
+                                                int(out_row0), int(out_col0), _lib.ptr(status)), "dali_segment_reduce2d")
+    if _status is None:
+        _tpl_status(status, who)
+    return out
+
+
+def _template_groups(bounds, cap):
+    """Greedy runs of whole templates of at most ``cap`` rows each (a longer template is a run of its own): -> list of (t0, t1)."""
+    groups, t0 = [], 0
+    T = bounds.size - 1
+    while t0 < T:
+        t1 = t0 + 1
+        while t1 < T and bounds[t1 + 1] - bounds[t0] <= cap:
+            t1 += 1
+        groups.append((t0, t1))
+        t0 = t1
+    return groups
+
+
+def _local_bounds(bounds, groups, dev):
+    """The bounds of every run, each starting at 0, as views of ONE uploaded tensor."""
+    parts = [bounds[t0:t1 + 1] - bounds[t0] for t0, t1 in groups]
+    flat = torch.from_numpy(np.concatenate(parts).astype(np.int32)).to(dev)
+    views, o = [], 0
+    for p in parts:
+        views.append(flat[o:o + p.size])
+        o += p.size
+    return views
+
+
+def link_templates(q, g, q_bounds, g_bounds, linkage="min", metric="cosine", precision="bf16x3", normalize=True, scratch_bytes=1 << 30):
+    """Set-to-set distances [Tq, Tg] between templates whose members are CONTIGUOUS rows of the CUDA fp32 features ``q`` / ``g``
+    (``q_bounds`` [Tq + 1], ``g_bounds`` [Tg + 1], host arrays): the "min" / "mean" / "max" over the frame-pair distances of ``pairdist``
+    (single / average / complete linkage).  The frame-level matrix never exists as a whole: ``pairdist`` writes a block of whole
+    templates x whole templates into a reused scratch of at most ``scratch_bytes`` and ``segment_reduce2d`` writes its output sub-block.
+    A template pair whose frame block alone exceeds the scratch is refused with the size it needs."""
+    who = "link_templates"
+    if linkage not in _SEG_MODE:
+        raise ValueError("%s: linkage must be 'min', 'mean' or 'max', got %r" % (who, linkage))
+    if metric not in _METRIC or precision not in _PREC:
+        raise ValueError("%s: metric %r / precision %r are not built" % (who, metric, precision))
+    if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise ValueError("%s: q %s and g %s must be 2-D with one width" % (who, tuple(q.shape), tuple(g.shape)))
+    if not q.is_cuda or not g.is_cuda or q.dtype != torch.float32 or g.dtype != torch.float32:
+        raise _lib.DaliError("%s: q and g must be CUDA float32 tensors" % who)
+    as_host = lambda b: b.cpu().numpy() if isinstance(b, torch.Tensor) else b
+    qb = _check_bounds(as_host(q_bounds), q.shape[0], who, "q_bounds").astype(np.int64)
+    gb = _check_bounds(as_host(g_bounds), g.shape[0], who, "g_bounds").astype(np.int64)
+    qmax, gmax = int(np.diff(qb).max()), int(np.diff(gb).max())
+    elems = int(scratch_bytes) // 4
+    if qmax * gmax > elems:
+        raise ValueError("%s: a template pair of %d x %d frames needs a scratch of %d bytes, scratch_bytes is %d"
+                         % (who, qmax, gmax, qmax * gmax * 4, int(scratch_bytes)))
+    q, g = q.contiguous(), g.contiguous()
+    dev = q.device
+    nq, ng = q.shape[0], g.shape[0]
+    if elems // ng >= qmax:        # the whole gallery width fits: the gallery is prepared once per row block
+        rcap = elems // ng
+    else:
+        rcap = max(qmax, min(int(np.sqrt(elems)), elems // gmax))
+    row_groups = _template_groups(qb, rcap)
+    row_local = _local_bounds(qb, row_groups, dev)
+    col_cache = {}
+    scratch = torch.empty(min(elems, max(int(qb[t1] - qb[t0]) for t0, t1 in row_groups) * ng), device=dev, dtype=torch.float32)
+    out = torch.empty(qb.size - 1, gb.size - 1, device=dev, dtype=torch.float32)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    for (a0, a1), rb in zip(row_groups, row_local):
+        r0, r1 = int(qb[a0]), int(qb[a1])
+        ccap = min(ng, elems // (r1 - r0))
+        if ccap not in col_cache:
+            groups = _template_groups(gb, ccap)
+            col_cache[ccap] = (groups, _local_bounds(gb, groups, dev))
+        for (b0, b1), cb in zip(*col_cache[ccap]):
+            c0, c1 = int(gb[b0]), int(gb[b1])
+            block = scratch[:(r1 - r0) * (c1 - c0)].view(r1 - r0, c1 - c0)
+            pairdist(q[r0:r1], g[c0:c1], metric=metric, precision=precision, normalize=normalize, out=block)
+            segment_reduce2d(block, rb, cb, linkage, out=out, out_row0=a0, out_col0=b0, _status=status)
+    _tpl_status(status, who)
+    return out
+
+
+def open_set_search(distmat, q_subj, g_subj):
+    """Per-probe open-set search (include/daliid.h, dali_open_set_search) of a CUDA fp32 ``distmat`` [nq, ng] (read by its pitch) with
+    int32 subject codes ``q_subj`` [nq] / ``g_subj`` [ng] (host arrays or tensors).  -> device tensors (mate_dist fp32, mate_col int32,
+    nonmate_dist fp32, nonmate_col int32, rank int32), each [nq]: the nearest gallery entry of the probe's own subject (+inf / -1 for
+    a probe that is not mated), the nearest entry of any other subject, and the number of other-subject entries that sort before the
+    best mate (-1: not mated)."""
+    who = "open_set_search"
+    if not isinstance(distmat, torch.Tensor) or distmat.dim() != 2:
+        raise ValueError("%s: distmat must be a 2-D tensor" % who)
+    if not distmat.is_cuda or distmat.dtype != torch.float32:
+        raise _lib.DaliError("%s: distmat must be a CUDA float32 tensor" % who)
+    nq, ng = distmat.shape
+    if nq == 0 or ng == 0:
+        raise ValueError("%s: empty distance matrix (%d x %d)" % (who, nq, ng))
+    if not (distmat.stride(1) == 1 and (nq == 1 or distmat.stride(0) >= ng)):
+        distmat = distmat.contiguous()
+    ld = max(int(distmat.stride(0)), ng) if nq > 1 else ng
+    dev = distmat.device
+
+    def codes(a, n, name):
+        a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(-1)))
+        if a.numel() != n or a.dtype not in (torch.int32, torch.int64):
+            raise ValueError("%s: %s must hold %d integer subject codes" % (who, name, n))
+        return a.to(dev, dtype=torch.int32).reshape(-1).contiguous()
+
+    qs, gs = codes(q_subj, nq, "q_subj"), codes(g_subj, ng, "g_subj")
+    mate_dist, nonmate_dist = (torch.empty(nq, device=dev, dtype=torch.float32) for _ in range(2))
+    mate_col, nonmate_col, rank = (torch.empty(nq, device=dev, dtype=torch.int32) for _ in range(3))
+    _lib.check(_lib.lib().dali_open_set_search(_lib.ctx(dev), _lib.stream_ptr(), _lib.c_void_p(distmat.data_ptr()), nq, ng, ld, _lib.ptr(qs),
+                                               _lib.ptr(gs), _lib.ptr(mate_dist), _lib.ptr(mate_col), _lib.ptr(nonmate_dist),
+                                               _lib.ptr(nonmate_col), _lib.ptr(rank)), "dali_open_set_search")
+    return mate_dist, mate_col, nonmate_dist, nonmate_col, rank
+
+
+def open_set_summary(mate_dist, nonmate_dist, rank, fpirs=(1e-1, 1e-2, 1e-3), ranks=(1, 20)):
+    """Host: open-set identification rates from ``open_set_search``'s per-probe results (numpy float32 comparisons).  A probe is mated
+    when rank >= 0.  With ``nm`` the ascending nonmate_dist of the NON-mated probes and N_nm their count, for every fpir:
+    m = floor(fpir * N_nm + 1e-9), threshold T = nm[m] (+inf when m >= N_nm, in particular without non-mated probes: everything is then
+    accepted), a candidate is accepted iff d < T; realised FPIR = the share of non-mated probes with nonmate_dist < T (at most fpir;
+    NaN without non-mated probes); FNIR(fpir, r) = the share of mated probes that do NOT have mate_dist < T and rank < r (NaN without
+    mated probes, as the closed-set rates are).  -> dict: fnir {(fpir, r)}, fpir {fpir: realised}, threshold {fpir: float32},
+    rank {r: share of mated probes with rank < r}, n_mated, n_nonmated."""
+    to_np = lambda a, dt: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dt).reshape(-1)
+    md, nd, rk = to_np(mate_dist, np.float32), to_np(nonmate_dist, np.float32), to_np(rank, np.int64)
+    if not md.size == nd.size == rk.size:
+        raise ValueError("open_set_summary: mate_dist, nonmate_dist and rank differ in length (%d, %d, %d)" % (md.size, nd.size, rk.size))
+    mated = rk >= 0
+    n_m, n_nm = int(mated.sum()), int((~mated).sum())
+    nm = np.sort(nd[~mated])
+    md_m, rk_m = md[mated], rk[mated]
+    nan = float("nan")
+    res = dict(fnir={}, fpir={}, threshold={}, rank={int(r): (float(np.mean(rk_m < r)) if n_m else nan) for r in ranks},
+               n_mated=n_m, n_nonmated=n_nm)
+    for f in fpirs:
+        m = int(np.floor(float(f) * n_nm + 1e-9))
+        thr = nm[m] if m < n_nm else np.float32(np.inf)
+        res["threshold"][f] = np.float32(thr)
+        res["fpir"][f] = float(np.mean(nm < thr)) if n_nm else nan
+        for r in ranks:
+            res["fnir"][(f, int(r))] = float(1.0 - np.mean((md_m < thr) & (rk_m < r))) if n_m else nan
+    return res
+
+
+def open_set_metrics(distmat, q_ids, g_ids, fpirs=(1e-1, 1e-2, 1e-3), ranks=(1, 20)):
+    """``factorize_ids`` + ``open_set_search`` + ``open_set_summary``: FNIR at fixed FPIR of a CUDA fp32 distance matrix whose rows /
+    columns carry the subject ids ``q_ids`` / ``g_ids`` (any dtype).  One copy of 5 nq words to the host."""
+    qs, gs = factorize_ids(q_ids, g_ids)
+    mate_dist, _, nonmate_dist, _, rank = open_set_search(distmat, qs, gs)
+    return open_set_summary(mate_dist, nonmate_dist, rank, fpirs, ranks)

@@ -246,6 +246,61 @@ int dali_pairdist_topk(dali_ctx* ctx, void* stream, const void* q_image, const f
 int dali_qe_combine(dali_ctx* ctx, void* stream, const float* pool, int n_pool, int d, const int32_t* idx, const float* val, int n, int k,
                     int val_is_distance, int alpha, float* out, int32_t* status);
 
+/* Template (set) evaluation: a set of rows -- the frames of a tracklet, the media of a subject, the images of a multi-query -- stands for
+ * one search unit (BRIAR templates, MARS tracklets, Market-1501 multi-query).  Three kernels that read their input once; the mirror's
+ * ops_eval.pool_templates / link_templates / open_set_metrics compose them.  All pointers are device pointers, 4-byte aligned; nothing
+ * synchronises; no workspace; no atomics on floats: bitwise identical results run to run, whatever the launch geometry.
+ * order / bounds are device data these entries cannot inspect.  The kernels compare every row number and bound with its range before it
+ * becomes an address; what lies outside is skipped and reported in status[0] (device int32, OR-ed with 1 = a row number outside [0, n),
+ * 2 = bounds that do not increase inside their range).  The calls never clear status: the caller zeroes it.
+ *
+ *   dali_pool_rows   feature-level pooling.  fvs [n][d] fp32; order [n] int32 row numbers grouped by template and bounds [n_templates + 1]
+ *                    int32, strictly increasing from 0 to n (the convention of dali_class_targets): template t owns
+ *                    order[bounds[t] .. bounds[t+1]), its members in that order; weights (nullable; mode 0 only) fp32 [n] indexed by ROW
+ *                    number; out [n_templates][d] fp32, not overlapping fvs.  Every operation is an IEEE fp32 operation rounded to nearest,
+ *                    no fused multiply-add.  For template t, element c, members r_0, r_1, ... in member order:
+ *                      mode 0 (weighted mean)  acc = 0.0f; wsum = 0.0f;
+ *                                              for i ascending:  acc = acc + (w_i * fvs[r_i][c]);  wsum = wsum + w_i      (w_i = weights[r_i])
+ *                                              out[t][c] = acc / wsum
+ *                                              without weights every w_i is 1.0f and the divisor is (float)count.  ONE running sum per
+ *                                              element over the whole template, however long: the order depends on neither the launch
+ *                                              geometry nor n_templates.
+ *                      mode 1 (max)            acc = -inf;  for i ascending:  acc = fvs[r_i][c] > acc ? fvs[r_i][c] : acc   (a NaN is never
+ *                                              taken; of +0.0 and -0.0 the one met first stays)
+ *                    Rows are read 16 bytes per lane when d % 4 == 0 and fvs and out are 16-byte aligned, 4 bytes per lane otherwise.
+ *                    A template with bad bounds gets a zero row.  Refused before any launch (DALI_ERR_INVALID): a mode other than 0 / 1,
+ *                    d < 1, n < 1, n_templates outside 1 .. n (an empty template cannot exist then), weights with mode 1, a null or
+ *                    misaligned pointer, out overlapping fvs.
+ *   dali_segment_reduce2d  score-level linkage.  x: rows x cols fp32 read by its pitch ld >= cols; row_bounds [n_row_segs + 1] and
+ *                    col_bounds [n_col_segs + 1] int32: contiguous segments, strictly increasing, covering 0 .. rows and 0 .. cols.
+ *                    out[out_row0 + a][out_col0 + b] (out: out_rows rows of pitch out_ld; entries outside the block are not touched) =
+ *                    the min (mode 0) / max (mode 1) / mean (mode 2) of the sub-matrix rows(a) x cols(b).
+ *                      min / max  in the total order of the bit patterns: -0.0 below +0.0, a NaN beyond the infinity of its sign.  No
+ *                                 result depends on the order of the entries; the result is one of the entries, bit for bit.
+ *                      mean       for every column j of cols(b):  p_j = x[r_0][j];  for the further rows r ascending:  p_j = p_j + x[r][j]
+ *                                 acc = p_{j_0};  for the further columns j ascending:  acc = acc + p_j
+ *                                 out = acc / (float)(|rows(a)| * |cols(b)|)        (fp32, rounded to nearest, as above)
+ *                    Refused before any launch: a mode other than 0 / 1 / 2, rows or cols < 1, ld < cols, a segment count outside
+ *                    1 .. rows / 1 .. cols, an output block that does not lie inside out, a null or misaligned pointer.
+ *   dali_open_set_search   per-probe open-set search of a distance matrix distmat [nq][ng] fp32 read by its pitch ld >= ng; q_subj [nq],
+ *                    g_subj [ng] int32 subject codes.  For probe i with mates M = {j : g_subj[j] == q_subj[i]}:
+ *                      mate_dist[i]    = min of distmat[i][j] over M; mate_col[i] = the smallest j that attains it.  +inf and -1 for an
+ *                                        empty M (a probe that is not mated)
+ *                      nonmate_dist[i], nonmate_col[i]   the same over the complement of M; +inf and -1 when it is empty
+ *                      rank[i]         = the number of non-mates j with distmat[i][j] < mate_dist[i], or distmat[i][j] == mate_dist[i] and
+ *                                        j < mate_col[i]: the 0-based position of the best mate in a stable ascending sort of the row
+ *                                        with the other mates removed.  -1 for a probe that is not mated
+ *                    Comparisons are IEEE (-0.0 == +0.0); a NaN entry is never a minimum and is never counted.  One pass over the row for
+ *                    the minima, a second for the count; no sort.  The row and g_subj are read 16 bytes per lane when distmat and g_subj
+ *                    are 16-byte aligned and ld % 4 == 0.  Refused before any launch: nq or ng < 1, ld < ng, a null or misaligned pointer. */
+int dali_pool_rows(dali_ctx* ctx, void* stream, const float* fvs, int n, int d, const int32_t* order, const int32_t* bounds, int n_templates,
+                   const float* weights, int mode, float* out, int32_t* status);
+int dali_segment_reduce2d(dali_ctx* ctx, void* stream, const float* x, int rows, int cols, int64_t ld, const int32_t* row_bounds,
+                          int n_row_segs, const int32_t* col_bounds, int n_col_segs, int mode, float* out, int out_rows, int64_t out_ld,
+                          int out_row0, int out_col0, int32_t* status);
+int dali_open_set_search(dali_ctx* ctx, void* stream, const float* distmat, int nq, int ng, int64_t ld, const int32_t* q_subj,
+                         const int32_t* g_subj, float* mate_dist, int32_t* mate_col, float* nonmate_dist, int32_t* nonmate_col, int32_t* rank);
+
 /* Weibull meta-recognition score fusion: libmr.FitHigh / libmr.wscore and Meta_Recognition.metarec / mrfuse (evaluate.py:394-627), the
  * `1.0 - meta_rec.mrfuse(1 - d_backbone, 1 - d_head01, 1 - d_head02)` line evaluate.py:277 leaves commented out.  Every gallery column of a
  * similarity matrix gets a Weibull fitted by maximum likelihood to the tail of its scores, a score becomes its w-score (the Weibull CDF),
